@@ -1,65 +1,57 @@
-"""CPU, build container only: the DiffVC model shell (speech-backbones_amd/diffvc/model/vc.py) live against the reference's
-`model.vc` (DiffVC/model/vc.py:17-148): state_dict layout, the average-voice encoder, and the HOST LOGIC of DiffVC.forward
+"""CPU: the DiffVC model shell (speech-backbones_amd/diffvc/model/vc.py) against the reference's `model.vc`
+(DiffVC/model/vc.py:17-148): state_dict layout, the average-voice encoder, and the HOST LOGIC of DiffVC.forward
 (masks, padding to a multiple of four, the terminal sample `mean_x + randn`) -- the decoder call itself is replaced by a
-recorder on both sides, so everything up to the C-ABI sampler is compared bit for bit."""
+recorder on both sides, so everything up to the C-ABI sampler is compared bit for bit.  What the reference returned is stored
+in tests/golden/live_*.npz (tests/golden/make_golden_live.py); the shell under torch.manual_seed(0) must reproduce the reference's
+default initialisation, which the reference's outputs were computed with."""
 import importlib
 
 import pytest
 import torch
 
-from oracle import ref_loader
+from live_golden import VC_ARGS, assert_reference_init, layout, live, vc_forward_inputs, vc_loss_inputs
 
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="/root/reference not mounted")
 
-# small but structurally complete: n_feats 80, 2 transformer layers, dec_dim 64
-ARGS = dict(n_feats=80, channels=48, filters=96, heads=2, layers=2, kernel=3, dropout=0.0, window_size=4, enc_dim=32,
-            spk_dim=128, use_ref_t=True, dec_dim=64, beta_min=0.05, beta_max=20.0)
+def _t(k):
+    return torch.from_numpy(live()[k])
 
 
 @pytest.fixture(scope="module")
 def pair():
-    ref = ref_loader.load_diffvc()
-    assert ref.vc is not None
     V = importlib.import_module("speech-backbones_amd.diffvc.model")
     torch.manual_seed(0)
-    r = ref.vc.DiffVC(*ARGS.values()).eval()
-    p = V.DiffVC(*ARGS.values()).eval()
-    return r, p
+    p = V.DiffVC(*VC_ARGS.values()).eval()
+    return live(), p
 
 
 def test_state_dict_layout_and_drop_in_load(pair):
     r, p = pair
-    assert [(k, tuple(v.shape)) for k, v in p.state_dict().items()] == [(k, tuple(v.shape)) for k, v in r.state_dict().items()]
-    p.load_state_dict(r.state_dict(), strict=True)
-    assert p.nparams == r.nparams
+    assert_reference_init(p.state_dict(), r, "vc")
+    p.load_state_dict(p.state_dict(), strict=True)
+    assert p.nparams == int(r["vc_nparams"])
     fa = importlib.import_module("speech-backbones_amd.diffvc.model").FwdDiffusion(80, 48, 96, 2, 2, 3, 0.0, 4, 32)
-    fa.load_state_dict(r.encoder.state_dict(), strict=True)
+    assert [(k, tuple(v.shape)) for k, v in fa.state_dict().items()] == layout(r, "vc_enc")
+    fa.load_state_dict(p.encoder.state_dict(), strict=True)
 
 
 def test_average_voice_encoder_matches_reference(pair):
     r, p = pair
-    p.load_state_dict(r.state_dict(), strict=True)
     g = torch.Generator().manual_seed(3)
     x = torch.randn(2, 80, 44, generator=g)
     lens = torch.tensor([44, 31])
     mask = (torch.arange(44)[None, :] < lens[:, None]).unsqueeze(1).float()
-    a, b = r.encoder(x, mask), p.encoder(x, mask)
+    a, b = _t("vc_avg_voice"), p.encoder(x, mask)
     assert torch.allclose(a, b, atol=1e-5, rtol=1e-5)
     y = torch.randn(2, 80, 44, generator=g)
-    assert torch.allclose(r.encoder.compute_loss(x, y, mask), p.encoder.compute_loss(x, y, mask), atol=1e-6)
+    assert torch.allclose(_t("vc_avg_voice_loss"), p.encoder.compute_loss(x, y, mask), atol=1e-6)
 
 
 def test_forward_host_logic_bit_identical(pair):
     """Everything DiffVC.forward hands to the decoder, and what it returns, with the decoder replaced by a recorder."""
     r, p = pair
-    p.load_state_dict(r.state_dict(), strict=True)
-    g = torch.Generator().manual_seed(5)
-    x = torch.randn(3, 80, 50, generator=g)
-    x_len = torch.tensor([50, 37, 42])                    # longest 50 -> padded to 52
-    x_ref = torch.randn(3, 80, 36, generator=g)
-    r_len = torch.tensor([36, 20, 29])
-    c = torch.randn(3, 256, generator=g)
-    got = {}
+    x, x_len, x_ref, r_len, c = vc_forward_inputs()       # longest 50 -> padded to 52
+    got = {"ref": {k: _t("vc_fwd_" + k) for k in ("z", "mask", "mean", "ref", "ref_mask", "mean_ref", "c")}}
+    got["ref"].update(n=int(r["vc_fwd_n"]), mode=str(r["vc_fwd_mode"]))
 
     def recorder(tag):
         def fwd(z, mask, mean, ref, ref_mask, mean_ref, c_, n_timesteps, mode):
@@ -68,10 +60,8 @@ def test_forward_host_logic_bit_identical(pair):
             return z * 2.0
         return fwd
 
-    r.decoder.forward = recorder("ref")
     p.decoder.forward = recorder("own")
-    torch.manual_seed(11)
-    ra = r(x, x_len, x_ref, r_len, c, 6, "ml")
+    ra = (_t("vc_fwd_out0"), _t("vc_fwd_out1"))
     torch.manual_seed(11)
     pa = p(x, x_len, x_ref, r_len, c, 6, "ml")
     assert got["ref"]["n"] == got["own"]["n"] == 6 and got["ref"]["mode"] == got["own"]["mode"] == "ml"
@@ -89,16 +79,9 @@ def test_forward_host_logic_bit_identical(pair):
 
 def test_compute_loss_matches_reference(pair):
     r, p = pair
-    r.decoder.__dict__.pop("forward", None)
     p.decoder.__dict__.pop("forward", None)
-    p.load_state_dict(r.state_dict(), strict=True)
-    g = torch.Generator().manual_seed(8)
-    x = torch.randn(2, 80, 32, generator=g)
-    x_len = torch.tensor([32, 24])
-    x_ref = torch.randn(2, 80, 32, generator=g)
-    c = torch.randn(2, 256, generator=g)
-    torch.manual_seed(2)
-    a = r.compute_loss(x, x_len, x_ref, c)
+    x, x_len, x_ref, c = vc_loss_inputs()
+    a = _t("vc_loss")
     torch.manual_seed(2)
     b = p.compute_loss(x, x_len, x_ref, c)
     assert torch.allclose(a, b, rtol=1e-4, atol=1e-6), (float(a), float(b))

@@ -8,7 +8,6 @@ import torch
 
 from conftest import golden
 from oracle import encoder_oracle as E
-from oracle import ref_loader
 
 
 def _t(a):
@@ -54,16 +53,14 @@ def test_product_modules_share_the_layout_and_match_the_oracle():
         assert torch.allclose(menc(mel, mm), E.mel_encoder_forward(sdm, mel, mm), atol=2e-5)
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="/root/reference not mounted")
 def test_oracle_against_reference_live():
-    ref = ref_loader.load_gradtts()
+    """Against the reference's TextEncoder on the same weights and ids (its outputs in tests/golden/live_*.npz, make_golden_live.py)."""
+    from live_golden import live
+    G = live()
     sd = E.make_state("text", seed=5)
-    enc = ref.text_encoder.TextEncoder(149, 80, 192, 768, 256, 2, 6, 3, 0.1, 4).eval()
-    enc.load_state_dict(sd, strict=True)
-    ids = torch.randint(0, 149, (2, 50))
+    ids = torch.from_numpy(G["textenc_ids"])
     lens = torch.tensor([50, 1])
-    with torch.no_grad():
-        mu, logw, mask = enc(ids, lens)
+    mu, logw, mask = (torch.from_numpy(G["textenc_" + k]) for k in ("mu", "logw", "mask"))
     mu_o, logw_o, mask_o = E.text_encoder_forward(sd, ids, lens)
     assert torch.equal(mask_o, mask) and torch.allclose(mu, mu_o, atol=1e-6) and torch.allclose(logw, logw_o, atol=1e-6)
 

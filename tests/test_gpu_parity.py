@@ -136,14 +136,11 @@ def test_mas_more_tokens_than_frames_all_paths_agree(S, dev, b, tx, ty, monkeypa
 
 
 def test_mas_matches_compiled_reference_when_available(S, dev):
-    if not MAS.ref_available():
-        pytest.skip("oracle/_ref not present")
-    g = torch.Generator().manual_seed(42)
-    value = torch.randn(8, 60, 333, generator=g) * 5
-    xl = torch.randint(1, 61, (8,), generator=g)
-    yl = torch.maximum(torch.randint(1, 334, (8,), generator=g), xl)
-    mask = (O.sequence_mask(xl, 60).unsqueeze(-1) * O.sequence_mask(yl, 333).unsqueeze(1)).float()
-    assert torch.equal(S.mas_maximum_path(value.to(dev), mask.to(dev)).cpu(), MAS.maximum_path_ref(value, mask))
+    """Against the compiled reference's result on this input, stored in tests/golden/live_*.npz (make_golden_live.py)."""
+    from live_golden import live, mas_gpu_case
+    value, mask = mas_gpu_case()
+    want = torch.from_numpy(live()["mas_gpu"]).float()
+    assert torch.equal(S.mas_maximum_path(value.to(dev), mask.to(dev)).cpu(), want)
 
 
 # ------------------------------------------------------------------------------------------------ estimator

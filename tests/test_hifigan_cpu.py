@@ -11,7 +11,6 @@ import torch
 
 from conftest import ROOT, golden
 from oracle import hifigan_oracle as H
-from oracle import ref_loader
 
 CFGS = {"v1": H.V1, "small": H.SMALL, "rb2": H.SMALL_RB2}
 
@@ -70,24 +69,31 @@ def test_drop_in_generator_state_dict_and_torch_path():
     assert S.Vocoder.from_config(h).param_layout() == layout
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Grad-TTS/hifi-gan"), reason="/root/reference not mounted")
 def test_oracle_and_module_against_reference_live():
+    """Against the reference's Generator on the same weights and mel (its layout, outputs and weight-norm-free weights -- per
+    tensor the |.|-sum and 64 entries -- in tests/golden/live_hifigan.npz, make_golden_live.py): under torch.manual_seed(0) the
+    drop-in module must reproduce the reference's default initialisation, which the reference's outputs were computed with."""
+    from live_golden import assert_reference_init, layout, live, sample_index
     warnings.simplefilter("ignore")
-    ref = ref_loader.load_hifigan()
+    G = live()
     M = importlib.import_module("speech-backbones_amd.hifi_gan.models")
     cfg = H.SMALL
     torch.manual_seed(0)
-    r = ref.Generator(ref.AttrDict(_attr(cfg)))
     m = M.Generator(_attr(cfg))
-    assert [(k, tuple(v.shape)) for k, v in r.state_dict().items()] == [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
-    m.load_state_dict(r.state_dict(), strict=True)       # checkpoint format: weight_g / weight_v
+    assert_reference_init(m.state_dict(), G, "hifigan")       # checkpoint format: weight_g / weight_v
     mel = H.make_mel(2, 9, seed=1)
-    with torch.no_grad():
-        want = r(mel)
+    want = torch.from_numpy(G["hifigan_wav"])
     got = m(mel)                                         # torch composition with weight norm attached
     assert torch.allclose(got, want, atol=1e-6)
     eff = m._effective_state()                           # what the HIP packer receives
-    r.remove_weight_norm()
-    for k, v in r.state_dict().items():
-        assert torch.allclose(eff[k], v, atol=1e-7), k
-    assert torch.allclose(H.generator_forward(dict(r.state_dict()), cfg, mel), want, atol=1e-6)
+    want_layout = layout(G, "hifigan_eff")
+    assert sorted((k, tuple(v.shape)) for k, v in eff.items()) == sorted(want_layout)
+    off = 0
+    for (k, _), abssum in zip(want_layout, G["hifigan_eff_abssum"]):
+        v = eff[k]
+        idx = sample_index(v.numel())
+        want_k = torch.from_numpy(G["hifigan_eff_vals"][off:off + idx.size])
+        off += idx.size
+        assert torch.allclose(v.detach().flatten()[torch.from_numpy(idx)], want_k, atol=1e-7), k
+        assert abs(float(v.double().abs().sum()) - float(abssum)) <= 1e-6 * float(abssum), k
+    assert torch.allclose(H.generator_forward({k: v.detach() for k, v in eff.items()}, cfg, mel), want, atol=1e-6)

@@ -1,6 +1,5 @@
 """CPU: the oracle restatement reproduces the committed outputs of the reference's own modules."""
 import numpy as np
-import pytest
 import torch
 
 from conftest import golden
@@ -70,15 +69,11 @@ def test_mas_port_matches_compiled_reference_golden():
     assert torch.equal(path.to(torch.uint8), _t(g["path"]))
 
 
-@pytest.mark.skipif(not MAS.ref_available(), reason="oracle/_ref not built and /root/reference absent")
 def test_mas_port_equals_compiled_reference_random():
-    g = torch.Generator().manual_seed(11)
-    for b, tx, ty in [(4, 31, 90), (3, 1, 7), (2, 50, 50), (6, 13, 200)]:
-        value = torch.randn(b, tx, ty, generator=g) * 4
-        xl = torch.randint(1, tx + 1, (b,), generator=g)
-        yl = torch.maximum(torch.randint(1, ty + 1, (b,), generator=g), xl)   # t_y >= t_x (defined regime)
-        mask = (O.sequence_mask(xl, tx).unsqueeze(-1) * O.sequence_mask(yl, ty).unsqueeze(1)).float()
-        assert torch.equal(MAS.maximum_path_port(value, mask), MAS.maximum_path_ref(value, mask))
+    """Against the compiled reference's paths on these inputs, stored in tests/golden/live_*.npz (make_golden_live.py)."""
+    from live_golden import live, mas_random_cases
+    for i, (value, mask) in enumerate(mas_random_cases()):
+        assert torch.equal(MAS.maximum_path_port(value, mask), torch.from_numpy(live()["mas_rand%d" % i]).float())
 
 
 def test_utils_match_reference_outputs():
