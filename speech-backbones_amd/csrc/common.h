@@ -314,37 +314,16 @@ static inline size_t conv_packed_bytes(int mode, int cin, int cout) {
 }
 
 hipError_t launch_conv(int mode, const ConvArgs &a, hipStream_t st);
-// GTTS_W64_RING=1 builds (A/B only): the 64-channel f16 + fp8 tile of conv_ws.hip takes its weights through per-wave LDS rings filled by
-// LDS-DMA, in column stages (round 6; conv_ws.hip, "W64").  Built, parity-green, measured on one box against the register-load kernel:
-// 275 / 261 us against 266 / 259 per level-0 launch -- not adopted (profiles/NEGATIVE_RESULTS.md).  The switch also selects the weight
-// packing of those layers (pack.hip: column stages) and keeps them off the small-launch form.
-#ifndef GTTS_W64_RING
-#define GTTS_W64_RING 0
-#endif
-// conv_ws.hip: the persistent wave-specialised Block convolution.  GTTS_WS=0 builds (A/B only) keep every layer on conv_mfma.hip.
-#ifndef GTTS_WS
-#define GTTS_WS 1
-#endif
+// conv_ws.hip: the persistent wave-specialised Block convolution
 bool conv_ws_eligible(int mode, int c0, int c1, int cout, int pro, int epi, int nsplit, int f16f8 = 0);
 int conv_ws_nparts(int cout, int Hout, int Wout);      // GroupNorm partial slots per sample it writes (one per 32-frame x 5-row block)
-bool conv_ws_small(int cout, int groups, int Hout, int Wout, int B, int f16f8 = 0);   // the launch takes the three-wave workgroup form (same arithmetic)
+bool conv_ws_small(int cout, int groups, int Hout, int Wout, int B);   // the launch takes the three-wave workgroup form (same arithmetic)
 hipError_t launch_conv_ws(const ConvArgs &a, hipStream_t st);
 // conv_up.hip: Upsample with the four output phases computed from one staged tile (fp32 storage, bf16x3)
 bool conv_up4_eligible(const ConvArgs &a);
-// GTTS_PREC_F16F8 plans: Upsample in the f16 + fp8 split (conv_up.hip); decides the packing of the layer's weights as well.  0: bf16x3 (A/B)
-#ifndef GTTS_UP_F16F8
-#define GTTS_UP_F16F8 1
-#endif
+// GTTS_PREC_F16F8 plans: Upsample in the f16 + fp8 split (conv_up.hip); decides the packing of the layer's weights as well
 bool conv_up4_f16f8_ok(int cin, int cout);
 const char *conv_up4_f8_name();      // the instance launch_conv_up4 launches for such layers (per-op tables)
-// conv_up_ws.hip: the wave-specialised form of the same (producer waves load, stage and STORE).  Built, parity-green, measured on one box
-// against conv_up.hip's uniform-wave kernel: 114.5 / 132.3 us against 110 / 142.6 (128- / 64-channel layer) -- level; OFF (1: A/B builds)
-#ifndef GTTS_UP_WS
-#define GTTS_UP_WS 0
-#endif
-bool conv_up4_ws_ok(int cin, int cout);
-const char *conv_up4_ws_name();
-hipError_t launch_conv_up4_ws(const ConvArgs &a, hipStream_t st);
 hipError_t launch_conv_up4(const ConvArgs &a, hipStream_t st);
 // Block convolutions that take the f16 + fp8 split when the plan's precision is GTTS_PREC_F16F8 (conv_mfma.hip): 3x3, whole
 // 32-channel chunks (a concatenated input splitting on one), mask / GroupNorm prologue, statistics epilogue, and an LDS

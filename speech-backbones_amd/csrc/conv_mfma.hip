@@ -45,21 +45,12 @@
 #ifndef GTTS_F8_WAVES
 #define GTTS_F8_WAVES 2
 #endif
-// 0 (A/B builds): 64-channel layers stay bf16x3 in GTTS_PREC_F16F8 plans
-#ifndef GTTS_F8_WS64
-#define GTTS_F8_WS64 1
-#endif
 #define GTTS_WAVES(MODE) ((MODE) == CONV_DN ? GTTS_DN_WAVES : GTTS_C3_WAVES)
 #define GTTS_WAVES_NS(MODE, NSPLIT) ((MODE) == CONV_DN ? GTTS_DN_WAVES : ((NSPLIT) == 3 ? GTTS_F8_WAVES : ((NSPLIT) == 1 ? GTTS_C3_WAVES_BF16 : GTTS_C3_WAVES)))
-// Diagnostics exist only in -DGTTS_DIAG builds (tools/abexp.sh, tools/trace_conv.py); the product library is compiled
-// without it and the three switches below are then forced off, whatever else is on the command line.
-// GTTS_EXP: timing-only ablations of the main loop (results are WRONG)
-//   1 no MFMAs   2 no fragment ds_reads   3 no activation transform/ds_write   4 no weight staging   5 no barriers
+// Diagnostics exist only in -DGTTS_DIAG builds (tools/trace_conv.py); the product library is compiled without it and the
+// two switches below are then forced off, whatever else is on the command line.
 #ifndef GTTS_DIAG
-#undef GTTS_EXP
 #undef GTTS_TRACE
-#undef GTTS_WDMA
-#undef GTTS_ADBUF
 #undef GTTS_LDS_MIN
 #endif
 // GTTS_LDS_MIN (diagnostic builds): minimum dynamic LDS bytes per workgroup, to force 1 (> 80 KB) or 2 (> 54 KB) workgroups
@@ -73,57 +64,18 @@
 #ifndef GTTS_C3_LDS_MIN
 #define GTTS_C3_LDS_MIN 0
 #endif
-#ifndef GTTS_EXP
-#define GTTS_EXP 0
-#endif
-// 0 = the round-1 conditional prefetches (kept for A/B builds only)
-#ifndef GTTS_UNCOND_PF
-#define GTTS_UNCOND_PF 1
-#endif
-// GTTS_PRIV=1 (measured, not adopted; kept buildable): private weight slices for the bf16x3 3x3 convolutions -- see the
-// kernel comment.  All parity tests pass; 4 of the 6 workgroup barriers per chunk and every wait in front of an MFMA are
-// gone, and the time does not move: 128-cout GroupNorm kernel 216 vs 221 us, 128-cout mask kernel 205 vs 205, the 64-cout
-// kernels 241 vs 231 and 211 vs 204 (they stage every weight twice), 7.40 vs 7.38 ms per U-Net call.  Together with the
-// unconditional-prefetch result (exact vmcnt, no change) this rules out waits and barriers as what holds the loop at ~80 % of
-// the matrix pipe; what is left is issue time of the non-MFMA instructions, which this variant does not reduce (it adds
-// two fragment reads per tap).
-#ifndef GTTS_PRIV
-#define GTTS_PRIV 0
-#endif
 // launches with fewer workgroups than this use half-height 3x3 tiles (conv_small_tiles).  Measured: 256 also catches the
 // 5-utterance sub-batches of the B = 16 sampler (200 workgroups) and costs 1 % there; 128 and 192 keep all of the B = 1 gain
 // (1.73 -> 1.57 ms per U-Net call) at no cost for B = 16.
 #ifndef GTTS_SMALL_WGS
 #define GTTS_SMALL_WGS 128
 #endif
-#ifndef GTTS_PRIV_WAVES
-#define GTTS_PRIV_WAVES 3
-#endif
-#define GTTS_SYNC() do { if (GTTS_EXP != 5) lds_barrier(); } while (0)     // LDS-only fence: prefetches stay in flight
 
 // GTTS_TRACE=1 (diagnostic builds only): per-wave s_memtime phase sums of the 3x3 GroupNorm kernel, read back with
 // gtts_debug_trace().  Phases: 0 top-of-chunk barrier, 1 activation transform + LDS write, 2 weight wait + LDS write,
 // 3 barrier after the weight write, 4 prefetch issue + fragment reads + MFMAs, 5 inter-stage barrier, 6 whole loop.
-// GTTS_WDMA=1: where LDS allows two weight-stage buffers at three workgroups per CU (the 64-cout tile of the 3x3
-// conv), the packed weight stage goes global -> LDS directly (buffer_load_dwordx4 ... lds): no staging VGPRs, no
-// ds_write_b128, and -- the stage being double-buffered -- one barrier per weight stage instead of two.  Verified
-// correct on MI355X (all parity tests) and speed-neutral (214.6 vs 215.9 us): waits and barriers of one wave are
-// covered by the other two waves of the SIMD; what adds to the MFMA time is VALU work, which this does not change.
-// Off by default (it costs 12 KB of LDS); kept as the building block for DMA-staged activations.
-#ifndef GTTS_WDMA
-#define GTTS_WDMA 0
-#endif
 #ifndef GTTS_TRACE
 #define GTTS_TRACE 0
-#endif
-// GTTS_ADBUF=1 (diagnostic builds; measured, not adopted): the 128-cout 3x3 kernel double-buffers its activation image
-// (13 KB more LDS, still three workgroups per CU) and transforms / stages chunk c+1 inside the last weight stage of chunk c,
-// branch-free so that the transform shares the MFMAs' basic block.  hipcc still emits the transform as one VALU block in
-// front of the stage's MFMAs (forcing the interleave with sched_group_barrier spills at 168 VGPRs), and the variant
-// measures 256 vs 238 us on the GroupNorm-prologue kernel and 221 vs 220 us on the mask-prologue kernel: the staging phase
-// cannot be hidden inside a wave from HIP source at this register budget.
-#ifndef GTTS_ADBUF
-#define GTTS_ADBUF 0
 #endif
 #ifndef GTTS_TRACE_CIN
 #define GTTS_TRACE_CIN 128      // traced layer: cin == cout == this
@@ -167,10 +119,6 @@ struct ConvCfg {
 };
 
 static inline int conv_npar(int pro) { return pro == PRO_GN ? 3 : (pro == PRO_IGLU ? 5 : 0); }
-template <int MODE, int WM, int FULLC>
-struct ConvAdbuf { static constexpr bool on = GTTS_ADBUF && !GTTS_TRACE && GTTS_EXP == 0 && !GTTS_WDMA && MODE == CONV_C3 && WM == 2 && FULLC; };
-template <int MODE, int WM, int FULLC>
-struct ConvWdma { static constexpr bool on = GTTS_WDMA && !GTTS_TRACE && GTTS_EXP == 0 && MODE == CONV_C3 && WM == 1 && FULLC; };
 
 static inline size_t conv_smem_bytes(int npix, int nkg, int wblk16, int cin, int pro, int mt) {
     size_t cpad = (size_t)((cin + 8 * nkg - 1) / (8 * nkg)) * 8 * nkg;
@@ -185,28 +133,20 @@ static inline size_t conv_smem_bytes(int npix, int nkg, int wblk16, int cin, int
 // AT = storage type of the activation tensors (float, or __bf16 for the bf16-storage mode of BASELINE config 3: every
 // activation is read / written as bf16, the accumulators and the GroupNorm statistics stay fp32).
 //
-// Wave tile: (MF x 32) output channels x (NF rows x 32 columns).  PRIV = 1 ("private weight slices", 3x3 only): every
-// wave owns MF x 32 output channels for the whole tile height (WM = 4, WN = 1 for the 128-channel tile), so the weights
-// a wave multiplies with are read by no other wave.  Each wave then copies ITS rows of the packed stage into its own
-// LDS region and nobody has to wait for anybody: the two workgroup barriers per weight stage disappear (2 barriers per
-// chunk -- around the shared activation image -- instead of 6).  LDS executes the DS operations of one wave in issue
-// order, which makes the weight path a register-free ring: right after the fragment reads of tap j are issued the
-// wave overwrites slot j with tap j of the NEXT stage (prefetched one stage ahead into wregs) and re-issues the global
-// load of the stage after that, so a weight fragment is in LDS a whole stage before its first reader and no wait on a
-// ds_write or a global load sits in front of an MFMA.
+// Wave tile: (MF x 32) output channels x (NF rows x 32 columns).
+// PRIV is always 0 (it selected an experiment, now removed); it stays so that every instance keeps its name (per-op tables, traffic.json).
 template <int MODE, int WM, int WN, int MF, int KCH, int PRO, int EPI, int NSPLIT, int FULLC, typename AT, int NF = 2, int PRIV = 0>
-__global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PRIV ? GTTS_PRIV_WAVES : GTTS_WAVES_NS(MODE, NSPLIT))) void conv_mfma_kernel(const ConvArgs a) {
+__global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : GTTS_WAVES_NS(MODE, NSPLIT)) void conv_mfma_kernel(const ConvArgs a) {
     constexpr int AB = (int)sizeof(AT);      // bytes per stored activation
     using C = ConvCfg<MODE, WM, WN, MF, KCH, NF>;
-    static_assert(!PRIV || (MODE == CONV_C3 && FULLC && KCH == 1 && MF == 1), "private weight slices: 3x3, whole chunks, one fragment row per wave");
-    static_assert(NSPLIT != 3 || (MODE == CONV_C3 && FULLC && KCH == 2 && !PRIV && sizeof(AT) == 4 && (PRO == PRO_MASK || PRO == PRO_GN)),
+    static_assert(PRIV == 0, "kernel-name parameter only");
+    static_assert(NSPLIT != 3 || (MODE == CONV_C3 && FULLC && KCH == 2 && sizeof(AT) == 4 && (PRO == PRO_MASK || PRO == PRO_GN)),
                   "f16 + fp8 split: 3x3 Block convolutions on whole 32-channel chunks, fp32 storage");
-    static_assert(NSPLIT != 3 || (!ConvWdma<MODE, WM, FULLC>::on && !ConvAdbuf<MODE, WM, FULLC>::on), "f16 + fp8 split: plain staging only");
     constexpr int MT = C::MT, TR = C::TR, TC = C::TC, NST = C::NST, TPS = C::TPS, NKG = C::NKG;
     constexpr int HC = C::HC, NPIX = C::NPIX, AITER = C::AITER, WBLK16 = C::WBLK16;
     // single-pass bf16 (NSPLIT == 1) multiplies with the hi halves only: the block's first half ([split][tap][kg][MT] order) is
     // all it stages -- half the weight loads and LDS writes of a chunk
-    constexpr int NW16 = (NSPLIT == 1 && !ConvWdma<MODE, WM, FULLC>::on) ? WBLK16 / 2 : WBLK16;
+    constexpr int NW16 = NSPLIT == 1 ? WBLK16 / 2 : WBLK16;
     constexpr int WITER = (NW16 + 255) / 256;
 
 #if GTTS_TRACE
@@ -215,14 +155,10 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32x4 *s_ah = reinterpret_cast<u32x4 *>(smem);      // [NKG][NPIX]  hi
     u32x4 *s_al = s_ah + NKG * NPIX;                    // [NKG][NPIX]  lo
-    constexpr bool WDMA = ConvWdma<MODE, WM, FULLC>::on;
-    constexpr bool ADBUF = ConvAdbuf<MODE, WM, FULLC>::on;
-    constexpr int AIMG = 2 * NKG * NPIX;                // one activation image (hi + lo) in 16-byte units
-    u32x4 *s_w = s_al + NKG * NPIX + (ADBUF ? AIMG : 0);   // [split][tap][kg][MT]  (WDMA: two such buffers)
+    u32x4 *s_w = s_al + NKG * NPIX;                     // [split][tap][kg][MT]
     const int cpad = a.nchunk * 8 * NKG;
     // PRO_GN: [3][cpad] scale, shift, time bias; PRO_IGLU: [5][cpad] scale_a, shift_a, time bias, scale_b, shift_b
-    constexpr int WLDS16 = PRIV ? 4 * NSPLIT * TPS * NKG * MF * 32 : WBLK16;   // PRIV: four private regions
-    float *s_par = reinterpret_cast<float *>(s_w + (WDMA ? 2 : 1) * WLDS16);
+    float *s_par = reinterpret_cast<float *>(s_w + WBLK16);
     constexpr int NPAR = PRO == PRO_GN ? 3 : (PRO == PRO_IGLU ? 5 : 0);
     float *s_red = s_par + NPAR * cpad;                       // [4 waves][MF][4 octets][2]
     float *s_epi = s_red + 4 * 2 * 4 * 2;                     // [3][MT]: bias, (EPI_TAIL) GN scale, shift
@@ -324,39 +260,14 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
     };
 
     const unsigned char *wbase = a.w + (size_t)b * a.w_bstride;
-    constexpr int PSEG = NSPLIT * TPS * NKG;              // PRIV: (split, tap, kgroup) segments of MF*32 rows per wave
-    constexpr int PITER = PRIV ? PSEG * MF * 32 / 64 : 1; // 16-byte items per lane and stage (NKG = 2: item i = (split, tap) i)
-    u32x4 wregs[PRIV ? PITER : WITER];
+    u32x4 wregs[WITER];
     const int wtotal = (MODE == CONV_UP ? 4 : 1) * a.nchunk * NST * ncot * WBLK16 * 16;       // bytes of this conv's blocks
     const __amdgpu_buffer_rsrc_t rsw = uniform_rsrc(wbase, wtotal);
     auto load_w = [&](int chunk, int stage) {
         const int blk = ((phase * a.nchunk + chunk) * NST + stage) * ncot + cot;
-        if constexpr (WDMA) {
-            // straight into LDS buffer (global stage index & 1): lane l of a wave lands at the wave's base + 16 l
-            u32x4 *dst = s_w + ((chunk * NST + stage) & 1) * WBLK16 + wave * 64;
 #pragma unroll
-            for (int i = 0; i < WITER; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (__attribute__((address_space(3))) void *)(dst + i * 256), 16,
-                                                         (tid + i * 256) * 16, blk * (WBLK16 * 16), 0, 0);
-        } else {
-#pragma unroll
-            for (int i = 0; i < WITER; ++i)
-                wregs[i] = __builtin_amdgcn_raw_buffer_load_b128(rsw, min(tid + i * 256, NW16 - 1) * 16, blk * (WBLK16 * 16), 0);
-        }
-    };
-
-    // PRIV: tap j of global stage g (= chunk * NST + stage, clamped to the last one) -> wregs[j] (hi), wregs[TPS + j] (lo)
-    u32x4 *s_wp = s_w + wave * (PSEG * MF * 32);          // this wave's private region: [split][tap][kg][MF*32 rows]
-    auto load_w_tap = [&](int g, int j) {
-        const int gl = min(g, a.nchunk * NST - 1);
-        const int blk = gl * ncot + cot;                   // phase == 0 for CONV_C3
-#pragma unroll
-        for (int sp = 0; sp < NSPLIT; ++sp) {
-            const int i = sp * TPS + j;
-            // per-lane offset shared by all items; the (split, tap) item offset rides in the scalar offset
-            wregs[i] = __builtin_amdgcn_raw_buffer_load_b128(rsw, (kg_l * MT + wm * MF * 32 + l31) * 16,
-                                                             blk * (WBLK16 * 16) + i * (NKG * MT * 16), 0);
-        }
+        for (int i = 0; i < WITER; ++i)
+            wregs[i] = __builtin_amdgcn_raw_buffer_load_b128(rsw, min(tid + i * 256, NW16 - 1) * 16, blk * (WBLK16 * 16), 0);
     };
 
     f32x16 acc[MF][NF];
@@ -368,14 +279,10 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
             for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
 
     // (ragged-channel first layers keep the conditional form: the extra live range spills there)
-    constexpr bool UNCOND_PF = GTTS_UNCOND_PF && FULLC;
+    constexpr bool UNCOND_PF = FULLC;
     // activations first, weights second: the same queue order as on the loop's back edge, so the waits at the loop head
     // are exact on both paths
-    if constexpr (PRIV) {
-        load_act(0);
-#pragma unroll
-        for (int j = 0; j < TPS; ++j) load_w_tap(0, j);
-    } else if (UNCOND_PF) { load_act(0); load_w(0, 0); }
+    if (UNCOND_PF) { load_act(0); load_w(0, 0); }
     else { load_w(0, 0); load_act(0); }
 
     // (filled after the first tile's loads are in flight: the parameter loads share one memory round trip with them
@@ -421,7 +328,7 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
     // ---- transform + split + stage the activation tile of a chunk (straight-line code) into image (dh, dl)
     auto stage_act = [&](int chunk, u32x4 *dh, u32x4 *dl) {
 #pragma unroll
-        for (int it = 0; it < (GTTS_EXP == 3 ? 0 : AITER); ++it) {
+        for (int it = 0; it < AITER; ++it) {
             const int idx = tid + it * 256;
             const int kg = min(idx / NPIX, NKG - 1);
             const int p = idx - (idx / NPIX) * NPIX;
@@ -511,14 +418,6 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
                     d8[(((kg >> 1)) * NPIX + slot) * 2 + (kg & 1)] = q0;
                     d8[((2 + (kg >> 1)) * NPIX + slot) * 2 + (kg & 1)] = q1;
                 }
-            } else
-            if constexpr (ADBUF) {
-                // branch-free (lanes without an item write a scratch slot): keeps the transform in the MFMAs' basic block
-                const int slot = kg * NPIX + pr * HC + lc;
-                u32x4 *ph = has ? dh + slot : reinterpret_cast<u32x4 *>(s_red);
-                u32x4 *pl = has ? dl + slot : reinterpret_cast<u32x4 *>(s_red) + 1;
-                *ph = *reinterpret_cast<u32x4 *>(&vh);
-                *pl = *reinterpret_cast<u32x4 *>(&vl);
             } else if (has) {
                 const int slot = kg * NPIX + pr * HC + lc;
                 dh[slot] = *reinterpret_cast<u32x4 *>(&vh);
@@ -526,98 +425,24 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
             }
         }
     };
-    if constexpr (PRIV) {
-        // ---- private-slice main loop: 2 workgroup barriers per chunk (both around the shared activation image)
-        // stage (0, 0) goes straight into the ring, stage (0, 1) (or (1, 0)) waits in wregs
-#pragma unroll
-        for (int i = 0; i < PITER; ++i) s_wp[i * 64 + lane] = wregs[i];
-#pragma unroll
-        for (int j = 0; j < TPS; ++j) load_w_tap(1, j);
-        int chunk = 0;
-        do {       // (bottom-tested by hand: hipcc left the exit test at the top of this loop and then copied all 64
-                   //  accumulator registers into the exit block's set and back on every iteration)
-            GTTS_SYNC();                               // every wave is done with the previous chunk's image (and s_par is written)
-            stage_act(chunk, s_ah, s_al);
-            GTTS_SYNC();
-            load_act(min(chunk + 1, a.nchunk - 1));    // unconditional: see the comment on prefetches below
-#pragma unroll
-            for (int stage = 0; stage < NST; ++stage) {
-                const int g = chunk * NST + stage;
-#pragma unroll
-                for (int j = 0; j < TPS; ++j) {
-                    bf16x8 wh[MF], wl[MF];
-#pragma unroll
-                    for (int mi = 0; mi < MF; ++mi) {
-                        const int wi = (j * NKG + kg_l) * (MF * 32) + mi * 32 + l31;
-                        wh[mi] = *reinterpret_cast<const bf16x8 *>(&s_wp[wi]);
-                        if (NSPLIT > 1) wl[mi] = *reinterpret_cast<const bf16x8 *>(&s_wp[wi + TPS * NKG * MF * 32]);
-                    }
-                    // slot j is free as soon as the reads above are ISSUED (DS operations of a wave execute in order):
-                    // refill it with tap j of the next stage, re-issue the global load of the stage after that
-#pragma unroll
-                    for (int sp = 0; sp < NSPLIT; ++sp) s_wp[(sp * TPS + j) * 64 + lane] = wregs[sp * TPS + j];
-                    load_w_tap(g + 2, j);
-#pragma unroll
-                    for (int np = 0; np < NF; np += 2) {
-                        bf16x8 xh[2], xl[2];
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const int r = wn * NF + np + q;
-                            const int xi = kg_l * NPIX + (r + stage) * HC + j + l31;
-                            xh[q] = *reinterpret_cast<const bf16x8 *>(&s_ah[xi]);
-                            if (NSPLIT > 1) xl[q] = *reinterpret_cast<const bf16x8 *>(&s_al[xi]);
-                        }
-#pragma unroll
-                        for (int mi = 0; mi < MF; ++mi)
-#pragma unroll
-                            for (int q = 0; q < 2; ++q) {
-                                if (NSPLIT > 1) {
-                                    acc[mi][np + q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl[mi], xh[q], acc[mi][np + q], 0, 0, 0);
-                                    acc[mi][np + q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[mi], xl[q], acc[mi][np + q], 0, 0, 0);
-                                }
-                                acc[mi][np + q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[mi], xh[q], acc[mi][np + q], 0, 0, 0);
-                            }
-                    }
-                    // keep hipcc from hoisting the next taps' fragment reads over this tap's MFMAs: the register budget
-                    // (168 at three waves per SIMD) has room for one tap's fragments, not for two
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        } while (++chunk < a.nchunk);
-    }
-    if constexpr (ADBUF) {
-        GTTS_SYNC();                                   // s_par is visible
-        stage_act(0, s_ah, s_al);
-        if (1 < a.nchunk) load_act(1);
-    }
-    for (int chunk = 0; chunk < (PRIV ? 0 : a.nchunk); ++chunk) {
-        if constexpr (!ADBUF) GTTS_SYNC();   // previous chunk's MFMAs are done with s_a* / s_w (and s_par is written)
+    for (int chunk = 0; chunk < a.nchunk; ++chunk) {
+        lds_barrier();                       // previous chunk's MFMAs are done with s_a* / s_w (and s_par is written)
         TR_MARK(0);
 #if GTTS_TRACE
         __builtin_amdgcn_s_waitcnt(0x0f70);     // vmcnt(0): separates the load wait (phase 7) from the transform (phase 1)
         TR_MARK(7);
 #endif
-        if constexpr (!ADBUF) stage_act(chunk, s_ah, s_al);
+        stage_act(chunk, s_ah, s_al);
         TR_MARK(1);
 #pragma unroll
         for (int stage = 0; stage < NST; ++stage) {
-            const u32x4 *s_wc = s_w;                        // weight buffer read by this stage's MFMAs
-            if constexpr (WDMA) {
-                // this stage's weights were DMA'd during the previous stage; every wave waits for its own pieces
-                // (and, conservatively, every other load in flight) and the barrier publishes them -- and, at
-                // stage 0, the activation image written above.  The same barrier frees the other buffer.
-                __builtin_amdgcn_s_waitcnt(0x0f70);         // vmcnt(0)
-                GTTS_SYNC();
-                s_wc = s_w + ((chunk * NST + stage) & 1) * WBLK16;
-            } else {
-                if (stage > 0 || ADBUF) { GTTS_SYNC(); TR_MARK(5); }   // previous stage's MFMAs are done with s_w
+            if (stage > 0) { lds_barrier(); TR_MARK(5); }   // previous stage's MFMAs are done with s_w
 #pragma unroll
-                for (int i = 0; i < (GTTS_EXP == 4 ? 0 : WITER); ++i)
-                    if (NW16 % 256 == 0 || tid + i * 256 < NW16) s_w[tid + i * 256] = wregs[i];
-                TR_MARK(2);
-                GTTS_SYNC();
-                TR_MARK(3);
-            }
+            for (int i = 0; i < WITER; ++i)
+                if (NW16 % 256 == 0 || tid + i * 256 < NW16) s_w[tid + i * 256] = wregs[i];
+            TR_MARK(2);
+            lds_barrier();
+            TR_MARK(3);
             // ---- prefetch behind the MFMAs: next weight block (one stage ahead) and, as early as the staging
             // registers are free again, the next activation chunk (a whole chunk of MFMAs ahead)
             // Both prefetches are UNCONDITIONAL (the last chunk re-requests its own blocks; the registers are never read).
@@ -625,24 +450,13 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
             // stage's s_waitcnt: hipcc then has to assume the shorter queue and emits vmcnt(5) for the weight stage,
             // which also waits for 11 of the 16 activation loads issued one stage (36 MFMAs) earlier -- the HBM latency
             // of the NEXT chunk's tile was exposed once per chunk.  Straight-line code gets the exact vmcnt(21).
-            if (GTTS_EXP == 4) {
-            } else if (stage + 1 < NST) load_w(chunk, stage + 1);
-            else if (ADBUF || UNCOND_PF) load_w(min(chunk + 1, a.nchunk - 1), 0);
+            if (stage + 1 < NST) load_w(chunk, stage + 1);
+            else if (UNCOND_PF) load_w(min(chunk + 1, a.nchunk - 1), 0);
             else if (chunk + 1 < a.nchunk) load_w(chunk + 1, 0);
-            if (!ADBUF && stage == 0) {
+            if (stage == 0) {
                 if (UNCOND_PF) load_act(min(chunk + 1, a.nchunk - 1));
                 else if (chunk + 1 < a.nchunk) load_act(chunk + 1);
             }
-            if (ADBUF && stage == NST - 1) {
-                // next chunk's image goes to the other buffer while this stage's MFMAs run (its last readers finished two
-                // barriers ago); the chunk after that is prefetched into the freed staging registers.  Unconditional (the
-                // last chunk restages itself into the idle buffer) so that the transform shares a basic block with the
-                // MFMAs and the scheduler can place its VALU work between them.
-                const int nc = min(chunk + 1, a.nchunk - 1);
-                stage_act(nc, s_ah + ((chunk + 1) & 1) * AIMG, s_al + ((chunk + 1) & 1) * AIMG);
-                load_act(min(chunk + 2, a.nchunk - 1));
-            }
-            const u32x4 *s_xh = s_ah + (ADBUF ? (chunk & 1) * AIMG : 0), *s_xl = s_al + (ADBUF ? (chunk & 1) * AIMG : 0);
 
 #pragma unroll
             for (int j = 0; j < TPS; ++j) {
@@ -667,22 +481,22 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
                     for (int kc = 0; kc < 2; ++kc) {
 #pragma unroll
                         for (int mi = 0; mi < MF; ++mi)
-                            fwh[kc][mi] = *reinterpret_cast<const f16x8 *>(&s_wc[(j * NKG + kc * 2 + kg_l) * MT + m0 + mi * 32 + l31]);
+                            fwh[kc][mi] = *reinterpret_cast<const f16x8 *>(&s_w[(j * NKG + kc * 2 + kg_l) * MT + m0 + mi * 32 + l31]);
 #pragma unroll
                         for (int ni = 0; ni < NF; ++ni)
-                            fxh[kc][ni] = *reinterpret_cast<const f16x8 *>(&s_xh[(kc * 2 + kg_l) * NPIX + po[ni] + l31]);
+                            fxh[kc][ni] = *reinterpret_cast<const f16x8 *>(&s_ah[(kc * 2 + kg_l) * NPIX + po[ni] + l31]);
                     }
 #pragma unroll
                     for (int mi = 0; mi < MF; ++mi) {
                         const int wi = TPS * NKG * MT + (j * NKG + kg_l * 2) * MT + m0 + mi * 32 + l31;
-                        const u32x4 q0 = s_wc[wi], q1 = s_wc[wi + MT];
+                        const u32x4 q0 = s_w[wi], q1 = s_w[wi + MT];
                         w8[mi][0] = (int)q0[0]; w8[mi][1] = (int)q0[1]; w8[mi][2] = (int)q0[2]; w8[mi][3] = (int)q0[3];
                         w8[mi][4] = (int)q1[0]; w8[mi][5] = (int)q1[1]; w8[mi][6] = (int)q1[2]; w8[mi][7] = (int)q1[3];
                     }
 #pragma unroll
                     for (int ni = 0; ni < NF; ++ni) {
                         const int xi = (kg_l * 2) * NPIX + po[ni] + l31;
-                        const u32x4 q0 = s_xl[xi], q1 = s_xl[xi + NPIX];
+                        const u32x4 q0 = s_al[xi], q1 = s_al[xi + NPIX];
                         x8[ni][0] = (int)q0[0]; x8[ni][1] = (int)q0[1]; x8[ni][2] = (int)q0[2]; x8[ni][3] = (int)q0[3];
                         x8[ni][4] = (int)q1[0]; x8[ni][5] = (int)q1[1]; x8[ni][6] = (int)q1[2]; x8[ni][7] = (int)q1[3];
                     }
@@ -698,34 +512,18 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
 #pragma unroll
                 for (int kc = 0; kc < KCH; ++kc) {
                     bf16x8 wh[MF], wl[MF], xh[NF], xl[NF];
-#if GTTS_EXP == 2
-                    for (int mi = 0; mi < MF; ++mi) { wh[mi] = __builtin_bit_cast(bf16x8, wregs[0]); wl[mi] = wh[mi]; }
-                    for (int ni = 0; ni < NF; ++ni) { xh[ni] = __builtin_bit_cast(bf16x8, wregs[1]); xl[ni] = xh[ni]; }
-#else
 #pragma unroll
                     for (int mi = 0; mi < MF; ++mi) {
                         int wi = (j * NKG + kc * 2 + kg_l) * MT + m0 + mi * 32 + l31;
-                        wh[mi] = *reinterpret_cast<const bf16x8 *>(&s_wc[wi]);
-                        if (NSPLIT > 1) wl[mi] = *reinterpret_cast<const bf16x8 *>(&s_wc[wi + TPS * NKG * MT]);
+                        wh[mi] = *reinterpret_cast<const bf16x8 *>(&s_w[wi]);
+                        if (NSPLIT > 1) wl[mi] = *reinterpret_cast<const bf16x8 *>(&s_w[wi + TPS * NKG * MT]);
                     }
 #pragma unroll
                     for (int ni = 0; ni < NF; ++ni) {
                         int xi = (kc * 2 + kg_l) * NPIX + po[ni] + l31;
-                        xh[ni] = *reinterpret_cast<const bf16x8 *>(&s_xh[xi]);
-                        if (NSPLIT > 1) xl[ni] = *reinterpret_cast<const bf16x8 *>(&s_xl[xi]);
+                        xh[ni] = *reinterpret_cast<const bf16x8 *>(&s_ah[xi]);
+                        if (NSPLIT > 1) xl[ni] = *reinterpret_cast<const bf16x8 *>(&s_al[xi]);
                     }
-#endif
-#if GTTS_EXP == 1
-#pragma unroll
-                    for (int mi = 0; mi < MF; ++mi)
-#pragma unroll
-                        for (int ni = 0; ni < NF; ++ni) {      // consume the fragments with a handful of VALU ops
-                            const u32x4 p = __builtin_bit_cast(u32x4, wh[mi]) ^ __builtin_bit_cast(u32x4, xh[ni]);
-                            u32x4 q = p;
-                            if (NSPLIT > 1) q = __builtin_bit_cast(u32x4, wl[mi]) ^ __builtin_bit_cast(u32x4, xl[ni]);
-                            acc[mi][ni][0] += __builtin_bit_cast(float, (p[0] ^ p[1] ^ p[2] ^ p[3] ^ q[0] ^ q[1] ^ q[2] ^ q[3]) & 0x3fffffffu);
-                        }
-#else
                     // (Issuing the three bf16x3 passes pass-major over the four accumulators, pinned with sched_barrier -- every
                     // same-accumulator pair then exactly four issue slots apart instead of hipcc's mix of 2..8 -- measured
                     // 7.164 vs 7.176 ms per U-Net call over three alternating repeats: no difference; not kept.)
@@ -739,7 +537,6 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
                             }
                             acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[mi], xh[ni], acc[mi][ni], 0, 0, 0);
                         }
-#endif
                 }
             }
             TR_MARK(4);
@@ -988,7 +785,7 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : (PR
 }
 
 
-template <int MODE, int WM, int WN, int MF, int KCH, int PRO, int EPI, int NSPLIT, int FULLC, typename AT = float, int NF = 2, int PRIV = 0>
+template <int MODE, int WM, int WN, int MF, int KCH, int PRO, int EPI, int NSPLIT, int FULLC, typename AT = float, int NF = 2>
 static hipError_t launch_cfg(const ConvArgs &a_in, hipStream_t st) {
     using C = ConvCfg<MODE, WM, WN, MF, KCH, NF>;
     ConvArgs a = a_in;
@@ -999,17 +796,14 @@ static hipError_t launch_cfg(const ConvArgs &a_in, hipStream_t st) {
     a.tiles_y = (th + C::TR - 1) / C::TR;
     const int ncot = (a.cout + C::MT - 1) / C::MT;
     a.stat_rows = (EPI == EPI_STATS && conv_rowpair_stats(MODE, a.cout, a.Hout, a.Wout)) ? 1 : 0;
-    if (a.stat_rows && NF != 2) return hipErrorInvalidValue;       // a wave row must be one row pair (not the PRIV experiment)
+    if (a.stat_rows && NF != 2) return hipErrorInvalidValue;       // a wave row must be one row pair
     dim3 grid(a.tiles_x * a.tiles_y * ncot * (MODE == CONV_UP ? 4 : 1) * a.B);
     if (a.cout % C::MT != 0) return hipErrorInvalidValue;   // epilogue assumes whole output-channel tiles
     // buffer descriptors address one sample's tensor with 32-bit byte offsets
     const size_t lim = (size_t)1 << 31;
     const size_t in_c = (size_t)(PRO == PRO_IGLU ? 2 * a.cin : std::max(a.c0, a.c1));
     if (in_c * a.Hin * a.Win * sizeof(AT) >= lim || (size_t)a.cout * a.Hout * a.Wout * sizeof(AT) >= lim) return hipErrorInvalidValue;
-    constexpr int WLDS16 = PRIV ? 4 * NSPLIT * C::TPS * C::NKG * MF * 32 : C::WBLK16;
-    size_t smem = conv_smem_bytes(C::NPIX, C::NKG, WLDS16, a.cin, PRO, C::MT) +
-                  (ConvWdma<MODE, WM, FULLC>::on ? (size_t)C::WBLK16 * 16 : 0) +
-                  (ConvAdbuf<MODE, WM, FULLC>::on ? (size_t)C::NPIX * C::NKG * 16 * 2 : 0);
+    size_t smem = conv_smem_bytes(C::NPIX, C::NKG, C::WBLK16, a.cin, PRO, C::MT);
     if (smem < (size_t)GTTS_LDS_MIN) smem = (size_t)GTTS_LDS_MIN;
     if (MODE == CONV_C3 && NSPLIT == 2 && (EPI == EPI_STATS || EPI == EPI_PLAIN) && smem < (size_t)GTTS_C3_LDS_MIN) smem = (size_t)GTTS_C3_LDS_MIN;
     // hipFuncSetAttribute is per device: remember the largest size set on each device (atomics: launches may come
@@ -1019,12 +813,12 @@ static hipError_t launch_cfg(const ConvArgs &a_in, hipStream_t st) {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (smem > attr_set[dev].load(std::memory_order_relaxed)) {
         hipError_t e = hipFuncSetAttribute(
-            reinterpret_cast<const void *>(&conv_mfma_kernel<MODE, WM, WN, MF, KCH, PRO, EPI, NSPLIT, FULLC, AT, NF, PRIV>),
+            reinterpret_cast<const void *>(&conv_mfma_kernel<MODE, WM, WN, MF, KCH, PRO, EPI, NSPLIT, FULLC, AT, NF, 0>),
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return e;
         attr_set[dev].store(smem, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((conv_mfma_kernel<MODE, WM, WN, MF, KCH, PRO, EPI, NSPLIT, FULLC, AT, NF, PRIV>), grid, dim3(256), smem, st, a);
+    hipLaunchKernelGGL((conv_mfma_kernel<MODE, WM, WN, MF, KCH, PRO, EPI, NSPLIT, FULLC, AT, NF, 0>), grid, dim3(256), smem, st, a);
     return hipGetLastError();
 }
 
@@ -1038,7 +832,7 @@ bool conv_f16f8_ok(int mode, int c0, int c1, int cout, int pro, int epi, int use
     // tile was built and measured (round 5, same box, us per launch at B = 16): 219.6 / 209.9 (mask / GroupNorm prologue) against
     // 214.2 / 186.5 in bf16x3 -- two workgroups per CU (68 KB of LDS at 32-channel chunks) instead of three, twice the staging per MFMA,
     // and LDS fragment traffic that no longer hides behind the shorter MFMA phase; those instances are gone.
-    if (cout == 64) return GTTS_WS && GTTS_F8_WS64 && use_ws && cin >= 64 && conv_ws_f8_fits(cin, pro, 64, cout);
+    if (cout == 64) return use_ws && cin >= 64 && conv_ws_f8_fits(cin, pro, 64, cout);
     if (cout % 128 != 0) return false;
     const ConvGeom g = conv_geom(mode, cin, cout, 1);
     const int npix = (g.TR + 2) * 34, nkg = 2 * g.kch;
@@ -1078,8 +872,8 @@ static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
             if (a.act_bf16 || a.nsplit != 2) return hipErrorInvalidValue;
             if constexpr (WM == 2) {      // (conv_f16f8_ok: 128-channel cout tiles only)
                 if (conv_small_tiles(MODE, a.cout, a.Hout, a.Wout, a.B))      // half-height tiles, as below
-                    return launch_cfg<MODE, 4, 1, 1, 2, PRO, EPI, 3, 1, float, 2, 0>(a, st);
-                return launch_cfg<MODE, WM, WN, MF, 2, PRO, EPI, 3, 1, float, 2, 0>(a, st);
+                    return launch_cfg<MODE, 4, 1, 1, 2, PRO, EPI, 3, 1, float>(a, st);
+                return launch_cfg<MODE, WM, WN, MF, 2, PRO, EPI, 3, 1, float>(a, st);
             }
             return hipErrorInvalidValue;
         }
@@ -1087,16 +881,12 @@ static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
     if constexpr (MODE == CONV_C3 && PRO != PRO_IGLU) {
         // half-height tiles for small launches (conv_small_tiles): same cout tile, waves re-arranged to 32 channels x 2 rows
         if (fullc && !a.act_bf16 && a.nsplit > 1 && conv_small_tiles(MODE, a.cout, a.Hout, a.Wout, a.B)) {
-            if constexpr (WM == 2) return launch_cfg<MODE, 4, 1, 1, 1, PRO, EPI, 2, 1, float, 2, 0>(a, st);
-            else return launch_cfg<MODE, 2, 2, 1, 1, PRO, EPI, 2, 1, float, 2, 0>(a, st);
+            if constexpr (WM == 2) return launch_cfg<MODE, 4, 1, 1, 1, PRO, EPI, 2, 1, float>(a, st);
+            else return launch_cfg<MODE, 2, 2, 1, 1, PRO, EPI, 2, 1, float>(a, st);
         }
     }
     // ragged channel counts only occur on first layers (stacked input, 1-channel reference): PRO_MASK variants
     constexpr bool ragged_ok = PRO == PRO_MASK && (MODE == CONV_C3 || MODE == CONV_P1);
-#ifdef GTTS_LEAN      // A/B builds: a code object without the single-pass bf16 / bf16-storage instances (do unlaunched kernels cost time?)
-    if (a.act_bf16 || a.nsplit == 1) return hipErrorInvalidValue;
-#endif
-#ifndef GTTS_LEAN
     if (a.act_bf16) {
         // bf16 storage (BASELINE config 3): single-pass bf16 MFMA only, Grad-TTS op set only (no InstanceNorm-GLU convs)
         if constexpr (PRO != PRO_IGLU && !(MODE == CONV_C3 && EPI == EPI_PLAIN)) {
@@ -1106,26 +896,12 @@ static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
         }
         return hipErrorInvalidValue;
     }
-#endif
-    if constexpr (GTTS_PRIV && MODE == CONV_C3 && PRO != PRO_IGLU) {
-        // bf16x3 3x3 convolutions on whole chunks: private weight slices (same workgroup tiles, waves re-arranged to
-        // 32 channels x 4 rows each): 128 x (4 x 32) as 4 x 1 waves, 64 x (8 x 32) as 2 x 2 waves
-        if (fullc && a.nsplit > 1) {
-            if constexpr (WM == 2) return launch_cfg<MODE, 4, 1, 1, 1, PRO, EPI, 2, 1, float, 4, 1>(a, st);
-            else return launch_cfg<MODE, 2, 2, 1, 1, PRO, EPI, 2, 1, float, 4, 1>(a, st);
-        }
-    }
-#ifdef GTTS_LEAN
-    if (fullc) return launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 2, 1>(a, st);
-    if constexpr (ragged_ok) return launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 2, 0>(a, st);
-#else
     if (fullc)
         return a.nsplit > 1 ? launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 2, 1>(a, st)
                             : launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 1>(a, st);
     if constexpr (ragged_ok)
         return a.nsplit > 1 ? launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 2, 0>(a, st)
                             : launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 0>(a, st);
-#endif
     return hipErrorInvalidValue;
 }
 

@@ -208,48 +208,39 @@ __global__ __launch_bounds__(256, 2) void conv_up4_kernel(const ConvArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ f16 + fp8 form (GTTS_PREC_F16F8)
-// The same tile (64 output channels x 4 input rows x 32 input columns -> 8 x 64 output pixels) in the f16 + fp8 split of common.h:
-// 32-channel chunks, per tap two fp16 k-steps + one fp8 K = 64 step -- 128 MFMA cycles per 32 channels and accumulator against
-// 192 in bf16x3.  EIGHT waves: wave = (output row parity py, input row pair rp, output COLUMN parity px) with accumulators
-// [2 x 32 channels][2 rows] = 4 (64 registers) -- the 16-register weight sets (fp16 k-step 0 / 1 + the fp8 operand) of both column
-// parities do not fit beside eight accumulators; the x tile is still staged once per chunk for all four phases (512 threads).
-// PERSISTENT: the workgroups a CU holds (template parameter NRP below) walk tiles slot, slot + grid, ...  The 64-channel layer has TWO chunks per tile, so a tile-per-
-// workgroup launch never fills its pipeline: measured (round 6, B = 16, T = 1024) 122 us WITHOUT its output stores against 35 us of
-// MFMA time at peak -- every tile pays the first chunk's load latency and its store drain with nothing beside them (one workgroup
-// per CU: 213 registers).  Here the last chunk of a tile issues the next tile's first activation loads and weight fragments, and the
-// epilogue's stores drain under the next tile's staging.
-// Epilogue: the waves of a (py, rp) pair swap half their accumulators through LDS -- wave px = 0 hands over row ni = 1 and takes the
-// partner's row ni = 0 -- so that a lane owns BOTH column parities of one row and stores them as 8 bytes (64 lanes = full lines, as
+// 64 output channels x 2 input rows x 32 input columns -> 4 x 64 output pixels in the f16 + fp8 split of common.h: 32-channel chunks,
+// per tap two fp16 k-steps + one fp8 K = 64 step -- 128 MFMA cycles per 32 channels and accumulator against 192 in bf16x3.  FOUR
+// waves: wave = (output row parity py, output COLUMN parity px) with accumulators [2 x 32 channels][2 rows] = 4 (64 registers) -- the
+// 16-register weight sets (fp16 k-step 0 / 1 + the fp8 operand) of both column parities do not fit beside eight accumulators; the x
+// tile is still staged once per chunk for all four phases.  TWO workgroups per CU (67 KB of LDS, 244 registers): one workgroup's
+// store burst can run beside the other's MFMAs.  (An eight-wave workgroup on 4-row tiles, one per CU, measured equal within noise:
+// 112 / 154 us against 113 / 149; bf16x3 122 / 152.)
+// PERSISTENT: the workgroups walk tiles slot, slot + grid, ...  The 64-channel layer has TWO chunks per tile, so a tile-per-workgroup
+// launch never fills its pipeline: measured (round 6, B = 16, T = 1024) 122 us WITHOUT its output stores against 35 us of MFMA time at
+// peak -- every tile pays the first chunk's load latency and its store drain with nothing beside them.  Here the last chunk of a tile
+// issues the next tile's first activation loads and weight fragments, and the epilogue's stores drain under the next tile's staging.
+// Epilogue: the two waves of a row parity py swap half their accumulators through LDS -- wave px = 0 hands over row ni = 1 and takes
+// the partner's row ni = 0 -- so that a lane owns BOTH column parities of one row and stores them as 8 bytes (64 lanes = full lines, as
 // the bf16x3 kernel does; 4-byte stores at stride 8 measured 217 us against 157 on the 64-channel layer).
 // Per-accumulator order: chunk, stage (ky), tap (kx): k-step 0, k-step 1, fp8 -- one form, so results do not depend on the batch.
-// Where the time goes (GTTS_UP_ABL builds, us per launch, 128- / 64-channel layer, one box): as built 111.6 / 152; no output stores
-// 106.5 / 121; no activation loads 81 / 98; neither 77 / 87.  The 84 MB of input cost 54 us on the 64-channel layer: latency, not
-// bandwidth -- a wave's loads return in order, so the wait for the NEXT TAP's weight fragments (L2 hits, issued after the next chunk's
-// activation loads) is a wait for those HBM loads as well, once per chunk, whatever the prefetch distance in chunks.  Taking the
+// Where the time goes (timing ablations, round 6, us per launch, 128- / 64-channel layer, one box): as built 111.6 / 152; no output
+// stores 106.5 / 121; no activation loads 81 / 98; neither 77 / 87.  The 84 MB of input cost 54 us on the 64-channel layer: latency,
+// not bandwidth -- a wave's loads return in order, so the wait for the NEXT TAP's weight fragments (L2 hits, issued after the next
+// chunk's activation loads) is a wait for those HBM loads as well, once per chunk, whatever the prefetch distance in chunks.  Taking the
 // activation loads out of the MFMA waves' queue needs producer waves, i.e. the MFMA waves in 168 registers (they use 213-244).
-#ifndef GTTS_UP_ABL      // timing ablations (results are WRONG): bit 0 no output stores, bit 1 no activation loads
-#define GTTS_UP_ABL 0
-#endif
-#ifndef GTTS_UP_NRP
-#define GTTS_UP_NRP 1
-#endif
-#ifndef GTTS_UP_PERSIST      // 0: one tile per workgroup (A/B)
-#define GTTS_UP_PERSIST 1
-#endif
-// NRP: input row pairs of a tile.  2: the eight-wave workgroup above, one per CU.  1: FOUR waves (py, px) on a 2-row tile, TWO workgroups
-// per CU (67 KB of LDS, 244 registers): a third more staging per MFMA (4 halo rows for 2); one workgroup's store burst can run beside
-// the other's MFMAs.  Measured equal within noise (113 / 149 us against 112 / 154 on one box; bf16x3 122 / 152); the product uses 1.
+// NRP (input row pairs of a tile) is always 1; it stays a template parameter so that the kernel keeps its name in the per-op tables.
 template <int NRP>
-__global__ __launch_bounds__(256 * NRP, 2) void conv_up4_f8_kernel(const ConvArgs a) {
-    constexpr int UP_TR = 2 * NRP, UP_NPIX = (UP_TR + 2) * UP_HC, NT = 256 * NRP, NWV = 4 * NRP;
+__global__ __launch_bounds__(256, 2) void conv_up4_f8_kernel(const ConvArgs a) {
+    static_assert(NRP == 1, "one input row pair per tile");
+    constexpr int UP_TR = 2, UP_NPIX = (UP_TR + 2) * UP_HC, NT = 256, NWV = 4;
     constexpr int UP8_ITEMS = 4 * UP_NPIX;                                             // (8-channel group of the 32-channel chunk, pixel)
     constexpr int UP8_LITER = (UP8_ITEMS + NT - 1) / NT;
-    __shared__ __attribute__((aligned(16))) u32x4 s_img[2][2][4 * UP_NPIX];            // [buffer][fp16 | fp8 plane][kg / g][pixel] (52 / 35 KB)
-    __shared__ float s_x[NWV * 32 * 64];                                               // the epilogue's exchange area: [wave][register][lane] (64 / 32 KB)
+    __shared__ __attribute__((aligned(16))) u32x4 s_img[2][2][4 * UP_NPIX];            // [buffer][fp16 | fp8 plane][kg / g][pixel] (34 KB)
+    __shared__ float s_x[NWV * 32 * 64];                                               // the epilogue's exchange area: [wave][register][lane] (32 KB)
     __shared__ float s_bias[2][64];                                                    // [tile parity]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, kg_l = lane >> 5;
-    const int py = wave & 1, rp = NRP == 2 ? (wave >> 1) & 1 : 0, px = wave >> NRP;
+    const int py = wave & 1, px = wave >> 1;
 
     const int ncot = a.cout / 64;
     const int ntiles = a.B * a.tiles_x * a.tiles_y * ncot, G = gridDim.x;
@@ -312,11 +303,7 @@ __global__ __launch_bounds__(256 * NRP, 2) void conv_up4_f8_kernel(const ConvArg
         for (int it = 0; it < UP8_LITER; ++it)
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-#if GTTS_UP_ABL & 2      // timing ablation: no activation loads
-                raw[it][i] = (float)(soff & 3);
-#else
                 raw[it][i] = it_off[it] >= 0 ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsx, it_off[it], soff + i * HW * 4, 0)) : 0.f;
-#endif
     };
     auto stage_chunk = [&](int buf) {
         typedef __attribute__((ext_vector_type(2))) int i32x2;
@@ -410,7 +397,7 @@ __global__ __launch_bounds__(256 * NRP, 2) void conv_up4_f8_kernel(const ConvArg
                     i32x8 b8[2];
 #pragma unroll
                     for (int ni = 0; ni < 2; ++ni) {
-                        const int pi = (rp * 2 + ni + 1 + dyr) * UP_HC + 1 + dxc + l31;
+                        const int pi = (ni + 1 + dyr) * UP_HC + 1 + dxc + l31;
                         fa[ni] = __builtin_bit_cast(f16x8, xh_p[pi]);
                         fb[ni] = __builtin_bit_cast(f16x8, xh_p[2 * UP_NPIX + pi]);
                         const u32x4 q0 = x8_p[pi], q1 = x8_p[UP_NPIX + pi];
@@ -438,7 +425,7 @@ __global__ __launch_bounds__(256 * NRP, 2) void conv_up4_f8_kernel(const ConvArg
         // ---- epilogue: half exchange, then acc 2^-S + bias as 8-byte stores.  (The exchange area is this tile's alone until the next
         // tile's first chunk barrier; the barrier below also says that every wave is done with the images.)
         {
-            float *mine = s_x + ((wave & (2 * NRP - 1)) * 2 + px) * (32 * 64) + lane;
+            float *mine = s_x + (py * 2 + px) * (32 * 64) + lane;
 #pragma unroll
             for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
@@ -447,10 +434,10 @@ __global__ __launch_bounds__(256 * NRP, 2) void conv_up4_f8_kernel(const ConvArg
         lds_barrier();
         const __amdgpu_buffer_rsrc_t rso = uniform_rsrc(reinterpret_cast<float *>(a.out) + (size_t)cur.b * a.cout * HWo, a.cout * HWo * 4);
         const int ix = cur.x0 + l31;
-        const int iy = cur.y0 + rp * 2 + px;                 // this wave stores row ni = px
+        const int iy = cur.y0 + px;                          // this wave stores row ni = px
         if (iy < a.Hin && ix < a.Win) {
             typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-            const float *theirs = s_x + ((wave & (2 * NRP - 1)) * 2 + (px ^ 1)) * (32 * 64) + lane;
+            const float *theirs = s_x + (py * 2 + (px ^ 1)) * (32 * 64) + lane;
             const int oy = 2 * iy + py;
             const int voff = (oy * a.Wout + 2 * ix + 4 * kg_l * HWo) * 4;
 #pragma unroll
@@ -464,9 +451,6 @@ __global__ __launch_bounds__(256 * NRP, 2) void conv_up4_f8_kernel(const ConvArg
                     u32x2 v;
                     v[0] = __builtin_bit_cast(unsigned, px ? oth : own);
                     v[1] = __builtin_bit_cast(unsigned, px ? own : oth);
-#if GTTS_UP_ABL & 1      // timing ablation: no output stores
-                    if (own != 12345.678f) continue;
-#endif
                     __builtin_amdgcn_raw_buffer_store_b64(v, rso, voff, (cur.cot * 64 + ch) * HWo * 4, GTTS_OUT_NT);
                 }
         }
@@ -490,10 +474,10 @@ bool conv_up4_eligible(const ConvArgs &a) {
 
 // GTTS_PREC_F16F8: Upsample layers whose weights the plan packs in the f16 + fp8 format (whole 32-channel chunks)
 bool conv_up4_f16f8_ok(int cin, int cout) {
-    return GTTS_UP_F16F8 && cin % 32 == 0 && cin >= 32 && cout % 64 == 0 && (cout <= 64 || cout % 128 == 0);
+    return cin % 32 == 0 && cin >= 32 && cout % 64 == 0 && (cout <= 64 || cout % 128 == 0);
 }
 
-const char *conv_up4_f8_name() { return GTTS_UP_NRP == 1 ? "gtts::conv_up4_f8_kernel<1>" : "gtts::conv_up4_f8_kernel<2>"; }
+const char *conv_up4_f8_name() { return "gtts::conv_up4_f8_kernel<1>"; }
 
 hipError_t launch_conv_up4(const ConvArgs &a_in, hipStream_t st) {
     ConvArgs a = a_in;
@@ -502,11 +486,9 @@ hipError_t launch_conv_up4(const ConvArgs &a_in, hipStream_t st) {
     a.tiles_y = (a.Hin + UP_TR - 1) / UP_TR;
     const long grid = (long)a.B * a.tiles_x * a.tiles_y * (a.cout / 64);
     if (grid <= 0 || grid > 0x7fffffffL) return hipErrorInvalidValue;
-    if (a.f16f8 && conv_up4_f16f8_ok(a.cin, a.cout) && conv_up4_ws_ok(a.cin, a.cout)) return launch_conv_up4_ws(a, st);
     if (a.f16f8 && conv_up4_f16f8_ok(a.cin, a.cout)) {
-        // persistent: GTTS_UP_NRP = 2: one eight-wave workgroup per CU; 1: two four-wave workgroups per CU on 2-row tiles
-        constexpr int NRP = GTTS_UP_NRP;
-        a.tiles_y = (a.Hin + 2 * NRP - 1) / (2 * NRP);
+        // persistent: two four-wave workgroups per CU on 2-row tiles
+        a.tiles_y = (a.Hin + 1) / 2;
         const long tiles = (long)a.B * a.tiles_x * a.tiles_y * (a.cout / 64);
         if (tiles > 0x7fffffffL) return hipErrorInvalidValue;
         static std::atomic<int> n_cu[64];
@@ -517,7 +499,7 @@ hipError_t launch_conv_up4(const ConvArgs &a_in, hipStream_t st) {
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
             n_cu[dev].store(cus, std::memory_order_relaxed);
         }
-        hipLaunchKernelGGL(conv_up4_f8_kernel<NRP>, dim3((unsigned)std::min<long>(tiles, GTTS_UP_PERSIST ? cus * (3 - NRP) : tiles)), dim3(256 * NRP), 0, st, a);
+        hipLaunchKernelGGL(conv_up4_f8_kernel<1>, dim3((unsigned)std::min<long>(tiles, (long)cus * 2)), dim3(256), 0, st, a);
     } else {
         hipLaunchKernelGGL(conv_up4_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
     }

@@ -33,15 +33,8 @@
 // GTTS_WS_TRACE (diagnostic builds only, -DGTTS_DIAG): per-wave s_memtime sums of one layer (cin == cout == GTTS_TRACE_CIN)
 // read back with gtts_debug_trace_ws().  Consumer waves: [0] barrier wait, [1] chunk loops, [2] tile epilogues, [3] items, [4] total.
 // Producer waves: [0] barrier wait, [1] staging (load wait + transform + LDS write), [2] re-request (+ tile setup), [3] finish_tile.
-// GTTS_WS_EXP (diagnostic builds only): timing ablations, results are WRONG.  1: the consumers never reload weights,
-// 2: the producers never re-request activations, 3: the producers skip transform + LDS write, 4: the consumers never re-read
-// B fragments, 5: no MFMAs, 6: no output stores, 7: no weight loads in the first three taps of a tile (f16 + fp8 form: 1, 4, 5, 6 in the consumer loop / epilogue; 2, 3 are common)
 #ifndef GTTS_DIAG
 #undef GTTS_WS_TRACE
-#undef GTTS_WS_EXP
-#endif
-#ifndef GTTS_WS_EXP
-#define GTTS_WS_EXP 0
 #endif
 #ifndef GTTS_WS_TRACE
 #define GTTS_WS_TRACE 0
@@ -84,49 +77,12 @@ namespace gtts {
 #ifndef GTTS_WS64_LEAD
 #define GTTS_WS64_LEAD 96
 #endif
-// the 64-channel f16 + fp8 tile (W64): sweep pipelining (0: a sweep reads its A fragments and first B rows itself; 1: the previous sweep
-// prefetches them at input row GTTS_W64_PFROW; 2: A fragments only), B rows fetched GTTS_W64_DIST rows ahead, ring refill after row
-// GTTS_W64_DMAROW (>= 2: every A fragment of the sweep has been consumed by then)
 // cache policy of the f16 + fp8 epilogue's output stores (A/B builds): 0 plain, 2 nt (streaming), 16 sc1 (write-through), 17 sc0 sc1
 #ifndef GTTS_WS_EPI_AUX
 #define GTTS_WS_EPI_AUX 2      // measured (same box, ms per U-Net call): plain 6.432-6.457, nt 6.351, sc1 6.439, sc0 sc1 6.427
-#endif
-#ifndef GTTS_W64_PF
-#define GTTS_W64_PF 0
-#endif
-#ifndef GTTS_W64_DIST
-#define GTTS_W64_DIST 2
-#endif
-// cache policy of the f16 + fp8 epilogue's output stores (A/B builds): 0 plain, 2 nt (streaming), 16 sc1 (write-through), 17 sc0 sc1
-#ifndef GTTS_WS_EPI_AUX
-#define GTTS_WS_EPI_AUX 2      // measured (same box, ms per U-Net call): plain 6.432-6.457, nt 6.351, sc1 6.439, sc0 sc1 6.427
-#endif
-#ifndef GTTS_W64_PFROW
-#define GTTS_W64_PFROW 5
-#endif
-#ifndef GTTS_W64_DMAROW
-#define GTTS_W64_DMAROW 2
 #endif
 #ifndef GTTS_WS_LEAD
 #define GTTS_WS_LEAD 160
-#endif
-// De-phased tile epilogues.  Persistent workgroups walk equal tiles in lock-step, so all 256 CUs reach their tile epilogue together
-// and the chip's write path (6.0-6.8 TB/s: 13-14 B/clk per CU when every CU stores, 28 at 128 CUs, 33 / 50 at 64 with dword / 16-byte
-// stores -- tools/probe/mem_probe.hip, profiles/r06_mem_probe.txt) bounds it: 10.7k cycles per 128-channel tile while the MFMAs idle.
-// With GTTS_WS_DEPHASE = P > 1 phase groups the workgroups of group g (both halves / all quarters of every XCD) start
-// g x (bytes a workgroup stores per tile) / GTTS_WS_DEPHASE_BPC cycles late: meant to leave only 1 / P of the CUs storing at any time.
-// MEASURED (round 6, profiles/r06_dephase_trace.txt): it does not hold -- the late group catches up (level 0: started 2.9k cycles
-// late, its first epilogue begins 1.1k after the early group's; the HBM-bound launch re-locks the phases) or stays 3.4k behind where
-// an epilogue lasts 9k (level 2), and per-tile epilogue time does not move (5 277 vs 5 257; 8 867-9 153 vs 9 277 cycles):
-// 153.3 vs 153.1 us on the dominant kernel, 6.52-6.56 ms per call with 0 / 2 / 4 groups.  Kept buildable, OFF.
-#ifndef GTTS_WS_DEPHASE
-#define GTTS_WS_DEPHASE 0
-#endif
-#ifndef GTTS_WS_DEPHASE_BPC
-#define GTTS_WS_DEPHASE_BPC 28
-#endif
-#ifndef GTTS_WS_DEPHASE_MIN
-#define GTTS_WS_DEPHASE_MIN 2
 #endif
 template <int WM, int WN, int MF, int NF, int NKGT = 2>
 struct WsCfg {
@@ -150,11 +106,9 @@ struct WsCfg {
 };
 
 // nsplit planes (1: hi; 2: hi + lo, or fp16 hi + fp8 cross-term operands) of nkg 8-channel groups per ring slot
-// wq16: 16-byte units of the weight ring (the f16 + fp8 64-channel tile keeps two (chunk, column stage) weight blocks in LDS)
-constexpr int WS64_WST16 = 3 * 64 * 2 * 4;      // one block: [split][tap = ky][kg / g][64 couts] x 16 B = 24 KB
-static inline size_t ws_smem_bytes(int npix, int nsplit, int ring, int cin, int pro, int cout, int mf, int ncw, int nkg = 2, int wq16 = 0) {
+static inline size_t ws_smem_bytes(int npix, int nsplit, int ring, int cin, int pro, int cout, int mf, int ncw, int nkg = 2) {
     const size_t cpad = (size_t)((cin + 31) / 32) * 32;
-    return (size_t)ring * nsplit * nkg * npix * 16 + (size_t)wq16 * 16 + (pro == PRO_GN ? (size_t)2 * 3 * cpad * 4 : 0) +
+    return (size_t)ring * nsplit * nkg * npix * 16 + (pro == PRO_GN ? (size_t)2 * 3 * cpad * 4 : 0) +
            (size_t)2 * ncw * mf * 8 * 4 + (size_t)((cout + 63) / 64) * 64 * 4;
 }
 
@@ -181,21 +135,10 @@ void conv3x3_ws_kernel(const ConvArgs a) {
     const int WBLK16 = 3 * MTP * 2 * NKG;
     static_assert(PRO == PRO_MASK || PRO == PRO_GN, "Block prologues only");
 
-    // W64 (GTTS_W64_RING builds only -- measured, not adopted: same box, us per level-0 64 -> 64 launch with the GroupNorm / mask
-    // prologue: 266.4 / 258.5 for the register-load loop below against 274.6-275.4 / 259.8-262.5 for this form; ups.1.0.b1 189 vs 193):
-    // the 12-wave 64-channel tile of the f16 + fp8 form.  Its weights do NOT come through the vector L1 tap by tap: the CU's L1
-    // returns loads in order, and behind the producers' HBM-miss halo loads an L2-hit fragment load waits ~1000-1500 cycles at 32 KB in
-    // flight, ~3000 at this tile's 52 KB (tools/probe/mem_probe.hip; round 5: chunk loop 10.25k cycles for 5.76k of MFMA issue, 7.05k
-    // without weight reloads).  Instead every consumer wave streams its block's A fragments of one (chunk, COLUMN stage) -- the three taps
-    // (ky = 0..2) of one kx -- into 12 KB of LDS of its own with LDS-DMA (buffer_load ... lds: no registers, a whole stage = 1920 MFMA
-    // cycles ahead of their use) and reads them from there; see the consumer loop.  Column stages also let a B fragment serve three taps.
-    constexpr bool W64 = GTTS_W64_RING && F8 && C::NCWP != C::NCW;
-    constexpr int WQ16 = W64 ? 2 * WS64_WST16 : 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u32x4 *s_img = reinterpret_cast<u32x4 *>(smem);                      // [RING][split][kg][NPIX]
-    [[maybe_unused]] u32x4 *s_wq = s_img + RING * IMG16;                 // W64: [4 consumer waves][12 pieces][64 lanes] A fragments
     const int cpad = a.nchunk * CH;
-    float *s_par = reinterpret_cast<float *>(s_img + RING * IMG16 + WQ16);   // PRO_GN: [2 (tile parity)][3][cpad] scale, shift, time bias
+    float *s_par = reinterpret_cast<float *>(s_img + RING * IMG16);      // PRO_GN: [2 (tile parity)][3][cpad] scale, shift, time bias
     float *s_red = s_par + (PRO == PRO_GN ? 2 * 3 * cpad : 0);           // [2 (tile parity)][NCW waves][MF][4 octets][2]
     float *s_epi = s_red + 2 * NCW * MF * 8;                             // [cout] bias of every output channel, written once (prologue)
 
@@ -239,14 +182,6 @@ void conv3x3_ws_kernel(const ConvArgs a) {
     unsigned long long tr_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned long long tr_entry = WT_NOW();
 #endif
-    if (GTTS_WS_DEPHASE > 1 && G >= 8 * GTTS_WS_DEPHASE && my_tiles >= GTTS_WS_DEPHASE_MIN) {
-        const int grp = (blockIdx.x >> 3) % GTTS_WS_DEPHASE;          // blockIdx % 8 is the XCD: every XCD has CUs in every group
-        if (grp != 0) {
-            const long long wait = (long long)grp * (MT * TR * 32 * AB / GTTS_WS_DEPHASE_BPC) * 2 / GTTS_WS_DEPHASE;
-            const long long t0 = (long long)__builtin_amdgcn_s_memtime();
-            while ((long long)__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(16);
-        }
-    }
     if (wave < NCWP) {
         // =================================================================================== CONSUMERS
         __builtin_amdgcn_s_setprio(3);         // MFMA issue wins the per-SIMD arbitration against the producers' VALU stream
@@ -268,7 +203,6 @@ void conv3x3_ws_kernel(const ConvArgs a) {
         // B-fragment base of this lane inside a plane (16-byte units): rows wn*NF.., column l31
         const int x_lane = kg_l * NPIX + wn * NF * HC + l31;
         auto wload_one = [&](bf16x8 (&w)[MF], int mi, int sp, int chunk, int stage, int tap, int cot) {
-            if (GTTS_WS_EXP == 1 && (chunk | stage | tap) != 0) return;
             const int blk = (chunk * 3 + stage) * ncotp + cot / cpp;
             const int w_voff = w_lane + (cot % cpp) * MT * 16;
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(
@@ -276,7 +210,6 @@ void conv3x3_ws_kernel(const ConvArgs a) {
             w[mi] = __builtin_bit_cast(bf16x8, v);
         };
         auto wload1 = [&](bf16x8 (&w)[MF], int sp, int chunk, int stage, int tap, int cot) {
-            if (GTTS_WS_EXP == 1 && (chunk | stage | tap) != 0) return;
             const int blk = (chunk * 3 + stage) * ncotp + cot / cpp;
             const int w_voff = w_lane + (cot % cpp) * MT * 16;
 #pragma unroll
@@ -451,7 +384,6 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                                 const int voff = (oy * a.Wout + oxx + 4 * kg_l * HW) * AB;
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) {
-                                    if (GTTS_WS_EXP == 6 && v[i] != 12345.678f) continue;      // (ablation: no output stores)
                                     if constexpr (AB == 4 && GTTS_WS_EPI_AUX != 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v[i]), rs_out, voff, soff + i * HW * AB, GTTS_WS_EPI_AUX);
                                     else st_act<AT>(v[i], rs_out, voff, soff + i * HW * AB);
                                 }
@@ -474,170 +406,6 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                     }
                 }
             };
-            if constexpr (W64) {
-                // ------------------------------------------------------ 64-channel tile: weights from a private LDS ring, column stages
-                // An item is three COLUMN stages j = kx = 0..2 of two sweeps each; one workgroup barrier per item (the image hand-over),
-                // nothing else between waves.  Every consumer wave keeps ITS 32-channel block's weights of one (chunk, kx) -- twelve
-                // A fragments of 1 KB: (ky, k-step) x 6 for the fp16 plane, (ky, half) x 6 for the fp8 plane -- in 12 KB of LDS of its own and
-                // refills each half BEHIND its own reads: once the six fp16 fragments of stage s are in registers (their first MFMAs
-                // have issued) the wave requests the fp16 fragments of stage s + 1 into the same 6 KB by LDS-DMA, likewise the fp8 half in
-                // the fp8 sweep -- a whole stage (1920 MFMA cycles) ahead of their use, no registers, no other wave involved (the two
-                // bands of a block each fetch their copy: L2 hits).  s_waitcnt vmcnt(6) before a sweep's fragment reads = "everything but
-                // the six pieces requested last has landed" (loads return in order).  At a tile's end the two pending refills are
-                // drained with vmcnt(0) BEFORE the epilogue's 80 stores enter the queue, and the first stage of the next tile skips its
-                // two waits (a counted wait would otherwise sit behind those stores).
-                // (History, same box: weights as per-tap register loads through the L1 303 / 286 us per level-0 launch (GroupNorm / mask
-                // prologue); one shared two-block ring with all twelve waves in three barriers per item 303 / 286 -- consumers and producers
-                // then wait for each other's slowest third; the shared ring with a consumer-only arrival counter 279 / 260.)
-                // Sweeps: input rows R = 0..6 of the wave's band, one B fragment (pair) per row fetched two rows ahead and used by every
-                // (output row r = R - ky, ky) pair: 84 + 36 fragment reads per item and wave instead of 180 + 36 weight loads.
-                // Order per accumulator (every band, every batch size -- the small-launch form does not take 64-channel layers in
-                // f16 + fp8): chunk, kx; then ky 0..2: k-step 0, k-step 1; then ky 0..2: fp8.
-                typedef __attribute__((address_space(3))) void *lds_vp;
-                u32x4 *wq = s_wq + wave * (WS64_WST16 / 2);            // this wave's 12 KB: pieces 0..5 fp16 (ky * 2 + k-step), 6..11 fp8 (ky * 2 + half)
-                const int src16 = (kg_l * 64 + fm0 + l31) * 16;       // lane's byte offset inside a (tap, kg pair) segment of the packed fp16 plane ...
-                const int src8 = ((3 * NKG + kg_l * 2) * 64 + fm0 + l31) * 16;   // ... and of the fp8 plane (g = kg_l * 2 + half)
-                auto dma16 = [&](int chunk, int stage) {              // fp16 A fragments of (chunk, kx = stage): piece = ky * 2 + k-step
-                    const int so = (chunk * 3 + stage) * (WS64_WST16 * 16);
-#pragma unroll
-                    for (int p = 0; p < 6; ++p)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_vp)(wq + p * 64), 16, src16, so + (((p >> 1) * NKG + (p & 1) * 2) * 64) * 16, 0, 0);
-                };
-                auto dma8 = [&](int chunk, int stage) {               // fp8 A fragments: piece = 6 + ky * 2 + half
-                    const int so = (chunk * 3 + stage) * (WS64_WST16 * 16);
-#pragma unroll
-                    for (int p = 0; p < 6; ++p)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_vp)(wq + (6 + p) * 64), 16, src8, so + (((p >> 1) * NKG + (p & 1)) * 64) * 16, 0, 0);
-                };
-                // The six sweeps of an item are software-pipelined: while a sweep works on its last input rows (R == 5) it reads the NEXT
-                // sweep's six A fragments and first two B rows (behind a vmcnt(6) for the refill they come from), so a sweep starts with
-                // its operands in registers -- without that every sweep opened on an exposed LDS round trip (A + two B rows, ~300-400
-                // cycles, six times per item: level-0 launches 273 / 267 us).  Only the first sweep of an item reads its two B rows after the
-                // item barrier (the image is not complete before it).
-                u32x4 Acur[6], Anext[6], Bn[GTTS_W64_DIST][2];
-                auto readA = [&](u32x4 (&A)[6], int piece0) {
-#pragma unroll
-                    for (int p = 0; p < 6; ++p) A[p] = wq[(piece0 + p) * 64 + lane];
-                };
-                if (nitems > 0) {
-                    dma16(0, 0);
-                    dma8(0, 0);
-                    if (GTTS_W64_PF != 0) {
-                        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                        readA(Acur, 0);
-                    }
-                    if (GTTS_WS_EXP == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (ablation: the ring is filled once)
-                }
-                for (int i = 0; i < nitems; ++i) {
-                    const int par = k & 1;
-                    const u32x4 *xh_p = s_img + slot * IMG16 + xl0;                                  // fp16 plane, k-step 0 (k-step 1: + 2 NPIX)
-                    const u32x4 *x8_p = s_img + slot * IMG16 + PLANE16 + xl0 + kg_l * NPIX;          // fp8 plane: g = 2 kg_l (second half: + NPIX)
-                    slot = slot + 1 == RING ? 0 : slot + 1;
-                    const bool last_c = cc + 1 == nchunk;
-                    [[maybe_unused]] const unsigned long long tw0 = WT_NOW();
-                    lds_barrier();                  // image of item i is complete; everybody is done with item i - 1
-                    [[maybe_unused]] const unsigned long long tw1 = WT_NOW();
-                    WT_ADD(0, tw1, tw0);
-                    auto readB = [&](u32x4 (&b)[2], int R, int j, bool f8s) {      // the B fragment (pair) of input row R at column shift j
-                        if (!f8s) { b[0] = xh_p[R * HC + j]; b[1] = xh_p[2 * NPIX + R * HC + j]; }
-                        else { b[0] = x8_p[R * HC + j]; b[1] = x8_p[NPIX + R * HC + j]; }
-                    };
-                    if (GTTS_W64_PF == 1) {
-#pragma unroll
-                        for (int d = 0; d < GTTS_W64_DIST; ++d) readB(Bn[d], d, 0, false);
-                    }
-                    if (cc == 0) {
-#pragma unroll
-                        for (int r = 0; r < FR; ++r)
-#pragma unroll
-                            for (int e = 0; e < 16; ++e) facc[r][e] = 0.f;
-                    }
-                    const bool fresh = i != 0 && cc == 0;             // first stage after an epilogue: both ring halves landed before it
-#pragma unroll
-                    for (int s = 0; s < 6; ++s) {
-                        const int j = s >> 1;
-                        const bool f8s = (s & 1) != 0;
-                        const int nch = j == 2 ? (last_c ? 0 : cc + 1) : cc, nst = j == 2 ? 0 : j + 1;      // the next stage (after the last item: block 0 again, never read)
-                        u32x4 Bw[FR + 2][2];
-                        if (GTTS_W64_PF == 0) {
-                            [[maybe_unused]] const unsigned long long tv0 = WT_NOW();
-                            if (GTTS_WS_EXP != 1 && !(fresh && j == 0)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                            WT_ADD(7, WT_NOW(), tv0);
-                            readA(Acur, f8s ? 6 : 0);
-                        }
-                        if (GTTS_W64_PF == 1) {
-#pragma unroll
-                            for (int d = 0; d < GTTS_W64_DIST; ++d) { Bw[d][0] = Bn[d][0]; Bw[d][1] = Bn[d][1]; }
-                        } else {
-#pragma unroll
-                            for (int d = 0; d < GTTS_W64_DIST; ++d) readB(Bw[d], d, j, f8s);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int R = 0; R < FR + 2; ++R) {
-                            if (R + GTTS_W64_DIST < FR + 2) readB(Bw[R + GTTS_W64_DIST], R + GTTS_W64_DIST, j, f8s);
-                            if (GTTS_W64_PF != 0 && R == GTTS_W64_PFROW) {
-                                // operands of the next sweep: its A fragments come from the ring half refilled one stage ago
-                                [[maybe_unused]] const unsigned long long tv0 = WT_NOW();
-                                if (GTTS_WS_EXP != 1 && !(fresh && s == 0)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-                                WT_ADD(7, WT_NOW(), tv0);
-                                readA(Anext, f8s ? 0 : 6);
-                                if (GTTS_W64_PF == 1 && s < 5) {
-#pragma unroll
-                                    for (int d = 0; d < GTTS_W64_DIST; ++d) readB(Bn[d], d, (s + 1) >> 1, !f8s);
-                                }
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            if (!f8s) {
-#pragma unroll
-                                for (int st = 0; st < 3; ++st)
-                                    if (R - st >= 0 && R - st < FR)
-                                        facc[R - st] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, Acur[st * 2]), __builtin_bit_cast(f16x8, Bw[R][0]), facc[R - st], 0, 0, 0);
-#pragma unroll
-                                for (int st = 0; st < 3; ++st)
-                                    if (R - st >= 0 && R - st < FR)
-                                        facc[R - st] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, Acur[st * 2 + 1]), __builtin_bit_cast(f16x8, Bw[R][1]), facc[R - st], 0, 0, 0);
-                            } else {
-                                i32x8 b8;
-                                b8[0] = (int)Bw[R][0][0]; b8[1] = (int)Bw[R][0][1]; b8[2] = (int)Bw[R][0][2]; b8[3] = (int)Bw[R][0][3];
-                                b8[4] = (int)Bw[R][1][0]; b8[5] = (int)Bw[R][1][1]; b8[6] = (int)Bw[R][1][2]; b8[7] = (int)Bw[R][1][3];
-#pragma unroll
-                                for (int st = 0; st < 3; ++st)
-                                    if (R - st >= 0 && R - st < FR) {
-                                        i32x8 a8;
-                                        a8[0] = (int)Acur[st * 2][0]; a8[1] = (int)Acur[st * 2][1]; a8[2] = (int)Acur[st * 2][2]; a8[3] = (int)Acur[st * 2][3];
-                                        a8[4] = (int)Acur[st * 2 + 1][0]; a8[5] = (int)Acur[st * 2 + 1][1]; a8[6] = (int)Acur[st * 2 + 1][2]; a8[7] = (int)Acur[st * 2 + 1][3];
-                                        facc[R - st] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, facc[R - st], 0, 0, 0, 0, 0, 0);
-                                    }
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            // every A fragment of this sweep has been consumed by an issued MFMA (ky = 2 first at R = 2): its ring half may be refilled
-                            if (R == GTTS_W64_DMAROW && GTTS_WS_EXP != 1) { if (!f8s) dma16(nch, nst); else dma8(nch, nst); }
-                        }
-                        if (GTTS_W64_PF != 0) {
-#pragma unroll
-                            for (int p = 0; p < 6; ++p) Acur[p] = Anext[p];
-                        }
-                    }
-                    [[maybe_unused]] const unsigned long long tw2 = WT_NOW();
-                    WT_ADD(1, tw2, tw1);
-                    WT_ADD(3, 1ull, 0ull);
-                    if (!last_c) { ++cc; continue; }
-#if GTTS_WS_TRACE
-                    if (tr_on) {      // ([7]: cycles in the sweeps' vmcnt waits)
-                        if (k == 0) tr_sum[5] = tw2 - tr_entry;
-                        tr_sum[6] = tw2 - tr_entry;
-                    }
-#endif
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next tile's first two refills land before the stores queue up behind them
-                    WT_ADD(7, WT_NOW(), tw2);
-                    f8_epilogue(par);
-                    cc = 0;
-                    ++k;
-                    tl = decode(k);
-                    WT_ADD(2, WT_NOW(), tw2);
-                }
-            } else
             for (int i = 0; i < nitems; ++i) {
                 [[maybe_unused]] const unsigned long long tw0 = WT_NOW();
                 lds_barrier();                                      // image of item i is complete; everybody is done with item i - 1
@@ -654,15 +422,10 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                     if (u < 9) wload(w, cc, u / 3, u % 3, tl.cot);
                     else wload(w, ncn, (u - 9) / 3, (u - 9) % 3, tl.cot);
                 };
-                // (ablation 7: taps 0..2 of every tile but the first run on stale weight registers -- what a tile start that issues no
-                // vector load behind the previous tile's stores for three taps would gain)
-                const bool abl7 = GTTS_WS_EXP == 7 && i != 0 && cc == 0;
                 if (cc == 0) {
                     // a tile starts cold: its first weight sets are requested here (one exposed round trip per tile)
-                    if (!abl7) {
 #pragma unroll
                     for (int q = 0; q + 1 < NWS; ++q) wload_tap(wq[q], q);
-                    }
 #pragma unroll
                     for (int r = 0; r < FR; ++r)
 #pragma unroll
@@ -689,7 +452,7 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                         const bool last_t = st == 2 && j == 2;
                         const int nst = j == 2 ? st + 1 : st, nj = j == 2 ? 0 : j + 1;      // next tap inside the chunk
                         // the set of tap + NWS - 1, NWS - 1 taps ahead
-                        if (GTTS_WS_EXP != 1 && !(abl7 && st == 0 && j < 2)) wload_tap(wq[NWS - 1], st * 3 + j + NWS - 1);
+                        wload_tap(wq[NWS - 1], st * 3 + j + NWS - 1);
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                         for (int s2 = 0; s2 < NS; ++s2) {
@@ -702,13 +465,6 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                             }
                             __builtin_amdgcn_sched_barrier(0);
                             const int r = s2 % FR;
-#if GTTS_WS_EXP == 5 && defined(__HIP_DEVICE_COMPILE__)
-                            // (diagnostic builds, device pass only: on the host pass an asm with a "v" operand silently drops the kernel's stub)
-                            if (s2 < FR) asm volatile("" ::"v"(wq[0].a), "v"(fa[r]));
-                            else if (s2 < 2 * FR) asm volatile("" ::"v"(wq[0].b), "v"(fb[r]));
-                            else asm volatile("" ::"v"(wq[0].w8), "v"(f8l[r]), "v"(f8h[r]));
-                            if (false)
-#endif
                             if (s2 < FR) {
                                 facc[r] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wq[0].a, fa[r], facc[r], 0, 0, 0);
                             } else if (s2 < 2 * FR) {
@@ -731,10 +487,9 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                 WT_ADD(3, 1ull, 0ull);
                 if (!last_c) { ++cc; continue; }
 #if GTTS_WS_TRACE
-                if (tr_on) {      // [5] start of the first, [6] of the last tile epilogue since kernel entry, [7] phase group
+                if (tr_on) {      // [5] start of the first, [6] of the last tile epilogue since kernel entry
                     if (k == 0) tr_sum[5] = tw2 - tr_entry;
                     tr_sum[6] = tw2 - tr_entry;
-                    tr_sum[7] = (blockIdx.x >> 3) % (GTTS_WS_DEPHASE > 1 ? GTTS_WS_DEPHASE : 1);
                 }
 #endif
                 f8_epilogue(par);
@@ -780,18 +535,11 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                     const bool last_t = st == 2 && j == 2;
                     const int nst = j == 2 ? st + 1 : st, nj = j == 2 ? 0 : j + 1;      // next tap inside the chunk
                     bf16x8 whn[MF], xl[NF], xhn[NF];
-                    if (GTTS_WS_EXP == 1) {
-#pragma unroll
-                        for (int mi = 0; mi < MF; ++mi) whn[mi] = wh[mi];
-                    }
                     // ---- pass 1
                     if (last_t) wload1(whn, 0, ncn, 0, 0, tl.cot); else wload1(whn, 0, cc, nst, nj, tl.cot);
                     if (NSPLIT > 1) {
 #pragma unroll
-                        for (int ni = 0; ni < NF; ++ni) {
-                            if (GTTS_WS_EXP == 4) xl[ni] = xh[ni];
-                            else xl[ni] = *reinterpret_cast<const bf16x8 *>(xl_p + (ni + st) * HC + j);
-                        }
+                        for (int ni = 0; ni < NF; ++ni) xl[ni] = *reinterpret_cast<const bf16x8 *>(xl_p + (ni + st) * HC + j);
                         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                         for (int mi = 0; mi < MF; ++mi) {
@@ -812,10 +560,7 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                             acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[mi], xh[ni], acc[mi][ni], 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);
                     // ---- pass 3 (single-pass bf16: nothing left but the prefetch)
-                    if (GTTS_WS_EXP == 4) {
-#pragma unroll
-                        for (int ni = 0; ni < NF; ++ni) xhn[ni] = xh[ni];
-                    } else if (last_t) {
+                    if (last_t) {
                         if (RING >= 3) {
 #pragma unroll
                             for (int ni = 0; ni < NF; ++ni) xhn[ni] = *reinterpret_cast<const bf16x8 *>(xn_p + ni * HC);
@@ -933,7 +678,6 @@ void conv3x3_ws_kernel(const ConvArgs a) {
             if (++lc == nchunk) { lc = 0; ++lk; }
         };
         auto load_one = [&](Raw &R, int voff, int it, int i) {
-            if (GTTS_WS_EXP == 2) return;
             if constexpr (AB == 4) R.x[it][i] = __builtin_amdgcn_raw_buffer_load_b128(Lc.rs, voff, Lc.soff + i * HW * AB, 0);
             else R.x[it][i] = __builtin_amdgcn_raw_buffer_load_b64(Lc.rs, voff, Lc.soff + i * HW * AB, 0);
         };
@@ -970,42 +714,40 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                 [[maybe_unused]] float vprev[4];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
-                    if (GTTS_WS_EXP != 3) {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            float v;
-                            if constexpr (AB == 4) {
-                                const unsigned u = R.x[it][i][j];
-                                v = __builtin_bit_cast(float, u);
+                    for (int j = 0; j < 4; ++j) {
+                        float v;
+                        if constexpr (AB == 4) {
+                            const unsigned u = R.x[it][i][j];
+                            v = __builtin_bit_cast(float, u);
+                        } else {
+                            const unsigned u = R.x[it][i][j >> 1];
+                            v = __builtin_bit_cast(float, (j & 1) ? (u & 0xffff0000u) : (u << 16));
+                        }
+                        const float m = m_cur[it][j];
+                        if constexpr (PRO == PRO_MASK) {
+                            v = mul_mask0(v, m);                 // (m == 0 also marks frames outside the tensor: NaN-proof, common.h)
+                        } else {
+                            const float y = fmaf(v, sc[i], sh[i]);
+                            v = mul_mask0(fmaf(mish_f(y), m, tb[i]), m);
+                        }
+                        if constexpr (F8) {
+                            const _Float16 h = (_Float16)v;
+                            fh[j][i] = h;
+                            if (i & 1) {        // channels (i - 1, i) of frame j -> two fp8 bytes of word i >> 2, half (i >> 1) & 1
+                                vmax = f8_range_track(vmax, vprev[j], v);
+                                if (i & 2) f8_cross_pair<true>(vprev[j], v, fh[j][i - 1], h, lw[j][i >> 2], xw[j][i >> 2]);
+                                else { lw[j][i >> 2] = 0; xw[j][i >> 2] = 0; f8_cross_pair<false>(vprev[j], v, fh[j][i - 1], h, lw[j][i >> 2], xw[j][i >> 2]); }
                             } else {
-                                const unsigned u = R.x[it][i][j >> 1];
-                                v = __builtin_bit_cast(float, (j & 1) ? (u & 0xffff0000u) : (u << 16));
+                                vprev[j] = v;
                             }
-                            const float m = m_cur[it][j];
-                            if constexpr (PRO == PRO_MASK) {
-                                v = mul_mask0(v, m);                 // (m == 0 also marks frames outside the tensor: NaN-proof, common.h)
-                            } else {
-                                const float y = fmaf(v, sc[i], sh[i]);
-                                v = mul_mask0(fmaf(mish_f(y), m, tb[i]), m);
-                            }
-                            if constexpr (F8) {
-                                const _Float16 h = (_Float16)v;
-                                fh[j][i] = h;
-                                if (i & 1) {        // channels (i - 1, i) of frame j -> two fp8 bytes of word i >> 2, half (i >> 1) & 1
-                                    vmax = f8_range_track(vmax, vprev[j], v);
-                                    if (i & 2) f8_cross_pair<true>(vprev[j], v, fh[j][i - 1], h, lw[j][i >> 2], xw[j][i >> 2]);
-                                    else { lw[j][i >> 2] = 0; xw[j][i >> 2] = 0; f8_cross_pair<false>(vprev[j], v, fh[j][i - 1], h, lw[j][i >> 2], xw[j][i >> 2]); }
-                                } else {
-                                    vprev[j] = v;
-                                }
-                            } else if constexpr (NSPLIT > 1) {
-                                __bf16 h, l;
-                                split_bf16(v, h, l);
-                                vh[j][i] = h;
-                                vl[j][i] = l;
-                            } else {
-                                vh[j][i] = (__bf16)v;
-                            }
+                        } else if constexpr (NSPLIT > 1) {
+                            __bf16 h, l;
+                            split_bf16(v, h, l);
+                            vh[j][i] = h;
+                            vl[j][i] = l;
+                        } else {
+                            vh[j][i] = (__bf16)v;
                         }
                     }
                     // the re-request of channel i may not move ahead of its transform (hipcc otherwise copies the four values
@@ -1017,31 +759,29 @@ void conv3x3_ws_kernel(const ConvArgs a) {
                     load_one(R, voff, it, i);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if (GTTS_WS_EXP != 3) {
-                    u32x4 *drow = dst + kg * NPIX + pr * HC + 4 * g;
-                    if constexpr (F8) {
-                        // fp8 plane: [g8 = plane * 2 + (kg >> 1)][pixel][16 bytes]; this item owns bytes 8 (kg & 1) .. + 7 of its pixels
-                        typedef __attribute__((ext_vector_type(2))) int i32x2;
-                        i32x2 *d8 = reinterpret_cast<i32x2 *>(dst + PLANE16) + (((kg >> 1) * NPIX + pr * HC + 4 * g) * 2 + (kg & 1));
+                u32x4 *drow = dst + kg * NPIX + pr * HC + 4 * g;
+                if constexpr (F8) {
+                    // fp8 plane: [g8 = plane * 2 + (kg >> 1)][pixel][16 bytes]; this item owns bytes 8 (kg & 1) .. + 7 of its pixels
+                    typedef __attribute__((ext_vector_type(2))) int i32x2;
+                    i32x2 *d8 = reinterpret_cast<i32x2 *>(dst + PLANE16) + (((kg >> 1) * NPIX + pr * HC + 4 * g) * 2 + (kg & 1));
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (has && 4 * g + j < HC) {
-                                drow[j] = __builtin_bit_cast(u32x4, fh[j]);
-                                i32x2 q0, q1;
-                                q0[0] = lw[j][0]; q0[1] = lw[j][1];
-                                q1[0] = xw[j][0]; q1[1] = xw[j][1];
-                                d8[2 * j] = q0;
-                                d8[2 * (2 * NPIX + j)] = q1;
-                            }
+                    for (int j = 0; j < 4; ++j) {
+                        if (has && 4 * g + j < HC) {
+                            drow[j] = __builtin_bit_cast(u32x4, fh[j]);
+                            i32x2 q0, q1;
+                            q0[0] = lw[j][0]; q0[1] = lw[j][1];
+                            q1[0] = xw[j][0]; q1[1] = xw[j][1];
+                            d8[2 * j] = q0;
+                            d8[2 * (2 * NPIX + j)] = q1;
                         }
-                    } else {
+                    }
+                } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         if (has && 4 * g + j < HC) {
                             drow[j] = *reinterpret_cast<u32x4 *>(&vh[j]);
                             if constexpr (NSPLIT > 1) drow[PLANE16 + j] = *reinterpret_cast<u32x4 *>(&vl[j]);
                         }
-                    }
                     }
                 }
             }
@@ -1232,11 +972,11 @@ void conv3x3_ws_kernel(const ConvArgs a) {
 //     slower at 40 x 512 (92 vs 79 us).
 // LDS of the f16 + fp8 form: two 32-channel images + parameters (mt: 128, or 64 = the 12-wave form of the 64-channel tile)
 bool conv_ws_f8_fits(int cin, int pro, int mt, int cout) {
-    return ws_smem_bytes(12 * 34, 2, 2, cin, pro, cout, 2, mt == 128 ? 4 : 2, 4, (GTTS_W64_RING && mt == 64) ? 2 * WS64_WST16 : 0) <= (size_t)160 * 1024;
+    return ws_smem_bytes(12 * 34, 2, 2, cin, pro, cout, 2, mt == 128 ? 4 : 2, 4) <= (size_t)160 * 1024;
 }
 bool conv_ws_eligible(int mode, int c0, int c1, int cout, int pro, int epi, int nsplit, int f16f8) {
     const int cin = c0 + c1;
-    if (!GTTS_WS || nsplit != 2) return false;
+    if (nsplit != 2) return false;
     if (mode != CONV_C3 || epi != EPI_STATS || (pro != PRO_MASK && pro != PRO_GN)) return false;
     if (f16f8) {
         // GTTS_PREC_F16F8: 32-channel chunks (two per tile at least), weights in the f16 + fp8 format (conv_f16f8_ok), two images;
@@ -1264,11 +1004,8 @@ int conv_ws_nparts(int cout, int Hout, int Wout) {
 #ifndef GTTS_WS_SMALL_WGS
 #define GTTS_WS_SMALL_WGS 160
 #endif
-bool conv_ws_small(int cout, int groups, int Hout, int Wout, int B, int f16f8) {
+bool conv_ws_small(int cout, int groups, int Hout, int Wout, int B) {
     if (groups <= 0 || cout / groups > 32) return false;
-    // f16 + fp8, 64 output channels: ONE form at every batch size (its weights are packed by column stage and it accumulates kx-major:
-    // the 32-channel small form walks row stages) -- a launch smaller than the chip simply runs fewer 12-wave workgroups
-    if (GTTS_W64_RING && f16f8 && cout == 64) return false;
     const long wgs = (long)B * ((Wout + 31) / 32) * ((Hout + 9) / 10) * (cout % 128 == 0 ? cout / 128 : cout / 64);
     return wgs < GTTS_WS_SMALL_WGS;
 }
@@ -1295,7 +1032,7 @@ static hipError_t launch_ws_ring(ConvArgs &a, hipStream_t st) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         n_cu[dev].store(cus, std::memory_order_relaxed);
     }
-    const size_t smem = ws_smem_bytes(C::NPIX, NPL, RING, a.cin, PRO, a.cout, MF, C::NCW, NKG, (GTTS_W64_RING && NSPLIT == 3 && C::NCWP != C::NCW) ? 2 * WS64_WST16 : 0);
+    const size_t smem = ws_smem_bytes(C::NPIX, NPL, RING, a.cin, PRO, a.cout, MF, C::NCW, NKG);
     if (smem > (size_t)160 * 1024) return hipErrorInvalidValue;      // (conv_ws_eligible keeps such layers on conv_mfma.hip)
     // persistent workgroups: one per CU for the eight-wave form; the three-wave form fits two per CU (registers: 8 waves)
     const int per_cu = C::NT >= 512 ? 1 : (int)std::min<size_t>(2, (size_t)160 * 1024 / smem);
@@ -1316,19 +1053,14 @@ static hipError_t launch_ws_ring(ConvArgs &a, hipStream_t st) {
 
 template <int PRO>
 static hipError_t launch_ws_pro(ConvArgs &a, hipStream_t st) {
-#ifdef GTTS_WS_PROBE      // compile-time probe builds (register / ISA inspection): one instantiation only
-    if constexpr (PRO == PRO_GN) return launch_ws_ring<GTTS_WS_PROBE == 1 ? 1 : 2, GTTS_WS_PROBE == 1 ? 1 : 2, GTTS_WS_PROBE == 1 ? 1 : 2, PRO_GN, 2, float>(a, st);
-    else return hipErrorInvalidValue;
-#else
     if (a.act_bf16 || a.nsplit != 2) return hipErrorInvalidValue;
     if (a.f16f8) {
-        if (conv_ws_small(a.cout, a.groups, a.Hout, a.Wout, a.B, 1)) return launch_ws_ring<1, 1, 1, PRO, 3, float>(a, st);
+        if (conv_ws_small(a.cout, a.groups, a.Hout, a.Wout, a.B)) return launch_ws_ring<1, 1, 1, PRO, 3, float>(a, st);
         if (a.cout % 128 != 0) return launch_ws_ring<1, 2, 2, PRO, 3, float>(a, st);      // the 64-channel tile
         return launch_ws_ring<2, 2, 2, PRO, 3, float>(a, st);
     }
     if (conv_ws_small(a.cout, a.groups, a.Hout, a.Wout, a.B)) return launch_ws_ring<1, 1, 1, PRO, 2, float>(a, st);
     return launch_ws_ring<2, 2, 2, PRO, 2, float>(a, st);
-#endif
 }
 
 hipError_t launch_conv_ws(const ConvArgs &a_in, hipStream_t st) {

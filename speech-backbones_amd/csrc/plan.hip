@@ -47,11 +47,6 @@ int set_error(int code, const char *msg) { g_err = msg; return code; }     // fo
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 struct gtts_plan;
 static int plan_nsplit(const gtts_plan *p);      // 2: hi/lo operand planes (BF16X3, and everything F16F8 leaves on it), 1: plain bf16
-#ifndef GTTS_FUSE_TAIL_CTX
-#define GTTS_FUSE_TAIL_CTX 1      // 0: tail_identity + attention context as two launches everywhere; 1: fused for C = 64; 2: for every C % 32 == 0
-                                  // (measured, same box: 2 loses -- the wider attentions stage their x tile in two workgroups, the tail's Mish
-                                  // runs twice in a VALU-bound kernel: tail + context 100 + 104 -> 231 us at level 1, 51 + 59 -> 135 at level 2)
-#endif
 
 // ------------------------------------------------------------------------------------------------ plan data
 enum TensorKind { TK_ACT, TK_PERB, TK_PART, TK_APART, TK_BYTES_PERB, TK_ROWS };
@@ -544,12 +539,12 @@ extern "C" int gtts_plan_create(const gtts_unet_cfg *cfg, gtts_plan **out) {
         if (o.kind == OP_CONV && o.c1 > 0 && (o.c0 % 8) != 0) { delete p; return fail(GTTS_E_CONFIG, "concat split must be a multiple of 8 channels"); }
     // ResnetBlock identity tail -> attention: the 64-channel context kernel applies the tail while it stages (attn.hip), so the tensor
     // is written once and read once less.  fp32 storage only; wider attentions keep the separate tail (their x tile is staged by two
-    // workgroups, the tail's Mish would run twice).
-    if (p->cfg.precision != GTTS_PREC_BF16_STORE && GTTS_FUSE_TAIL_CTX) {
+    // workgroups, the tail's Mish would run twice -- measured: tail + context 100 + 104 -> 231 us at level 1, 51 + 59 -> 135 at level 2).
+    if (p->cfg.precision != GTTS_PREC_BF16_STORE) {
         for (size_t i = 0; i + 1 < p->ops.size(); ++i) {
             Op &t = p->ops[i], &c = p->ops[i + 1];
             if (t.kind != OP_TAILID || c.kind != OP_ACTX || c.src0 != t.out || t.C != c.C) continue;
-            if (!attn_head_per_wave(c.C) && !(GTTS_FUSE_TAIL_CTX > 1 && c.C % 32 == 0)) continue;
+            if (!attn_head_per_wave(c.C)) continue;
             t.fused = 1;
             c.fused = 1;
             c.eh = t.eh; c.esc = t.esc; c.esh = t.esh; c.eres = t.src0;
@@ -1461,14 +1456,14 @@ static std::string conv_kernel_name(int mode, int cin, int cout, int pro, int ep
     const bool wide = cout > 64;
     if (ws) {      // conv_ws.hip (launch_ws_pro)
         char wb[128];
-        const bool sm = conv_ws_small(cout, groups, Ho, Wo, B, f8 ? 1 : 0);
+        const bool sm = conv_ws_small(cout, groups, Ho, Wo, B);
         const int wm = sm ? 1 : (cout % 128 == 0 ? 2 : 1), wn = sm ? 1 : 2;       // (the f16 + fp8 64-channel tile: <1, 2, 2>)
         snprintf(wb, sizeof wb, "gtts::conv3x3_ws_kernel<%d, %d, %d, 5, %d, %d, %s, %d>", wm, wn, sm ? 1 : 2, pro, f8 ? 3 : nsplit,
                  abf ? "__bf16" : "float", f8 ? 2 : 3);
         return wb;
     }
     if (mode == CONV_UP && nsplit == 2 && !abf && cin % 16 == 0 && pro == PRO_MASK && epi == EPI_PLAIN)      // conv_up.hip
-        return (up_f8 && conv_up4_f16f8_ok(cin, cout)) ? (conv_up4_ws_ok(cin, cout) ? conv_up4_ws_name() : conv_up4_f8_name()) : "gtts::conv_up4_kernel";
+        return (up_f8 && conv_up4_f16f8_ok(cin, cout)) ? conv_up4_f8_name() : "gtts::conv_up4_kernel";
     const int kch = conv_geom(mode, cin, cout, f8 ? 1 : 0).kch;
     if (f8) nsplit = 3;
     const bool fullc = cin % 16 == 0;

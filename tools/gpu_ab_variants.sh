@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box alternating A/B of library variants on the headline bench, plus the batch-size sweep that picks the drop-in module's plan.
-# Variant libraries:  bash tools/build_variants.sh ws64off "-DGTTS_F8_WS64=0" npw4 "-DGTTS_WS64_NPW=4"
+# Variant library:  bash tools/build_variants.sh npw4 "-DGTTS_WS64_NPW=4"
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp
 OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 run() { n=$1; shift
@@ -9,7 +9,6 @@ run() { n=$1; shift
 for rep in 1 2 3; do
 run bf16x3_$rep --precision bf16x3
 run f8_$rep --precision f16f8
-GTTS_LIB=$PWD/speech-backbones_amd/libgtts_ws64off.so run f8_ws64off_$rep --precision f16f8
 GTTS_LIB=$PWD/speech-backbones_amd/libgtts_npw4.so run f8_npw4_$rep --precision f16f8
 done
 run b1_x3 --precision bf16x3 --batch 1
