@@ -419,6 +419,34 @@ int gtts_in_glu_forward(const float *y, const float *gamma, const float *beta, f
 int gtts_in_glu_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *stats, float *dy,
                          float *dgamma, float *dbeta, float *scratch, int B, int C, int H, int W, gtts_stream_t stream);
 
+/* ---- ABI 6 (additive): DiffVC "average voice" encoder training, the PostNet (DiffVC/model/postnet.py:15-53, FwdDiffusion.compute_loss
+ * of DiffVC/train_enc.py) --------------------------------------------------------------------------------------------------------
+ * Block's 7x7 convolution: y = Conv2d_7x7(x * mask, padding 3) + bias with weights packed by gtts_conv7x7_pack (transposed = 0);
+ * the data gradient is the same call on dy with weights packed transposed = 1 (cin / cout swapped), an all-ones mask, a zero bias
+ * and omask = the column mask (d loss / d x of the masked convolution in one pass; omask nullable).  x [B,cin,H,W], mask / omask
+ * [B,W].  The weight / bias gradient gtts_conv7x7_wgrad overwrites dw [cout][cin][7][7] and db [cout] (nullable): split-bf16 MFMA,
+ * deterministic; workspace: gtts_conv7x7_wgrad_workspace_bytes(...) bytes of device memory.  cin and cout multiples of 64
+ * (GTTS_E_CONFIG), B * max(cin, cout) * H * W < 2^29 (GTTS_E_SHAPE); arguments are checked before the device is touched. */
+size_t gtts_conv7x7_packed_bytes(int cin, int cout);
+int gtts_conv7x7_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream);
+int gtts_conv7x7_masked(const float *x, const float *mask, const float *omask, const void *packed, const float *bias, float *y, int B,
+                        int cin, int cout, int H, int W, gtts_stream_t stream);
+size_t gtts_conv7x7_wgrad_workspace_bytes(int B, int cin, int cout, int H, int W);
+int gtts_conv7x7_wgrad(const float *x, const float *mask, const float *dy, float *dw, float *db, void *workspace, size_t workspace_bytes,
+                       int B, int cin, int cout, int H, int W, gtts_stream_t stream);
+/* PostNet's single-channel 1x1 convolutions (init_conv 1 -> C, final_conv C -> 1) and their gradients:
+ *   expand    out [B,C,F,T] = w[c] * x[b,f,t] * mask[b,t] + bias[c]           (init_conv forward; final_conv's data gradient, zero bias)
+ *   collapse  out [B,F,T]   = sum_c w[c] * x[b,c,f,t] * mask[b,t] + bias[0]    (final_conv forward; init_conv's data gradient, zero bias)
+ *   chan_dot  dot[c] = sum_{b,f,t} a[b,c,f,t] * v[b,f,t] * mask[b,t],  sum[c] = sum_{b,f,t} a[b,c,f,t]   (v, mask, one of dot / sum
+ *             nullable; fixed-order two-pass reduction; scratch: gtts_postnet_chan_dot_scratch_floats(B, C, F, T) floats) */
+int gtts_postnet_expand(const float *x, const float *mask, const float *w, const float *bias, float *out, int B, int C, int F, int T,
+                        gtts_stream_t stream);
+int gtts_postnet_collapse(const float *x, const float *mask, const float *w, const float *bias, float *out, int B, int C, int F, int T,
+                          gtts_stream_t stream);
+size_t gtts_postnet_chan_dot_scratch_floats(int B, int C, int F, int T);
+int gtts_postnet_chan_dot(const float *a, const float *v, const float *mask, float *dot, float *sum, float *scratch, int B, int C, int F,
+                          int T, gtts_stream_t stream);
+
 /* ---- debugging / tests: named intermediates of the last estimator call (keep_intermediates plans) ----- */
 int gtts_plan_num_tensors(const gtts_plan *plan);
 /* offset is in bytes into the workspace for the given (B,T); dims = {B,C,H,W}. */

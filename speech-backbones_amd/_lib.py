@@ -204,6 +204,18 @@ def lib():
         L.gtts_in_glu_scratch_floats.restype = sz
         L.gtts_in_glu_forward.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, vp]
         L.gtts_in_glu_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
+        L.gtts_conv7x7_packed_bytes.argtypes = [i, i]
+        L.gtts_conv7x7_packed_bytes.restype = sz
+        L.gtts_conv7x7_pack.argtypes = [vp, vp, i, i, i, vp]
+        L.gtts_conv7x7_masked.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
+        L.gtts_conv7x7_wgrad_workspace_bytes.argtypes = [i, i, i, i, i]
+        L.gtts_conv7x7_wgrad_workspace_bytes.restype = sz
+        L.gtts_conv7x7_wgrad.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
+        L.gtts_postnet_expand.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
+        L.gtts_postnet_collapse.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
+        L.gtts_postnet_chan_dot_scratch_floats.argtypes = [i, i, i, i]
+        L.gtts_postnet_chan_dot_scratch_floats.restype = sz
+        L.gtts_postnet_chan_dot.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
         if L.gtts_abi_version() != 6:
             raise RuntimeError("libgradtts_gfx950.so ABI version mismatch")
         _lib = L
@@ -974,8 +986,9 @@ def _packed_weight(weight, cin, cout, transposed, kind):
             hit[3].device == weight.device):
         return hit[3]
     L = lib()
-    if kind in ("3x3", "1x1"):
-        nbytes, pack = ((L.gtts_conv3x3_packed_bytes, L.gtts_conv3x3_pack) if kind == "3x3" else (L.gtts_conv1x1_packed_bytes, L.gtts_conv1x1_pack))
+    if kind in ("3x3", "1x1", "7x7"):
+        nbytes, pack = {"3x3": (L.gtts_conv3x3_packed_bytes, L.gtts_conv3x3_pack), "1x1": (L.gtts_conv1x1_packed_bytes, L.gtts_conv1x1_pack),
+                        "7x7": (L.gtts_conv7x7_packed_bytes, L.gtts_conv7x7_pack)}[kind]
         packed = torch.empty(int(nbytes(cin, cout)), dtype=torch.uint8, device=weight.device)
         _check(pack(_ptr(weight), _ptr(packed), cin, cout, 1 if transposed else 0, _stream()), "gtts_conv%s_pack" % kind)
     else:
@@ -1119,6 +1132,94 @@ def conv3x3_wgrad(x, mask_cols, dy, x1=None):
             _check(lib().gtts_conv3x3_wgrad(_ptr(x), _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), B, cin, cout, H, W, _stream()),
                    "gtts_conv3x3_wgrad")
     return dw, db
+
+
+def conv7x7_supported(cin, cout, need_dgrad=True, shape=None):
+    """Channel counts (and, with shape = (B, H, W), tensor sizes) the 7x7 training kernels take (DiffVC PostNet Block): forward,
+    data gradient and weight gradient all work on whole 64-channel tiles."""
+    if shape is not None and not conv_size_ok(shape[0], cin, cout, shape[1], shape[2]):
+        return False
+    return int(cin) > 0 and int(cout) > 0 and int(cin) % 64 == 0 and int(cout) % 64 == 0
+
+
+def _conv7x7_run(x, mask_cols, weight, bias, transposed, out_mask=None):
+    B, cin, H, W = x.shape
+    cout = weight.shape[1] if transposed else weight.shape[0]
+    L = lib()
+    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        packed = _packed_weight(weight, cin, cout, transposed, "7x7")
+        _check(L.gtts_conv7x7_masked(_ptr(x), _ptr(mask_cols), _ptr(out_mask), _ptr(packed), _ptr(bias), _ptr(y), B, cin, cout, H, W,
+                                     _stream()), "gtts_conv7x7_masked")
+    return y
+
+
+def conv7x7_masked(x, mask_cols, weight, bias):
+    """Conv2d_7x7(x * mask, padding 3) + bias (PostNet Block, DiffVC/model/postnet.py:21-23): x [B,cin,H,W], mask_cols [B,W],
+    weight [cout,cin,7,7]."""
+    x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
+    return _conv7x7_run(x, mask_cols, weight, bias, False)
+
+
+def conv7x7_dgrad(dy, weight, mask_cols=None):
+    """Gradient of conv7x7_masked w.r.t. (x * mask): a 7x7 convolution of dy with the transposed, flipped weights; with mask_cols
+    [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue)."""
+    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
+    B, cout, H, W = dy.shape
+    return _conv7x7_run(dy, _const(dy.device, "ones", B, W), weight, _const(dy.device, "zeros", int(weight.shape[1])), True,
+                        out_mask=_f32c(mask_cols, "mask"))
+
+
+def conv7x7_wgrad(x, mask_cols, dy):
+    """(dW [cout,cin,7,7], db [cout]) of conv7x7_masked (train_wgrad7.hip: deterministic split-bf16 MFMA reduction)."""
+    x, mask_cols, dy = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy")
+    B, cin, H, W = x.shape
+    cout = int(dy.shape[1])
+    dw = torch.empty((cout, cin, 7, 7), dtype=torch.float32, device=x.device)
+    db = torch.empty((cout,), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        nws = int(lib().gtts_conv7x7_wgrad_workspace_bytes(B, cin, cout, H, W))
+        ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+        _check(lib().gtts_conv7x7_wgrad(_ptr(x), _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws, B, cin, cout, H, W, _stream()),
+               "gtts_conv7x7_wgrad")
+    return dw, db
+
+
+def postnet_expand(x, mask, w, bias=None):
+    """out [B,C,F,T] = w[c] * x[b,f,t] * mask[b,t] + bias[c] (PostNet init_conv; final_conv's data gradient with bias None)."""
+    x, mask, w = _f32c(x, "x"), _f32c(mask, "mask"), _f32c(w, "weight")
+    B, F, T = x.shape
+    C = int(w.numel())
+    bias = _const(x.device, "zeros", C) if bias is None else _f32c(bias, "bias")
+    out = torch.empty((B, C, F, T), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        _check(lib().gtts_postnet_expand(_ptr(x), _ptr(mask), _ptr(w), _ptr(bias), _ptr(out), B, C, F, T, _stream()), "gtts_postnet_expand")
+    return out
+
+
+def postnet_collapse(x, mask, w, bias=None):
+    """out [B,F,T] = sum_c w[c] * x[b,c,f,t] * mask[b,t] + bias (PostNet final_conv; init_conv's data gradient with bias None)."""
+    x, mask, w = _f32c(x, "x"), _f32c(mask, "mask"), _f32c(w, "weight")
+    B, C, F, T = x.shape
+    bias = _const(x.device, "zeros", 1) if bias is None else _f32c(bias, "bias")
+    out = torch.empty((B, F, T), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        _check(lib().gtts_postnet_collapse(_ptr(x), _ptr(mask), _ptr(w), _ptr(bias), _ptr(out), B, C, F, T, _stream()), "gtts_postnet_collapse")
+    return out
+
+
+def postnet_chan_dot(a, v, mask, want_dot=True, want_sum=True):
+    """(dot [C], sum [C]) over a [B,C,F,T]: dot[c] = sum a[b,c] * v[b] * mask[b,t] (v [B,F,T], v / mask None: 1), sum[c] = sum a[b,c]
+    (fixed-order reduction; an output not wanted is None)."""
+    a, v, mask = _f32c(a, "a"), _f32c(v, "v"), _f32c(mask, "mask")
+    B, C, F, T = a.shape
+    dot = torch.empty((C,), dtype=torch.float32, device=a.device) if want_dot else None
+    sm = torch.empty((C,), dtype=torch.float32, device=a.device) if want_sum else None
+    with _on(a.device):
+        scratch = torch.empty(int(lib().gtts_postnet_chan_dot_scratch_floats(B, C, F, T)), dtype=torch.float32, device=a.device)
+        _check(lib().gtts_postnet_chan_dot(_ptr(a), _ptr(v), _ptr(mask), _ptr(dot), _ptr(sm), _ptr(scratch), B, C, F, T, _stream()),
+               "gtts_postnet_chan_dot")
+    return dot, sm
 
 
 def conv1x1_supported(cin, cout, need_dgrad=True, shape=None):

@@ -862,7 +862,7 @@ int conv_nparts(int mode, int cout, int Hout, int Wout) {
 
 // (mode, tiling) x (prologue, epilogue) x precision -> template instance; must agree with conv_geom() in common.h.
 // Only the combinations the op program uses are instantiated:
-//   C3: (MASK | GN, STATS)   DN, UP: (MASK, PLAIN)   P1: (MASK, TAIL) | (PLAIN, ATTN) | (MASK, PLAIN: training)
+//   C3: (MASK | GN, STATS)   C7: (MASK | GN, STATS) | (MASK, PLAIN: training)   DN, UP: (MASK, PLAIN)   P1: (MASK, TAIL) | (PLAIN, ATTN) | (MASK, PLAIN: training)
 template <int MODE, int WM, int WN, int MF, int PRO, int EPI>
 static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
     const bool fullc = a.cin % 16 == 0 && (a.c1 == 0 || a.c0 % 16 == 0);
@@ -929,8 +929,11 @@ hipError_t launch_conv(int mode, const ConvArgs &a, hipStream_t st) {
                             : launch_prec<CONV_C3, 1, 4, 2, PRO_GN, EPI_STATS>(a, st);
             break;
         case CONV_C7:          // DiffVC PostNet Block (postnet.py:15-23): 64-cout tiles, fp32 storage, bf16x3
-            if (a.epi != EPI_STATS || a.act_bf16 || a.nsplit != 2) break;
-            if (a.cin % 16 != 0) break;
+            if (a.act_bf16 || a.nsplit != 2 || a.cin % 16 != 0) break;
+            // training (train.hip gtts_conv7x7_masked): raw output of x * mask (+ bias) for the autograd save, and the data
+            // gradient (transposed weights, column mask in the epilogue)
+            if (a.epi == EPI_PLAIN && a.pro == PRO_MASK) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_MASK, EPI_PLAIN, 2, 1>(a, st);
+            if (a.epi != EPI_STATS) break;
             if (a.pro == PRO_MASK) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_MASK, EPI_STATS, 2, 1>(a, st);
             if (a.pro == PRO_GN) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_GN, EPI_STATS, 2, 1>(a, st);
             break;

@@ -131,6 +131,10 @@ struct PackDesc {
 void pack_describe(int mode, const float *w, void *dst, int cin, int cout, PackDesc *out);
 hipError_t launch_pack_batch(const PackDesc *descs_dev, int n, int grid_x, hipStream_t st);
 hipError_t launch_pack_attn_kv(const float *wqkv, unsigned char *dst, int C, hipStream_t st);
+// train_wgrad.hip: dw [cout][cin][taps] (+ db [cout]) = fixed-order sum over nslice partial tiles [nslice][tiles][taps][64 co][64 ci]
+// (+ bias partials [nslice][cout]) -- the second pass of every tiled weight gradient (3x3, 1x1, and train_wgrad7.hip's 7x7)
+hipError_t launch_wgrad_reduce(const float *part, const float *dbpart, float *dw, float *db, int cin, int cout, int nslice, int taps,
+                               hipStream_t st);
 hipError_t launch_copy_f32(const float *src, float *dst, size_t n, hipStream_t st);
 
 // ---- glue.hip (generate_path + aligned prior mean + terminal sample: tts.py:84-94, utils.py:26-39)

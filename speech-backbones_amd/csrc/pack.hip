@@ -37,6 +37,9 @@ __device__ __forceinline__ void pack_conv_element(const float *__restrict__ w, _
         if (mode == CONV_C3 + 16) {
             // data-gradient convolution of a 3x3 conv: W'[co'][ci'][ky][kx] = W[ci'][co'][2-ky][2-kx], W stored [cout_orig = cin][cin_orig = cout]
             v = w[(((size_t)ci * cout + co) * 3 + (2 - stage)) * 3 + (2 - tap)];
+        } else if (mode == CONV_C7 + 16) {
+            // data-gradient convolution of a 7x7 conv: W'[co'][ci'][ky][kx] = W[ci'][co'][6-ky][6-kx], W stored [cout_orig = cin][cin_orig = cout]
+            v = w[(((size_t)ci * cout + co) * 7 + (6 - stage)) * 7 + (6 - tap)];
         } else if (mode == CONV_C7) {
             v = w[(((size_t)co * cin + ci) * 7 + stage) * 7 + tap];          // ky = stage, kx = tap
         } else if (mode == CONV_C3 || mode == CONV_DN) {
@@ -128,7 +131,7 @@ hipError_t launch_pack_batch(const PackDesc *descs_dev, int n, int grid_x, hipSt
     return hipGetLastError();
 }
 
-// mode CONV_C3 + 16 / CONV_P1 + 16: the transposed (and, 3x3, flipped) packing of a conv for its data gradient (cin, cout are
+// mode CONV_C3 + 16 / CONV_C7 + 16 / CONV_P1 + 16: the transposed (and, 3x3, flipped) packing of a conv for its data gradient (cin, cout are
 // those of the gradient convolution, i.e. swapped with respect to the forward weight tensor)
 hipError_t launch_pack_conv(int mode, const float *w, unsigned char *dst, int cin, int cout, hipStream_t st, unsigned *status, unsigned tag) {
     PackDesc d;

@@ -47,6 +47,52 @@ __global__ void postnet_final_kernel(const float *__restrict__ x, const float *_
     out[(size_t)b * FT + i] = acc + bias[0];
 }
 
+// ---- training (model/_train_ops.py PostNet path): the channel reductions of the two single-channel 1x1 convolutions' weight / bias
+// gradients.  dot[c] = sum_{b,p} a[b][c][p] v[b][p] mask[b][p % T], sum[c] = sum_{b,p} a[b][c][p] (v, mask, sum nullable), p over F x T.
+// Pass 1: workgroup (j, c) reduces elements [j * PN_SEG, (j + 1) * PN_SEG) of the flattened [B][P] range in a fixed order; pass 2 adds
+// the nblk partials of a channel in a fixed order: deterministic, no atomics.
+constexpr int PN_SEG = 4096;
+__global__ __launch_bounds__(256) void postnet_chan_dot_kernel(const float *__restrict__ a, const float *__restrict__ v,
+                                                               const float *__restrict__ mask, float *__restrict__ part, int C, int P, int T,
+                                                               size_t n, int nblk) {
+    __shared__ float red[2][4];
+    const int c = blockIdx.y, j = blockIdx.x;
+    float s1 = 0.f, s2 = 0.f;
+    const size_t e1 = min(n, (size_t)(j + 1) * PN_SEG);
+    for (size_t i = (size_t)j * PN_SEG + threadIdx.x; i < e1; i += 256) {
+        const size_t b = i / P, p = i % P;
+        const float x = a[(b * C + c) * P + p];
+        float w = v ? v[i] : 1.f;
+        if (mask) w *= mask[b * T + p % T];
+        s1 = fmaf(x, w, s1);
+        s2 += x;
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2) part[((size_t)c * nblk + j) * 2 + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+__global__ __launch_bounds__(256) void postnet_chan_dot_finish(const float *__restrict__ part, float *__restrict__ dot, float *__restrict__ sum,
+                                                               int nblk) {
+    __shared__ float red[2][4];
+    const int c = blockIdx.x;
+    float s1 = 0.f, s2 = 0.f;
+    for (int j = threadIdx.x; j < nblk; j += 256) {
+        s1 += part[((size_t)c * nblk + j) * 2];
+        s2 += part[((size_t)c * nblk + j) * 2 + 1];
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (dot) dot[c] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        if (sum) sum[c] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    }
+}
+
 }  // namespace gtts
 
 using namespace gtts;
@@ -216,6 +262,50 @@ extern "C" int gtts_postnet_forward(const gtts_postnet *p, const void *packed, c
     }
     hipLaunchKernelGGL(postnet_final_kernel, dim3((F * T + 255) / 256, B), dim3(256), (size_t)C * 4, st, R, mask,
                        (const float *)(blob + p->off("final_conv.weight")), (const float *)(blob + p->off("final_conv.bias")), out, C, F, T);
+    PCHK(hipGetLastError());
+    return GTTS_OK;
+}
+
+// ---- PostNet training ops (ABI 6, additive): the bandwidth-bound single-channel 1x1 convolutions on the same kernels as the inference
+// forward above (model/_train_ops.py composes them with the 7x7 / GroupNorm / 1x1 training kernels)
+extern "C" int gtts_postnet_expand(const float *x, const float *mask, const float *w, const float *bias, float *out, int B, int C, int F, int T,
+                                   gtts_stream_t stream) {
+    if (!x || !mask || !w || !bias || !out) return pfail(GTTS_E_NULL, "gtts_postnet_expand: null argument");
+    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || C > 65535 || B > 65535) return pfail(GTTS_E_SHAPE, "gtts_postnet_expand: bad shape");
+    if ((size_t)B * C * F * T >= ((size_t)1 << 31)) return pfail(GTTS_E_SHAPE, "gtts_postnet_expand: tensor too large");
+    hipLaunchKernelGGL(postnet_init_kernel, dim3((F * T + 255) / 256, C, B), dim3(256), 0, (hipStream_t)stream, x, mask, w, bias, out, C, F, T);
+    PCHK(hipGetLastError());
+    return GTTS_OK;
+}
+
+extern "C" int gtts_postnet_collapse(const float *x, const float *mask, const float *w, const float *bias, float *out, int B, int C, int F,
+                                     int T, gtts_stream_t stream) {
+    if (!x || !mask || !w || !bias || !out) return pfail(GTTS_E_NULL, "gtts_postnet_collapse: null argument");
+    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || B > 65535 || C > 16384) return pfail(GTTS_E_SHAPE, "gtts_postnet_collapse: bad shape");
+    if ((size_t)B * C * F * T >= ((size_t)1 << 31)) return pfail(GTTS_E_SHAPE, "gtts_postnet_collapse: tensor too large");
+    hipLaunchKernelGGL(postnet_final_kernel, dim3((F * T + 255) / 256, B), dim3(256), (size_t)C * 4, (hipStream_t)stream, x, mask, w, bias, out,
+                       C, F, T);
+    PCHK(hipGetLastError());
+    return GTTS_OK;
+}
+
+extern "C" size_t gtts_postnet_chan_dot_scratch_floats(int B, int C, int F, int T) {
+    if (B <= 0 || C <= 0 || F <= 0 || T <= 0) return 0;
+    const size_t n = (size_t)B * F * T;
+    return (size_t)C * ((n + PN_SEG - 1) / PN_SEG) * 2;
+}
+
+extern "C" int gtts_postnet_chan_dot(const float *a, const float *v, const float *mask, float *dot, float *sum, float *scratch, int B, int C,
+                                     int F, int T, gtts_stream_t stream) {
+    if (!a || !scratch || (!dot && !sum)) return pfail(GTTS_E_NULL, "gtts_postnet_chan_dot: null argument");
+    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || C > 65535) return pfail(GTTS_E_SHAPE, "gtts_postnet_chan_dot: bad shape");
+    const size_t n = (size_t)B * F * T;
+    const size_t nblk = (n + PN_SEG - 1) / PN_SEG;
+    if (nblk > 0x7fffffff) return pfail(GTTS_E_SHAPE, "gtts_postnet_chan_dot: tensor too large");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(postnet_chan_dot_kernel, dim3((unsigned)nblk, C), dim3(256), 0, st, a, v, mask, scratch, C, F * T, T, n, (int)nblk);
+    PCHK(hipGetLastError());
+    hipLaunchKernelGGL(postnet_chan_dot_finish, dim3(C), dim3(256), 0, st, scratch, dot, sum, (int)nblk);
     PCHK(hipGetLastError());
     return GTTS_OK;
 }

@@ -279,6 +279,54 @@ extern "C" int gtts_conv3x3_masked(const float *x, const float *mask, const void
     return gtts_conv3x3_masked3(x, nullptr, 0, mask, nullptr, packed, bias, y, B, cin, cout, H, W, stream);
 }
 
+// ---- 7x7 convolutions of the training path (DiffVC PostNet Block, DiffVC/model/postnet.py:15-23): forward and data gradient on
+// the inference CONV_C7 kernel (mask prologue, plain epilogue); the weight gradient is gtts_conv7x7_wgrad (train_wgrad7.hip).
+// Channel counts are multiples of 64 (GTTS_E_CONFIG otherwise: the kernel's 64-cout tile and the weight gradient's 64 x 64 tile);
+// every tensor of a call must stay below 2^31 bytes (GTTS_E_SHAPE): the kernels address it with 32-bit byte offsets.
+static int conv7x7_check(const char *fn, int B, int cin, int cout, int H, int W) {
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return tfail(GTTS_E_SHAPE, "%s: bad shape", fn);
+    if (cin % 64 || cout % 64) return tfail(GTTS_E_CONFIG, "%s: cin and cout must be multiples of 64 (got %d, %d)", fn, cin, cout);
+    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return tfail(GTTS_E_SHAPE, "%s: tensor too large for 32-bit offsets", fn);
+    return GTTS_OK;
+}
+
+extern "C" size_t gtts_conv7x7_packed_bytes(int cin, int cout) {
+    if (cin <= 0 || cout <= 0 || cin % 64 || cout % 64) return 0;
+    return (conv_packed_bytes(CONV_C7, cin, cout) + 255) / 256 * 256;
+}
+
+// transposed != 0: w is the FORWARD weight [forward cout = cin of this conv][forward cin = cout of this conv][7][7], packed
+// transposed with flipped taps (the data-gradient convolution)
+extern "C" int gtts_conv7x7_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream) {
+    if (!w || !packed) return tfail(GTTS_E_NULL, "gtts_conv7x7_pack: null argument");
+    if (cin <= 0 || cout <= 0) return tfail(GTTS_E_SHAPE, "gtts_conv7x7_pack: bad shape");
+    if (cin % 64 || cout % 64) return tfail(GTTS_E_CONFIG, "gtts_conv7x7_pack: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
+    TCHK(launch_pack_conv(transposed ? CONV_C7 + 16 : CONV_C7, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
+    return GTTS_OK;
+}
+
+// y = Conv2d_7x7(x * mask, packed W, padding 3) + bias; x [B,cin,H,W], mask [B,W] (columns), bias [cout], y [B,cout,H,W];
+// omask (nullable): [B][W] column mask multiplied into the output (the data gradient of the masked convolution in one pass)
+extern "C" int gtts_conv7x7_masked(const float *x, const float *mask, const float *omask, const void *packed, const float *bias,
+                                   float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
+    if (!x || !mask || !packed || !bias || !y) return tfail(GTTS_E_NULL, "gtts_conv7x7_masked: null argument");
+    const int rc = conv7x7_check("gtts_conv7x7_masked", B, cin, cout, H, W);
+    if (rc != GTTS_OK) return rc;
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src0 = x; a.src1 = x; a.c0 = cin; a.c1 = 0; a.cin = cin;
+    a.B = B; a.Hin = a.Hout = H; a.Win = a.Wout = W;
+    a.mask = mask; a.T = W; a.lvl_in = a.lvl_out = 0;
+    a.pro = PRO_MASK; a.epi = EPI_PLAIN;
+    a.w = (const unsigned char *)packed; a.w_bstride = 0;
+    a.bias = bias; a.bias_bstride = 0;
+    a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
+    a.omask = omask;
+    const hipError_t e = launch_conv(CONV_C7, a, (hipStream_t)stream);
+    if (e != hipSuccess) return tfail(GTTS_E_HIP, "conv7x7 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
+    return GTTS_OK;
+}
+
 // ---- 1x1 convolutions of the training path (res_conv, to_qkv, to_out: diffusion.py:70,87-88): forward and data gradient on
 // the inference CONV_P1 kernel (mask prologue, plain epilogue); the weight gradient is gtts_conv1x1_wgrad (train_wgrad.hip)
 extern "C" size_t gtts_conv1x1_packed_bytes(int cin, int cout) {

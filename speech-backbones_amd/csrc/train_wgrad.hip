@@ -304,6 +304,14 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
     }
 }
 
+hipError_t launch_wgrad_reduce(const float *part, const float *dbpart, float *dw, float *db, int cin, int cout, int nslice, int taps,
+                               hipStream_t st) {
+    const size_t total = (size_t)(cin / 64) * (cout / 64) * taps * (64 * 64) + (db ? (size_t)cout : 0);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, part, dbpart, dw, db, cin, cout,
+                       nslice, taps);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------- 1x1 convolutions
 // dW[co][ci] = sum_{b,p} dy[b,co,p] * (x * mask)[b,ci,p]  (res_conv, to_qkv, to_out: diffusion.py:70,87-88) -- the same
 // pixel-contraction GEMM without taps: a chunk is 64 consecutive pixels of one sample's flattened H x W plane, the workgroup

@@ -1,6 +1,8 @@
 """PostNet -- drop-in for DiffVC/model/postnet.py:15-53 (same module tree and state_dict: `init_conv`, `res_block.block{1,2}.
 block.{0,1}`, `res_block.res`, `final_conv`).  Inference on HIP tensors runs gtts_postnet_forward (csrc/postnet.hip: the two
-7x7 convolutions on the MFMA kernel with GroupNorm + Mish applied on load); with autograd it composes torch ops."""
+7x7 convolutions on the MFMA kernel with GroupNorm + Mish applied on load); with autograd on HIP tensors it composes the training
+kernels (model/_train_ops.postnet: 7x7 forward / data / weight gradient, GroupNorm + Mish, 1x1, the single-channel convolutions);
+on CPU tensors, and under _train_ops.FORCE_TORCH, it composes stock torch ops."""
 import torch
 import torch.nn.functional as F
 
@@ -66,6 +68,10 @@ class PostNet(BaseModule):
                 self._hip_blob = self._hip.pack({n: p for n, p in params}, x.device)
                 self._hip_key = key
             return self._hip.forward(self._hip_blob, x, mask)
+        if x.is_cuda:                       # training (autograd on): the same module tree on the gtts:: training kernels
+            from ...model import _train_ops
+            if not _train_ops.FORCE_TORCH:
+                return _train_ops.postnet(self, x, mask)
         v, m = x.unsqueeze(1), mask.unsqueeze(1)
         v = self.init_conv(v * m)
         v = self.res_block(v, m)

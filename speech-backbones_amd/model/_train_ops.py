@@ -6,6 +6,8 @@ csrc/train*.hip behind torch.autograd.Function wrappers:
   MaskedConv3x3        Block's 3x3 convolution (forward / data gradient on the inference MFMA kernel, weight gradient as a
                        wave-specialised MFMA reduction over pixels); the up path's torch.cat is read in place (two sources)
   GnMishMask           GroupNorm + Mish + mask (+ ResnetBlock's time term), forward and backward fused
+  MaskedConv7x7        DiffVC PostNet Block's 7x7 convolution (forward / data gradient on the inference CONV_C7 kernel, weight
+                       gradient on train_wgrad7.hip); PostNetInitConv / PostNetFinalConv its single-channel 1x1 convolutions (postnet())
   MaskedConv1x1        res_conv, to_qkv, to_out (forward / data gradient on the CONV_P1 kernel, MFMA weight gradient)
   LinearAttentionCore  softmax over pixels, context, output (forward and backward)
   RezeroResidual, MaskedResidualAdd, the plain residual add, FinalConv (64 -> 1 with both masks), ScoreLoss
@@ -51,6 +53,30 @@ class MaskedConv3x3(torch.autograd.Function):
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:      # (one kernel produces both)
             dw, db = be.conv3x3_wgrad(x, cols, dy, x1)
         return dx, None, (dw if ctx.needs_input_grad[2] else None), (db if ctx.needs_input_grad[3] else None), dx1
+
+
+class MaskedConv7x7(torch.autograd.Function):
+    """y = Conv2d_7x7(x * mask, padding 3) + bias (DiffVC PostNet Block, DiffVC/model/postnet.py:21-23) with all three gradients on
+    the HIP kernels: forward and data gradient on the inference CONV_C7 kernel, weight / bias gradient on csrc/train_wgrad7.hip."""
+
+    @staticmethod
+    def forward(ctx, x, mask, weight, bias):
+        be = backend()
+        cols = mask.reshape(mask.shape[0], mask.shape[-1])          # [B,1,1,W] -> [B,W]
+        ctx.save_for_backward(x, cols, weight)
+        return be.conv7x7_masked(x, cols, weight, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        be = backend()
+        x, cols, weight = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = be.conv7x7_dgrad(dy, weight, cols)                 # (the mask rides in the convolution's epilogue)
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:      # (one kernel produces both)
+            dw, db = be.conv7x7_wgrad(x, cols, dy)
+        return dx, None, (dw if ctx.needs_input_grad[2] else None), (db if ctx.needs_input_grad[3] else None)
 
 
 class MaskedConv1x1(torch.autograd.Function):
@@ -182,6 +208,45 @@ class FinalConv(torch.autograd.Function):
         return dx, None, dw, db
 
 
+class PostNetInitConv(torch.autograd.Function):
+    """init_conv(x * mask) for PostNet's 1 -> C 1x1 convolution (DiffVC/model/postnet.py:43,49-51): x [B,F,T] -> [B,C,F,T].  The bias
+    lands on masked frames too, as in the reference (every consumer multiplies by the mask again)."""
+
+    @staticmethod
+    def forward(ctx, x, cols, weight, bias):
+        ctx.save_for_backward(x, cols, weight)
+        return backend().postnet_expand(x, cols, weight.reshape(-1), bias)
+
+    @staticmethod
+    def backward(ctx, dout):
+        be = backend()
+        x, cols, weight = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = be.postnet_collapse(dout, cols, weight.reshape(-1)) if ctx.needs_input_grad[0] else None
+        dw, db = be.postnet_chan_dot(dout, x, cols)
+        return dx, None, dw.reshape(weight.shape), db
+
+
+class PostNetFinalConv(torch.autograd.Function):
+    """final_conv(x * mask) for PostNet's C -> 1 1x1 convolution (DiffVC/model/postnet.py:45,53): [B,C,F,T] -> [B,F,T], NO output
+    mask (unlike the decoder's FinalConv)."""
+
+    @staticmethod
+    def forward(ctx, x, cols, weight, bias):
+        ctx.save_for_backward(x, cols, weight)
+        return backend().postnet_collapse(x, cols, weight.reshape(-1), bias)
+
+    @staticmethod
+    def backward(ctx, dout):
+        be = backend()
+        x, cols, weight = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = be.postnet_expand(dout, cols, weight.reshape(-1)) if ctx.needs_input_grad[0] else None
+        dw, _ = be.postnet_chan_dot(x, dout, cols, want_sum=False)
+        _, db = be.postnet_chan_dot(dout.unsqueeze(1), None, None, want_dot=False)
+        return dx, None, dw.reshape(weight.shape), db
+
+
 class ResampleConv(torch.autograd.Function):
     """Downsample / Upsample of x * mask (diffusion.py:19-34,158,171): forward on the inference kernels; Downsample's data
     gradient is an Upsample call with the zero-padded kernel and its weight gradient the stride-1 MFMA reduction against the
@@ -289,12 +354,28 @@ def _count(hip):
         _COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
 
 
+def _block_conv_kind(conv):
+    """Which training kernel family a Block's convolution belongs to: "3x3" (Grad-TTS / DiffVC decoder Blocks), "7x7" (DiffVC PostNet
+    Blocks: 7x7, padding 3, stride 1 -- what the CONV_C7 kernels compute), or None (no kernel: stock torch)."""
+    if conv.kernel_size == (3, 3):
+        return "3x3"
+    if conv.kernel_size == (7, 7) and conv.padding == (3, 3) and conv.stride == (1, 1) and conv.dilation == (1, 1):
+        return "7x7"
+    return None
+
+
 def _hip_conv_ok(v, conv):
     # (shape: the kernels address one call's tensors with 32-bit byte offsets -- oversize batches / crops take the torch path
     # up front instead of failing inside loss.backward())
-    return (not FORCE_TORCH and v.is_cuda and v.dtype == torch.float32 and conv.kernel_size == (3, 3) and
-            backend().conv3x3_supported(conv.in_channels, conv.out_channels, need_dgrad=v.requires_grad,
-                                        shape=(v.shape[0], v.shape[2], v.shape[3])))
+    if FORCE_TORCH or not v.is_cuda or v.dtype != torch.float32:
+        return False
+    shape = (v.shape[0], v.shape[2], v.shape[3])
+    kind = _block_conv_kind(conv)
+    if kind == "3x3":
+        return backend().conv3x3_supported(conv.in_channels, conv.out_channels, need_dgrad=v.requires_grad, shape=shape)
+    if kind == "7x7":
+        return backend().conv7x7_supported(conv.in_channels, conv.out_channels, need_dgrad=v.requires_grad, shape=shape)
+    return False
 
 
 def _conv1x1(v, m, conv):
@@ -319,14 +400,17 @@ def _hip(v):
 def _conv_gn_mish(blk, v, m, tb=None, v1=None):
     """Block.forward [+ the time term tb[:, :, None, None]] on v (or on the concatenation cat(v, v1), read in place)."""
     conv, norm = blk.block[0], blk.block[1]
-    if v1 is not None and not (_hip_conv_ok(v, conv) and v.shape[1] % 64 == 0):
+    if v1 is not None and not (_hip_conv_ok(v, conv) and conv.kernel_size == (3, 3) and v.shape[1] % 64 == 0):
         v, v1 = torch.cat((v, v1), dim=1), None
     if _hip_conv_ok(v, conv):
         _count(True)
-        y = MaskedConv3x3.apply(v.contiguous(), m, conv.weight, conv.bias, None if v1 is None else v1.contiguous())
+        if conv.kernel_size == (7, 7):
+            y = MaskedConv7x7.apply(v.contiguous(), m, conv.weight, conv.bias)
+        else:
+            y = MaskedConv3x3.apply(v.contiguous(), m, conv.weight, conv.bias, None if v1 is None else v1.contiguous())
     else:
         _count(False)
-        y = F.conv2d(v * m, conv.weight, conv.bias, padding=1)
+        y = F.conv2d(v * m, conv.weight, conv.bias, padding=conv.padding)
     if _hip(y) and y.dim() == 4 and y.shape[1] % norm.num_groups == 0:
         _count(True)
         return GnMishMask.apply(y.contiguous(), m, norm.weight, norm.bias, norm.num_groups, norm.eps,
@@ -493,3 +577,32 @@ def final_conv(fc, v, m):
     _count(False)
     out = F.conv2d(v * m, fc.weight, fc.bias)
     return (out * m).squeeze(1)
+
+
+def postnet(pn, x, mask):
+    """PostNet.forward (DiffVC/model/postnet.py:47-53) with autograd on HIP tensors: x [B, n_feats, T], mask [B, 1, T] -> [B, n_feats, T].
+    The same module tree as the stock path, every tensor-sized op on the gtts:: kernels: init_conv / final_conv on the single-channel
+    kernels of csrc/postnet.hip, the two Blocks as MaskedConv7x7 + GnMishMask, res as MaskedConv1x1.  The gradient w.r.t. x flows
+    back to the caller (the MelEncoder)."""
+    if not FORCE_TORCH and x.is_cuda:
+        backend().new_pack_generation()      # (packed copies of the weights live for this forward + backward only)
+    m = mask.unsqueeze(1)                                           # [B,1,1,T]
+    ic, fc = pn.init_conv, pn.final_conv
+    hip_io = _hip(x) and mask.dtype == torch.float32 and ic.in_channels == 1 and fc.out_channels == 1
+    cols = mask.reshape(mask.shape[0], mask.shape[-1]).contiguous() if hip_io else None
+    if hip_io:
+        _count(True)
+        v = PostNetInitConv.apply(x.contiguous(), cols, ic.weight, ic.bias)
+    else:
+        _count(False)
+        v = F.conv2d(x.unsqueeze(1) * m, ic.weight, ic.bias)
+    rb = pn.res_block
+    h = _conv_gn_mish(rb.block1, v, m)
+    h = _conv_gn_mish(rb.block2, h, m)
+    r = _conv1x1(v, m, rb.res)
+    h = MaskedResidualAdd.apply(h, r.contiguous(), None) if _hip(h) and _hip(r) else h + r
+    if hip_io:
+        _count(True)
+        return PostNetFinalConv.apply(h.contiguous(), cols, fc.weight, fc.bias)
+    _count(False)
+    return F.conv2d(h * m, fc.weight, fc.bias).squeeze(1)

@@ -1,0 +1,192 @@
+"""GPU tests (-m gpu) of DiffVC "average voice" encoder TRAINING (FwdDiffusion.compute_loss, DiffVC/model/vc.py:43-48, as
+DiffVC/train_enc.py:83-91 drives it) with the PostNet on the gtts:: training kernels (model/_train_ops.postnet): the 7x7 convolution's
+forward / data gradient / weight gradient against CPU autograd, the PostNet's gradients against the same module on the CPU, the whole
+loss against the reference's own numbers (tests/golden/enc_loss_grads.npz, tests/golden/make_golden_grads_enc.py), bitwise-repeatable
+backward passes, and the re-pack of the packed weights after optimizer steps."""
+import copy
+import importlib
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import encoder_oracle as E
+from oracle import postnet_oracle as P
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def S():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return importlib.import_module("speech-backbones_amd")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return torch.device("cuda:0")
+
+
+def _modules():
+    return (importlib.import_module("speech-backbones_amd.model._train_ops"),
+            importlib.import_module("speech-backbones_amd.diffvc.model.postnet"),
+            importlib.import_module("speech-backbones_amd.diffvc.model.vc"))
+
+
+def _rel(a, b):
+    return float((a.detach().double().cpu() - b.detach().double().cpu()).abs().max()) / (float(b.detach().double().abs().max()) + 1e-30)
+
+
+@pytest.mark.parametrize("C,W,B", [(64, 45, 3), (64, 128, 1), (128, 45, 1), (128, 128, 3)])
+def test_conv7x7_forward_and_gradients_match_cpu_autograd(S, dev, C, W, B):
+    TO, _, _ = _modules()
+    H = 80
+    g = torch.Generator().manual_seed(C * 1000 + W * 10 + B)
+    x = torch.randn(B, C, H, W, generator=g)
+    w = torch.randn(C, C, 7, 7, generator=g) / (7.0 * C ** 0.5)
+    b = torch.randn(C, generator=g) * 0.1
+    dy = torch.randn(B, C, H, W, generator=g)
+    mask = torch.ones(B, 1, 1, W)
+    if W == 45:                                    # ragged: every utterance but the first is shorter
+        for i in range(1, B):
+            mask[i, ..., W - 7 * i:] = 0
+        if B == 1:
+            mask[0, ..., 40:] = 0
+    xc, wc, bc = (t.double().requires_grad_() for t in (x, w, b))
+    yc = F.conv2d(xc * mask.double(), wc, bc, padding=3)
+    (yc * dy.double()).sum().backward()
+    xg, wg, bg = (t.to(dev).requires_grad_() for t in (x, w, b))
+    yg = TO.MaskedConv7x7.apply(xg, mask.to(dev), wg, bg)
+    (yg * dy.to(dev)).sum().backward()
+    errs = {"y": _rel(yg, yc), "dx": _rel(xg.grad, xc.grad), "dw": _rel(wg.grad, wc.grad), "db": _rel(bg.grad, bc.grad)}
+    print("conv7x7 C %d W %d B %d: %s" % (C, W, B, " ".join("%s %.2e" % kv for kv in errs.items())))
+    assert max(errs.values()) <= 1e-4, errs
+    assert float(xg.grad.abs().sum()) > 0 and bool((xg.grad.cpu() * (1 - mask) == 0).all())     # masked frames get no gradient
+
+
+def _postnet_pair(dev, dim=128, seed=5):
+    _, PN, _ = _modules()
+    pn = PN.PostNet(dim)
+    pn.load_state_dict(P.make_state(dim, seed=seed), strict=True)
+    return pn, copy.deepcopy(pn).to(dev)
+
+
+def _pn_inputs(B=2, T=48, seed=9):
+    g = torch.Generator().manual_seed(seed)
+    mask = torch.ones(B, 1, T)
+    mask[1, :, 37:] = 0
+    z = torch.randn(B, 80, T, generator=g)
+    gout = torch.randn(B, 80, T, generator=g)
+    return z, mask, gout
+
+
+def test_postnet_gradients_match_cpu_and_stay_on_kernels(S, dev):
+    TO, _, _ = _modules()
+    cpu, gpu = _postnet_pair(dev)
+    z, mask, gout = _pn_inputs()
+    zc = z.clone().requires_grad_()
+    oc = cpu(zc, mask)
+    (oc * gout).sum().backward()
+    zg = z.to(dev).requires_grad_()
+    TO.reset_op_counts()
+    og = gpu(zg, mask.to(dev))
+    (og * gout.to(dev)).sum().backward()
+    hip_ops, fallbacks = TO.op_counts()
+    print("PostNet training step: %d gated ops on gtts:: kernels, %d torch fallbacks" % (hip_ops, fallbacks))
+    assert fallbacks == 0 and hip_ops >= 7, (hip_ops, fallbacks)
+    errs = {"out": _rel(og, oc), "dz": _rel(zg.grad, zc.grad)}
+    gmax = {n: float(p.grad.abs().max()) for n, p in cpu.named_parameters()}
+    for (n, pc), (_, pg) in zip(cpu.named_parameters(), gpu.named_parameters()):
+        scale = gmax[n]
+        if ".block." in n and n.endswith("0.bias"):
+            scale = gmax[n[:-len("bias")] + "weight"]       # a conv bias in front of a GroupNorm: identically-zero gradient
+        errs[n] = float((pg.grad.cpu() - pc.grad).abs().max()) / (scale + 1e-30)
+    worst = max(errs.items(), key=lambda kv: kv[1])
+    print("PostNet GPU vs CPU autograd: worst %.2e (%s)" % (worst[1], worst[0]))
+    assert worst[1] <= 1e-4, errs
+
+
+def _fwd_from_golden(G, dev):
+    _, _, VC = _modules()
+    enc = VC.FwdDiffusion(80, 192, 768, 2, 6, 3, 0.1, 4, int(G["dim"]))
+    s_enc, s_pn, _ = (int(v) for v in G["seeds"])
+    sd = {"encoder." + k: v for k, v in E.make_state("mel", seed=s_enc).items()}
+    sd.update({"postnet." + k: v for k, v in P.make_state(int(G["dim"]), seed=s_pn).items()})
+    assert abs(sum(float(v.double().abs().sum()) for v in sd.values()) - float(G["checksum"])) <= 1e-6 * float(G["checksum"])
+    enc.load_state_dict(sd, strict=True)
+    return enc.eval().to(dev)
+
+
+def test_enc_compute_loss_matches_reference_golden(S, dev):
+    TO, _, _ = _modules()
+    G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "enc_loss_grads.npz"))
+    enc = _fwd_from_golden(G, dev)
+    x, y, mask = (torch.from_numpy(G[k]).to(dev) for k in ("x", "y", "mask"))
+    TO.reset_op_counts()
+    loss = enc.compute_loss(x, y, mask)
+    assert abs(float(loss.detach()) - float(G["loss"])) <= 2e-5 * abs(float(G["loss"]))
+    loss.backward()
+    hip_ops, fallbacks = TO.op_counts()
+    assert fallbacks == 0 and hip_ops >= 7, (hip_ops, fallbacks)
+    names = [str(n) for n in G["names"]]
+    grads = {n: p.grad for n, p in enc.named_parameters() if p.grad is not None}
+    assert sorted(grads) == sorted(names)
+    gmax = {n: float(m) for n, m in zip(names, G["max"])}
+    worst = ("", 0.0)
+    for i, n in enumerate(names):
+        g = grads[n].detach().double().flatten().cpu().numpy()
+        idx = np.unique(np.linspace(0, g.size - 1, 16).round().astype(np.int64))
+        scale = gmax[n] + 1e-12
+        wn = n[:-len("bias")] + "weight"
+        # an identically-zero gradient is rounding noise in the reference: a conv bias in front of a GroupNorm (PostNet Blocks), the key
+        # bias of a softmax attention (the softmax is shift-invariant per query) -- compared on the scale of the weight's gradient, and
+        # without its norm (the norm of the noise)
+        zero_grad = n.endswith("bias") and wn in gmax and gmax[n] < 1e-6 * gmax[wn]
+        if zero_grad:
+            scale = gmax[wn]
+        e = float(np.abs(g[idx] - G["vals"][i][:idx.size]).max()) / scale
+        if not zero_grad:
+            e = max(e, abs(float(np.sqrt((g * g).sum())) - float(G["norm"][i])) / (float(G["norm"][i]) + 1e-12))
+        worst = max(worst, (n, e), key=lambda kv: kv[1])
+    print("FwdDiffusion.compute_loss gradients vs the reference golden: worst %.2e (%s)" % (worst[1], worst[0]))
+    assert worst[1] <= 2e-4, worst
+
+
+def test_postnet_backward_is_bitwise_repeatable(S, dev):
+    _, gpu = _postnet_pair(dev, seed=6)
+    z, mask, gout = _pn_inputs(B=3, T=64, seed=4)
+    mask = torch.ones(3, 1, 64)
+    mask[2, :, 50:] = 0
+    runs = []
+    for _ in range(2):
+        gpu.zero_grad(set_to_none=True)
+        zg = z.to(dev).requires_grad_()
+        (gpu(zg, mask.to(dev)) * gout.to(dev)).sum().backward()
+        runs.append([zg.grad.clone()] + [p.grad.clone() for p in gpu.parameters()])
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+
+
+def test_sgd_steps_match_cpu_and_inference_repacks(S, dev):
+    cpu, gpu = _postnet_pair(dev, seed=7)
+    z, mask, gout = _pn_inputs(seed=11)
+    oc_opt = torch.optim.SGD(cpu.parameters(), lr=0.01)
+    og_opt = torch.optim.SGD(gpu.parameters(), lr=0.01)
+    with torch.no_grad():
+        gpu(z.to(dev), mask.to(dev))                 # the inference path packs its blob from the initial weights
+    for _ in range(2):
+        for mod, opt, d in ((cpu, oc_opt, torch.device("cpu")), (gpu, og_opt, dev)):
+            opt.zero_grad(set_to_none=True)
+            (mod(z.to(d), mask.to(d)) * gout.to(d)).sum().backward()
+            opt.step()
+    for (n, pc), (_, pg) in zip(cpu.named_parameters(), gpu.named_parameters()):
+        assert _rel(pg, pc) <= 1e-4, n          # (the updates are of the order of the weights: a 1e-4 gradient error shows)
+    sd = {n: p.detach().cpu() for n, p in gpu.named_parameters()}
+    ref = P.postnet_forward(sd, z, mask)
+    with torch.no_grad():
+        out = gpu(z.to(dev), mask.to(dev)).cpu()
+    err = _rel(out, ref)
+    print("no_grad PostNet after two SGD steps vs oracle: rel err %.2e" % err)
+    assert err <= 1e-4

@@ -1,0 +1,132 @@
+"""CPU: the DiffVC PostNet training entry points (7x7 convolution forward / data gradient / weight gradient, the single-channel 1x1
+convolutions) are declared, exported and validate their arguments before touching a device; the Python gate takes the train_enc.py
+shape and refuses channel counts the kernels do not tile."""
+import ctypes
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT, pkg
+
+NEW = ["gtts_conv7x7_packed_bytes", "gtts_conv7x7_pack", "gtts_conv7x7_masked", "gtts_conv7x7_wgrad_workspace_bytes",
+       "gtts_conv7x7_wgrad", "gtts_postnet_expand", "gtts_postnet_collapse", "gtts_postnet_chan_dot_scratch_floats",
+       "gtts_postnet_chan_dot"]
+E_NULL, E_SHAPE, E_CONFIG = -1, -2, -3
+
+
+@pytest.fixture(scope="module")
+def L():
+    S = pkg()
+    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
+    return S._lib.lib()
+
+
+def test_new_symbols_declared_and_exported(L):
+    S = pkg()
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gradtts_abi.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(gtts_[a-z_0-9]+)\s*\(", src))
+    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
+    exported = set(re.findall(r"\bT (gtts_[a-z_0-9]+)", out))
+    for name in NEW:
+        assert name in declared, name
+        assert name in exported, name
+    assert L.gtts_abi_version() == 6
+
+
+def _fake(n=1):
+    """Non-null host addresses: validation must fail before any of them is dereferenced or handed to the device."""
+    return [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(n)]
+
+
+def test_conv7x7_pack_validates(L):
+    w, p = _fake(2)
+    assert L.gtts_conv7x7_pack(None, p, 128, 128, 0, None) == E_NULL
+    assert L.gtts_conv7x7_pack(w, None, 128, 128, 1, None) == E_NULL
+    assert L.gtts_conv7x7_pack(w, p, 0, 128, 0, None) == E_SHAPE
+    assert L.gtts_conv7x7_pack(w, p, 96, 128, 0, None) == E_CONFIG
+    assert L.gtts_conv7x7_packed_bytes(96, 128) == 0
+    assert L.gtts_conv7x7_packed_bytes(128, 128) >= 128 * 128 * 49 * 4      # bf16 hi + lo of every weight
+
+
+def test_conv7x7_masked_validates(L):
+    x, m, om, p, b, y = _fake(6)
+    assert L.gtts_conv7x7_masked(None, m, om, p, b, y, 2, 128, 128, 80, 128, None) == E_NULL
+    assert L.gtts_conv7x7_masked(x, None, om, p, b, y, 2, 128, 128, 80, 128, None) == E_NULL
+    assert L.gtts_conv7x7_masked(x, m, om, None, b, y, 2, 128, 128, 80, 128, None) == E_NULL
+    assert L.gtts_conv7x7_masked(x, m, om, p, b, None, 2, 128, 128, 80, 128, None) == E_NULL
+    assert L.gtts_conv7x7_masked(x, m, om, p, b, y, 0, 128, 128, 80, 128, None) == E_SHAPE
+    assert L.gtts_conv7x7_masked(x, m, om, p, b, y, 2, 128, 128, 80, -1, None) == E_SHAPE
+    assert L.gtts_conv7x7_masked(x, m, om, p, b, y, 2, 96, 128, 80, 128, None) == E_CONFIG
+    assert L.gtts_conv7x7_masked(x, m, om, p, b, y, 2, 128, 32, 80, 128, None) == E_CONFIG
+    # 32-bit byte offsets: B * C * H * W must stay below 2^29
+    assert L.gtts_conv7x7_masked(x, m, om, p, b, y, 512, 128, 128, 80, 128, None) == E_SHAPE
+
+
+def test_conv7x7_wgrad_validates(L):
+    x, m, dy, dw, db, ws = _fake(6)
+    nws = L.gtts_conv7x7_wgrad_workspace_bytes(128, 128, 128, 80, 128)
+    assert nws >= 49 * 128 * 128 * 4
+    assert L.gtts_conv7x7_wgrad_workspace_bytes(2, 64, 96, 80, 45) == 0
+    assert L.gtts_conv7x7_wgrad(None, m, dy, dw, db, ws, nws, 128, 128, 128, 80, 128, None) == E_NULL
+    assert L.gtts_conv7x7_wgrad(x, None, dy, dw, db, ws, nws, 128, 128, 128, 80, 128, None) == E_NULL
+    assert L.gtts_conv7x7_wgrad(x, m, dy, None, db, ws, nws, 128, 128, 128, 80, 128, None) == E_NULL
+    assert L.gtts_conv7x7_wgrad(x, m, dy, dw, db, None, nws, 128, 128, 128, 80, 128, None) == E_NULL
+    assert L.gtts_conv7x7_wgrad(x, m, dy, dw, db, ws, nws, 0, 128, 128, 80, 128, None) == E_SHAPE
+    assert L.gtts_conv7x7_wgrad(x, m, dy, dw, db, ws, nws, 128, 100, 128, 80, 128, None) == E_CONFIG
+    assert L.gtts_conv7x7_wgrad(x, m, dy, dw, db, ws, nws, 1024, 128, 128, 80, 128, None) == E_SHAPE
+    assert L.gtts_conv7x7_wgrad(x, m, dy, dw, db, ws, nws - 4, 128, 128, 128, 80, 128, None) == -6     # GTTS_E_WORKSPACE
+
+
+def test_postnet_single_channel_ops_validate(L):
+    x, m, w, b, o, s = _fake(6)
+    assert L.gtts_postnet_expand(None, m, w, b, o, 2, 128, 80, 48, None) == E_NULL
+    assert L.gtts_postnet_expand(x, m, w, b, o, 0, 128, 80, 48, None) == E_SHAPE
+    assert L.gtts_postnet_collapse(x, m, w, None, o, 2, 128, 80, 48, None) == E_NULL
+    assert L.gtts_postnet_collapse(x, m, w, b, o, 2, 128, 80, 0, None) == E_SHAPE
+    assert L.gtts_postnet_chan_dot(x, None, None, None, None, s, 2, 128, 80, 48, None) == E_NULL
+    assert L.gtts_postnet_chan_dot(x, None, None, o, None, s, 2, -1, 80, 48, None) == E_SHAPE
+    assert L.gtts_postnet_chan_dot_scratch_floats(2, 128, 80, 48) == 128 * 2 * ((2 * 80 * 48 + 4095) // 4096)
+
+
+def test_conv7x7_supported_gate():
+    lib = pkg()._lib
+    assert lib.conv7x7_supported(128, 128, need_dgrad=True, shape=(128, 80, 128))        # DiffVC/train_enc.py: B 128, 128-frame crops
+    assert lib.conv7x7_supported(64, 64, shape=(3, 80, 45))
+    assert not lib.conv7x7_supported(96, 128)
+    assert not lib.conv7x7_supported(128, 32)
+    assert not lib.conv7x7_supported(128, 128, shape=(1024, 80, 128))                     # beyond 32-bit offsets
+
+
+def test_block_conv_kinds_of_the_training_gate():
+    """_hip_conv_ok routes a Block convolution by _block_conv_kind: the PostNet Block's 7x7 (padding 3, stride 1) to the 7x7 kernels,
+    the U-Net Blocks' 3x3 to the 3x3 ones; a 7x7 convolution the CONV_C7 kernels do not compute stays on stock torch."""
+    import importlib
+    import torch
+    TO = importlib.import_module("speech-backbones_amd.model._train_ops")
+    PN = importlib.import_module("speech-backbones_amd.diffvc.model.postnet")
+    assert TO._block_conv_kind(PN.Block(128).block[0]) == "7x7"
+    assert TO._block_conv_kind(torch.nn.Conv2d(64, 64, 3, padding=1)) == "3x3"
+    assert TO._block_conv_kind(torch.nn.Conv2d(64, 64, 7, padding=2)) is None
+    assert TO._block_conv_kind(torch.nn.Conv2d(64, 64, 7, padding=3, stride=2)) is None
+    assert TO._block_conv_kind(torch.nn.Conv2d(64, 64, 5, padding=2)) is None
+
+
+def test_block_torch_fallback_uses_the_convs_own_padding():
+    """The torch fallback of a Block (the path on CPU tensors and for shapes the kernels refuse) uses the convolution's own padding
+    (3 for the PostNet's 7x7, 1 for the U-Net's 3x3) -- checked on CPU tensors against the module's reference formula."""
+    import importlib
+    import torch
+    TO = importlib.import_module("speech-backbones_amd.model._train_ops")
+    PN = importlib.import_module("speech-backbones_amd.diffvc.model.postnet")
+    torch.manual_seed(0)
+    blk = PN.Block(64)
+    v = torch.randn(2, 64, 10, 12)
+    m = torch.ones(2, 1, 1, 12)
+    m[1, ..., 9:] = 0
+    with torch.no_grad():
+        ref = blk(v, m)
+        out = TO._conv_gn_mish(blk, v, m)
+    assert out.shape == ref.shape
+    assert torch.equal(out, ref)
