@@ -311,7 +311,8 @@ int gtts_conv3x3_wgrad(const float *x, const float *mask, const float *dy, float
                        int W, gtts_stream_t stream);
 
 /* The same weight / bias gradient as an LDS-tiled, deterministic reduction (no atomics): cin and cout multiples of 64;
- * workspace: gtts_conv3x3_wgrad_workspace_bytes(...) bytes of device memory (per-slice partial tiles). */
+ * workspace: gtts_conv3x3_wgrad_workspace_bytes(...) bytes of device memory (per-slice partial tiles).  The kernel addresses a
+ * call's tensors with 32-bit byte offsets: B * max(cin, cout) * H * W < 2^29 (GTTS_E_SHAPE), as for gtts_conv1x1_wgrad. */
 size_t gtts_conv3x3_wgrad_workspace_bytes(int B, int cin, int cout, int H, int W);
 int gtts_conv3x3_wgrad_tiled(const float *x, const float *mask, const float *dy, float *dw, float *db, void *workspace,
                              size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream);

@@ -471,7 +471,7 @@ extern "C" int gtts_conv3x3_wgrad_tiled2(const float *x, const float *x1, int c0
     if (x1 && (c0 <= 0 || c0 >= cin || c0 % 64)) return wfail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: c0 must be a multiple of 64 inside (0, cin) (got %d of %d)", c0, cin);
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 64 || cout % 64)
         return wfail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
-    if ((size_t)std::max(cin, cout) * H * W >= ((size_t)1 << 30)) return wfail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: tensor too large");
+    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return wfail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: tensor too large");
     Wgrad2Args a;
     wgrad2_geometry(B, cin, cout, H, W, a);
     const size_t need = gtts_conv3x3_wgrad_workspace_bytes(B, cin, cout, H, W);
