@@ -269,6 +269,11 @@ int gtts_enc_param_info(const gtts_enc *enc, int i, const char **name, int *rank
 size_t gtts_enc_packed_bytes(const gtts_enc *enc);
 int gtts_enc_pack(const gtts_enc *enc, const void *const *param_ptrs, int n_params, void *packed, gtts_stream_t stream);
 size_t gtts_enc_workspace_bytes(const gtts_enc *enc, int B, int L);
+/* Which attention kernel gtts_enc_forward runs at sequence length L: 16 (16 queries per workgroup, lanes along the keys: needs
+ * channels / n_heads % 4 == 0, window_size <= 7 and (16 * channels / n_heads + 16 * roundup(L, 64) + 512) * 4 <= 160 KB of LDS),
+ * 8 (8 queries per workgroup: (8 * channels / n_heads + 8 * L) * 4 <= 160 KB), or 0: gtts_enc_forward refuses L with GTTS_E_SHAPE
+ * (also for a null encoder or L <= 0).  The defaults (192 channels, 2 heads, window 4): 16 up to L = 2432, 8 up to 5024. */
+int gtts_enc_attention_path(const gtts_enc *enc, int L);
 /* mode 0: ids [B,L] int64 (device), x_mask [B,L] fp32 -> mu [B,n_feats,L], logw [B,1,L];  mel is ignored.
  * mode 1: mel [B,n_feats,L], x_mask -> mu [B,n_feats,L] (the encoded mel); ids / logw are ignored. */
 int gtts_enc_forward(const gtts_enc *enc, const void *packed, const long long *ids, const float *mel, const float *x_mask,

@@ -149,6 +149,7 @@ def lib():
         L.gtts_enc_pack.argtypes = [vp, ctypes.POINTER(vp), i, vp, vp]
         L.gtts_enc_workspace_bytes.argtypes = [vp, i, i]
         L.gtts_enc_workspace_bytes.restype = sz
+        L.gtts_enc_attention_path.argtypes = [vp, i]
         L.gtts_enc_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_postnet_create.argtypes = [i, i, i, ctypes.POINTER(vp)]
         L.gtts_postnet_destroy.argtypes = [vp]
@@ -771,6 +772,11 @@ class Encoder:
             _check(lib().gtts_enc_pack(self._h, arr, len(keep), _ptr(blob), _stream()), "gtts_enc_pack")
             torch.cuda.current_stream().synchronize()
         return blob
+
+    def attention_path(self, L):
+        """Which attention kernel forward() runs at sequence length L: 16 (16 queries per workgroup), 8 (the 8-query kernel: long
+        sequences, windows above 7, head widths not divisible by 4) or 0 (forward() refuses L: no kernel holds its probabilities)."""
+        return int(lib().gtts_enc_attention_path(self._h, int(L)))
 
     def _workspace(self, B, L, device):
         key = (B, L, str(device))

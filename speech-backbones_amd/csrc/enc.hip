@@ -436,6 +436,21 @@ extern "C" int gtts_enc_pack(const gtts_enc *e, const void *const *ptrs, int n_p
     return GTTS_OK;
 }
 
+// Which attention kernel serves length L: 16 (enc_attention16_kernel), 8 (enc_attention_kernel) or 0 (refused: neither kernel's
+// probabilities fit the 160 KB of LDS a workgroup can have).  Dynamic LDS per workgroup, in floats:
+//   16: dk * 16 + 16 * 16 + 16 * roundup(L, 64) + 4 * 64  (needs dk % 4 == 0 and a window of at most 7: s_rel has 16 slots per query)
+//    8: 8 * dk + 8 * L
+// The one place this is decided: gtts_enc_forward dispatches and refuses by it, gtts_enc_attention_path reports it.
+constexpr size_t ATT_LDS_LIMIT = (size_t)160 * 1024;
+static int enc_attention_path(const gtts_enc_cfg &cf, int L) {
+    if (L <= 0) return 0;
+    const int dk = cf.channels / cf.n_heads;
+    if (att16_smem_bytes(dk, L) <= ATT_LDS_LIMIT && dk % 4 == 0 && cf.window_size <= 7) return 16;
+    if (((size_t)ATT_QT * dk + (size_t)ATT_QT * L) * sizeof(float) <= ATT_LDS_LIMIT) return 8;
+    return 0;
+}
+extern "C" int gtts_enc_attention_path(const gtts_enc *e, int L) { return e ? enc_attention_path(e->cfg, L) : 0; }
+
 // workspace: X, Y, Z (C channels), Q, K, V, A (C channels), H (max(filter, filter_dp) channels)
 static size_t enc_slot(const gtts_enc *e, int B, int L, int ch) { return ealign((size_t)B * ch * L * 4); }
 extern "C" size_t gtts_enc_workspace_bytes(const gtts_enc *e, int B, int L) {
@@ -494,7 +509,8 @@ extern "C" int gtts_enc_forward(const gtts_enc *e, const void *packed, const lon
     if (cf.mode == 1 && !mel) return efail(GTTS_E_NULL, "MelEncoder needs mel");
     if (workspace_bytes < gtts_enc_workspace_bytes(e, B, L)) return efail(GTTS_E_WORKSPACE, "workspace too small");
     const int C = cf.channels, dk = C / cf.n_heads;
-    if ((size_t)(ATT_QT * dk + ATT_QT * L) * 4 > 160 * 1024) return efail(GTTS_E_SHAPE, "sequence too long for the attention kernel (%d)", L);
+    const int path = enc_attention_path(cf, L);
+    if (!path) return efail(GTTS_E_SHAPE, "sequence too long for the attention kernel (%d)", L);
     hipStream_t st = (hipStream_t)stream;
     EncRun r{e, (const unsigned char *)packed, x_mask, B, L, st};
     unsigned char *ws = (unsigned char *)workspace;
@@ -533,8 +549,8 @@ extern "C" int gtts_enc_forward(const gtts_enc *e, const void *packed, const lon
         if ((rc = enc_conv(r, p + "conv_v", x, V, true, false, nullptr, false))) return rc;
         const float *ek = bp(r, p + "emb_rel_k"), *ev = bp(r, p + "emb_rel_v");
         const int win = cf.window_size > 0 ? cf.window_size : -1;
-        const size_t smem16 = att16_smem_bytes(dk, L);
-        if (smem16 <= (size_t)160 * 1024 && dk % 4 == 0 && win <= 7) {
+        if (path == 16) {
+            const size_t smem16 = att16_smem_bytes(dk, L);
             // 16 queries per workgroup, lanes along the keys (two workgroups per CU up to L ~ 1000)
             ECHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&enc_attention16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem16));
             hipLaunchKernelGGL(enc_attention16_kernel, dim3((L + ATT16_QT - 1) / ATT16_QT, cf.n_heads, B), dim3(256), smem16, st, Q, K, V,

@@ -6,7 +6,7 @@ glow-tts code); inference on HIP tensors runs the kernels of csrc/enc.hip (gtts_
 """
 import torch
 
-from ...model.text_encoder import ConvReluNorm, Encoder
+from ...model.text_encoder import ConvReluNorm, Encoder, _warn_too_long
 from .base import BaseModule
 
 
@@ -35,12 +35,15 @@ class MelEncoder(BaseModule):
             if self._hip_enc is None:
                 self._hip_enc = be.Encoder("mel", 0, self.n_feats, self.channels, self.filters, 0, self.heads, self.layers,
                                            self.kernel, self.window_size)
-            params = list(self.named_parameters())
-            key = (str(x.device),) + tuple((p.data_ptr(), p._version) for _, p in params)
-            if self._hip_blob is None or self._hip_key != key:
-                self._hip_blob = self._hip_enc.pack({n: p for n, p in params}, x.device)
-                self._hip_key = key
-            return self._hip_enc.forward(self._hip_blob, x, x_mask)
+            if self._hip_enc.attention_path(x.shape[-1]):
+                params = list(self.named_parameters())
+                key = (str(x.device),) + tuple((p.data_ptr(), p._version) for _, p in params)
+                if self._hip_blob is None or self._hip_key != key:
+                    self._hip_blob = self._hip_enc.pack({n: p for n, p in params}, x.device)
+                    self._hip_key = key
+                return self._hip_enc.forward(self._hip_blob, x, x_mask)
+            # beyond the attention kernels' length limit (gtts_enc_attention_path): the torch composition below, said once
+            _warn_too_long("MelEncoder", x.shape[-1])
         x = self.init_proj(x * x_mask)
         x = self.prenet(x, x_mask)
         x = self.encoder(x, x_mask)

@@ -207,6 +207,18 @@ class Encoder(BaseModule):
         return x * x_mask
 
 
+_WARNED_TOO_LONG = set()
+
+
+def _warn_too_long(who, length):
+    """One warning per module class: a sequence beyond the attention kernels' length limit runs the torch composition."""
+    if who not in _WARNED_TOO_LONG:
+        _WARNED_TOO_LONG.add(who)
+        import warnings
+        warnings.warn("%s: sequence too long for the attention kernel (%d) -- running the module's torch composition instead"
+                      % (who, length), RuntimeWarning, stacklevel=3)
+
+
 class TextEncoder(BaseModule):
     """text_encoder.py:281-326.  Note the reference quirk: GradTTS builds it with the default n_spks=1, so the
     speaker embedding never reaches the encoder (tts.py:45-47)."""
@@ -241,6 +253,8 @@ class TextEncoder(BaseModule):
         if self._hip_enc is None:
             self._hip_enc = be.Encoder("text", self.n_vocab, self.n_feats, self.n_channels, self.filter_channels,
                                        self.filter_channels_dp, self.n_heads, self.n_layers, self.kernel_size, self.window_size)
+        if not self._hip_enc.attention_path(x.shape[1]):
+            return None
         params = list(self.named_parameters())
         key = (str(x.device),) + tuple((p.data_ptr(), p._version) for _, p in params)
         if self._hip_blob is None or self._hip_key != key:
@@ -252,7 +266,13 @@ class TextEncoder(BaseModule):
 
     def forward(self, x, x_lengths, spk=None):
         if x.is_cuda and not torch.is_grad_enabled() and not self.training and self.n_spks == 1:
-            return self._hip_forward(x, x_lengths)
+            out = self._hip_forward(x, x_lengths)
+            if out is not None:
+                return out
+            # the attention kernels hold a query tile's probabilities over the whole sequence in LDS, which bounds the length
+            # (include/gradtts_abi.h: gtts_enc_attention_path); the reference module has no such bound.  A longer input is never
+            # refused: it runs this module's own torch composition (same arithmetic as under autograd), and says so once.
+            _warn_too_long("TextEncoder", x.shape[1])
         h = (self.emb(x) * math.sqrt(self.n_channels)).transpose(1, -1)
         x_mask = sequence_mask(x_lengths, h.size(2)).unsqueeze(1).to(h.dtype)
         h = self.prenet(h, x_mask)
