@@ -4,6 +4,7 @@ PyTorch is only plumbing here: it owns device memory (packed weights, workspace,
 There is NO fallback: if the library is missing or a call fails, a RuntimeError is raised.
 """
 import ctypes
+import math
 import weakref
 import os
 import threading
@@ -49,6 +50,16 @@ class PackItem(ctypes.Structure):           # gtts_pack_item
                 ("cout", ctypes.c_int), ("transposed", ctypes.c_int)]
 
 
+# Every handle family spells its life-cycle entry points gtts_<family>_<op>, except three names the plan has had since ABI 1.
+_PLAN_NAMES = {"packed_bytes": "gtts_packed_weight_bytes", "pack": "gtts_pack_weights", "workspace_bytes": "gtts_workspace_bytes"}
+
+
+def _sym(family, op):
+    if family == "plan" and op in _PLAN_NAMES:
+        return _PLAN_NAMES[op]
+    return "gtts_%s_%s" % (family, op)
+
+
 def lib():
     """Load the HIP library (once).  Fails loudly when it has not been built."""
     global _lib
@@ -64,21 +75,22 @@ def lib():
         vp, i, f, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
         L.gtts_abi_version.restype = i
         L.gtts_last_error.restype = ctypes.c_char_p
-        L.gtts_plan_create.argtypes = [ctypes.POINTER(UnetCfg), ctypes.POINTER(vp)]
-        L.gtts_plan_destroy.argtypes = [vp]
-        L.gtts_plan_destroy.restype = None
-        L.gtts_plan_num_params.argtypes = [vp]
-        L.gtts_plan_param_info.argtypes = [vp, i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i),
-                                           ctypes.POINTER(i * 4)]
-        L.gtts_packed_weight_bytes.argtypes = [vp]
-        L.gtts_packed_weight_bytes.restype = sz
-        L.gtts_workspace_bytes.argtypes = [vp, i, i]
-        L.gtts_workspace_bytes.restype = sz
+        # the four handle families (_Native): create takes the family's configuration, gtts_pack_weights also the frequency table
+        for fam, cfg, extra in (("plan", [ctypes.POINTER(UnetCfg)], [vp]), ("voc", [ctypes.POINTER(VocCfg)], []),
+                                ("enc", [ctypes.POINTER(EncCfg)], []), ("postnet", [i, i, i], [])):
+            fn = {op: getattr(L, _sym(fam, op)) for op in ("create", "destroy", "num_params", "param_info", "packed_bytes", "pack",
+                                                            "workspace_bytes")}
+            fn["create"].argtypes = cfg + [ctypes.POINTER(vp)]
+            fn["destroy"].argtypes, fn["destroy"].restype = [vp], None
+            fn["num_params"].argtypes = [vp]
+            fn["param_info"].argtypes = [vp, i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i), ctypes.POINTER(i * 4)]
+            fn["packed_bytes"].argtypes, fn["packed_bytes"].restype = [vp], sz
+            fn["pack"].argtypes = [vp, ctypes.POINTER(vp), i] + extra + [vp, vp]
+            fn["workspace_bytes"].argtypes, fn["workspace_bytes"].restype = [vp, i, i], sz
         L.gtts_plan_set_streams.argtypes = [vp, ctypes.POINTER(vp), i]
         L.gtts_plan_set_graph.argtypes = [vp, i]
         L.gtts_mas_maximum_path_cpu.argtypes = [vp, vp, vp, vp, vp, i, i, i]
         L.gtts_bcast_weights.argtypes = [vp, sz, i, vp, vp]
-        L.gtts_pack_weights.argtypes = [vp, ctypes.POINTER(vp), i, vp, vp, vp]
         L.gtts_estimator_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_euler_step.argtypes = [vp, vp, vp, vp, vp, f, f, i, i, i, vp]
         L.gtts_reverse_diffusion.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
@@ -139,39 +151,9 @@ def lib():
         L.gtts_gn_mish_scratch_bytes.argtypes = [i, i]
         L.gtts_gn_mish_scratch_bytes.restype = sz
         L.gtts_gn_mish_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
-        L.gtts_enc_create.argtypes = [ctypes.POINTER(EncCfg), ctypes.POINTER(vp)]
-        L.gtts_enc_destroy.argtypes = [vp]
-        L.gtts_enc_destroy.restype = None
-        L.gtts_enc_num_params.argtypes = [vp]
-        L.gtts_enc_param_info.argtypes = [vp, i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i), ctypes.POINTER(i * 4)]
-        L.gtts_enc_packed_bytes.argtypes = [vp]
-        L.gtts_enc_packed_bytes.restype = sz
-        L.gtts_enc_pack.argtypes = [vp, ctypes.POINTER(vp), i, vp, vp]
-        L.gtts_enc_workspace_bytes.argtypes = [vp, i, i]
-        L.gtts_enc_workspace_bytes.restype = sz
         L.gtts_enc_attention_path.argtypes = [vp, i]
         L.gtts_enc_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
-        L.gtts_postnet_create.argtypes = [i, i, i, ctypes.POINTER(vp)]
-        L.gtts_postnet_destroy.argtypes = [vp]
-        L.gtts_postnet_destroy.restype = None
-        L.gtts_postnet_num_params.argtypes = [vp]
-        L.gtts_postnet_param_info.argtypes = [vp, i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i), ctypes.POINTER(i * 4)]
-        L.gtts_postnet_packed_bytes.argtypes = [vp]
-        L.gtts_postnet_packed_bytes.restype = sz
-        L.gtts_postnet_pack.argtypes = [vp, ctypes.POINTER(vp), i, vp, vp]
-        L.gtts_postnet_workspace_bytes.argtypes = [vp, i, i]
-        L.gtts_postnet_workspace_bytes.restype = sz
         L.gtts_postnet_forward.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, vp]
-        L.gtts_voc_create.argtypes = [ctypes.POINTER(VocCfg), ctypes.POINTER(vp)]
-        L.gtts_voc_destroy.argtypes = [vp]
-        L.gtts_voc_destroy.restype = None
-        L.gtts_voc_num_params.argtypes = [vp]
-        L.gtts_voc_param_info.argtypes = [vp, i, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i), ctypes.POINTER(i * 4)]
-        L.gtts_voc_packed_bytes.argtypes = [vp]
-        L.gtts_voc_packed_bytes.restype = sz
-        L.gtts_voc_pack.argtypes = [vp, ctypes.POINTER(vp), i, vp, vp]
-        L.gtts_voc_workspace_bytes.argtypes = [vp, i, i]
-        L.gtts_voc_workspace_bytes.restype = sz
         L.gtts_voc_hop.argtypes = [vp]
         L.gtts_voc_forward.argtypes = [vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_plan_num_tensors.argtypes = [vp]
@@ -271,8 +253,98 @@ def _f32c(t, name):
     return t.contiguous()
 
 
-class Plan:
+def _rebuild(cls, kw):
+    return cls(**kw)
+
+
+class _Native:
+    """Owner of one native handle of the family gtts_<_family>_*.  A handle is host metadata: copies and pickles rebuild it from its
+    constructor arguments (EMA deep copies, torch.save(model) of a module that already ran)."""
+    _family = None
+
+    def _open(self, kw, *create_args):
+        """kw: the constructor arguments a copy is rebuilt from; create_args: what gtts_<family>_create takes before the handle."""
+        self._kw = kw
+        self._h = ctypes.c_void_p()
+        self._ws = {}               # the single live workspace: {(shape..., str(device)): uint8 tensor}
+        self._call("create", *create_args, ctypes.byref(self._h))
+
+    def _fn(self, op):
+        return getattr(lib(), _sym(self._family, op))
+
+    def _call(self, op, *args):
+        _check(self._fn(op)(*args), _sym(self._family, op))
+
+    def __reduce__(self):
+        return (_rebuild, (type(self), self._kw))
+
+    def __deepcopy__(self, memo):
+        return type(self)(**self._kw)
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._fn("destroy")(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    # ---- state_dict layout
+    def param_layout(self):
+        out = []
+        for k in range(self._fn("num_params")(self._h)):
+            name, rank, dims = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int * 4)()
+            self._call("param_info", self._h, k, ctypes.byref(name), ctypes.byref(rank), ctypes.byref(dims))
+            out.append((name.value.decode(), tuple(dims[:rank.value])))
+        return out
+
+    def packed_bytes(self):
+        return int(self._fn("packed_bytes")(self._h))
+
+    # ---- weights
+    def _params(self, state, device, hint=""):
+        """The fp32 device tensors of param_layout(), checked against it, and their pointer array (which does not own them)."""
+        keep = []
+        for name, shape in self.param_layout():
+            if name not in state:
+                raise RuntimeError("state_dict is missing '%s'%s" % (name, hint))
+            t = state[name].detach().to(device=device, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != shape:
+                raise RuntimeError("parameter %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
+            keep.append(t)
+        return keep, (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+
+    def _pack(self, params, device, *extra):
+        keep, arr = params
+        blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
+        with torch.cuda.device(blob.device):
+            self._call("pack", self._h, arr, len(keep), *extra, _ptr(blob), _stream())
+            torch.cuda.current_stream().synchronize()     # sources in `keep` may be temporaries
+        return blob
+
+    def pack(self, state, device):
+        """state: mapping name -> tensor with the names of param_layout() (the reference module's state_dict)."""
+        return self._pack(self._params(state, device), device)
+
+    # ---- workspace
+    def workspace_bytes(self, B, T):
+        return int(self._fn("workspace_bytes")(self._h, int(B), int(T)))
+
+    def _one_workspace(self, key, device, nbytes):
+        ws = self._ws.get(key)
+        if ws is None:
+            self._ws.clear()      # one shape at a time: the caching allocator recycles the old block
+            ws = torch.empty(nbytes(), dtype=torch.uint8, device=device)
+            self._ws[key] = ws
+        return ws
+
+    def workspace(self, B, T, device):
+        return self._one_workspace((int(B), int(T), str(device)), device, lambda: self.workspace_bytes(B, T))
+
+
+class Plan(_Native):
     """Host-side plan of one score U-Net (mirrors GradLogPEstimator2d.__init__, diffusion.py:129-172)."""
+    _family = "plan"
 
     def __init__(self, dim=64, n_feats=80, n_spks=1, spk_emb_dim=64, groups=8, pe_scale=1000.0, beta_min=0.05,
                  beta_max=20.0, precision=PREC_BF16X3, keep_intermediates=False, arch=0, dim_cond=128, use_ref_t=True,
@@ -297,18 +369,15 @@ class Plan:
         if conv_ws is None:
             conv_ws = int(dim) >= 128 or int(precision) == PREC_F16F8
         conv_ws = bool(conv_ws) and int(precision) in (PREC_BF16X3, PREC_F16F8)
-        self._kw = dict(dim=dim, n_feats=n_feats, n_spks=n_spks, spk_emb_dim=spk_emb_dim, groups=groups,
-                        pe_scale=pe_scale, beta_min=beta_min, beta_max=beta_max, precision=precision,
-                        keep_intermediates=keep_intermediates, arch=arch, dim_cond=dim_cond, use_ref_t=use_ref_t,
-                        c_dim=c_dim, streams=streams, conv_ws=conv_ws)
         self.conv_ws = conv_ws
         self.cfg = UnetCfg(int(dim), int(n_feats), int(n_spks), int(spk_emb_dim), int(groups), float(pe_scale),
                            float(beta_min), float(beta_max), int(precision), 1 if keep_intermediates else 0, int(arch),
                            int(dim_cond), 1 if use_ref_t else 0, int(c_dim), float(beta_min), float(beta_max),
                            1 if conv_ws else 0)
-        self._h = ctypes.c_void_p()
-        _check(lib().gtts_plan_create(ctypes.byref(self.cfg), ctypes.byref(self._h)), "gtts_plan_create")
-        self._ws = {}
+        self._open(dict(dim=dim, n_feats=n_feats, n_spks=n_spks, spk_emb_dim=spk_emb_dim, groups=groups, pe_scale=pe_scale,
+                        beta_min=beta_min, beta_max=beta_max, precision=precision, keep_intermediates=keep_intermediates, arch=arch,
+                        dim_cond=dim_cond, use_ref_t=use_ref_t, c_dim=c_dim, streams=streams, conv_ws=conv_ws),
+                   ctypes.byref(self.cfg))
         if streams is None:
             streams = int(os.environ.get("GTTS_STREAMS", ("0" if int(precision) == PREC_F16F8 else "2") if conv_ws else "3"))
         self._nstreams = 0 if int(streams) < 2 else min(int(streams), 4)
@@ -316,14 +385,6 @@ class Plan:
         self._graph = False
         self._gstream = None
         self._stage = {}            # graph mode: persistent argument buffers (stable addresses -> graph cache hits)
-
-    # a Plan is host metadata: copies / pickles rebuild it from its constructor arguments (EMA deep copies,
-    # torch.save(model) of a module that already sampled)
-    def __reduce__(self):
-        return (_rebuild_plan, (self._kw,))
-
-    def __deepcopy__(self, memo):
-        return Plan(**self._kw)
 
     def set_graph(self, on=True):
         """hipGraph replay of whole reverse_diffusion calls (launch-bound small batches).  Inputs are copied into
@@ -345,47 +406,17 @@ class Plan:
         self._side = (device, side)
         self._ws.clear()            # the workspace size depends on the number of sub-batches
 
-    def __del__(self):
-        try:
-            if self._h:
-                lib().gtts_plan_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    # ---- state_dict layout
-    def param_layout(self):
-        L = lib()
-        out = []
-        for k in range(L.gtts_plan_num_params(self._h)):
-            name, rank, dims = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int * 4)()
-            _check(L.gtts_plan_param_info(self._h, k, ctypes.byref(name), ctypes.byref(rank), ctypes.byref(dims)),
-                   "gtts_plan_param_info")
-            out.append((name.value.decode(), tuple(dims[:rank.value])))
-        return out
-
-    def packed_bytes(self):
-        return int(lib().gtts_packed_weight_bytes(self._h))
-
     def workspace_bytes(self, B, T):
-        n = int(lib().gtts_workspace_bytes(self._h, int(B), int(T)))
+        n = super().workspace_bytes(B, T)
         if n == 0:
             raise RuntimeError("gtts_workspace_bytes: %s" % lib().gtts_last_error().decode())
         return n
 
-    def workspace(self, B, T, device):
-        key = (int(B), int(T), str(device))
-        ws = self._ws.get(key)
-        if ws is None:
-            self._ws.clear()      # one shape at a time: the caching allocator recycles the old block
-            ws = torch.empty(self.workspace_bytes(B, T), dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
-
     def range_status(self, device=None):
-        """(events, max |x|) of the activation range record of the last estimator / sampler call (PREC_F16F8: staging lanes x
-        launches that split an activation with |x| >= 1024, which keeps fp16-grade cross terms only; always (0, 0.0) in the other
-        precisions).  Synchronises the current stream."""
+        """(events, max |x|) of the activation range record of the last estimator / sampler call, as gtts_workspace_status counts
+        them (gradtts_abi.h).  PREC_F16F8: staging lanes x launches that split an activation with |x| >= 1024, which keeps fp16-grade
+        cross terms only.  Every precision: (samples x Block convolutions) whose GroupNorm statistics came out non-finite; max |x| is
+        then inf.  (0, 0.0) before the first call.  Synchronises the current stream."""
         ws = None
         for key, w in self._ws.items():
             if device is None or key[-1] == str(device):
@@ -401,26 +432,11 @@ class Plan:
     def pack(self, state, device):
         """state: mapping name -> tensor with the estimator-level names of the reference state_dict.
         PREC_F16F8: raises RangeError when a 3x3 Block-convolution weight does not fit the format (|w| >= 63.97)."""
-        layout = self.param_layout()
-        keep = []
-        for name, shape in layout:
-            if name not in state:
-                raise RuntimeError("state_dict is missing '%s'" % name)
-            t = state[name].detach().to(device=device, dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise RuntimeError("parameter %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            keep.append(t)
-        arr = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+        params = self._params(state, device)
         half = self.cfg.dim // 2
         # exactly SinusoidalPosEmb's frequency table, computed on the host CPU like the reference (diffusion.py:121-122)
-        import math
         freq = torch.exp(torch.arange(half).float() * -(math.log(10000) / (half - 1))).to(device)
-        blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
-        with torch.cuda.device(blob.device):
-            _check(lib().gtts_pack_weights(self._h, arr, len(keep), _ptr(freq), _ptr(blob), _stream()),
-                   "gtts_pack_weights")
-            torch.cuda.current_stream().synchronize()     # sources in `keep` may be temporaries
-        return blob
+        return self._pack(params, device, _ptr(freq))
 
     # ---- GradLogPEstimator2d.forward
     def estimator_forward(self, blob, x, mask, mu, t, spk=None):
@@ -468,35 +484,32 @@ class Plan:
             z, mask, mu, spk, noise, out = st["z"], st["mask"], st["mu"], st["spk"], st["noise"], st["out"]
         else:
             out = torch.empty_like(z)
-        with torch.cuda.device(z.device):
-            if self._graph:
-                cur = torch.cuda.current_stream()
-                if self._gstream is None or self._gstream.device != z.device:
-                    self._gstream = torch.cuda.Stream(device=z.device)
-                self._gstream.wait_stream(cur)
-                with torch.cuda.stream(self._gstream):
-                    _check(lib().gtts_reverse_diffusion(self._h, _ptr(blob), _ptr(z), _ptr(mask), _ptr(mu), _ptr(spk),
-                                                        _ptr(noise), _ptr(out), _ptr(ws), ws.numel(), B, T, int(n_timesteps),
-                                                        0, int(n_timesteps), _stream()), "gtts_reverse_diffusion")
-                cur.wait_stream(self._gstream)
-                return out.clone()
+
+        def run():          # on the stream that is current where it is called
             _check(lib().gtts_reverse_diffusion(self._h, _ptr(blob), _ptr(z), _ptr(mask), _ptr(mu), _ptr(spk),
                                                 _ptr(noise), _ptr(out), _ptr(ws), ws.numel(), B, T, int(n_timesteps),
                                                 0, int(n_timesteps), _stream()), "gtts_reverse_diffusion")
-        return out
+        with torch.cuda.device(z.device):
+            if not self._graph:
+                run()
+                return out
+            cur = torch.cuda.current_stream()
+            if self._gstream is None or self._gstream.device != z.device:
+                self._gstream = torch.cuda.Stream(device=z.device)
+            self._gstream.wait_stream(cur)
+            with torch.cuda.stream(self._gstream):
+                run()
+            cur.wait_stream(self._gstream)
+            return out.clone()
 
     # ---- DiffVC (arch=1)
     def vc_workspace(self, B, T, Tr, device):
-        key = ("vc", int(B), int(T), int(Tr), str(device))
-        ws = self._ws.get(key)
-        if ws is None:
-            self._ws.clear()
+        def nbytes():
             n = int(lib().gtts_vc_workspace_bytes(self._h, int(B), int(T), int(Tr)))
             if n == 0:
                 raise RuntimeError("gtts_vc_workspace_bytes: %s" % lib().gtts_last_error().decode())
-            ws = torch.empty(n, dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
+            return n
+        return self._one_workspace(("vc", int(B), int(T), int(Tr), str(device)), device, nbytes)
 
     def vc_estimator_forward(self, blob, x, x_mask, mean, xt_ref, ref_mask, c, t):
         """DiffVC GradLogPEstimator.forward(x, x_mask, mean, ref, ref_mask, c, t) (DiffVC/model/diffusion.py:61-106)."""
@@ -553,15 +566,8 @@ class Plan:
 
     def vc_tensors(self, B, T, Tr, device):
         """Named intermediates of the last DiffVC estimator call (keep_intermediates plans); ref tensors use T_ref."""
-        L = lib()
         ws = self.vc_workspace(B, T, Tr, device)
-        out = {}
-        for k in range(L.gtts_plan_num_tensors(self._h)):
-            name, off, dims = ctypes.c_char_p(), ctypes.c_size_t(), (ctypes.c_int * 4)()
-            _check(L.gtts_vc_tensor_info(self._h, k, int(B), int(T), int(Tr), ctypes.byref(name), ctypes.byref(off),
-                                         ctypes.byref(dims)), "gtts_vc_tensor_info")
-            out[name.value.decode()] = (off.value, tuple(dims))
-        return ws, out
+        return ws, {name: (off, dims) for name, off, dims in self._tensor_infos("gtts_vc_tensor_info", B, T, Tr)}
 
     # ---- measurement (bench.py): per-op HIP-event timing
     def ops(self, B, T):
@@ -601,32 +607,30 @@ class Plan:
         if int(self.cfg.precision) == PREC_BF16_STORE:
             raise RuntimeError("Plan.tensors(): the named-intermediate views are fp32; a keep_intermediates plan with bf16 "
                                "activation storage stores 2-byte activations -- use PREC_BF16 / PREC_BF16X3 for tap tests")
-        L = lib()
         ws = self.workspace(B, T, device)
         out = {}
-        for k in range(L.gtts_plan_num_tensors(self._h)):
-            name, off, dims = ctypes.c_char_p(), ctypes.c_size_t(), (ctypes.c_int * 4)()
-            _check(L.gtts_plan_tensor_info(self._h, k, int(B), int(T), ctypes.byref(name), ctypes.byref(off),
-                                           ctypes.byref(dims)), "gtts_plan_tensor_info")
+        for name, off, dims in self._tensor_infos("gtts_plan_tensor_info", B, T):
             n = dims[0] * dims[1] * dims[2] * dims[3]
-            if n <= 0:
-                continue
-            view = ws[off.value: off.value + 4 * n].view(torch.float32).view(*dims)
-            out[name.value.decode()] = view
+            if n > 0:
+                out[name] = ws[off: off + 4 * n].view(torch.float32).view(*dims)
         return out
 
+    def _tensor_infos(self, entry, *shape):
+        """(name, workspace byte offset, dims [4]) of every named intermediate at `shape` = (B, T[, T_ref])."""
+        info = getattr(lib(), entry)
+        for k in range(lib().gtts_plan_num_tensors(self._h)):
+            name, off, dims = ctypes.c_char_p(), ctypes.c_size_t(), (ctypes.c_int * 4)()
+            _check(info(self._h, k, *[int(v) for v in shape], ctypes.byref(name), ctypes.byref(off), ctypes.byref(dims)), entry)
+            yield name.value.decode(), off.value, tuple(dims)
 
-class Vocoder:
+
+class Vocoder(_Native):
     """HiFi-GAN generator on the HIP kernels (csrc/voc.hip): Generator(h).forward of Grad-TTS/hifi-gan/models.py:77-120."""
+    _family = "voc"
 
     def __init__(self, upsample_rates=(8, 8, 2, 2), upsample_kernel_sizes=(16, 16, 4, 4), upsample_initial_channel=512,
                  resblock_kernel_sizes=(3, 7, 11), resblock_dilation_sizes=((1, 3, 5), (1, 3, 5), (1, 3, 5)), resblock="1",
                  n_mels=80):
-        self._kw = dict(upsample_rates=tuple(upsample_rates), upsample_kernel_sizes=tuple(upsample_kernel_sizes),
-                        upsample_initial_channel=int(upsample_initial_channel),
-                        resblock_kernel_sizes=tuple(resblock_kernel_sizes),
-                        resblock_dilation_sizes=tuple(tuple(d) for d in resblock_dilation_sizes), resblock=str(resblock),
-                        n_mels=int(n_mels))
         cfg = VocCfg()
         cfg.n_mels = int(n_mels)
         cfg.upsample_initial_channel = int(upsample_initial_channel)
@@ -647,11 +651,11 @@ class Vocoder:
             for j in range(3):
                 cfg.resblock_dilations[k][j] = int(dil[j]) if j < len(dil) else 1
         self.cfg = cfg
-        self._h = ctypes.c_void_p()
-        L = lib()
-        _check(L.gtts_voc_create(ctypes.byref(cfg), ctypes.byref(self._h)), "gtts_voc_create")
-        self.hop = int(L.gtts_voc_hop(self._h))
-        self._ws = {}
+        self._open(dict(upsample_rates=tuple(upsample_rates), upsample_kernel_sizes=tuple(upsample_kernel_sizes),
+                        upsample_initial_channel=int(upsample_initial_channel), resblock_kernel_sizes=tuple(resblock_kernel_sizes),
+                        resblock_dilation_sizes=tuple(tuple(d) for d in resblock_dilation_sizes), resblock=str(resblock),
+                        n_mels=int(n_mels)), ctypes.byref(cfg))
+        self.hop = int(lib().gtts_voc_hop(self._h))
 
     @classmethod
     def from_config(cls, h):
@@ -659,58 +663,16 @@ class Vocoder:
         return cls(h["upsample_rates"], h["upsample_kernel_sizes"], h["upsample_initial_channel"],
                    h["resblock_kernel_sizes"], h["resblock_dilation_sizes"], h["resblock"], h.get("num_mels", 80))
 
-    def __reduce__(self):
-        return (_rebuild_voc, (self._kw,))
-
-    def __deepcopy__(self, memo):
-        return Vocoder(**self._kw)
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().gtts_voc_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def param_layout(self):
-        L = lib()
-        out = []
-        for k in range(L.gtts_voc_num_params(self._h)):
-            name, rank, dims = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int * 4)()
-            _check(L.gtts_voc_param_info(self._h, k, ctypes.byref(name), ctypes.byref(rank), ctypes.byref(dims)),
-                   "gtts_voc_param_info")
-            out.append((name.value.decode(), tuple(dims[:rank.value])))
-        return out
-
     def pack(self, state, device):
         """state: name -> tensor with weight normalisation folded (`<module>.weight`, `<module>.bias`)."""
-        keep = []
-        for name, shape in self.param_layout():
-            if name not in state:
-                raise RuntimeError("state_dict is missing '%s' (call remove_weight_norm() or fold weight_g / weight_v)" % name)
-            t = state[name].detach().to(device=device, dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise RuntimeError("parameter %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            keep.append(t)
-        arr = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-        blob = torch.empty(int(lib().gtts_voc_packed_bytes(self._h)), dtype=torch.uint8, device=device)
-        with torch.cuda.device(blob.device):
-            _check(lib().gtts_voc_pack(self._h, arr, len(keep), _ptr(blob), _stream()), "gtts_voc_pack")
-            torch.cuda.current_stream().synchronize()
-        return blob
+        return self._pack(self._params(state, device, " (call remove_weight_norm() or fold weight_g / weight_v)"), device)
 
     def forward(self, blob, mel):
         mel = _f32c(mel, "mel")
         B, F, T = mel.shape
         if F != self.cfg.n_mels:
             raise RuntimeError("expected %d mel bins, got %d" % (self.cfg.n_mels, F))
-        key = (B, T, str(mel.device))
-        ws = self._ws.get(key)
-        if ws is None:
-            self._ws.clear()
-            ws = torch.empty(int(lib().gtts_voc_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=mel.device)
-            self._ws[key] = ws
+        ws = self.workspace(B, T, mel.device)
         wav = torch.empty((B, 1, T * self.hop), dtype=torch.float32, device=mel.device)
         with torch.cuda.device(mel.device):
             _check(lib().gtts_voc_forward(self._h, _ptr(blob), _ptr(mel), _ptr(wav), _ptr(ws), ws.numel(), B, T, _stream()),
@@ -718,74 +680,23 @@ class Vocoder:
         return wav
 
 
-class Encoder:
+class Encoder(_Native):
     """Grad-TTS TextEncoder (mode 'text') / DiffVC MelEncoder (mode 'mel') on the HIP kernels (csrc/enc.hip)."""
+    _family = "enc"
 
     def __init__(self, mode="text", n_vocab=149, n_feats=80, channels=192, filter_channels=768, filter_channels_dp=256,
                  n_heads=2, n_layers=6, kernel_size=3, window_size=4):
-        self._kw = dict(mode=mode, n_vocab=n_vocab, n_feats=n_feats, channels=channels, filter_channels=filter_channels,
-                        filter_channels_dp=filter_channels_dp, n_heads=n_heads, n_layers=n_layers, kernel_size=kernel_size,
-                        window_size=window_size)
         self.mode = mode
         self.cfg = EncCfg({"text": 0, "mel": 1}[mode], int(n_vocab), int(n_feats), int(channels), int(filter_channels),
                           int(filter_channels_dp), int(n_heads), int(n_layers), int(kernel_size), int(window_size or 0))
-        self._h = ctypes.c_void_p()
-        _check(lib().gtts_enc_create(ctypes.byref(self.cfg), ctypes.byref(self._h)), "gtts_enc_create")
-        self._ws = {}
-
-    def __reduce__(self):
-        return (_rebuild_enc, (self._kw,))
-
-    def __deepcopy__(self, memo):
-        return Encoder(**self._kw)
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().gtts_enc_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def param_layout(self):
-        L = lib()
-        out = []
-        for k in range(L.gtts_enc_num_params(self._h)):
-            name, rank, dims = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int * 4)()
-            _check(L.gtts_enc_param_info(self._h, k, ctypes.byref(name), ctypes.byref(rank), ctypes.byref(dims)),
-                   "gtts_enc_param_info")
-            out.append((name.value.decode(), tuple(dims[:rank.value])))
-        return out
-
-    def pack(self, state, device):
-        keep = []
-        for name, shape in self.param_layout():
-            if name not in state:
-                raise RuntimeError("state_dict is missing '%s'" % name)
-            t = state[name].detach().to(device=device, dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise RuntimeError("parameter %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            keep.append(t)
-        arr = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-        blob = torch.empty(int(lib().gtts_enc_packed_bytes(self._h)), dtype=torch.uint8, device=device)
-        with torch.cuda.device(blob.device):
-            _check(lib().gtts_enc_pack(self._h, arr, len(keep), _ptr(blob), _stream()), "gtts_enc_pack")
-            torch.cuda.current_stream().synchronize()
-        return blob
+        self._open(dict(mode=mode, n_vocab=n_vocab, n_feats=n_feats, channels=channels, filter_channels=filter_channels,
+                        filter_channels_dp=filter_channels_dp, n_heads=n_heads, n_layers=n_layers, kernel_size=kernel_size,
+                        window_size=window_size), ctypes.byref(self.cfg))
 
     def attention_path(self, L):
         """Which attention kernel forward() runs at sequence length L: 16 (16 queries per workgroup), 8 (the 8-query kernel: long
         sequences, windows above 7, head widths not divisible by 4) or 0 (forward() refuses L: no kernel holds its probabilities)."""
         return int(lib().gtts_enc_attention_path(self._h, int(L)))
-
-    def _workspace(self, B, L, device):
-        key = (B, L, str(device))
-        ws = self._ws.get(key)
-        if ws is None:
-            self._ws.clear()
-            ws = torch.empty(int(lib().gtts_enc_workspace_bytes(self._h, B, L)), dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
 
     def forward(self, blob, x, x_mask):
         """text: x = ids [B,L] int64 -> (mu [B,n_feats,L], logw [B,1,L]);  mel: x = mel [B,n_feats,L] -> [B,n_feats,L].
@@ -806,62 +717,20 @@ class Encoder:
         dev = x.device
         mu = torch.empty((B, self.cfg.n_feats, L), dtype=torch.float32, device=dev)
         logw = torch.empty((B, 1, L), dtype=torch.float32, device=dev) if self.mode == "text" else None
-        ws = self._workspace(B, L, dev)
+        ws = self.workspace(B, L, dev)
         with torch.cuda.device(dev):
             _check(lib().gtts_enc_forward(self._h, _ptr(blob), _ptr(ids), _ptr(mel), _ptr(m), _ptr(mu), _ptr(logw), _ptr(ws),
                                           ws.numel(), B, L, _stream()), "gtts_enc_forward")
         return (mu, logw) if self.mode == "text" else mu
 
 
-class PostNetPlan:
+class PostNetPlan(_Native):
     """DiffVC PostNet (DiffVC/model/postnet.py:40-53) on the HIP kernels (csrc/postnet.hip)."""
+    _family = "postnet"
 
     def __init__(self, dim=128, n_feats=80, groups=8):
-        self._kw = dict(dim=int(dim), n_feats=int(n_feats), groups=int(groups))
         self.dim, self.n_feats = int(dim), int(n_feats)
-        self._h = ctypes.c_void_p()
-        _check(lib().gtts_postnet_create(int(dim), int(n_feats), int(groups), ctypes.byref(self._h)), "gtts_postnet_create")
-        self._ws = {}
-
-    def __reduce__(self):
-        return (_rebuild_postnet, (self._kw,))
-
-    def __deepcopy__(self, memo):
-        return PostNetPlan(**self._kw)
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().gtts_postnet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
-    def param_layout(self):
-        L = lib()
-        out = []
-        for k in range(L.gtts_postnet_num_params(self._h)):
-            name, rank, dims = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int * 4)()
-            _check(L.gtts_postnet_param_info(self._h, k, ctypes.byref(name), ctypes.byref(rank), ctypes.byref(dims)),
-                   "gtts_postnet_param_info")
-            out.append((name.value.decode(), tuple(dims[:rank.value])))
-        return out
-
-    def pack(self, state, device):
-        keep = []
-        for name, shape in self.param_layout():
-            if name not in state:
-                raise RuntimeError("state_dict is missing '%s'" % name)
-            t = state[name].detach().to(device=device, dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise RuntimeError("parameter %s has shape %s, expected %s" % (name, tuple(t.shape), shape))
-            keep.append(t)
-        arr = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-        blob = torch.empty(int(lib().gtts_postnet_packed_bytes(self._h)), dtype=torch.uint8, device=device)
-        with torch.cuda.device(blob.device):
-            _check(lib().gtts_postnet_pack(self._h, arr, len(keep), _ptr(blob), _stream()), "gtts_postnet_pack")
-            torch.cuda.current_stream().synchronize()
-        return blob
+        self._open(dict(dim=int(dim), n_feats=int(n_feats), groups=int(groups)), int(dim), int(n_feats), int(groups))
 
     def forward(self, blob, x, mask):
         """x [B,n_feats,T], mask [B,1,T] -> [B,n_feats,T]."""
@@ -869,33 +738,12 @@ class PostNetPlan:
         B, F, T = x.shape
         if F != self.n_feats or mask.numel() != B * T:
             raise RuntimeError("shape mismatch: x %s mask %s" % (tuple(x.shape), tuple(mask.shape)))
-        key = (B, T, str(x.device))
-        ws = self._ws.get(key)
-        if ws is None:
-            self._ws.clear()
-            ws = torch.empty(int(lib().gtts_postnet_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=x.device)
-            self._ws[key] = ws
+        ws = self.workspace(B, T, x.device)
         out = torch.empty_like(x)
         with torch.cuda.device(x.device):
             _check(lib().gtts_postnet_forward(self._h, _ptr(blob), _ptr(x), _ptr(mask), _ptr(out), _ptr(ws), ws.numel(), B, T,
                                               _stream()), "gtts_postnet_forward")
         return out
-
-
-def _rebuild_postnet(kw):
-    return PostNetPlan(**kw)
-
-
-def _rebuild_enc(kw):
-    return Encoder(**kw)
-
-
-def _rebuild_voc(kw):
-    return Vocoder(**kw)
-
-
-def _rebuild_plan(kw):
-    return Plan(**kw)
 
 
 def euler_step(xt, mu, est, mask, beta_t, h, noise=None):
@@ -916,22 +764,16 @@ def mas_maximum_path(value, mask):
     HIP tensors run the GPU kernel.  Host tensors run the library's C++ twin gtts_mas_maximum_path_cpu -- the
     reference's wrapper accepts tensors on any device and always runs its Cython kernel on the host
     (monotonic_align/__init__.py:8-23); both are bit-identical to it."""
-    if not value.is_cuda:
-        v = value.detach().float().contiguous()
-        m = mask.detach().to(dtype=torch.float32).contiguous()
-        b, tx, ty = v.shape
-        t_x = m.sum(1)[:, 0].to(torch.int32).contiguous()
-        t_y = m.sum(2)[:, 0].to(torch.int32).contiguous()
-        path = torch.empty((b, tx, ty), dtype=torch.int32)
-        _check(lib().gtts_mas_maximum_path_cpu(_ptr(v), _ptr(m), _ptr(t_x), _ptr(t_y), _ptr(path), b, tx, ty),
-               "gtts_mas_maximum_path_cpu")
-        return path.to(dtype=value.dtype)
     v = value.detach().float().contiguous()
     m = mask.detach().to(device=v.device, dtype=torch.float32).contiguous()
     b, tx, ty = v.shape
     t_x = m.sum(1)[:, 0].to(torch.int32).contiguous()       # __init__.py:20-21
     t_y = m.sum(2)[:, 0].to(torch.int32).contiguous()
     path = torch.empty((b, tx, ty), dtype=torch.int32, device=v.device)
+    if not v.is_cuda:
+        _check(lib().gtts_mas_maximum_path_cpu(_ptr(v), _ptr(m), _ptr(t_x), _ptr(t_y), _ptr(path), b, tx, ty),
+               "gtts_mas_maximum_path_cpu")
+        return path.to(dtype=value.dtype)
     scratch = torch.empty(int(lib().gtts_mas_scratch_bytes(b, tx, ty)), dtype=torch.uint8, device=v.device)
     with torch.cuda.device(v.device):
         _check(lib().gtts_mas_maximum_path(_ptr(v), _ptr(m), _ptr(t_x), _ptr(t_y), _ptr(path), _ptr(scratch), b, tx,
@@ -948,17 +790,20 @@ def conv_size_ok(B, cin, cout, H, W):
     return int(B) * max(int(cin), int(cout)) * int(H) * int(W) < _MAX_TENSOR_ELEMS
 
 
+def _tiles(c):
+    """Whole output tiles of the MFMA convolution kernels: 64 channels, or a multiple of 128."""
+    return c == 64 or (c > 64 and c % 128 == 0)
+
+
 def conv3x3_supported(cin, cout, need_dgrad=True, shape=None):
     """Channel counts (and, with shape = (B, H, W), tensor sizes) the training conv kernels take (forward / data gradient /
     weight gradient).  The first layer (the stacked 2- or 3-plane input, no data gradient wanted) has its own weight-gradient
     kernel."""
-    def tiles(c):
-        return c == 64 or (c > 64 and c % 128 == 0)
     if shape is not None and not conv_size_ok(shape[0], cin, cout, shape[1], shape[2]):
         return False
     if cin in (2, 3) and not need_dgrad:
-        return tiles(cout)
-    return cin % 32 == 0 and cout % 32 == 0 and tiles(cin) and tiles(cout)
+        return _tiles(cout)
+    return cin % 32 == 0 and cout % 32 == 0 and _tiles(cin) and _tiles(cout)
 
 
 _PACKED = {}       # (id(weight), transposed, kind) -> (weakref to the weight, its version, pack generation, packed blob)
@@ -1011,10 +856,6 @@ def _packed_weight(weight, cin, cout, transposed, kind):
             _PACKED.clear()
     _PACKED[key] = (weakref.ref(weight), int(weight._version), _PACK_GEN, packed)
     return packed
-
-
-def _packed_conv3x3(weight, cin, cout, transposed):
-    return _packed_weight(weight, cin, cout, transposed, "3x3")
 
 
 _KIND_CODE = {"3x3": 0, "1x1": 1, "dn": 2, "up": 3, "dn_T": 4}
@@ -1094,7 +935,7 @@ def _conv3x3_run(x, mask_cols, weight, bias, transposed, x1=None, out_mask=None)
     L = lib()
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
     with _on(x.device):
-        packed = _packed_conv3x3(weight, cin, cout, transposed)
+        packed = _packed_weight(weight, cin, cout, transposed, "3x3")
         _check(L.gtts_conv3x3_masked3(_ptr(x), _ptr(x1), c0, _ptr(mask_cols), _ptr(out_mask), _ptr(packed), _ptr(bias), _ptr(y), B, cin,
                                       cout, H, W, _stream()), "gtts_conv3x3_masked")
     return y
@@ -1231,17 +1072,11 @@ def postnet_chan_dot(a, v, mask, want_dot=True, want_sum=True):
 def conv1x1_supported(cin, cout, need_dgrad=True, shape=None):
     """Channel counts (and, with shape = (B, H, W), tensor sizes) the 1x1 training kernels take: forward cout (and, for the
     data gradient, cin) a whole number of the kernel's output tiles; the weight gradient whole 64 x 64 tiles."""
-    def tiles(c):
-        return c == 64 or (c > 64 and c % 128 == 0)
     if shape is not None and not conv_size_ok(shape[0], cin, cout, shape[1], shape[2]):
         return False
     if cin in (2, 3) and not need_dgrad:          # first layer: own weight-gradient kernel
-        return tiles(cout)
-    return tiles(cout) and cin % 64 == 0 and (tiles(cin) or not need_dgrad)
-
-
-def _packed_conv1x1(weight, cin, cout, transposed):
-    return _packed_weight(weight, cin, cout, transposed, "1x1")
+        return _tiles(cout)
+    return _tiles(cout) and cin % 64 == 0 and (_tiles(cin) or not need_dgrad)
 
 
 def _conv1x1_run(x, mask_cols, weight, bias, transposed):
@@ -1249,7 +1084,7 @@ def _conv1x1_run(x, mask_cols, weight, bias, transposed):
     cout = weight.shape[1] if transposed else weight.shape[0]
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
     with _on(x.device):
-        packed = _packed_conv1x1(weight, cin, cout, transposed)
+        packed = _packed_weight(weight, cin, cout, transposed, "1x1")
         _check(lib().gtts_conv1x1_masked(_ptr(x), _ptr(mask_cols), _ptr(packed), _ptr(bias), _ptr(y), B, cin, cout, H, W, _stream()),
                "gtts_conv1x1_masked")
     return y
@@ -1362,12 +1197,10 @@ def final_conv_backward(x, weight, mask_cols, dout):
 
 
 def resample_supported(cin, cout, H, W, up, B=1):
-    def tiles(c):
-        return c == 64 or (c > 64 and c % 128 == 0)
     # largest tensor of the call and of its gradients: Upsample's output (and its space_to_depth planes) is 4 cout planes of H x W
     if not conv_size_ok(B, 4 * max(cin, cout) if up else max(cin, cout), 1, H, W):
         return False
-    return tiles(cin) and tiles(cout) and (up or (H % 2 == 0 and W % 2 == 0))
+    return _tiles(cin) and _tiles(cout) and (up or (H % 2 == 0 and W % 2 == 0))
 
 
 def conv_resample(x, mask_cols, weight, bias, up, dgrad_of_down=False):

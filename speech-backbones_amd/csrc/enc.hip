@@ -10,7 +10,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -302,20 +301,6 @@ __global__ __launch_bounds__(256) void enc_attention16_kernel(const float *__res
 
 using namespace gtts;
 
-static int efail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-#define ECHK(expr)                                                                                                \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return efail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 struct EncParam { std::string name; int rank; int dims[4]; int kind; int cin, cout, K; size_t off; };   // kind 0 fp32 copy, 1 conv1d
 struct gtts_enc {
     gtts_enc_cfg cfg;
@@ -326,7 +311,6 @@ struct gtts_enc {
         return -1;
     }
 };
-static size_t ealign(size_t x) { return (x + 255) / 256 * 256; }
 static void enc_add(gtts_enc *e, const std::string &name, std::vector<int> dims, int kind, int cin = 0, int cout = 0, int K = 0) {
     EncParam p;
     p.name = name; p.rank = (int)dims.size(); p.kind = kind; p.cin = cin; p.cout = cout; p.K = K;
@@ -334,7 +318,7 @@ static void enc_add(gtts_enc *e, const std::string &name, std::vector<int> dims,
     size_t n = 1;
     for (int d : dims) n *= (size_t)d;
     p.off = e->blob_bytes;
-    e->blob_bytes = ealign(e->blob_bytes + (kind == 1 ? conv1d_packed_bytes(0, cin, cout, K, 1) : n * 4));
+    e->blob_bytes = align256(e->blob_bytes + (kind == 1 ? conv1d_packed_bytes(0, cin, cout, K, 1) : n * 4));
     e->params.push_back(p);
 }
 static void enc_add_conv(gtts_enc *e, const std::string &name, int cin, int cout, int K) {
@@ -348,11 +332,11 @@ static void enc_add_ln(gtts_enc *e, const std::string &name, int C) {
 
 // parameters in the reference's registration order (text_encoder.py:296-309 / DiffVC encoder.py:270-278)
 extern "C" int gtts_enc_create(const gtts_enc_cfg *cfg, gtts_enc **out) {
-    if (!cfg || !out) return efail(GTTS_E_NULL, "gtts_enc_create: null argument");
-    if (cfg->mode != 0 && cfg->mode != 1) return efail(GTTS_E_CONFIG, "mode must be 0 (TextEncoder) or 1 (MelEncoder)");
+    if (!cfg || !out) return fail(GTTS_E_NULL, "gtts_enc_create: null argument");
+    if (cfg->mode != 0 && cfg->mode != 1) return fail(GTTS_E_CONFIG, "mode must be 0 (TextEncoder) or 1 (MelEncoder)");
     if (cfg->channels <= 0 || cfg->n_heads <= 0 || cfg->channels % cfg->n_heads || cfg->n_layers < 0 || cfg->kernel_size % 2 == 0 ||
         cfg->kernel_size > 11 || cfg->window_size < 0 || cfg->n_feats <= 0)
-        return efail(GTTS_E_CONFIG, "unsupported encoder configuration");
+        return fail(GTTS_E_CONFIG, "unsupported encoder configuration");
     gtts_enc *e = new gtts_enc();
     e->cfg = *cfg;
     const int C = cfg->channels, dk = C / cfg->n_heads;
@@ -407,8 +391,8 @@ extern "C" int gtts_enc_create(const gtts_enc_cfg *cfg, gtts_enc **out) {
 extern "C" void gtts_enc_destroy(gtts_enc *e) { delete e; }
 extern "C" int gtts_enc_num_params(const gtts_enc *e) { return e ? (int)e->params.size() : 0; }
 extern "C" int gtts_enc_param_info(const gtts_enc *e, int i, const char **name, int *rank, int dims[4]) {
-    if (!e) return efail(GTTS_E_NULL, "null encoder");
-    if (i < 0 || i >= (int)e->params.size()) return efail(GTTS_E_SHAPE, "parameter index out of range");
+    if (!e) return fail(GTTS_E_NULL, "null encoder");
+    if (i < 0 || i >= (int)e->params.size()) return fail(GTTS_E_SHAPE, "parameter index out of range");
     const EncParam &p = e->params[i];
     if (name) *name = p.name.c_str();
     if (rank) *rank = p.rank;
@@ -417,20 +401,20 @@ extern "C" int gtts_enc_param_info(const gtts_enc *e, int i, const char **name, 
 }
 extern "C" size_t gtts_enc_packed_bytes(const gtts_enc *e) { return e ? e->blob_bytes : 0; }
 extern "C" int gtts_enc_pack(const gtts_enc *e, const void *const *ptrs, int n_params, void *packed, gtts_stream_t stream) {
-    if (!e || !ptrs || !packed) return efail(GTTS_E_NULL, "gtts_enc_pack: null argument");
-    if (n_params != (int)e->params.size()) return efail(GTTS_E_PARAMS, "expected %d parameters, got %d", (int)e->params.size(), n_params);
+    if (!e || !ptrs || !packed) return fail(GTTS_E_NULL, "gtts_enc_pack: null argument");
+    if (n_params != (int)e->params.size()) return fail(GTTS_E_PARAMS, "expected %d parameters, got %d", (int)e->params.size(), n_params);
     hipStream_t st = (hipStream_t)stream;
     unsigned char *blob = (unsigned char *)packed;
-    ECHK(hipMemsetAsync(blob, 0, e->blob_bytes, st));
+    GTTS_HIPCHK(hipMemsetAsync(blob, 0, e->blob_bytes, st));
     for (int i = 0; i < n_params; ++i) {
         const EncParam &p = e->params[i];
-        if (!ptrs[i]) return efail(GTTS_E_NULL, "parameter %s is null", p.name.c_str());
+        if (!ptrs[i]) return fail(GTTS_E_NULL, "parameter %s is null", p.name.c_str());
         if (p.kind == 1) {
-            ECHK(launch_pack_conv1d((const float *)ptrs[i], blob + p.off, 0, p.cin, p.cout, p.K, 1, 0, st));
+            GTTS_HIPCHK(launch_pack_conv1d((const float *)ptrs[i], blob + p.off, 0, p.cin, p.cout, p.K, 1, 0, st));
         } else {
             size_t n = 1;
             for (int k = 0; k < p.rank; ++k) n *= (size_t)p.dims[k];
-            ECHK(hipMemcpyAsync(blob + p.off, ptrs[i], n * 4, hipMemcpyDeviceToDevice, st));
+            GTTS_HIPCHK(hipMemcpyAsync(blob + p.off, ptrs[i], n * 4, hipMemcpyDeviceToDevice, st));
         }
     }
     return GTTS_OK;
@@ -452,7 +436,7 @@ static int enc_attention_path(const gtts_enc_cfg &cf, int L) {
 extern "C" int gtts_enc_attention_path(const gtts_enc *e, int L) { return e ? enc_attention_path(e->cfg, L) : 0; }
 
 // workspace: X, Y, Z (C channels), Q, K, V, A (C channels), H (max(filter, filter_dp) channels)
-static size_t enc_slot(const gtts_enc *e, int B, int L, int ch) { return ealign((size_t)B * ch * L * 4); }
+static size_t enc_slot(const gtts_enc *e, int B, int L, int ch) { return align256((size_t)B * ch * L * 4); }
 extern "C" size_t gtts_enc_workspace_bytes(const gtts_enc *e, int B, int L) {
     if (!e || B <= 0 || L <= 0) return 0;
     const int C = e->cfg.channels;
@@ -475,7 +459,7 @@ static const float *bp(const EncRun &r, const std::string &name) {
 static int enc_conv(const EncRun &r, const std::string &name, const float *x, float *out, bool in_mask, bool relu_in,
                     const float *res, bool out_mask) {
     const int wi = r.e->find(name + ".weight"), bi = r.e->find(name + ".bias");
-    if (wi < 0 || bi < 0) return efail(GTTS_E_CONFIG, "encoder has no layer %s", name.c_str());
+    if (wi < 0 || bi < 0) return fail(GTTS_E_CONFIG, "encoder has no layer %s", name.c_str());
     const EncParam &p = r.e->params[wi];
     C1Args a;
     a.x = x; a.out = out; a.res = res; a.accsrc = nullptr; a.accmode = 0; a.div = 1.f;
@@ -485,16 +469,16 @@ static int enc_conv(const EncRun &r, const std::string &name, const float *x, fl
     a.in_mask = in_mask ? r.mask : nullptr;
     a.out_mask = out_mask ? r.mask : nullptr;
     const hipError_t e = launch_conv1d(a, 0, p.K, 1, r.st);
-    if (e != hipSuccess) return efail(GTTS_E_HIP, "conv1d %s: %s", name.c_str(), hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv1d %s: %s", name.c_str(), hipGetErrorString(e));
     return GTTS_OK;
 }
 static int enc_ln(const EncRun &r, const std::string &name, const float *a, const float *bres, float *out, int C, bool a_mask,
                   bool relu_in, bool relu_out) {
     const float *g = bp(r, name + ".gamma"), *b = bp(r, name + ".beta");
-    if (!g || !b) return efail(GTTS_E_CONFIG, "encoder has no layer %s", name.c_str());
+    if (!g || !b) return fail(GTTS_E_CONFIG, "encoder has no layer %s", name.c_str());
     hipLaunchKernelGGL(enc_layernorm_kernel, dim3((r.L + 15) / 16, r.B), dim3(256), 0, r.st, a, bres, g, b, a_mask ? r.mask : nullptr,
                        (const float *)nullptr, out, C, r.L, 1e-4f, relu_in ? 1 : 0, relu_out ? 1 : 0);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -502,15 +486,15 @@ static int enc_ln(const EncRun &r, const std::string &name, const float *a, cons
 //   mode 0: ids [B,L] int64 -> mu [B,n_feats,L], logw [B,1,L];   mode 1: mel [B,n_feats,L] -> out [B,n_feats,L] (in `mu`)
 extern "C" int gtts_enc_forward(const gtts_enc *e, const void *packed, const long long *ids, const float *mel, const float *x_mask,
                                 float *mu, float *logw, void *workspace, size_t workspace_bytes, int B, int L, gtts_stream_t stream) {
-    if (!e || !packed || !x_mask || !mu || !workspace) return efail(GTTS_E_NULL, "gtts_enc_forward: null argument");
-    if (B <= 0 || L <= 0) return efail(GTTS_E_SHAPE, "gtts_enc_forward: bad shape B=%d L=%d", B, L);
+    if (!e || !packed || !x_mask || !mu || !workspace) return fail(GTTS_E_NULL, "gtts_enc_forward: null argument");
+    if (B <= 0 || L <= 0) return fail(GTTS_E_SHAPE, "gtts_enc_forward: bad shape B=%d L=%d", B, L);
     const gtts_enc_cfg &cf = e->cfg;
-    if (cf.mode == 0 && (!ids || !logw)) return efail(GTTS_E_NULL, "TextEncoder needs ids and logw");
-    if (cf.mode == 1 && !mel) return efail(GTTS_E_NULL, "MelEncoder needs mel");
-    if (workspace_bytes < gtts_enc_workspace_bytes(e, B, L)) return efail(GTTS_E_WORKSPACE, "workspace too small");
+    if (cf.mode == 0 && (!ids || !logw)) return fail(GTTS_E_NULL, "TextEncoder needs ids and logw");
+    if (cf.mode == 1 && !mel) return fail(GTTS_E_NULL, "MelEncoder needs mel");
+    if (workspace_bytes < gtts_enc_workspace_bytes(e, B, L)) return fail(GTTS_E_WORKSPACE, "workspace too small");
     const int C = cf.channels, dk = C / cf.n_heads;
     const int path = enc_attention_path(cf, L);
-    if (!path) return efail(GTTS_E_SHAPE, "sequence too long for the attention kernel (%d)", L);
+    if (!path) return fail(GTTS_E_SHAPE, "sequence too long for the attention kernel (%d)", L);
     hipStream_t st = (hipStream_t)stream;
     EncRun r{e, (const unsigned char *)packed, x_mask, B, L, st};
     unsigned char *ws = (unsigned char *)workspace;
@@ -523,7 +507,7 @@ extern "C" int gtts_enc_forward(const gtts_enc *e, const void *packed, const lon
     if (cf.mode == 0) {
         hipLaunchKernelGGL(enc_embed_kernel, dim3((L + 255) / 256, C, B), dim3(256), 0, st, ids, bp(r, "emb.weight"), X, C, L, cf.n_vocab,
                            sqrtf((float)C));
-        ECHK(hipGetLastError());
+        GTTS_HIPCHK(hipGetLastError());
     } else {
         if ((rc = enc_conv(r, "init_proj", mel, X, true, false, nullptr, false))) return rc;          // init_proj(x * x_mask)
     }
@@ -552,16 +536,16 @@ extern "C" int gtts_enc_forward(const gtts_enc *e, const void *packed, const lon
         if (path == 16) {
             const size_t smem16 = att16_smem_bytes(dk, L);
             // 16 queries per workgroup, lanes along the keys (two workgroups per CU up to L ~ 1000)
-            ECHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&enc_attention16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem16));
+            GTTS_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&enc_attention16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem16));
             hipLaunchKernelGGL(enc_attention16_kernel, dim3((L + ATT16_QT - 1) / ATT16_QT, cf.n_heads, B), dim3(256), smem16, st, Q, K, V,
                                x_mask, ek, ev, A, C, L, cf.n_heads, win);
         } else {
             const size_t smem = (size_t)(ATT_QT * dk + ATT_QT * L) * 4;
-            ECHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&enc_attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            GTTS_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&enc_attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
             hipLaunchKernelGGL(enc_attention_kernel, dim3((L + ATT_QT - 1) / ATT_QT, cf.n_heads, B), dim3(256), smem, st, Q, K, V, x_mask,
                                ek, ev, A, C, L, cf.n_heads, win);
         }
-        ECHK(hipGetLastError());
+        GTTS_HIPCHK(hipGetLastError());
         if ((rc = enc_conv(r, p + "conv_o", A, Z, false, false, nullptr, false))) return rc;
         snprintf(nm, sizeof nm, "encoder.norm_layers_1.%d", i);
         if ((rc = enc_ln(r, nm, x, Z, t1, C, true, false, false))) return rc;                          // LN(x * mask + y)

@@ -4,8 +4,17 @@
 
 namespace gtts {
 
-// error text of the calling thread (plan.hip; returned by gtts_last_error)
-int set_error(int code, const char *msg);
+// sets the error text of the calling thread (plan.hip; returned by gtts_last_error) and returns `code`
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+#define GTTS_HIPCHK(expr)                                                                                                 \
+    do {                                                                                                                  \
+        hipError_t e_ = (expr);                                                                                           \
+        if (e_ != hipSuccess)                                                                                             \
+            return gtts::fail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);     \
+    } while (0)
+
+// blob and workspace sections start on 256-byte boundaries
+static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
 // ---- misc.hip
 struct TimeMlpDesc {

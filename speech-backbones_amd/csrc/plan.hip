@@ -25,7 +25,7 @@ using namespace gtts;
 
 // ------------------------------------------------------------------------------------------------ errors
 static thread_local std::string g_err;
-static int fail(int code, const char *fmt, ...) {
+int gtts::fail(int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -34,17 +34,7 @@ static int fail(int code, const char *fmt, ...) {
     g_err = buf;
     return code;
 }
-namespace gtts {
-int set_error(int code, const char *msg) { g_err = msg; return code; }     // for the other translation units
-}
-#define HIPCHK(expr)                                                                                        \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return fail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                          __FILE__, __LINE__);                                              \
-    } while (0)
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 struct gtts_plan;
 static int plan_nsplit(const gtts_plan *p);      // 2: hi/lo operand planes (BF16X3, and everything F16F8 leaves on it), 1: plain bf16
 
@@ -166,10 +156,10 @@ static int add_param(gtts_plan *p, const std::string &name, std::vector<int> dim
         case 4: bytes = conv_packed_bytes(CONV_P1, cin, cout); break;
         case 5: bytes = attn_kv_packed_bytes(cin); break;
     }
-    p->blob_bytes = align_up(p->blob_bytes + bytes, 256);
+    p->blob_bytes = align256(p->blob_bytes + bytes);
     if (pack == 5) {
         d.off2 = p->blob_bytes;
-        p->blob_bytes = align_up(p->blob_bytes + (size_t)128 * cin * 4, 256);
+        p->blob_bytes = align256(p->blob_bytes + (size_t)128 * cin * 4);
     }
     p->pidx[name] = (int)p->params.size();
     p->params.push_back(d);
@@ -277,7 +267,7 @@ static int add_attn(gtts_plan *p, const std::string &name, int src, int C, int l
     const int apart = add_tensor(p, name + ".apart", TK_APART, C, lvl);
     const int ctxn = add_tensor(p, name + ".ctx", TK_PERB, 4096, 0);
     const int wpk = add_tensor(p, name + ".wfold", TK_BYTES_PERB, 0, 0);
-    p->tensors[wpk].bytes = align_up(conv_packed_bytes(CONV_P1, C, C), 256);
+    p->tensors[wpk].bytes = align256(conv_packed_bytes(CONV_P1, C, C));
     const int biasb = add_tensor(p, name + ".bfold", TK_PERB, C, 0);
     const int out = add_tensor(p, name + ".out", TK_ACT, C, lvl);
     const ParamDesc &qkv = p->params[p->pidx.at(pre + "fn.fn.to_qkv.weight")];
@@ -378,7 +368,7 @@ extern "C" int gtts_plan_create(const gtts_unet_cfg *cfg, gtts_plan **out) {
 
     // blob: frequencies first
     p->freq_off = p->blob_bytes;
-    p->blob_bytes = align_up(p->blob_bytes + (size_t)(dim / 2) * 4, 256);
+    p->blob_bytes = align256(p->blob_bytes + (size_t)(dim / 2) * 4);
     p->status_off = p->blob_bytes;
     p->blob_bytes += 256;
     // ---- parameters in the reference's registration order (diffusion.py:139-172)
@@ -580,10 +570,10 @@ extern "C" int gtts_plan_set_streams(gtts_plan *plan, const gtts_stream_t *strea
     if (n > 0 && !streams) return fail(GTTS_E_NULL, "gtts_plan_set_streams: null stream array");
     std::lock_guard<std::mutex> lk(plan->mu);
     for (int h = 0; h < n; ++h) {
-        if (!plan->ev_join[h]) HIPCHK(hipEventCreateWithFlags(&plan->ev_join[h], hipEventDisableTiming));
+        if (!plan->ev_join[h]) GTTS_HIPCHK(hipEventCreateWithFlags(&plan->ev_join[h], hipEventDisableTiming));
         plan->sub[h] = (hipStream_t)streams[h];
     }
-    if (n > 0 && !plan->ev_fork) HIPCHK(hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming));
+    if (n > 0 && !plan->ev_fork) GTTS_HIPCHK(hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming));
     plan->nsub = n;
     return GTTS_OK;
 }
@@ -643,8 +633,8 @@ extern "C" int gtts_pack_weights(const gtts_plan *plan, const void *const *param
     if (n_params != (int)plan->params.size()) return fail(GTTS_E_PARAMS, "expected %d parameters, got %d", (int)plan->params.size(), n_params);
     hipStream_t st = (hipStream_t)stream;
     unsigned char *blob = (unsigned char *)packed;
-    HIPCHK(hipMemsetAsync(blob, 0, plan->blob_bytes, st));
-    HIPCHK(launch_copy_f32(freq, (float *)(blob + plan->freq_off), plan->cfg.dim / 2, st));
+    GTTS_HIPCHK(hipMemsetAsync(blob, 0, plan->blob_bytes, st));
+    GTTS_HIPCHK(launch_copy_f32(freq, (float *)(blob + plan->freq_off), plan->cfg.dim / 2, st));
     std::vector<int> order = reg_order(plan);
     for (int i = 0; i < n_params; ++i) {
         const ParamDesc &d = plan->params[order[i]];
@@ -653,16 +643,16 @@ extern "C" int gtts_pack_weights(const gtts_plan *plan, const void *const *param
         size_t n = 1;
         for (int k = 0; k < d.rank; ++k) n *= (size_t)d.dims[k];
         switch (d.pack) {
-            case 0: HIPCHK(launch_copy_f32(src, (float *)(blob + d.off), n, st)); break;
-            case 1: HIPCHK(launch_pack_conv(CONV_C3, src, blob + d.off, d.cin, d.cout, st)); break;
-            case 2: HIPCHK(launch_pack_conv(CONV_DN, src, blob + d.off, d.cin, d.cout, st)); break;
-            case 3: HIPCHK(launch_pack_conv(CONV_UP, src, blob + d.off, d.cin, d.cout, st)); break;
-            case 7: HIPCHK(launch_pack_conv(CONV_UP | 32, src, blob + d.off, d.cin, d.cout, st, (unsigned *)(blob + plan->status_off), (unsigned)i)); break;
-            case 4: HIPCHK(launch_pack_conv(CONV_P1, src, blob + d.off, d.cin, d.cout, st)); break;
-            case 6: HIPCHK(launch_pack_conv(CONV_C3 | 32, src, blob + d.off, d.cin, d.cout, st, (unsigned *)(blob + plan->status_off), (unsigned)i)); break;
+            case 0: GTTS_HIPCHK(launch_copy_f32(src, (float *)(blob + d.off), n, st)); break;
+            case 1: GTTS_HIPCHK(launch_pack_conv(CONV_C3, src, blob + d.off, d.cin, d.cout, st)); break;
+            case 2: GTTS_HIPCHK(launch_pack_conv(CONV_DN, src, blob + d.off, d.cin, d.cout, st)); break;
+            case 3: GTTS_HIPCHK(launch_pack_conv(CONV_UP, src, blob + d.off, d.cin, d.cout, st)); break;
+            case 7: GTTS_HIPCHK(launch_pack_conv(CONV_UP | 32, src, blob + d.off, d.cin, d.cout, st, (unsigned *)(blob + plan->status_off), (unsigned)i)); break;
+            case 4: GTTS_HIPCHK(launch_pack_conv(CONV_P1, src, blob + d.off, d.cin, d.cout, st)); break;
+            case 6: GTTS_HIPCHK(launch_pack_conv(CONV_C3 | 32, src, blob + d.off, d.cin, d.cout, st, (unsigned *)(blob + plan->status_off), (unsigned)i)); break;
             case 5:
-                HIPCHK(launch_pack_attn_kv(src, blob + d.off, d.cin, st));
-                HIPCHK(launch_copy_f32(src, (float *)(blob + d.off2), (size_t)128 * d.cin, st));   // q rows 0..127
+                GTTS_HIPCHK(launch_pack_attn_kv(src, blob + d.off, d.cin, st));
+                GTTS_HIPCHK(launch_copy_f32(src, (float *)(blob + d.off2), (size_t)128 * d.cin, st));   // q rows 0..127
                 break;
         }
     }
@@ -672,8 +662,8 @@ extern "C" int gtts_pack_weights(const gtts_plan *plan, const void *const *param
         // one call of the ABI synchronises its stream to read the count, so that a checkpoint outside the range is REFUSED here
         // instead of sampling silently at a lower grade.
         unsigned rec[3] = {0, 0, 0};
-        HIPCHK(hipMemcpyAsync(rec, blob + plan->status_off, sizeof(rec), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
+        GTTS_HIPCHK(hipMemcpyAsync(rec, blob + plan->status_off, sizeof(rec), hipMemcpyDeviceToHost, st));
+        GTTS_HIPCHK(hipStreamSynchronize(st));
         if (rec[0] != 0) {
             const float mx = __builtin_bit_cast(float, rec[1]);
             const int pi = (int)rec[2] - 1;
@@ -713,7 +703,7 @@ static Layout compute_layout(const gtts_plan *p, int B, int T, int rows, int Tr)
     const int n = (int)p->tensors.size();
     L.offsets.assign(n, 0);
     std::vector<size_t> sz(n);
-    for (int i = 0; i < n; ++i) sz[i] = align_up(tensor_bytes(p, p->tensors[i], B, T, rows, Tr), 256);
+    for (int i = 0; i < n; ++i) sz[i] = align256(tensor_bytes(p, p->tensors[i], B, T, rows, Tr));
     // 256 bytes of slack on both sides: the 16-byte halo loads of conv_ws.hip start one frame in front of a row and end up to
     // three frames behind it (those frames are masked out, but the addresses must be mapped)
     constexpr size_t PAD = 256;
@@ -772,7 +762,7 @@ extern "C" size_t gtts_workspace_bytes(const gtts_plan *plan, int B, int T) {
     const int parts = sampler_parts(plan, B);     // the sampler runs sub-batches side by side, each in its own slice
     if (parts > 1) {
         const int Bh = (B + parts - 1) / parts;
-        whole = std::max(whole, parts * align_up(compute_layout(plan, Bh, T, std::max(Bh, 4096), T).ws_bytes, 256));
+        whole = std::max(whole, parts * align256(compute_layout(plan, Bh, T, std::max(Bh, 4096), T).ws_bytes));
     }
     return whole;
 }
@@ -782,8 +772,8 @@ extern "C" size_t gtts_workspace_bytes(const gtts_plan *plan, int B, int T) {
 extern "C" int gtts_workspace_status(const void *workspace, unsigned *n_events, float *max_abs, gtts_stream_t stream) {
     if (!workspace) return fail(GTTS_E_NULL, "gtts_workspace_status: null workspace");
     unsigned rec[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(rec, workspace, sizeof(rec), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    GTTS_HIPCHK(hipMemcpyAsync(rec, workspace, sizeof(rec), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    GTTS_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     if (n_events) *n_events = rec[0];
     if (max_abs) *max_abs = __builtin_bit_cast(float, rec[1]);
     return GTTS_OK;
@@ -1028,22 +1018,22 @@ extern "C" int gtts_estimator_forward(gtts_plan *plan, const void *packed, const
     RunCtx c{p, blob, (unsigned char *)workspace, mask, B, T, nullptr, 0, st};
     const int F = p->cfg.n_feats;
     c.sat = (unsigned *)workspace;
-    HIPCHK(hipMemsetAsync(workspace, 0, 16, st));                             // activation range record of this call (gtts_workspace_status)
-    HIPCHK(hipMemsetAsync(tptr(c, p->t_ticket), 0, (size_t)B * 4, st));      // tickets of the fused GroupNorm finalize
+    GTTS_HIPCHK(hipMemsetAsync(workspace, 0, 16, st));                             // activation range record of this call (gtts_workspace_status)
+    GTTS_HIPCHK(hipMemsetAsync(tptr(c, p->t_ticket), 0, (size_t)B * 4, st));      // tickets of the fused GroupNorm finalize
     float *s = nullptr;
     if (multi) {
         s = tptr(c, p->t_s);
-        { ProfScope ps_(p, st, (int)p->ops.size() + XOP_SPK); HIPCHK(launch_spk_mlp(spk, (const float *)(blob + p->spk_w0), (const float *)(blob + p->spk_b0),
+        { ProfScope ps_(p, st, (int)p->ops.size() + XOP_SPK); GTTS_HIPCHK(launch_spk_mlp(spk, (const float *)(blob + p->spk_w0), (const float *)(blob + p->spk_b0),
                               (const float *)(blob + p->spk_w2), (const float *)(blob + p->spk_b2), s, B, p->cfg.spk_emb_dim, F, st)); }
     }
     float *tb = tptr(c, p->t_tb);
-    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_TIME); HIPCHK(launch_time_mlp(t, (const float *)(blob + p->freq_off), p->cfg.pe_scale, blob, p->tmlp, tb, B, st)); }
+    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_TIME); GTTS_HIPCHK(launch_time_mlp(t, (const float *)(blob + p->freq_off), p->cfg.pe_scale, blob, p->tmlp, tb, B, st)); }
     c.tb_row = tb;
     c.tb_bstride = p->tmlp.tb_stride;
-    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_PREP); HIPCHK(launch_prep_input(mu, x, s, tptr(c, p->t_x0), B, F, T, p->cin0, st, p->cfg.precision == GTTS_PREC_BF16_STORE)); }
+    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_PREP); GTTS_HIPCHK(launch_prep_input(mu, x, s, tptr(c, p->t_x0), B, F, T, p->cin0, st, p->cfg.precision == GTTS_PREC_BF16_STORE)); }
     rc = run_ops(c);
     if (rc) return rc;
-    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_FINAL); HIPCHK(launch_final_euler(tptr(c, p->t_final_raw), tptr(c, p->t_final_sc), tptr(c, p->t_final_sh),
+    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_FINAL); GTTS_HIPCHK(launch_final_euler(tptr(c, p->t_final_raw), tptr(c, p->t_final_sc), tptr(c, p->t_final_sh),
                               (const float *)(blob + p->fw_off), (const float *)(blob + p->fb_off), mask, B, p->cfg.dim, F, T,
                               out, nullptr, nullptr, nullptr, 0.f, 0.f, st, nullptr, p->cfg.precision == GTTS_PREC_BF16_STORE)); }
     return GTTS_OK;
@@ -1053,7 +1043,7 @@ extern "C" int gtts_euler_step(float *xt, const float *mu, const float *est, con
                                float beta_t, float h, int B, int F, int T, gtts_stream_t stream) {
     if (!xt || !mu || !est || !mask) return fail(GTTS_E_NULL, "gtts_euler_step: null argument");
     if (B <= 0 || F <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_euler_step: bad shape");
-    HIPCHK(launch_euler_step(xt, mu, est, mask, noise, beta_t, h, B, F, T, (hipStream_t)stream));
+    GTTS_HIPCHK(launch_euler_step(xt, mu, est, mask, noise, beta_t, h, B, F, T, (hipStream_t)stream));
     return GTTS_OK;
 }
 
@@ -1074,7 +1064,7 @@ static int enqueue_reverse_diffusion(gtts_plan *p, const void *packed, const flo
     const int nhalf = p->prof_on == 1 ? 1 : sampler_parts(p, B);
     const int Bh0 = (B + nhalf - 1) / nhalf;
     layout_workspace(p, Bh0, T, std::max(Bh0, 4096));
-    const size_t ws_half = align_up(p->ws_bytes, 256);
+    const size_t ws_half = align256(p->ws_bytes);
     if (workspace_bytes < ws_half * nhalf)
         return fail(GTTS_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", ws_half * nhalf, workspace_bytes);
 
@@ -1084,10 +1074,10 @@ static int enqueue_reverse_diffusion(gtts_plan *p, const void *packed, const flo
     float *tb = tptr(c0, p->t_tb);
     float *tvals = tb + (size_t)std::max(Bh0, 4096) * p->tmlp.tb_stride;
     hipLaunchKernelGGL(sampler_times_kernel, dim3((N + 255) / 256), dim3(256), 0, st, tvals, N, 0.5);
-    HIPCHK(hipGetLastError());
-    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_TIME); HIPCHK(launch_time_mlp(tvals, (const float *)(blob + p->freq_off), p->cfg.pe_scale, blob, p->tmlp, tb, N, st)); }
-    if (step_begin == 0) { ProfScope ps_(p, st, (int)p->ops.size() + XOP_MULMASK); HIPCHK(launch_mul_mask(z, mask, out, B, F, T, st)); }   // xt = z * mask  (diffusion.py:257)
-    if (step_begin == 0) HIPCHK(hipMemsetAsync(workspace, 0, 16, st));      // activation range record: sticky over the step ranges of one sampling run
+    GTTS_HIPCHK(hipGetLastError());
+    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_TIME); GTTS_HIPCHK(launch_time_mlp(tvals, (const float *)(blob + p->freq_off), p->cfg.pe_scale, blob, p->tmlp, tb, N, st)); }
+    if (step_begin == 0) { ProfScope ps_(p, st, (int)p->ops.size() + XOP_MULMASK); GTTS_HIPCHK(launch_mul_mask(z, mask, out, B, F, T, st)); }   // xt = z * mask  (diffusion.py:257)
+    if (step_begin == 0) GTTS_HIPCHK(hipMemsetAsync(workspace, 0, 16, st));      // activation range record: sticky over the step ranges of one sampling run
 
     struct Half { RunCtx c; int b0; float *s; };
     Half hv[MAX_SUB];
@@ -1103,22 +1093,22 @@ static int enqueue_reverse_diffusion(gtts_plan *p, const void *packed, const flo
         hv[h].s = nullptr;
     }
     if (nhalf > 1) {
-        HIPCHK(hipEventRecord(p->ev_fork, st));
-        for (int h = 0; h < nhalf; ++h) HIPCHK(hipStreamWaitEvent(p->sub[h], p->ev_fork, 0));
+        GTTS_HIPCHK(hipEventRecord(p->ev_fork, st));
+        for (int h = 0; h < nhalf; ++h) GTTS_HIPCHK(hipStreamWaitEvent(p->sub[h], p->ev_fork, 0));
     }
     const double hd = 1.0 / (double)N;
     const float h = (float)hd;
     const float bmin = p->cfg.beta_min, bdiff = (float)((double)p->cfg.beta_max - (double)p->cfg.beta_min);
     auto steps = [&]() -> int {
         for (int hh = 0; hh < nhalf; ++hh)
-            if (hv[hh].c.B > 0) HIPCHK(hipMemsetAsync(tptr(hv[hh].c, p->t_ticket), 0, (size_t)hv[hh].c.B * 4, hv[hh].c.st));
+            if (hv[hh].c.B > 0) GTTS_HIPCHK(hipMemsetAsync(tptr(hv[hh].c, p->t_ticket), 0, (size_t)hv[hh].c.B * 4, hv[hh].c.st));
         if (multi) {
             for (int hh = 0; hh < nhalf; ++hh) {
                 Half &H = hv[hh];
                 if (H.c.B <= 0) continue;
                 H.s = tptr(H.c, p->t_s);
                 ProfScope ps_(p, H.c.st, (int)p->ops.size() + XOP_SPK);
-                HIPCHK(launch_spk_mlp(spk + (size_t)H.b0 * E, (const float *)(blob + p->spk_w0), (const float *)(blob + p->spk_b0),
+                GTTS_HIPCHK(launch_spk_mlp(spk + (size_t)H.b0 * E, (const float *)(blob + p->spk_w0), (const float *)(blob + p->spk_b0),
                                       (const float *)(blob + p->spk_w2), (const float *)(blob + p->spk_b2), H.s, H.c.B, E, F, H.c.st));
             }
         }
@@ -1131,11 +1121,11 @@ static int enqueue_reverse_diffusion(gtts_plan *p, const void *packed, const flo
                 const size_t off = (size_t)H.b0 * F * T;
                 H.c.tb_row = tb + (size_t)i * p->tmlp.tb_stride;
                 H.c.tb_bstride = 0;
-                { ProfScope ps_(p, H.c.st, (int)p->ops.size() + XOP_PREP); HIPCHK(launch_prep_input(mu + off, out + off, H.s, tptr(H.c, p->t_x0), H.c.B, F, T, p->cin0, H.c.st, p->cfg.precision == GTTS_PREC_BF16_STORE)); }
+                { ProfScope ps_(p, H.c.st, (int)p->ops.size() + XOP_PREP); GTTS_HIPCHK(launch_prep_input(mu + off, out + off, H.s, tptr(H.c, p->t_x0), H.c.B, F, T, p->cin0, H.c.st, p->cfg.precision == GTTS_PREC_BF16_STORE)); }
                 const int rc2 = run_ops(H.c);
                 if (rc2) return rc2;
                 const float *nz = noise ? noise + (size_t)(i - step_begin) * B * F * T + off : nullptr;
-                { ProfScope ps_(p, H.c.st, (int)p->ops.size() + XOP_FINAL); HIPCHK(launch_final_euler(tptr(H.c, p->t_final_raw), tptr(H.c, p->t_final_sc), tptr(H.c, p->t_final_sh),
+                { ProfScope ps_(p, H.c.st, (int)p->ops.size() + XOP_FINAL); GTTS_HIPCHK(launch_final_euler(tptr(H.c, p->t_final_raw), tptr(H.c, p->t_final_sc), tptr(H.c, p->t_final_sh),
                                           (const float *)(blob + p->fw_off), (const float *)(blob + p->fb_off), H.c.mask, H.c.B, p->cfg.dim, F, T,
                                           nullptr, out + off, mu + off, nz, beta, h, H.c.st, nullptr, p->cfg.precision == GTTS_PREC_BF16_STORE)); }
             }
@@ -1199,11 +1189,11 @@ extern "C" int gtts_reverse_diffusion(gtts_plan *plan, const void *packed, const
     for (auto &g : p->graphs)
         if (g.key == key) {
             g.used = ++p->graph_clock;
-            HIPCHK(hipGraphLaunch(g.exec, st));
+            GTTS_HIPCHK(hipGraphLaunch(g.exec, st));
             return GTTS_OK;
         }
     if (!st) return fail(GTTS_E_CONFIG, "hipGraph capture needs a non-default stream (got the null stream)");
-    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+    GTTS_HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
     rc = enqueue_reverse_diffusion(p, packed, z, mask, mu, spk, noise, out, workspace, workspace_bytes, B, T, n_timesteps,
                                    step_begin, step_end, st);
     hipGraph_t graph = nullptr;
@@ -1220,7 +1210,7 @@ extern "C" int gtts_reverse_diffusion(gtts_plan *plan, const void *packed, const
         p->graphs.erase(p->graphs.begin() + lru);
     }
     p->graphs.push_back({key, graph, exec, ++p->graph_clock});
-    HIPCHK(hipGraphLaunch(exec, st));
+    GTTS_HIPCHK(hipGraphLaunch(exec, st));
     return GTTS_OK;
 }
 
@@ -1257,17 +1247,17 @@ extern "C" int gtts_vc_estimator_forward(gtts_plan *plan, const void *packed, co
     cx.ref_mask = ref_mask; cx.Tr = T_ref; cx.in_x = x; cx.in_mean = mean; cx.in_c = c;
     const int F = p->cfg.n_feats;
     cx.sat = (unsigned *)workspace;
-    HIPCHK(hipMemsetAsync(workspace, 0, 16, st));
-    HIPCHK(hipMemsetAsync(tptr(cx, p->t_ticket), 0, (size_t)B * 4, st));
+    GTTS_HIPCHK(hipMemsetAsync(workspace, 0, 16, st));
+    GTTS_HIPCHK(hipMemsetAsync(tptr(cx, p->t_ticket), 0, (size_t)B * 4, st));
     float *tb = tptr(cx, p->t_tb);
-    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_TIME); HIPCHK(launch_time_mlp(t, (const float *)(blob + p->freq_off), p->cfg.pe_scale, blob, p->tmlp, tb, B, st)); }
+    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_TIME); GTTS_HIPCHK(launch_time_mlp(t, (const float *)(blob + p->freq_off), p->cfg.pe_scale, blob, p->tmlp, tb, B, st)); }
     cx.tb_row = tb;
     cx.tb_bstride = p->tmlp.tb_stride;
     if (p->cfg.use_ref_t)
-        HIPCHK(hipMemcpyAsync(tptr(cx, p->t_xtref), xt_ref, (size_t)B * F * T_ref * sizeof(float), hipMemcpyDeviceToDevice, st));
+        GTTS_HIPCHK(hipMemcpyAsync(tptr(cx, p->t_xtref), xt_ref, (size_t)B * F * T_ref * sizeof(float), hipMemcpyDeviceToDevice, st));
     rc = run_ops(cx);
     if (rc) return rc;
-    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_FINAL); HIPCHK(launch_final_euler(tptr(cx, p->t_final_raw), tptr(cx, p->t_final_sc), tptr(cx, p->t_final_sh),
+    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_FINAL); GTTS_HIPCHK(launch_final_euler(tptr(cx, p->t_final_raw), tptr(cx, p->t_final_sc), tptr(cx, p->t_final_sh),
                               (const float *)(blob + p->fw_off), (const float *)(blob + p->fb_off), x_mask, B, p->cfg.dim, F, T,
                               out, nullptr, nullptr, nullptr, 0.f, 0.f, st)); }
     return GTTS_OK;
@@ -1305,16 +1295,16 @@ extern "C" int gtts_vc_reverse_diffusion(gtts_plan *plan, const void *packed, co
     cx.ref_mask = ref_mask; cx.Tr = T_ref; cx.in_mean = mean; cx.in_c = c; cx.in_x = out;
     const int F = cf.n_feats, N = n_timesteps;
     cx.sat = (unsigned *)workspace;
-    if (step_begin == 0) HIPCHK(hipMemsetAsync(workspace, 0, 16, st));
-    HIPCHK(hipMemsetAsync(tptr(cx, p->t_ticket), 0, (size_t)B * 4, st));
+    if (step_begin == 0) GTTS_HIPCHK(hipMemsetAsync(workspace, 0, 16, st));
+    GTTS_HIPCHK(hipMemsetAsync(tptr(cx, p->t_ticket), 0, (size_t)B * 4, st));
     // step times t_i = 1 - i*h (left endpoint, diffusion.py:170) -> fp32 `time` tensor values, all rows in one launch
     float *tb = tptr(cx, p->t_tb);
     float *tvals = tb + (size_t)std::max(B, 4096) * p->tmlp.tb_stride;
     const double hd = 1.0 / (double)N;
     hipLaunchKernelGGL(sampler_times_kernel, dim3((N + 255) / 256), dim3(256), 0, st, tvals, N, 0.0);
-    HIPCHK(hipGetLastError());
-    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_TIME); HIPCHK(launch_time_mlp(tvals, (const float *)(blob + p->freq_off), cf.pe_scale, blob, p->tmlp, tb, N, st)); }
-    if (step_begin == 0) { ProfScope ps_(p, st, (int)p->ops.size() + XOP_MULMASK); HIPCHK(launch_mul_mask(z, mask, out, B, F, T, st)); }
+    GTTS_HIPCHK(hipGetLastError());
+    { ProfScope ps_(p, st, (int)p->ops.size() + XOP_TIME); GTTS_HIPCHK(launch_time_mlp(tvals, (const float *)(blob + p->freq_off), cf.pe_scale, blob, p->tmlp, tb, N, st)); }
+    if (step_begin == 0) { ProfScope ps_(p, st, (int)p->ops.size() + XOP_MULMASK); GTTS_HIPCHK(launch_mul_mask(z, mask, out, B, F, T, st)); }
     for (int i = step_begin; i < step_end; ++i) {
         const double t = 1.0 - (double)i * hd;
         const double beta_t = cf.vc_beta_min + (cf.vc_beta_max - cf.vc_beta_min) * t;
@@ -1341,14 +1331,14 @@ extern "C" int gtts_vc_reverse_diffusion(gtts_plan *plan, const void *packed, co
         vs.sigma = (float)sigma;
         if (cf.use_ref_t) {
             const double g0 = vc_gamma(cf, 0, t);
-            HIPCHK(launch_xt_ref(ref, mean_ref, ref_mask, tptr(cx, p->t_xtref), (float)g0, (float)(1.0 - g0), B, F, T_ref, st));
+            GTTS_HIPCHK(launch_xt_ref(ref, mean_ref, ref_mask, tptr(cx, p->t_xtref), (float)g0, (float)(1.0 - g0), B, F, T_ref, st));
         }
         cx.tb_row = tb + (size_t)i * p->tmlp.tb_stride;
         cx.tb_bstride = 0;
         rc = run_ops(cx);
         if (rc) return rc;
         const float *nz = (mode != 0) ? noise + (size_t)(i - step_begin) * B * F * T : nullptr;
-        { ProfScope ps_(p, st, (int)p->ops.size() + XOP_FINAL); HIPCHK(launch_final_euler(tptr(cx, p->t_final_raw), tptr(cx, p->t_final_sc), tptr(cx, p->t_final_sh),
+        { ProfScope ps_(p, st, (int)p->ops.size() + XOP_FINAL); GTTS_HIPCHK(launch_final_euler(tptr(cx, p->t_final_raw), tptr(cx, p->t_final_sc), tptr(cx, p->t_final_sh),
                                   (const float *)(blob + p->fw_off), (const float *)(blob + p->fb_off), mask, B, cf.dim, F, T,
                                   nullptr, out, mean, nz, 0.f, 0.f, st, &vs)); }
     }
@@ -1366,7 +1356,7 @@ extern "C" int gtts_mas_maximum_path(const float *value, const float *mask, cons
     if (!value || !t_x || !t_y || !path || !scratch) return fail(GTTS_E_NULL, "gtts_mas_maximum_path: null argument");
     if (b <= 0 || tx <= 0 || ty <= 0) return fail(GTTS_E_SHAPE, "gtts_mas_maximum_path: bad shape b=%d tx=%d ty=%d", b, tx, ty);
     if ((size_t)2 * tx * 4 > 160 * 1024) return fail(GTTS_E_SHAPE, "t_x too large for the LDS column buffer (%d)", tx);
-    HIPCHK(launch_mas(value, mask, t_x, t_y, path, (unsigned char *)scratch, b, tx, ty, (hipStream_t)stream));
+    GTTS_HIPCHK(launch_mas(value, mask, t_x, t_y, path, (unsigned char *)scratch, b, tx, ty, (hipStream_t)stream));
     return GTTS_OK;
 }
 
@@ -1435,7 +1425,7 @@ extern "C" int gtts_expand_alignment(const float *duration, const float *x_mask,
     if (B <= 0 || F <= 0 || t_x <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_expand_alignment: bad shape B=%d F=%d t_x=%d T=%d", B, F, t_x, T);
     if (noise && !(temperature > 0.f)) return fail(GTTS_E_SHAPE, "gtts_expand_alignment: temperature must be positive");
     if (((size_t)t_x + T) * 4 > 160 * 1024) return fail(GTTS_E_SHAPE, "t_x + T too large for the LDS tables (%d + %d)", t_x, T);
-    HIPCHK(launch_expand_alignment(duration, x_mask, y_lengths, mu_x, noise, temperature, attn, mu_y, z, B, F, t_x, T,
+    GTTS_HIPCHK(launch_expand_alignment(duration, x_mask, y_lengths, mu_x, noise, temperature, attn, mu_y, z, B, F, t_x, T,
                                    (hipStream_t)stream));
     return GTTS_OK;
 }
@@ -1445,7 +1435,7 @@ extern "C" int gtts_log_prior(const float *mu_x, const float *y, float *log_prio
                               gtts_stream_t stream) {
     if (!mu_x || !y || !log_prior) return fail(GTTS_E_NULL, "gtts_log_prior: null argument");
     if (B <= 0 || F <= 0 || t_x <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_log_prior: bad shape B=%d F=%d t_x=%d T=%d", B, F, t_x, T);
-    HIPCHK(launch_log_prior(mu_x, y, log_prior, B, F, t_x, T, (hipStream_t)stream));
+    GTTS_HIPCHK(launch_log_prior(mu_x, y, log_prior, B, F, t_x, T, (hipStream_t)stream));
     return GTTS_OK;
 }
 
@@ -1574,10 +1564,10 @@ extern "C" int gtts_profile_timeline(gtts_plan *plan, int cap, int *op, int *str
     if (plan->prof.empty()) return GTTS_OK;
     const hipEvent_t base = plan->prof[0].a;
     for (auto &r : plan->prof) {
-        HIPCHK(hipEventSynchronize(r.b));
+        GTTS_HIPCHK(hipEventSynchronize(r.b));
         float a = 0.f, b = 0.f;
-        HIPCHK(hipEventElapsedTime(&a, base, r.a));
-        HIPCHK(hipEventElapsedTime(&b, base, r.b));
+        GTTS_HIPCHK(hipEventElapsedTime(&a, base, r.a));
+        GTTS_HIPCHK(hipEventElapsedTime(&b, base, r.b));
         if (*n < cap) { op[*n] = r.op; stream[*n] = r.stream; t0_ms[*n] = a; t1_ms[*n] = b; ++*n; }
         plan->prof_pool.push_back({r.a, r.b});
     }
@@ -1589,9 +1579,9 @@ extern "C" int gtts_profile_collect(gtts_plan *plan, double *ms_per_op, long lon
     if (!plan || !ms_per_op || !launches_per_op) return fail(GTTS_E_NULL, "gtts_profile_collect: null argument");
     const int n = (int)plan->ops.size() + XOP_COUNT;
     for (auto &r : plan->prof) {
-        HIPCHK(hipEventSynchronize(r.b));
+        GTTS_HIPCHK(hipEventSynchronize(r.b));
         float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
+        GTTS_HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
         if (r.op >= 0 && r.op < n) { ms_per_op[r.op] += ms; launches_per_op[r.op] += 1; }
         plan->prof_pool.push_back({r.a, r.b});
     }

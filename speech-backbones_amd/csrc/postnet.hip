@@ -8,8 +8,6 @@
 // 1x1 + tail is the decoder's EPI_TAIL kernel; the two single-channel 1x1 convolutions are bandwidth kernels.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -97,22 +95,6 @@ __global__ __launch_bounds__(256) void postnet_chan_dot_finish(const float *__re
 
 using namespace gtts;
 
-static int pfail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-#define PCHK(expr)                                                                                                \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return pfail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-static size_t palign(size_t x) { return (x + 255) / 256 * 256; }
-
 struct PnParam { const char *name; int rank; int dims[4]; int kind; size_t off; };   // kind 0 fp32, 1 conv 7x7, 2 conv 1x1 (MFMA)
 struct gtts_postnet {
     int dim, n_feats, groups;
@@ -125,8 +107,8 @@ struct gtts_postnet {
 };
 
 extern "C" int gtts_postnet_create(int dim, int n_feats, int groups, gtts_postnet **out) {
-    if (!out) return pfail(GTTS_E_NULL, "gtts_postnet_create: null argument");
-    if (dim <= 0 || dim % 64 != 0 || groups != 8 || n_feats <= 0) return pfail(GTTS_E_CONFIG, "PostNet needs dim %% 64 == 0 and 8 groups (dim %d, groups %d)", dim, groups);
+    if (!out) return fail(GTTS_E_NULL, "gtts_postnet_create: null argument");
+    if (dim <= 0 || dim % 64 != 0 || groups != 8 || n_feats <= 0) return fail(GTTS_E_CONFIG, "PostNet needs dim %% 64 == 0 and 8 groups (dim %d, groups %d)", dim, groups);
     gtts_postnet *p = new gtts_postnet();
     p->dim = dim; p->n_feats = n_feats; p->groups = groups;
     auto add = [&](const char *name, std::vector<int> d, int kind) {
@@ -137,7 +119,7 @@ extern "C" int gtts_postnet_create(int dim, int n_feats, int groups, gtts_postne
         for (int v : d) n *= (size_t)v;
         q.off = p->blob_bytes;
         const size_t bytes = kind == 1 ? conv_packed_bytes(CONV_C7, dim, dim) : (kind == 2 ? conv_packed_bytes(CONV_P1, dim, dim) : n * 4);
-        p->blob_bytes = palign(p->blob_bytes + bytes);
+        p->blob_bytes = align256(p->blob_bytes + bytes);
         p->params.push_back(q);
     };
     // registration order of PostNet (postnet.py:42-45): init_conv, res_block (block1, block2, res), final_conv
@@ -161,8 +143,8 @@ extern "C" int gtts_postnet_create(int dim, int n_feats, int groups, gtts_postne
 extern "C" void gtts_postnet_destroy(gtts_postnet *p) { delete p; }
 extern "C" int gtts_postnet_num_params(const gtts_postnet *p) { return p ? (int)p->params.size() : 0; }
 extern "C" int gtts_postnet_param_info(const gtts_postnet *p, int i, const char **name, int *rank, int dims[4]) {
-    if (!p) return pfail(GTTS_E_NULL, "null postnet");
-    if (i < 0 || i >= (int)p->params.size()) return pfail(GTTS_E_SHAPE, "parameter index out of range");
+    if (!p) return fail(GTTS_E_NULL, "null postnet");
+    if (i < 0 || i >= (int)p->params.size()) return fail(GTTS_E_SHAPE, "parameter index out of range");
     if (name) *name = p->params[i].name;
     if (rank) *rank = p->params[i].rank;
     if (dims) for (int k = 0; k < 4; ++k) dims[k] = p->params[i].dims[k];
@@ -170,20 +152,20 @@ extern "C" int gtts_postnet_param_info(const gtts_postnet *p, int i, const char 
 }
 extern "C" size_t gtts_postnet_packed_bytes(const gtts_postnet *p) { return p ? p->blob_bytes : 0; }
 extern "C" int gtts_postnet_pack(const gtts_postnet *p, const void *const *ptrs, int n, void *packed, gtts_stream_t stream) {
-    if (!p || !ptrs || !packed) return pfail(GTTS_E_NULL, "gtts_postnet_pack: null argument");
-    if (n != (int)p->params.size()) return pfail(GTTS_E_PARAMS, "expected %d parameters, got %d", (int)p->params.size(), n);
+    if (!p || !ptrs || !packed) return fail(GTTS_E_NULL, "gtts_postnet_pack: null argument");
+    if (n != (int)p->params.size()) return fail(GTTS_E_PARAMS, "expected %d parameters, got %d", (int)p->params.size(), n);
     hipStream_t st = (hipStream_t)stream;
     unsigned char *blob = (unsigned char *)packed;
-    PCHK(hipMemsetAsync(blob, 0, p->blob_bytes, st));
+    GTTS_HIPCHK(hipMemsetAsync(blob, 0, p->blob_bytes, st));
     for (int i = 0; i < n; ++i) {
         const PnParam &q = p->params[i];
-        if (!ptrs[i]) return pfail(GTTS_E_NULL, "parameter %s is null", q.name);
-        if (q.kind == 1) PCHK(launch_pack_conv(CONV_C7, (const float *)ptrs[i], blob + q.off, p->dim, p->dim, st));
-        else if (q.kind == 2) PCHK(launch_pack_conv(CONV_P1, (const float *)ptrs[i], blob + q.off, p->dim, p->dim, st));
+        if (!ptrs[i]) return fail(GTTS_E_NULL, "parameter %s is null", q.name);
+        if (q.kind == 1) GTTS_HIPCHK(launch_pack_conv(CONV_C7, (const float *)ptrs[i], blob + q.off, p->dim, p->dim, st));
+        else if (q.kind == 2) GTTS_HIPCHK(launch_pack_conv(CONV_P1, (const float *)ptrs[i], blob + q.off, p->dim, p->dim, st));
         else {
             size_t cnt = 1;
             for (int k = 0; k < q.rank; ++k) cnt *= (size_t)q.dims[k];
-            PCHK(hipMemcpyAsync(blob + q.off, ptrs[i], cnt * 4, hipMemcpyDeviceToDevice, st));
+            GTTS_HIPCHK(hipMemcpyAsync(blob + q.off, ptrs[i], cnt * 4, hipMemcpyDeviceToDevice, st));
         }
     }
     return GTTS_OK;
@@ -191,14 +173,14 @@ extern "C" int gtts_postnet_pack(const gtts_postnet *p, const void *const *ptrs,
 
 // workspace: X0, raw1, raw2, R (each [B,dim,F,T] fp32), partials, scale/shift x2, tickets, a zero time-bias row
 static size_t pn_ws(const gtts_postnet *p, int B, int T, size_t off[10]) {
-    const size_t act = palign((size_t)B * p->dim * p->n_feats * T * 4);
-    const size_t part = palign((size_t)B * conv_nparts(CONV_C7, p->dim, p->n_feats, T) * p->groups * 2 * 4);
-    const size_t perb = palign((size_t)B * p->dim * 4);
+    const size_t act = align256((size_t)B * p->dim * p->n_feats * T * 4);
+    const size_t part = align256((size_t)B * conv_nparts(CONV_C7, p->dim, p->n_feats, T) * p->groups * 2 * 4);
+    const size_t perb = align256((size_t)B * p->dim * 4);
     size_t o = 0;
     for (int i = 0; i < 4; ++i) { off[i] = o; o += act; }
     off[4] = o; o += part;
     for (int i = 5; i < 9; ++i) { off[i] = o; o += perb; }      // sc1, sh1, sc2, sh2
-    off[9] = o; o += palign((size_t)B * 4) + perb;              // tickets, then zeros (time bias)
+    off[9] = o; o += align256((size_t)B * 4) + perb;              // tickets, then zeros (time bias)
     return o;
 }
 extern "C" size_t gtts_postnet_workspace_bytes(const gtts_postnet *p, int B, int T) {
@@ -210,10 +192,10 @@ extern "C" size_t gtts_postnet_workspace_bytes(const gtts_postnet *p, int B, int
 // PostNet.forward (postnet.py:47-53): x [B,n_feats,T], mask [B,T] -> out [B,n_feats,T]
 extern "C" int gtts_postnet_forward(const gtts_postnet *p, const void *packed, const float *x, const float *mask, float *out,
                                     void *workspace, size_t workspace_bytes, int B, int T, gtts_stream_t stream) {
-    if (!p || !packed || !x || !mask || !out || !workspace) return pfail(GTTS_E_NULL, "gtts_postnet_forward: null argument");
-    if (B <= 0 || T <= 0) return pfail(GTTS_E_SHAPE, "gtts_postnet_forward: bad shape B=%d T=%d", B, T);
+    if (!p || !packed || !x || !mask || !out || !workspace) return fail(GTTS_E_NULL, "gtts_postnet_forward: null argument");
+    if (B <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_postnet_forward: bad shape B=%d T=%d", B, T);
     size_t off[10];
-    if (workspace_bytes < pn_ws(p, B, T, off)) return pfail(GTTS_E_WORKSPACE, "workspace too small");
+    if (workspace_bytes < pn_ws(p, B, T, off)) return fail(GTTS_E_WORKSPACE, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const unsigned char *blob = (const unsigned char *)packed;
     unsigned char *ws = (unsigned char *)workspace;
@@ -222,11 +204,11 @@ extern "C" int gtts_postnet_forward(const gtts_postnet *p, const void *packed, c
     float *part = (float *)(ws + off[4]);
     float *sc1 = (float *)(ws + off[5]), *sh1 = (float *)(ws + off[6]), *sc2 = (float *)(ws + off[7]), *sh2 = (float *)(ws + off[8]);
     unsigned *ticket = (unsigned *)(ws + off[9]);
-    float *zeros = (float *)(ws + off[9] + palign((size_t)B * 4));
-    PCHK(hipMemsetAsync(ticket, 0, palign((size_t)B * 4) + palign((size_t)B * C * 4), st));
+    float *zeros = (float *)(ws + off[9] + align256((size_t)B * 4));
+    GTTS_HIPCHK(hipMemsetAsync(ticket, 0, align256((size_t)B * 4) + align256((size_t)B * C * 4), st));
     hipLaunchKernelGGL(postnet_init_kernel, dim3((F * T + 255) / 256, C, B), dim3(256), 0, st, x, mask,
                        (const float *)(blob + p->off("init_conv.weight")), (const float *)(blob + p->off("init_conv.bias")), X0, C, F, T);
-    PCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     auto block = [&](const float *src, int pro, const float *psc, const float *psh, const char *wn, const char *bn, const char *gn,
                      const char *be, float *raw, float *sc, float *sh) -> hipError_t {
         ConvArgs a;
@@ -243,11 +225,11 @@ extern "C" int gtts_postnet_forward(const gtts_postnet *p, const void *packed, c
         return launch_conv(CONV_C7, a, st);
     };
     // Block 1: Conv7x7(x * mask) -> GroupNorm statistics           (postnet.py:21-23)
-    PCHK(block(X0, PRO_MASK, nullptr, nullptr, "res_block.block1.block.0.weight", "res_block.block1.block.0.bias",
-               "res_block.block1.block.1.weight", "res_block.block1.block.1.bias", raw1, sc1, sh1));
+    GTTS_HIPCHK(block(X0, PRO_MASK, nullptr, nullptr, "res_block.block1.block.0.weight", "res_block.block1.block.0.bias",
+                      "res_block.block1.block.1.weight", "res_block.block1.block.1.bias", raw1, sc1, sh1));
     // Block 2 on Mish(GN(raw1)) * mask (applied on load; no time bias here)
-    PCHK(block(raw1, PRO_GN, sc1, sh1, "res_block.block2.block.0.weight", "res_block.block2.block.0.bias",
-               "res_block.block2.block.1.weight", "res_block.block2.block.1.bias", raw2, sc2, sh2));
+    GTTS_HIPCHK(block(raw1, PRO_GN, sc1, sh1, "res_block.block2.block.0.weight", "res_block.block2.block.0.bias",
+                      "res_block.block2.block.1.weight", "res_block.block2.block.1.bias", raw2, sc2, sh2));
     // res(x * mask) + Mish(GN(raw2)) * mask                         (postnet.py:33-37)
     {
         ConvArgs a;
@@ -258,11 +240,11 @@ extern "C" int gtts_postnet_forward(const gtts_postnet *p, const void *packed, c
         a.pro = PRO_MASK; a.epi = EPI_TAIL;
         a.w = blob + p->off("res_block.res.weight"); a.bias = (const float *)(blob + p->off("res_block.res.bias"));
         a.cout = C; a.out = R; a.eh = raw2; a.esc = sc2; a.esh = sh2; a.groups = p->groups; a.nsplit = 2;
-        PCHK(launch_conv(CONV_P1, a, st));
+        GTTS_HIPCHK(launch_conv(CONV_P1, a, st));
     }
     hipLaunchKernelGGL(postnet_final_kernel, dim3((F * T + 255) / 256, B), dim3(256), (size_t)C * 4, st, R, mask,
                        (const float *)(blob + p->off("final_conv.weight")), (const float *)(blob + p->off("final_conv.bias")), out, C, F, T);
-    PCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -270,22 +252,22 @@ extern "C" int gtts_postnet_forward(const gtts_postnet *p, const void *packed, c
 // forward above (model/_train_ops.py composes them with the 7x7 / GroupNorm / 1x1 training kernels)
 extern "C" int gtts_postnet_expand(const float *x, const float *mask, const float *w, const float *bias, float *out, int B, int C, int F, int T,
                                    gtts_stream_t stream) {
-    if (!x || !mask || !w || !bias || !out) return pfail(GTTS_E_NULL, "gtts_postnet_expand: null argument");
-    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || C > 65535 || B > 65535) return pfail(GTTS_E_SHAPE, "gtts_postnet_expand: bad shape");
-    if ((size_t)B * C * F * T >= ((size_t)1 << 31)) return pfail(GTTS_E_SHAPE, "gtts_postnet_expand: tensor too large");
+    if (!x || !mask || !w || !bias || !out) return fail(GTTS_E_NULL, "gtts_postnet_expand: null argument");
+    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || C > 65535 || B > 65535) return fail(GTTS_E_SHAPE, "gtts_postnet_expand: bad shape");
+    if ((size_t)B * C * F * T >= ((size_t)1 << 31)) return fail(GTTS_E_SHAPE, "gtts_postnet_expand: tensor too large");
     hipLaunchKernelGGL(postnet_init_kernel, dim3((F * T + 255) / 256, C, B), dim3(256), 0, (hipStream_t)stream, x, mask, w, bias, out, C, F, T);
-    PCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
 extern "C" int gtts_postnet_collapse(const float *x, const float *mask, const float *w, const float *bias, float *out, int B, int C, int F,
                                      int T, gtts_stream_t stream) {
-    if (!x || !mask || !w || !bias || !out) return pfail(GTTS_E_NULL, "gtts_postnet_collapse: null argument");
-    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || B > 65535 || C > 16384) return pfail(GTTS_E_SHAPE, "gtts_postnet_collapse: bad shape");
-    if ((size_t)B * C * F * T >= ((size_t)1 << 31)) return pfail(GTTS_E_SHAPE, "gtts_postnet_collapse: tensor too large");
+    if (!x || !mask || !w || !bias || !out) return fail(GTTS_E_NULL, "gtts_postnet_collapse: null argument");
+    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || B > 65535 || C > 16384) return fail(GTTS_E_SHAPE, "gtts_postnet_collapse: bad shape");
+    if ((size_t)B * C * F * T >= ((size_t)1 << 31)) return fail(GTTS_E_SHAPE, "gtts_postnet_collapse: tensor too large");
     hipLaunchKernelGGL(postnet_final_kernel, dim3((F * T + 255) / 256, B), dim3(256), (size_t)C * 4, (hipStream_t)stream, x, mask, w, bias, out,
                        C, F, T);
-    PCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -297,15 +279,15 @@ extern "C" size_t gtts_postnet_chan_dot_scratch_floats(int B, int C, int F, int 
 
 extern "C" int gtts_postnet_chan_dot(const float *a, const float *v, const float *mask, float *dot, float *sum, float *scratch, int B, int C,
                                      int F, int T, gtts_stream_t stream) {
-    if (!a || !scratch || (!dot && !sum)) return pfail(GTTS_E_NULL, "gtts_postnet_chan_dot: null argument");
-    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || C > 65535) return pfail(GTTS_E_SHAPE, "gtts_postnet_chan_dot: bad shape");
+    if (!a || !scratch || (!dot && !sum)) return fail(GTTS_E_NULL, "gtts_postnet_chan_dot: null argument");
+    if (B <= 0 || C <= 0 || F <= 0 || T <= 0 || C > 65535) return fail(GTTS_E_SHAPE, "gtts_postnet_chan_dot: bad shape");
     const size_t n = (size_t)B * F * T;
     const size_t nblk = (n + PN_SEG - 1) / PN_SEG;
-    if (nblk > 0x7fffffff) return pfail(GTTS_E_SHAPE, "gtts_postnet_chan_dot: tensor too large");
+    if (nblk > 0x7fffffff) return fail(GTTS_E_SHAPE, "gtts_postnet_chan_dot: tensor too large");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(postnet_chan_dot_kernel, dim3((unsigned)nblk, C), dim3(256), 0, st, a, v, mask, scratch, C, F * T, T, n, (int)nblk);
-    PCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(postnet_chan_dot_finish, dim3(C), dim3(256), 0, st, scratch, dot, sum, (int)nblk);
-    PCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }

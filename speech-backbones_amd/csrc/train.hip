@@ -14,8 +14,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
 #include "../../include/gradtts_abi.h"
@@ -189,29 +187,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(const WgradArgs a
 
 using namespace gtts;
 
-static int tfail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-#define TCHK(expr)                                                                                                \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return tfail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 extern "C" int gtts_diffusion_noising(const float *x0, const float *mu, const float *z, const float *mask, const float *t,
                                       float beta_min, float beta_max, float *xt, float *z_masked, int B, int F, int T,
                                       gtts_stream_t stream) {
-    if (!x0 || !mu || !z || !mask || !t || !xt || !z_masked) return tfail(GTTS_E_NULL, "gtts_diffusion_noising: null argument");
-    if (B <= 0 || F <= 0 || T <= 0) return tfail(GTTS_E_SHAPE, "gtts_diffusion_noising: bad shape");
+    if (!x0 || !mu || !z || !mask || !t || !xt || !z_masked) return fail(GTTS_E_NULL, "gtts_diffusion_noising: null argument");
+    if (B <= 0 || F <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_diffusion_noising: bad shape");
     const size_t total = (size_t)B * F * T;
     hipLaunchKernelGGL(noising_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x0, mu, z, mask, t,
                        beta_min, beta_max, xt, z_masked, F, T, total);
-    TCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -219,27 +203,27 @@ extern "C" size_t gtts_score_loss_partials(int B, int F, int T) { return ((size_
 
 extern "C" int gtts_score_loss(const float *eps, const float *z_masked, const float *t, float beta_min, float beta_max,
                                float inv_denom, float *partials, float *grad_eps, int B, int F, int T, gtts_stream_t stream) {
-    if (!eps || !z_masked || !t || !partials) return tfail(GTTS_E_NULL, "gtts_score_loss: null argument");
-    if (B <= 0 || F <= 0 || T <= 0) return tfail(GTTS_E_SHAPE, "gtts_score_loss: bad shape");
+    if (!eps || !z_masked || !t || !partials) return fail(GTTS_E_NULL, "gtts_score_loss: null argument");
+    if (B <= 0 || F <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_score_loss: bad shape");
     const size_t total = (size_t)B * F * T;
     hipLaunchKernelGGL(score_loss_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, eps, z_masked, t,
                        beta_min, beta_max, inv_denom, partials, grad_eps, F, T, total);
-    TCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
 extern "C" size_t gtts_conv3x3_packed_bytes(int cin, int cout) {
     if (cin <= 0 || cout <= 0) return 0;
-    return (conv_packed_bytes(CONV_C3, cin, cout) + 255) / 256 * 256;
+    return align256(conv_packed_bytes(CONV_C3, cin, cout));
 }
 
 // transposed != 0: w is the FORWARD weight [cin_of_this_conv... i.e. forward cout][forward cin = cout of this conv][3][3] and
 // is packed transposed with flipped taps (the data-gradient convolution)
 extern "C" int gtts_conv3x3_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream) {
-    if (!w || !packed) return tfail(GTTS_E_NULL, "gtts_conv3x3_pack: null argument");
-    if (cin <= 0 || cout <= 0) return tfail(GTTS_E_SHAPE, "gtts_conv3x3_pack: bad shape");
+    if (!w || !packed) return fail(GTTS_E_NULL, "gtts_conv3x3_pack: null argument");
+    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv3x3_pack: bad shape");
     // cin / cout are those of the convolution being packed (for the data gradient: cin = forward cout, cout = forward cin)
-    TCHK(launch_pack_conv(transposed ? CONV_C3 + 16 : CONV_C3, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
+    GTTS_HIPCHK(launch_pack_conv(transposed ? CONV_C3 + 16 : CONV_C3, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
     return GTTS_OK;
 }
 
@@ -250,10 +234,10 @@ extern "C" int gtts_conv3x3_pack(const float *w, void *packed, int cin, int cout
 // conv(dy; transposed weights) * mask, and the mask rides in the epilogue instead of a second pass over dx
 extern "C" int gtts_conv3x3_masked3(const float *x, const float *x1, int c0, const float *mask, const float *omask, const void *packed,
                                     const float *bias, float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
-    if (!x || !mask || !packed || !bias || !y) return tfail(GTTS_E_NULL, "gtts_conv3x3_masked: null argument");
-    if (x1 && (c0 <= 0 || c0 >= cin || c0 % 16)) return tfail(GTTS_E_SHAPE, "gtts_conv3x3_masked: c0 must be a multiple of 16 inside (0, cin) (got %d of %d)", c0, cin);
-    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return tfail(GTTS_E_SHAPE, "gtts_conv3x3_masked: bad shape");
-    if (cout % (cout > 64 ? 128 : 64) != 0) return tfail(GTTS_E_SHAPE, "gtts_conv3x3_masked: cout must be 64 or a multiple of 128 (got %d)", cout);
+    if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv3x3_masked: null argument");
+    if (x1 && (c0 <= 0 || c0 >= cin || c0 % 16)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: c0 must be a multiple of 16 inside (0, cin) (got %d of %d)", c0, cin);
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: bad shape");
+    if (cout % (cout > 64 ? 128 : 64) != 0) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: cout must be 64 or a multiple of 128 (got %d)", cout);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.src0 = x; a.src1 = x1 ? x1 : x; a.c0 = x1 ? c0 : cin; a.c1 = x1 ? cin - c0 : 0; a.cin = cin;
@@ -265,7 +249,7 @@ extern "C" int gtts_conv3x3_masked3(const float *x, const float *x1, int c0, con
     a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
     a.omask = omask;
     const hipError_t e = launch_conv(CONV_C3, a, (hipStream_t)stream);
-    if (e != hipSuccess) return tfail(GTTS_E_HIP, "conv3x3 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv3x3 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
     return GTTS_OK;
 }
 
@@ -284,24 +268,24 @@ extern "C" int gtts_conv3x3_masked(const float *x, const float *mask, const void
 // Channel counts are multiples of 64 (GTTS_E_CONFIG otherwise: the kernel's 64-cout tile and the weight gradient's 64 x 64 tile);
 // every tensor of a call must stay below 2^31 bytes (GTTS_E_SHAPE): the kernels address it with 32-bit byte offsets.
 static int conv7x7_check(const char *fn, int B, int cin, int cout, int H, int W) {
-    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return tfail(GTTS_E_SHAPE, "%s: bad shape", fn);
-    if (cin % 64 || cout % 64) return tfail(GTTS_E_CONFIG, "%s: cin and cout must be multiples of 64 (got %d, %d)", fn, cin, cout);
-    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return tfail(GTTS_E_SHAPE, "%s: tensor too large for 32-bit offsets", fn);
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "%s: bad shape", fn);
+    if (cin % 64 || cout % 64) return fail(GTTS_E_CONFIG, "%s: cin and cout must be multiples of 64 (got %d, %d)", fn, cin, cout);
+    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return fail(GTTS_E_SHAPE, "%s: tensor too large for 32-bit offsets", fn);
     return GTTS_OK;
 }
 
 extern "C" size_t gtts_conv7x7_packed_bytes(int cin, int cout) {
     if (cin <= 0 || cout <= 0 || cin % 64 || cout % 64) return 0;
-    return (conv_packed_bytes(CONV_C7, cin, cout) + 255) / 256 * 256;
+    return align256(conv_packed_bytes(CONV_C7, cin, cout));
 }
 
 // transposed != 0: w is the FORWARD weight [forward cout = cin of this conv][forward cin = cout of this conv][7][7], packed
 // transposed with flipped taps (the data-gradient convolution)
 extern "C" int gtts_conv7x7_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream) {
-    if (!w || !packed) return tfail(GTTS_E_NULL, "gtts_conv7x7_pack: null argument");
-    if (cin <= 0 || cout <= 0) return tfail(GTTS_E_SHAPE, "gtts_conv7x7_pack: bad shape");
-    if (cin % 64 || cout % 64) return tfail(GTTS_E_CONFIG, "gtts_conv7x7_pack: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
-    TCHK(launch_pack_conv(transposed ? CONV_C7 + 16 : CONV_C7, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
+    if (!w || !packed) return fail(GTTS_E_NULL, "gtts_conv7x7_pack: null argument");
+    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv7x7_pack: bad shape");
+    if (cin % 64 || cout % 64) return fail(GTTS_E_CONFIG, "gtts_conv7x7_pack: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
+    GTTS_HIPCHK(launch_pack_conv(transposed ? CONV_C7 + 16 : CONV_C7, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
     return GTTS_OK;
 }
 
@@ -309,7 +293,7 @@ extern "C" int gtts_conv7x7_pack(const float *w, void *packed, int cin, int cout
 // omask (nullable): [B][W] column mask multiplied into the output (the data gradient of the masked convolution in one pass)
 extern "C" int gtts_conv7x7_masked(const float *x, const float *mask, const float *omask, const void *packed, const float *bias,
                                    float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
-    if (!x || !mask || !packed || !bias || !y) return tfail(GTTS_E_NULL, "gtts_conv7x7_masked: null argument");
+    if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv7x7_masked: null argument");
     const int rc = conv7x7_check("gtts_conv7x7_masked", B, cin, cout, H, W);
     if (rc != GTTS_OK) return rc;
     ConvArgs a;
@@ -323,7 +307,7 @@ extern "C" int gtts_conv7x7_masked(const float *x, const float *mask, const floa
     a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
     a.omask = omask;
     const hipError_t e = launch_conv(CONV_C7, a, (hipStream_t)stream);
-    if (e != hipSuccess) return tfail(GTTS_E_HIP, "conv7x7 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv7x7 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
     return GTTS_OK;
 }
 
@@ -331,23 +315,23 @@ extern "C" int gtts_conv7x7_masked(const float *x, const float *mask, const floa
 // the inference CONV_P1 kernel (mask prologue, plain epilogue); the weight gradient is gtts_conv1x1_wgrad (train_wgrad.hip)
 extern "C" size_t gtts_conv1x1_packed_bytes(int cin, int cout) {
     if (cin <= 0 || cout <= 0) return 0;
-    return (conv_packed_bytes(CONV_P1, cin, cout) + 255) / 256 * 256;
+    return align256(conv_packed_bytes(CONV_P1, cin, cout));
 }
 
 // transposed != 0: w is the FORWARD weight [forward cout = cin of this conv][forward cin = cout of this conv]
 extern "C" int gtts_conv1x1_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream) {
-    if (!w || !packed) return tfail(GTTS_E_NULL, "gtts_conv1x1_pack: null argument");
-    if (cin <= 0 || cout <= 0) return tfail(GTTS_E_SHAPE, "gtts_conv1x1_pack: bad shape");
-    TCHK(launch_pack_conv(transposed ? CONV_P1 + 16 : CONV_P1, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
+    if (!w || !packed) return fail(GTTS_E_NULL, "gtts_conv1x1_pack: null argument");
+    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv1x1_pack: bad shape");
+    GTTS_HIPCHK(launch_pack_conv(transposed ? CONV_P1 + 16 : CONV_P1, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
     return GTTS_OK;
 }
 
 // y = Conv2d_1x1(x * mask, packed W) + bias; x [B,cin,H,W], mask [B,W] (columns), bias [cout], y [B,cout,H,W]
 extern "C" int gtts_conv1x1_masked(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B,
                                    int cin, int cout, int H, int W, gtts_stream_t stream) {
-    if (!x || !mask || !packed || !bias || !y) return tfail(GTTS_E_NULL, "gtts_conv1x1_masked: null argument");
-    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return tfail(GTTS_E_SHAPE, "gtts_conv1x1_masked: bad shape");
-    if (cout % (cout > 64 ? 128 : 64) != 0) return tfail(GTTS_E_SHAPE, "gtts_conv1x1_masked: cout must be 64 or a multiple of 128 (got %d)", cout);
+    if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv1x1_masked: null argument");
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv1x1_masked: bad shape");
+    if (cout % (cout > 64 ? 128 : 64) != 0) return fail(GTTS_E_SHAPE, "gtts_conv1x1_masked: cout must be 64 or a multiple of 128 (got %d)", cout);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.src0 = x; a.src1 = x; a.c0 = cin; a.c1 = 0; a.cin = cin;
@@ -358,7 +342,7 @@ extern "C" int gtts_conv1x1_masked(const float *x, const float *mask, const void
     a.bias = bias; a.bias_bstride = 0;
     a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
     const hipError_t e = launch_conv(CONV_P1, a, (hipStream_t)stream);
-    if (e != hipSuccess) return tfail(GTTS_E_HIP, "conv1x1 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv1x1 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
     return GTTS_OK;
 }
 
@@ -369,13 +353,13 @@ extern "C" int gtts_conv1x1_masked(const float *x, const float *mask, const void
 // y = 2 oy - 1 + ky), so the host packs the zero-padded forward weight with up = 1.
 extern "C" size_t gtts_conv_resample_packed_bytes(int cin, int cout, int up) {
     if (cin <= 0 || cout <= 0) return 0;
-    return (conv_packed_bytes(up ? CONV_UP : CONV_DN, cin, cout) + 255) / 256 * 256;
+    return align256(conv_packed_bytes(up ? CONV_UP : CONV_DN, cin, cout));
 }
 
 extern "C" int gtts_conv_resample_pack(const float *w, void *packed, int cin, int cout, int up, gtts_stream_t stream) {
-    if (!w || !packed) return tfail(GTTS_E_NULL, "gtts_conv_resample_pack: null argument");
-    if (cin <= 0 || cout <= 0) return tfail(GTTS_E_SHAPE, "gtts_conv_resample_pack: bad shape");
-    TCHK(launch_pack_conv(up ? CONV_UP : CONV_DN, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
+    if (!w || !packed) return fail(GTTS_E_NULL, "gtts_conv_resample_pack: null argument");
+    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv_resample_pack: bad shape");
+    GTTS_HIPCHK(launch_pack_conv(up ? CONV_UP : CONV_DN, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
     return GTTS_OK;
 }
 
@@ -386,13 +370,13 @@ extern "C" int gtts_conv_resample_pack(const float *w, void *packed, int cin, in
 extern "C" size_t gtts_pack_batch_desc_bytes(int n) { return n > 0 ? (size_t)n * sizeof(PackDesc) : 0; }
 
 extern "C" int gtts_pack_batch_describe(const gtts_pack_item *items, int n, void *desc_host, int *grid_x) {
-    if (!items || !desc_host || !grid_x) return tfail(GTTS_E_NULL, "gtts_pack_batch_describe: null argument");
-    if (n <= 0) return tfail(GTTS_E_SHAPE, "gtts_pack_batch_describe: n must be positive");
+    if (!items || !desc_host || !grid_x) return fail(GTTS_E_NULL, "gtts_pack_batch_describe: null argument");
+    if (n <= 0) return fail(GTTS_E_SHAPE, "gtts_pack_batch_describe: n must be positive");
     PackDesc *d = reinterpret_cast<PackDesc *>(desc_host);
     size_t mx = 0;
     for (int k = 0; k < n; ++k) {
         const gtts_pack_item &it = items[k];
-        if (!it.w || !it.packed || it.cin <= 0 || it.cout <= 0) return tfail(GTTS_E_SHAPE, "gtts_pack_batch_describe: bad item %d", k);
+        if (!it.w || !it.packed || it.cin <= 0 || it.cout <= 0) return fail(GTTS_E_SHAPE, "gtts_pack_batch_describe: bad item %d", k);
         int mode;
         switch (it.kind) {
             case 0: mode = it.transposed ? CONV_C3 + 16 : CONV_C3; break;
@@ -400,7 +384,7 @@ extern "C" int gtts_pack_batch_describe(const gtts_pack_item *items, int n, void
             case 2: mode = CONV_DN; break;
             case 3: mode = CONV_UP; break;
             case 4: mode = CONV_UP + 16; break;       // Downsample's data gradient: the 3x3 forward weight as a zero-padded 4x4 transposed conv
-            default: return tfail(GTTS_E_SHAPE, "gtts_pack_batch_describe: unknown kind %d", it.kind);
+            default: return fail(GTTS_E_SHAPE, "gtts_pack_batch_describe: unknown kind %d", it.kind);
         }
         memset(&d[k], 0, sizeof(PackDesc));
         pack_describe(mode, it.w, it.packed, it.cin, it.cout, &d[k]);
@@ -411,20 +395,20 @@ extern "C" int gtts_pack_batch_describe(const gtts_pack_item *items, int n, void
 }
 
 extern "C" int gtts_pack_batch(const void *desc_dev, int n, int grid_x, gtts_stream_t stream) {
-    if (!desc_dev) return tfail(GTTS_E_NULL, "gtts_pack_batch: null argument");
-    if (n <= 0 || grid_x <= 0) return tfail(GTTS_E_SHAPE, "gtts_pack_batch: bad sizes");
-    TCHK(launch_pack_batch(reinterpret_cast<const PackDesc *>(desc_dev), n, grid_x, (hipStream_t)stream));
+    if (!desc_dev) return fail(GTTS_E_NULL, "gtts_pack_batch: null argument");
+    if (n <= 0 || grid_x <= 0) return fail(GTTS_E_SHAPE, "gtts_pack_batch: bad sizes");
+    GTTS_HIPCHK(launch_pack_batch(reinterpret_cast<const PackDesc *>(desc_dev), n, grid_x, (hipStream_t)stream));
     return GTTS_OK;
 }
 
 // y = conv(x * mask) + bias; x [B,cin,H,W], mask [B,W] (columns of the INPUT).  H and W even for up = 0.
 extern "C" int gtts_conv_resample(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B, int cin,
                                   int cout, int H, int W, int up, gtts_stream_t stream) {
-    if (!x || !mask || !packed || !bias || !y) return tfail(GTTS_E_NULL, "gtts_conv_resample: null argument");
-    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return tfail(GTTS_E_SHAPE, "gtts_conv_resample: bad shape");
-    if (!up && ((H | W) & 1)) return tfail(GTTS_E_SHAPE, "gtts_conv_resample: Downsample needs even H and W (got %d x %d)", H, W);
+    if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv_resample: null argument");
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv_resample: bad shape");
+    if (!up && ((H | W) & 1)) return fail(GTTS_E_SHAPE, "gtts_conv_resample: Downsample needs even H and W (got %d x %d)", H, W);
     if (cin % 16 != 0 || cout % (cout > 64 ? 128 : 64) != 0)
-        return tfail(GTTS_E_SHAPE, "gtts_conv_resample: cin must be a multiple of 16 and cout 64 or a multiple of 128 (got %d, %d)", cin, cout);
+        return fail(GTTS_E_SHAPE, "gtts_conv_resample: cin must be a multiple of 16 and cout 64 or a multiple of 128 (got %d, %d)", cin, cout);
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.src0 = x; a.src1 = x; a.c0 = cin; a.c1 = 0; a.cin = cin;
@@ -436,18 +420,18 @@ extern "C" int gtts_conv_resample(const float *x, const float *mask, const void 
     a.bias = bias; a.bias_bstride = 0;
     a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
     const hipError_t e = launch_conv(up ? CONV_UP : CONV_DN, a, (hipStream_t)stream);
-    if (e != hipSuccess) return tfail(GTTS_E_HIP, "conv resample (cin %d, cout %d, up %d): %s", cin, cout, up, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv resample (cin %d, cout %d, up %d): %s", cin, cout, up, hipGetErrorString(e));
     return GTTS_OK;
 }
 
 extern "C" int gtts_conv3x3_wgrad(const float *x, const float *mask, const float *dy, float *dw, float *db, int B, int cin, int cout,
                                   int H, int W, gtts_stream_t stream) {
-    if (!x || !dy || !dw) return tfail(GTTS_E_NULL, "gtts_conv3x3_wgrad: null argument");
+    if (!x || !dy || !dw) return fail(GTTS_E_NULL, "gtts_conv3x3_wgrad: null argument");
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 32 || cout % 32)
-        return tfail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad: cin and cout must be multiples of 32 (got %d, %d)", cin, cout);
+        return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad: cin and cout must be multiples of 32 (got %d, %d)", cin, cout);
     hipStream_t st = (hipStream_t)stream;
-    TCHK(hipMemsetAsync(dw, 0, (size_t)cout * cin * 9 * 4, st));
-    if (db) TCHK(hipMemsetAsync(db, 0, (size_t)cout * 4, st));
+    GTTS_HIPCHK(hipMemsetAsync(dw, 0, (size_t)cout * cin * 9 * 4, st));
+    if (db) GTTS_HIPCHK(hipMemsetAsync(db, 0, (size_t)cout * 4, st));
     WgradArgs a;
     a.x = x; a.mask = mask; a.dy = dy; a.dw = dw; a.db = db;
     a.B = B; a.cin = cin; a.cout = cout; a.H = H; a.W = W;
@@ -459,6 +443,6 @@ extern "C" int gtts_conv3x3_wgrad(const float *x, const float *mask, const float
     a.nslice = nslice;
     const long long waves = (long long)tiles * nslice;
     hipLaunchKernelGGL(conv3x3_wgrad_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a);
-    TCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }

@@ -14,8 +14,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 
 #include "../../include/gradtts_abi.h"
 #include "common.h"
@@ -272,20 +270,6 @@ __global__ __launch_bounds__(256) void rezero_bwd_finish_kernel(const double *__
 
 using namespace gtts;
 
-static int afail(int code, const char *fmt, ...) {       // text goes to gtts_last_error() (plan.hip)
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-#define ACHK(expr)                                                                                                \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return afail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 static int attn_nslice(int N) { return (N + AT_TPS * AT_TILE - 1) / (AT_TPS * AT_TILE); }
 
 // floats of scratch either direction needs: the slice records
@@ -297,34 +281,34 @@ extern "C" size_t gtts_attn_train_scratch_floats(int B, int N) {
 // qkv [B][384][N] (to_qkv's output: q | k | v, each 4 heads x 32) -> out [B][128][N], ctx [B][4][32][32], stat [B][4][32][2]
 extern "C" int gtts_attn_train_forward(const float *qkv, float *out, float *ctx, float *stat, float *scratch, int B, int N,
                                        gtts_stream_t stream) {
-    if (!qkv || !out || !ctx || !stat || !scratch) return afail(GTTS_E_NULL, "gtts_attn_train_forward: null argument");
-    if (B <= 0 || N <= 0) return afail(GTTS_E_SHAPE, "gtts_attn_train_forward: bad shape");
+    if (!qkv || !out || !ctx || !stat || !scratch) return fail(GTTS_E_NULL, "gtts_attn_train_forward: null argument");
+    if (B <= 0 || N <= 0) return fail(GTTS_E_SHAPE, "gtts_attn_train_forward: bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int ns = attn_nslice(N);
     const size_t C = (size_t)AT_H * AT_D, bs = 3 * C * N;
     hipLaunchKernelGGL(attn_outer_kernel, dim3(ns, AT_H, B), dim3(256), 0, st, qkv + C * N, qkv + 2 * C * N, scratch, N, bs, bs, ns, 1);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(attn_combine_kernel, dim3(B * AT_H), dim3(1024), 0, st, scratch, ctx, stat, (const float *)nullptr, (float *)nullptr, ns, 1);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(attn_apply_kernel, dim3((N + 255) / 256, AT_H, B), dim3(256), 0, st, qkv, ctx, out, N, bs, C * N);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
 // dout [B][128][N] -> dqkv [B][384][N]; dctx [B][4][32][32] and rdot [B][4][32] are scratch outputs
 extern "C" int gtts_attn_train_backward(const float *qkv, const float *dout, const float *ctx, const float *stat, float *dqkv,
                                         float *dctx, float *rdot, float *scratch, int B, int N, gtts_stream_t stream) {
-    if (!qkv || !dout || !ctx || !stat || !dqkv || !dctx || !rdot || !scratch) return afail(GTTS_E_NULL, "gtts_attn_train_backward: null argument");
-    if (B <= 0 || N <= 0) return afail(GTTS_E_SHAPE, "gtts_attn_train_backward: bad shape");
+    if (!qkv || !dout || !ctx || !stat || !dqkv || !dctx || !rdot || !scratch) return fail(GTTS_E_NULL, "gtts_attn_train_backward: null argument");
+    if (B <= 0 || N <= 0) return fail(GTTS_E_SHAPE, "gtts_attn_train_backward: bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int ns = attn_nslice(N);
     const size_t C = (size_t)AT_H * AT_D, bs = 3 * C * N;
     hipLaunchKernelGGL(attn_outer_kernel, dim3(ns, AT_H, B), dim3(256), 0, st, qkv, dout, scratch, N, bs, C * N, ns, 0);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(attn_combine_kernel, dim3(B * AT_H), dim3(1024), 0, st, scratch, dctx, (float *)nullptr, ctx, rdot, ns, 0);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(attn_bwd_pixel_kernel, dim3((N + 255) / 256, AT_H, B), dim3(256), 0, st, qkv, dout, ctx, dctx, stat, rdot, dqkv, N);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -332,11 +316,11 @@ static int ew_blocks(size_t n4) { return (int)std::min<size_t>((n4 + 255) / 256,
 
 // y = f * g + x over n floats (n % 4 == 0); g is a device scalar
 extern "C" int gtts_rezero_forward(const float *f, const float *x, const float *g, float *y, size_t n, gtts_stream_t stream) {
-    if (!f || !x || !g || !y) return afail(GTTS_E_NULL, "gtts_rezero_forward: null argument");
-    if (n == 0 || n % 4) return afail(GTTS_E_SHAPE, "gtts_rezero_forward: element count must be a positive multiple of 4");
+    if (!f || !x || !g || !y) return fail(GTTS_E_NULL, "gtts_rezero_forward: null argument");
+    if (n == 0 || n % 4) return fail(GTTS_E_SHAPE, "gtts_rezero_forward: element count must be a positive multiple of 4");
     hipLaunchKernelGGL(rezero_fwd_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float4 *)f, (const float4 *)x, g,
                        (float4 *)y, n / 4);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -345,13 +329,13 @@ extern "C" size_t gtts_rezero_scratch_bytes(size_t n) { return (size_t)ew_blocks
 // df = dy * g, dg = sum(dy * f)
 extern "C" int gtts_rezero_backward(const float *dy, const float *f, const float *g, float *df, float *dg, void *scratch, size_t n,
                                     gtts_stream_t stream) {
-    if (!dy || !f || !g || !df || !dg || !scratch) return afail(GTTS_E_NULL, "gtts_rezero_backward: null argument");
-    if (n == 0 || n % 4) return afail(GTTS_E_SHAPE, "gtts_rezero_backward: element count must be a positive multiple of 4");
+    if (!dy || !f || !g || !df || !dg || !scratch) return fail(GTTS_E_NULL, "gtts_rezero_backward: null argument");
+    if (n == 0 || n % 4) return fail(GTTS_E_SHAPE, "gtts_rezero_backward: element count must be a positive multiple of 4");
     const int nb = ew_blocks(n / 4);
     hipLaunchKernelGGL(rezero_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const float4 *)dy, (const float4 *)f, g, (float4 *)df,
                        (double *)scratch, n / 4);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(rezero_bwd_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double *)scratch, nb, dg);
-    ACHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }

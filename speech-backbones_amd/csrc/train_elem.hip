@@ -4,8 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 
 #include "../../include/gradtts_abi.h"
 #include "common.h"
@@ -202,30 +200,16 @@ __global__ __launch_bounds__(256) void final_conv_bwd_finish_kernel(const float 
 
 using namespace gtts;
 
-static int efail(int code, const char *fmt, ...) {       // text goes to gtts_last_error() (plan.hip)
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-#define ECHK(expr)                                                                                                \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return efail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 // out = a + b * mask (a nullable: out = b * mask; mask nullable: out = a + b); a, b, out [B,C,H,W], mask [B,W]
 // b_cstride: channels of the tensor b is a slice of (0: b is contiguous [B,C,H,W])
 extern "C" int gtts_add_masked(const float *a, const float *b, const float *mask, float *out, int B, int C, int H, int W, int b_cstride,
                                gtts_stream_t stream) {
-    if (!b || !out || (!a && !mask)) return efail(GTTS_E_NULL, "gtts_add_masked: null argument");
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (long)H * W >= (1l << 30)) return efail(GTTS_E_SHAPE, "gtts_add_masked: bad shape");
+    if (!b || !out || (!a && !mask)) return fail(GTTS_E_NULL, "gtts_add_masked: null argument");
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || (long)H * W >= (1l << 30)) return fail(GTTS_E_SHAPE, "gtts_add_masked: bad shape");
     const int HW = H * W;
     hipLaunchKernelGGL(add_masked_kernel, dim3(B * C, (HW + 1023) / 1024), dim3(256), 0, (hipStream_t)stream, a, b, mask, out, C, HW, W,
                        (size_t)(b_cstride > 0 ? b_cstride : C) * HW);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -237,48 +221,48 @@ extern "C" size_t gtts_conv_wgrad_small_scratch_floats(int B, int cin, int cout,
 // dw [cout][cin][k][k], db [cout] (nullable) of y = Conv2d_kxk(x * mask) + bias for the first layer: cin 2 or 3, k 3 or 1
 extern "C" int gtts_conv_wgrad_small(const float *x, const float *mask, const float *dy, float *dw, float *db, float *scratch, int B, int cin,
                                      int cout, int H, int W, int ksize, gtts_stream_t stream) {
-    if (!x || !mask || !dy || !dw || !scratch) return efail(GTTS_E_NULL, "gtts_conv_wgrad_small: null argument");
+    if (!x || !mask || !dy || !dw || !scratch) return fail(GTTS_E_NULL, "gtts_conv_wgrad_small: null argument");
     if (B <= 0 || cout <= 0 || cout % WS_CO || H <= 0 || W <= 0 || (cin != 2 && cin != 3) || (ksize != 1 && ksize != 3))
-        return efail(GTTS_E_SHAPE, "gtts_conv_wgrad_small: cin must be 2 or 3 and the kernel 1x1 or 3x3 (got cin %d, k %d)", cin, ksize);
+        return fail(GTTS_E_SHAPE, "gtts_conv_wgrad_small: cin must be 2 or 3 and the kernel 1x1 or 3x3 (got cin %d, k %d)", cin, ksize);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(cout / WS_CO, B, WS_SPLIT);
     if (cin == 2 && ksize == 3) hipLaunchKernelGGL((wgrad_small_kernel<2, 3>), grid, dim3(256), 0, st, x, mask, dy, scratch, cout, H, W);
     else if (cin == 3 && ksize == 3) hipLaunchKernelGGL((wgrad_small_kernel<3, 3>), grid, dim3(256), 0, st, x, mask, dy, scratch, cout, H, W);
     else if (cin == 2) hipLaunchKernelGGL((wgrad_small_kernel<2, 1>), grid, dim3(256), 0, st, x, mask, dy, scratch, cout, H, W);
     else hipLaunchKernelGGL((wgrad_small_kernel<3, 1>), grid, dim3(256), 0, st, x, mask, dy, scratch, cout, H, W);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     const int nt = cin * ksize * ksize;
     hipLaunchKernelGGL(wgrad_small_finish_kernel, dim3((cout * (nt + 1) + 255) / 256), dim3(256), 0, st, scratch, dw, db, B * WS_SPLIT, cout, nt);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
 // out [B,4C,h,w] = the four stride-2 phases of in [B,C,2h,2w] (channel block (pr * 2 + pc): rows 2y + 1 - pr, columns 2x + 1 - pc)
 extern "C" int gtts_space_to_depth2(const float *in, float *out, int B, int C, int h, int w, gtts_stream_t stream) {
-    if (!in || !out) return efail(GTTS_E_NULL, "gtts_space_to_depth2: null argument");
-    if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || (long)h * w >= (1l << 28)) return efail(GTTS_E_SHAPE, "gtts_space_to_depth2: bad shape");
+    if (!in || !out) return fail(GTTS_E_NULL, "gtts_space_to_depth2: null argument");
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || (long)h * w >= (1l << 28)) return fail(GTTS_E_SHAPE, "gtts_space_to_depth2: bad shape");
     hipLaunchKernelGGL(space_to_depth2_kernel, dim3(B * C, (h * w + 255) / 256), dim3(256), 0, (hipStream_t)stream, in, out, C, h, w);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
 // out [B,C,2h,2w] = in [B,C,h,w] at the even positions, zero elsewhere
 extern "C" int gtts_zero_insert2(const float *in, float *out, int B, int C, int h, int w, gtts_stream_t stream) {
-    if (!in || !out) return efail(GTTS_E_NULL, "gtts_zero_insert2: null argument");
-    if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || (long)h * w >= (1l << 28)) return efail(GTTS_E_SHAPE, "gtts_zero_insert2: bad shape");
+    if (!in || !out) return fail(GTTS_E_NULL, "gtts_zero_insert2: null argument");
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || (long)h * w >= (1l << 28)) return fail(GTTS_E_SHAPE, "gtts_zero_insert2: bad shape");
     hipLaunchKernelGGL(zero_insert2_kernel, dim3(B * C, (4 * h * w + 1023) / 1024), dim3(256), 0, (hipStream_t)stream, in, out, h, w);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
 // out [B,1,H,W] = (Conv2d_1x1(x * mask; w [C], bias [1]) ) * mask
 extern "C" int gtts_final_conv_forward(const float *x, const float *w, const float *bias, const float *mask, float *out, int B, int C,
                                        int H, int W, gtts_stream_t stream) {
-    if (!x || !w || !bias || !mask || !out) return efail(GTTS_E_NULL, "gtts_final_conv_forward: null argument");
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return efail(GTTS_E_SHAPE, "gtts_final_conv_forward: bad shape");
+    if (!x || !w || !bias || !mask || !out) return fail(GTTS_E_NULL, "gtts_final_conv_forward: null argument");
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_final_conv_forward: bad shape");
     const int HW = H * W;
     hipLaunchKernelGGL(final_conv_fwd_kernel, dim3((HW + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, x, w, bias, mask, out, C, HW, W);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -290,14 +274,14 @@ extern "C" size_t gtts_final_conv_scratch_floats(int B, int C, int H, int W) {
 // dx [B,C,H,W], dw [C], db [1] of gtts_final_conv_forward given dout [B,1,H,W]
 extern "C" int gtts_final_conv_backward(const float *x, const float *w, const float *mask, const float *dout, float *dx, float *dw,
                                         float *db, float *scratch, int B, int C, int H, int W, gtts_stream_t stream) {
-    if (!x || !w || !mask || !dout || !dx || !dw || !db || !scratch) return efail(GTTS_E_NULL, "gtts_final_conv_backward: null argument");
-    if (B <= 0 || C <= 0 || C > 1024 || H <= 0 || W <= 0) return efail(GTTS_E_SHAPE, "gtts_final_conv_backward: bad shape");
+    if (!x || !w || !mask || !dout || !dx || !dw || !db || !scratch) return fail(GTTS_E_NULL, "gtts_final_conv_backward: null argument");
+    if (B <= 0 || C <= 0 || C > 1024 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_final_conv_backward: bad shape");
     const int HW = H * W, nblk = (HW + 255) / 256;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(final_conv_bwd_kernel, dim3(nblk, B), dim3(256), (size_t)4 * (C + 1) * sizeof(float), st, x, w, mask, dout, dx, scratch, C,
                        HW, W);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(final_conv_bwd_finish_kernel, dim3(C + 1), dim3(256), 0, st, scratch, B * nblk, C, dw, db);
-    ECHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }

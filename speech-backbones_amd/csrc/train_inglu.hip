@@ -13,9 +13,6 @@
 // gradients are reduced over the batch by a second, tiny kernel in sample order.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
 #include "../../include/gradtts_abi.h"
 #include "common.h"
 #include "kernels.h"
@@ -131,15 +128,6 @@ __global__ void in_glu_param_kernel(const float *__restrict__ pgrad, float *__re
     dbeta[ch] = (float)bsum;
 }
 
-static int ifail(int code, const char *fmt, ...) {       // text goes to gtts_last_error() (plan.hip)
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-
 }  // namespace gtts
 
 using namespace gtts;
@@ -149,23 +137,23 @@ extern "C" size_t gtts_in_glu_scratch_floats(int B, int C) { return B > 0 && C >
 
 extern "C" int gtts_in_glu_forward(const float *y, const float *gamma, const float *beta, float *out, float *stats, int B, int C, int H,
                                    int W, float eps, gtts_stream_t stream) {
-    if (!y || !gamma || !beta || !out || !stats) return ifail(GTTS_E_NULL, "gtts_in_glu_forward: null argument");
+    if (!y || !gamma || !beta || !out || !stats) return fail(GTTS_E_NULL, "gtts_in_glu_forward: null argument");
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
-        return ifail(GTTS_E_SHAPE, "gtts_in_glu_forward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+        return fail(GTTS_E_SHAPE, "gtts_in_glu_forward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
     hipLaunchKernelGGL(in_glu_fwd_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, out, stats, C, H * W, eps);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GTTS_OK : ifail(GTTS_E_HIP, "gtts_in_glu_forward: %s", hipGetErrorString(e));
+    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_forward: %s", hipGetErrorString(e));
 }
 
 extern "C" int gtts_in_glu_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *stats, float *dy,
                                     float *dgamma, float *dbeta, float *scratch, int B, int C, int H, int W, gtts_stream_t stream) {
     if (!dout || !y || !gamma || !beta || !stats || !dy || !dgamma || !dbeta || !scratch)
-        return ifail(GTTS_E_NULL, "gtts_in_glu_backward: null argument");
+        return fail(GTTS_E_NULL, "gtts_in_glu_backward: null argument");
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
-        return ifail(GTTS_E_SHAPE, "gtts_in_glu_backward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+        return fail(GTTS_E_SHAPE, "gtts_in_glu_backward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(in_glu_bwd_kernel, dim3(C, B), dim3(256), 0, st, dout, y, gamma, beta, stats, dy, scratch, C, H * W);
     hipLaunchKernelGGL(in_glu_param_kernel, dim3((2 * C + 127) / 128), dim3(128), 0, st, scratch, dgamma, dbeta, B, 2 * C);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GTTS_OK : ifail(GTTS_E_HIP, "gtts_in_glu_backward: %s", hipGetErrorString(e));
+    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_backward: %s", hipGetErrorString(e));
 }

@@ -11,9 +11,6 @@
 // combined across the workgroup in fp64.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
 #include "../../include/gradtts_abi.h"
 #include "common.h"
 #include "kernels.h"
@@ -211,20 +208,6 @@ __global__ __launch_bounds__(256) void gn_mish_bwd_apply_kernel(const float *__r
 
 using namespace gtts;
 
-static int nfail(int code, const char *fmt, ...) {       // text goes to gtts_last_error() (plan.hip)
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-#define NCHK(expr)                                                                                                \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return nfail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 static int norm_shape_ok(int B, int C, int H, int W, int groups) {
     return B > 0 && C > 0 && H > 0 && W > 0 && groups > 0 && C % groups == 0 && (long)H * W < (1l << 30);
 }
@@ -233,18 +216,18 @@ static int norm_shape_ok(int B, int C, int H, int W, int groups) {
 extern "C" int gtts_gn_mish_forward_tb(const float *y, const float *gamma, const float *beta, const float *mask, const float *tb,
                                        float *out, float *stats, int B, int C, int H, int W, int groups, float eps,
                                        gtts_stream_t stream) {
-    if (!y || !gamma || !beta || !mask || !out || !stats) return nfail(GTTS_E_NULL, "gtts_gn_mish_forward: null argument");
-    if (!norm_shape_ok(B, C, H, W, groups)) return nfail(GTTS_E_SHAPE, "gtts_gn_mish_forward: bad shape B=%d C=%d H=%d W=%d groups=%d", B, C, H, W, groups);
+    if (!y || !gamma || !beta || !mask || !out || !stats) return fail(GTTS_E_NULL, "gtts_gn_mish_forward: null argument");
+    if (!norm_shape_ok(B, C, H, W, groups)) return fail(GTTS_E_SHAPE, "gtts_gn_mish_forward: bad shape B=%d C=%d H=%d W=%d groups=%d", B, C, H, W, groups);
     const int HW = H * W, cpg = C / groups;
     hipStream_t st = (hipStream_t)stream;
     double *partial = reinterpret_cast<double *>(stats + (size_t)B * groups * 2);      // behind the (mean, rstd) pairs (8-byte aligned)
     hipLaunchKernelGGL(gn_stats_kernel, dim3(B * groups, GN_SPLIT), dim3(256), 0, st, y, partial, (size_t)cpg * HW);
-    NCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(gn_stats_finish_kernel, dim3((B * groups + 255) / 256), dim3(256), 0, st, partial, stats, B * groups,
                        1.0 / ((double)cpg * HW), eps);
-    NCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(gn_mish_fwd_kernel, dim3(B * C, (HW + 1023) / 1024), dim3(256), 0, st, y, gamma, beta, mask, stats, tb, out, C, HW, W, cpg);
-    NCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -264,20 +247,20 @@ extern "C" int gtts_gn_mish_backward_tb(const float *dout, const float *y, const
                                         const float *stats, float *dy, float *dgamma, float *dbeta, float *dtb, void *scratch, int B,
                                         int C, int H, int W, int groups, gtts_stream_t stream) {
     if (!dout || !y || !gamma || !beta || !mask || !stats || !dy || !dgamma || !dbeta || !scratch)
-        return nfail(GTTS_E_NULL, "gtts_gn_mish_backward: null argument");
-    if (!norm_shape_ok(B, C, H, W, groups)) return nfail(GTTS_E_SHAPE, "gtts_gn_mish_backward: bad shape B=%d C=%d H=%d W=%d groups=%d", B, C, H, W, groups);
+        return fail(GTTS_E_NULL, "gtts_gn_mish_backward: null argument");
+    if (!norm_shape_ok(B, C, H, W, groups)) return fail(GTTS_E_SHAPE, "gtts_gn_mish_backward: bad shape B=%d C=%d H=%d W=%d groups=%d", B, C, H, W, groups);
     const int HW = H * W, cpg = C / groups;
     hipStream_t st = (hipStream_t)stream;
     float *ws = (float *)scratch;                 // [B][C][2]
     float *coef = ws + (size_t)B * C * 2;         // [B][groups][2]  (fits: groups <= C)
     hipLaunchKernelGGL(gn_mish_bwd_reduce_kernel, dim3(B * C), dim3(256), 0, st, dout, y, gamma, beta, mask, stats, ws, dtb, C, HW, W, cpg);
-    NCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(gn_mish_bwd_finish_kernel, dim3(1), dim3(256), 0, st, ws, gamma, dgamma, dbeta, coef, B, C, cpg,
                        1.0 / ((double)cpg * HW));
-    NCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(gn_mish_bwd_apply_kernel, dim3(B * C, (HW + 1023) / 1024), dim3(256), 0, st, dout, y, gamma, beta, mask, stats, coef,
                        dy, C, HW, W, cpg);
-    NCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 

@@ -17,8 +17,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cstdarg>
-#include <cstdio>
 
 #include "../../include/gradtts_abi.h"
 #include "common.h"
@@ -442,20 +440,6 @@ static void wgrad2_geometry(int B, int cin, int cout, int H, int W, Wgrad2Args &
 
 using namespace gtts;
 
-static int wfail(int code, const char *fmt, ...) {       // text goes to gtts_last_error() (plan.hip)
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-#define WCHK(expr)                                                                                                \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess) return wfail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 extern "C" size_t gtts_conv3x3_wgrad_workspace_bytes(int B, int cin, int cout, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 64 || cout % 64) return 0;
     Wgrad2Args a;
@@ -467,15 +451,15 @@ extern "C" size_t gtts_conv3x3_wgrad_workspace_bytes(int B, int cin, int cout, i
 extern "C" int gtts_conv3x3_wgrad_tiled2(const float *x, const float *x1, int c0, const float *mask, const float *dy, float *dw, float *db,
                                          void *workspace, size_t workspace_bytes, int B, int cin, int cout, int H, int W,
                                          gtts_stream_t stream) {
-    if (!x || !mask || !dy || !dw || !workspace) return wfail(GTTS_E_NULL, "gtts_conv3x3_wgrad_tiled: null argument");
-    if (x1 && (c0 <= 0 || c0 >= cin || c0 % 64)) return wfail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: c0 must be a multiple of 64 inside (0, cin) (got %d of %d)", c0, cin);
+    if (!x || !mask || !dy || !dw || !workspace) return fail(GTTS_E_NULL, "gtts_conv3x3_wgrad_tiled: null argument");
+    if (x1 && (c0 <= 0 || c0 >= cin || c0 % 64)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: c0 must be a multiple of 64 inside (0, cin) (got %d of %d)", c0, cin);
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 64 || cout % 64)
-        return wfail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
-    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return wfail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: tensor too large");
+        return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
+    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: tensor too large");
     Wgrad2Args a;
     wgrad2_geometry(B, cin, cout, H, W, a);
     const size_t need = gtts_conv3x3_wgrad_workspace_bytes(B, cin, cout, H, W);
-    if (workspace_bytes < need) return wfail(GTTS_E_WORKSPACE, "gtts_conv3x3_wgrad_tiled: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "gtts_conv3x3_wgrad_tiled: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     const int tiles = (cin / 64) * (cout / 64);
     a.x = x; a.x1 = x1; a.c0 = x1 ? c0 : cin; a.mask = mask; a.dy = dy; a.part = (float *)workspace;
     a.dbpart = db ? a.part + (size_t)a.nslice * tiles * (9 * 64 * 64) : nullptr;
@@ -485,15 +469,15 @@ extern "C" int gtts_conv3x3_wgrad_tiled2(const float *x, const float *x1, int c0
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        WCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wgrad2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        GTTS_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wgrad2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
         attr_set[dev].store(1, std::memory_order_relaxed);
     }
     hipLaunchKernelGGL(conv3x3_wgrad2_kernel, dim3((unsigned)(tiles * a.nslice)), dim3(512), smem, st, a);
-    WCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     const size_t total = (size_t)tiles * (9 * 64 * 64) + (db ? (size_t)cout : 0);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, a.part, a.dbpart, dw, db, cin, cout,
                        a.nslice, 9);
-    WCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 
@@ -507,24 +491,24 @@ extern "C" size_t gtts_conv1x1_wgrad_workspace_bytes(int B, int cin, int cout, i
 // dw [cout][cin], db [cout] (or null) of y = Conv2d_1x1(x * mask) + bias; mask [B][W] columns or null (no mask)
 extern "C" int gtts_conv1x1_wgrad(const float *x, const float *mask, const float *dy, float *dw, float *db, void *workspace,
                                   size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
-    if (!x || !dy || !dw || !workspace) return wfail(GTTS_E_NULL, "gtts_conv1x1_wgrad: null argument");
+    if (!x || !dy || !dw || !workspace) return fail(GTTS_E_NULL, "gtts_conv1x1_wgrad: null argument");
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 64 || cout % 64)
-        return wfail(GTTS_E_SHAPE, "gtts_conv1x1_wgrad: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
-    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return wfail(GTTS_E_SHAPE, "gtts_conv1x1_wgrad: tensor too large");
+        return fail(GTTS_E_SHAPE, "gtts_conv1x1_wgrad: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
+    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return fail(GTTS_E_SHAPE, "gtts_conv1x1_wgrad: tensor too large");
     Wgrad1Args a;
     wgrad1_geometry(B, cin, cout, H * W, W, a);
     const size_t need = gtts_conv1x1_wgrad_workspace_bytes(B, cin, cout, H, W);
-    if (workspace_bytes < need) return wfail(GTTS_E_WORKSPACE, "gtts_conv1x1_wgrad: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "gtts_conv1x1_wgrad: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     const int tiles = (cin / 64) * (cout / 64);
     a.x = x; a.mask = mask; a.dy = dy; a.part = (float *)workspace;
     a.dbpart = db ? a.part + (size_t)a.nslice * tiles * (64 * 64) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(conv1x1_wgrad_kernel, dim3((unsigned)(tiles * a.nslice)), dim3(256), 0, st, a);
-    WCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     const size_t total = (size_t)tiles * (64 * 64) + (db ? (size_t)cout : 0);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, a.part, a.dbpart, dw, db, cin, cout,
                        a.nslice, 1);
-    WCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }
 

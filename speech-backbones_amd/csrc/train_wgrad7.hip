@@ -31,8 +31,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 
 #include "../../include/gradtts_abi.h"
 #include "common.h"
@@ -263,15 +261,6 @@ static void wgrad7_geometry(int B, int cin, int cout, int H, int W, Wgrad7Args &
 
 using namespace gtts;
 
-static int w7fail(int code, const char *fmt, ...) {       // text goes to gtts_last_error() (plan.hip)
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-
 extern "C" size_t gtts_conv7x7_wgrad_workspace_bytes(int B, int cin, int cout, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 64 || cout % 64) return 0;
     Wgrad7Args a;
@@ -282,15 +271,15 @@ extern "C" size_t gtts_conv7x7_wgrad_workspace_bytes(int B, int cin, int cout, i
 // dw [cout][cin][7][7] and db [cout] (nullable) of y = Conv2d_7x7(x * mask, padding 3) + bias; both are overwritten
 extern "C" int gtts_conv7x7_wgrad(const float *x, const float *mask, const float *dy, float *dw, float *db, void *workspace,
                                   size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
-    if (!x || !mask || !dy || !dw || !workspace) return w7fail(GTTS_E_NULL, "gtts_conv7x7_wgrad: null argument");
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return w7fail(GTTS_E_SHAPE, "gtts_conv7x7_wgrad: bad shape");
-    if (cin % 64 || cout % 64) return w7fail(GTTS_E_CONFIG, "gtts_conv7x7_wgrad: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
+    if (!x || !mask || !dy || !dw || !workspace) return fail(GTTS_E_NULL, "gtts_conv7x7_wgrad: null argument");
+    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv7x7_wgrad: bad shape");
+    if (cin % 64 || cout % 64) return fail(GTTS_E_CONFIG, "gtts_conv7x7_wgrad: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
     if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29))
-        return w7fail(GTTS_E_SHAPE, "gtts_conv7x7_wgrad: tensor too large for 32-bit offsets");
+        return fail(GTTS_E_SHAPE, "gtts_conv7x7_wgrad: tensor too large for 32-bit offsets");
     Wgrad7Args a;
     wgrad7_geometry(B, cin, cout, H, W, a);
     const size_t need = gtts_conv7x7_wgrad_workspace_bytes(B, cin, cout, H, W);
-    if (workspace_bytes < need) return w7fail(GTTS_E_WORKSPACE, "gtts_conv7x7_wgrad: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "gtts_conv7x7_wgrad: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     const int tiles = (cin / 64) * (cout / 64);
     a.x = x; a.mask = mask; a.dy = dy; a.part = (float *)workspace;
     a.dbpart = db ? a.part + (size_t)a.nslice * tiles * (49 * 64 * 64) : nullptr;
@@ -298,6 +287,6 @@ extern "C" int gtts_conv7x7_wgrad(const float *x, const float *mask, const float
     hipLaunchKernelGGL(conv7x7_wgrad_kernel, dim3((unsigned)(tiles * 7 * a.nslice)), dim3(256), 0, st, a);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = launch_wgrad_reduce(a.part, a.dbpart, dw, db, cin, cout, a.nslice, 49, st);
-    if (e != hipSuccess) return w7fail(GTTS_E_HIP, "gtts_conv7x7_wgrad: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "gtts_conv7x7_wgrad: %s", hipGetErrorString(e));
     return GTTS_OK;
 }

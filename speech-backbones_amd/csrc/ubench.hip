@@ -128,8 +128,8 @@ extern "C" {
 size_t gtts_ubench_mfma_out_floats(int workgroups) { return workgroups > 0 ? (size_t)workgroups * 256 : 0; }
 
 int gtts_ubench_mfma(const void *src, size_t src_bytes, float *out, int workgroups, int iters, double *flops, gtts_stream_t stream) {
-    if (!src || !out) return gtts::set_error(GTTS_E_NULL, "gtts_ubench_mfma: null buffer");
-    if (src_bytes < 4096 || workgroups <= 0 || iters == 0) return gtts::set_error(GTTS_E_SHAPE, "gtts_ubench_mfma: bad sizes");
+    if (!src || !out) return gtts::fail(GTTS_E_NULL, "gtts_ubench_mfma: null buffer");
+    if (src_bytes < 4096 || workgroups <= 0 || iters == 0) return gtts::fail(GTTS_E_SHAPE, "gtts_ubench_mfma: bad sizes");
     if (iters > 0) {
         hipLaunchKernelGGL((gtts::ubench_mfma_kernel<2, 4>), dim3(workgroups), dim3(256), 0, (hipStream_t)stream,
                            reinterpret_cast<const unsigned short *>(src), src_bytes / 2, out, iters);
@@ -140,13 +140,13 @@ int gtts_ubench_mfma(const void *src, size_t src_bytes, float *out, int workgrou
         if (flops) *flops = (double)workgroups * 4.0 * (-iters) * 16.0 * (2.0 * 16 * 16 * 32);
     }
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GTTS_OK : gtts::set_error(GTTS_E_HIP, hipGetErrorString(e));
+    return e == hipSuccess ? GTTS_OK : gtts::fail(GTTS_E_HIP, "%s", hipGetErrorString(e));
 }
 
 int gtts_ubench_hbm(const float *a, const float *b, float *c, size_t n, int mode, int workgroups, double *bytes, gtts_stream_t stream) {
     const int m = mode & 3, nt = mode >> 2;
-    if (!a || (m == 1 && !b) || !c) return gtts::set_error(GTTS_E_NULL, "gtts_ubench_hbm: null buffer");
-    if (n < 4 || n % 4 != 0 || workgroups <= 0 || mode < 0 || m > 2 || nt > 1) return gtts::set_error(GTTS_E_SHAPE, "gtts_ubench_hbm: bad sizes");
+    if (!a || (m == 1 && !b) || !c) return gtts::fail(GTTS_E_NULL, "gtts_ubench_hbm: null buffer");
+    if (n < 4 || n % 4 != 0 || workgroups <= 0 || mode < 0 || m > 2 || nt > 1) return gtts::fail(GTTS_E_SHAPE, "gtts_ubench_hbm: bad sizes");
     const gtts::f32x4 *a4 = reinterpret_cast<const gtts::f32x4 *>(a), *b4 = reinterpret_cast<const gtts::f32x4 *>(b);
     gtts::f32x4 *c4 = reinterpret_cast<gtts::f32x4 *>(c);
     hipStream_t st = (hipStream_t)stream;
@@ -157,7 +157,7 @@ int gtts_ubench_hbm(const float *a, const float *b, float *c, size_t n, int mode
 #undef GTTS_UB
     if (bytes) *bytes = (double)n * (m == 0 ? 8.0 : (m == 1 ? 12.0 : 4.0));
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GTTS_OK : gtts::set_error(GTTS_E_HIP, hipGetErrorString(e));
+    return e == hipSuccess ? GTTS_OK : gtts::fail(GTTS_E_HIP, "%s", hipGetErrorString(e));
 }
 
 }  // extern "C"

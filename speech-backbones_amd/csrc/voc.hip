@@ -14,7 +14,6 @@
 // Layout: [B][C][L] fp32, L fastest -> coalesced along time.  conv_post (32 -> 1 channel, tanh) is a VALU kernel.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -64,20 +63,6 @@ __global__ void conv_post_kernel(const float *__restrict__ x, const float *__res
 using namespace gtts;
 
 // ------------------------------------------------------------------------------------------------ host plan + C ABI
-static int vfail(int code, const char *fmt, ...) {       // text goes to gtts_last_error() (plan.hip)
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-#define VCHK(expr)                                                                                               \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return vfail(GTTS_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
 struct VocLayer {
     std::string name;
     int mode;              // 0 Conv1d, 1 ConvTranspose1d
@@ -98,8 +83,6 @@ struct gtts_voc {
     std::vector<std::vector<std::vector<int>>> rb;   // [stage][kernel][conv index in reference order] layer ids
 };
 
-static size_t valign(size_t x) { return (x + 255) / 256 * 256; }
-
 static int voc_add_layer(gtts_voc *v, const std::string &name, int mode, int cin, int cout, int K, int dil, int S, int pad) {
     VocLayer L;
     L.name = name; L.mode = mode; L.cin = cin; L.cout = cout; L.K = K; L.dil = dil; L.S = S; L.pad = pad;
@@ -118,18 +101,18 @@ static int voc_add_layer(gtts_voc *v, const std::string &name, int mode, int cin
     L.halo_lo = -lo; L.halo_hi = hi;
     const size_t nchunk = (cin + 15) / 16, ncot = ((size_t)cout * S + g.MT - 1) / g.MT;
     L.w_off = v->blob_bytes;
-    v->blob_bytes = valign(v->blob_bytes + nchunk * L.nst * ncot * (size_t)2 * g.tps * 2 * g.MT * 16);
+    v->blob_bytes = align256(v->blob_bytes + nchunk * L.nst * ncot * (size_t)2 * g.tps * 2 * g.MT * 16);
     L.b_off = v->blob_bytes;
-    v->blob_bytes = valign(v->blob_bytes + (size_t)cout * 4);
+    v->blob_bytes = align256(v->blob_bytes + (size_t)cout * 4);
     v->layers.push_back(L);
     return (int)v->layers.size() - 1;
 }
 
 extern "C" int gtts_voc_create(const gtts_voc_cfg *cfg, gtts_voc **out) {
-    if (!cfg || !out) return vfail(GTTS_E_NULL, "gtts_voc_create: null argument");
+    if (!cfg || !out) return fail(GTTS_E_NULL, "gtts_voc_create: null argument");
     if (cfg->n_ups < 1 || cfg->n_ups > 8 || cfg->n_kernels < 1 || cfg->n_kernels > 8)
-        return vfail(GTTS_E_CONFIG, "unsupported number of upsamplers / resblock kernels");
-    if (cfg->resblock_type != 1 && cfg->resblock_type != 2) return vfail(GTTS_E_CONFIG, "resblock must be 1 or 2");
+        return fail(GTTS_E_CONFIG, "unsupported number of upsamplers / resblock kernels");
+    if (cfg->resblock_type != 1 && cfg->resblock_type != 2) return fail(GTTS_E_CONFIG, "resblock must be 1 or 2");
     gtts_voc *v = new gtts_voc();
     v->cfg = *cfg;
     int ch = cfg->upsample_initial_channel;
@@ -138,7 +121,7 @@ extern "C" int gtts_voc_create(const gtts_voc_cfg *cfg, gtts_voc **out) {
         const int u = cfg->upsample_rates[i], k = cfg->upsample_kernel_sizes[i];
         if (ch % 2 || k % u || (k - u) % 2 || k / u != 2 || (u & (u - 1))) {
             delete v;
-            return vfail(GTTS_E_CONFIG, "upsampler %d: need kernel = 2 * rate, a power-of-two rate and even channels (k=%d, u=%d)", i, k, u);
+            return fail(GTTS_E_CONFIG, "upsampler %d: need kernel = 2 * rate, a power-of-two rate and even channels (k=%d, u=%d)", i, k, u);
         }
         char nm[64];
         snprintf(nm, sizeof nm, "ups.%d", i);
@@ -147,7 +130,7 @@ extern "C" int gtts_voc_create(const gtts_voc_cfg *cfg, gtts_voc **out) {
         v->rb.emplace_back();
         for (int j = 0; j < cfg->n_kernels; ++j) {
             const int kk = cfg->resblock_kernel_sizes[j];
-            if (kk % 2 == 0 || kk > C1_MAXTAP - 1) { delete v; return vfail(GTTS_E_CONFIG, "resblock kernel %d unsupported", kk); }
+            if (kk % 2 == 0 || kk > C1_MAXTAP - 1) { delete v; return fail(GTTS_E_CONFIG, "resblock kernel %d unsupported", kk); }
             std::vector<int> ids;
             const int rbi = i * cfg->n_kernels + j;
             const int nd = cfg->resblock_type == 1 ? 3 : 2;
@@ -167,15 +150,15 @@ extern "C" int gtts_voc_create(const gtts_voc_cfg *cfg, gtts_voc **out) {
                 }
             }
             for (int id : ids)
-                if (v->layers[id].halo_lo + v->layers[id].halo_hi > 128) { delete v; return vfail(GTTS_E_CONFIG, "receptive field too wide"); }
+                if (v->layers[id].halo_lo + v->layers[id].halo_hi > 128) { delete v; return fail(GTTS_E_CONFIG, "receptive field too wide"); }
             v->rb.back().push_back(ids);
         }
     }
     v->post_cin = ch;
     v->post_w_off = v->blob_bytes;
-    v->blob_bytes = valign(v->blob_bytes + (size_t)ch * 7 * 4);
+    v->blob_bytes = align256(v->blob_bytes + (size_t)ch * 7 * 4);
     v->post_b_off = v->blob_bytes;
-    v->blob_bytes = valign(v->blob_bytes + 4);
+    v->blob_bytes = align256(v->blob_bytes + 4);
     *out = v;
     return GTTS_OK;
 }
@@ -186,10 +169,10 @@ extern "C" void gtts_voc_destroy(gtts_voc *v) { delete v; }
 // weight, bias; then conv_post.weight, conv_post.bias.  Names are the reference's module paths (models.py).
 extern "C" int gtts_voc_num_params(const gtts_voc *v) { return v ? (int)v->layers.size() * 2 + 2 : 0; }
 extern "C" int gtts_voc_param_info(const gtts_voc *v, int i, const char **name, int *rank, int dims[4]) {
-    if (!v) return vfail(GTTS_E_NULL, "null vocoder");
+    if (!v) return fail(GTTS_E_NULL, "null vocoder");
     static thread_local std::string s;
     const int n = (int)v->layers.size();
-    if (i < 0 || i >= 2 * n + 2) return vfail(GTTS_E_SHAPE, "parameter index out of range");
+    if (i < 0 || i >= 2 * n + 2) return fail(GTTS_E_SHAPE, "parameter index out of range");
     int d[4] = {1, 1, 1, 1}, rk = 1;
     if (i < 2 * n) {
         const VocLayer &L = v->layers[i / 2];
@@ -208,27 +191,27 @@ extern "C" int gtts_voc_param_info(const gtts_voc *v, int i, const char **name, 
 extern "C" size_t gtts_voc_packed_bytes(const gtts_voc *v) { return v ? v->blob_bytes : 0; }
 
 extern "C" int gtts_voc_pack(const gtts_voc *v, const void *const *ptrs, int n_params, void *packed, gtts_stream_t stream) {
-    if (!v || !ptrs || !packed) return vfail(GTTS_E_NULL, "gtts_voc_pack: null argument");
-    if (n_params != gtts_voc_num_params(v)) return vfail(GTTS_E_PARAMS, "expected %d parameters, got %d", gtts_voc_num_params(v), n_params);
+    if (!v || !ptrs || !packed) return fail(GTTS_E_NULL, "gtts_voc_pack: null argument");
+    if (n_params != gtts_voc_num_params(v)) return fail(GTTS_E_PARAMS, "expected %d parameters, got %d", gtts_voc_num_params(v), n_params);
     hipStream_t st = (hipStream_t)stream;
     unsigned char *blob = (unsigned char *)packed;
-    VCHK(hipMemsetAsync(blob, 0, v->blob_bytes, st));
+    GTTS_HIPCHK(hipMemsetAsync(blob, 0, v->blob_bytes, st));
     const int n = (int)v->layers.size();
     for (int li = 0; li < n; ++li) {
         const VocLayer &L = v->layers[li];
         const float *w = (const float *)ptrs[2 * li], *bb = (const float *)ptrs[2 * li + 1];
-        if (!w || !bb) return vfail(GTTS_E_NULL, "parameter of %s is null", L.name.c_str());
+        if (!w || !bb) return fail(GTTS_E_NULL, "parameter of %s is null", L.name.c_str());
         const int nchunk = (L.cin + 15) / 16, ncot = (L.cout * L.S + L.MT - 1) / L.MT;
         const size_t total = (size_t)nchunk * L.nst * ncot * L.tps * 2 * L.MT * 8;
         hipLaunchKernelGGL(pack_conv1d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w,
                            reinterpret_cast<__bf16 *>(blob + L.w_off), L.mode, L.cin, L.cout, L.K, L.S, L.pad, L.MT, L.nst, L.tps,
                            nchunk, ncot, total);
-        VCHK(hipGetLastError());
-        VCHK(hipMemcpyAsync(blob + L.b_off, bb, (size_t)L.cout * 4, hipMemcpyDeviceToDevice, st));
+        GTTS_HIPCHK(hipGetLastError());
+        GTTS_HIPCHK(hipMemcpyAsync(blob + L.b_off, bb, (size_t)L.cout * 4, hipMemcpyDeviceToDevice, st));
     }
-    if (!ptrs[2 * n] || !ptrs[2 * n + 1]) return vfail(GTTS_E_NULL, "conv_post parameter is null");
-    VCHK(hipMemcpyAsync(blob + v->post_w_off, ptrs[2 * n], (size_t)v->post_cin * v->post_K * 4, hipMemcpyDeviceToDevice, st));
-    VCHK(hipMemcpyAsync(blob + v->post_b_off, ptrs[2 * n + 1], 4, hipMemcpyDeviceToDevice, st));
+    if (!ptrs[2 * n] || !ptrs[2 * n + 1]) return fail(GTTS_E_NULL, "conv_post parameter is null");
+    GTTS_HIPCHK(hipMemcpyAsync(blob + v->post_w_off, ptrs[2 * n], (size_t)v->post_cin * v->post_K * 4, hipMemcpyDeviceToDevice, st));
+    GTTS_HIPCHK(hipMemcpyAsync(blob + v->post_b_off, ptrs[2 * n + 1], 4, hipMemcpyDeviceToDevice, st));
     return GTTS_OK;
 }
 
@@ -245,7 +228,7 @@ extern "C" size_t gtts_voc_workspace_bytes(const gtts_voc *v, int B, int T) {
     if (!v || B <= 0 || T <= 0) return 0;
     size_t big = (size_t)B * v->cfg.upsample_initial_channel * T;
     for (int i = 0; i < v->cfg.n_ups; ++i) big = std::max(big, voc_stage_elems(v, B, T, i, nullptr, nullptr));
-    return 5 * valign(big * 4);
+    return 5 * align256(big * 4);
 }
 extern "C" int gtts_voc_hop(const gtts_voc *v) {
     if (!v) return 0;
@@ -269,19 +252,19 @@ static int voc_run_layer(const gtts_voc *v, const unsigned char *blob, int li, c
     a.in_mask = nullptr; a.out_mask = nullptr;
     a.ls = 0;
     while ((1 << a.ls) < L.S) ++a.ls;
-    if ((size_t)L.cout * Lin * L.S >= ((size_t)1 << 31)) return vfail(GTTS_E_SHAPE, "%s: tensor too large", L.name.c_str());
+    if ((size_t)L.cout * Lin * L.S >= ((size_t)1 << 31)) return fail(GTTS_E_SHAPE, "%s: tensor too large", L.name.c_str());
     const hipError_t e = L.tps == 3 ? launch_c1_t<3>(a, st) : launch_c1_t<4>(a, st);
-    if (e != hipSuccess) return vfail(GTTS_E_HIP, "conv1d %s: %s", L.name.c_str(), hipGetErrorString(e));
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv1d %s: %s", L.name.c_str(), hipGetErrorString(e));
     return GTTS_OK;
 }
 
 // Generator.forward (models.py:103-120): mel [B, n_mels, T] -> wav [B, 1, T * hop]
 extern "C" int gtts_voc_forward(const gtts_voc *v, const void *packed, const float *mel, float *wav, void *workspace,
                                 size_t workspace_bytes, int B, int T, gtts_stream_t stream) {
-    if (!v || !packed || !mel || !wav || !workspace) return vfail(GTTS_E_NULL, "gtts_voc_forward: null argument");
-    if (B <= 0 || T <= 0) return vfail(GTTS_E_SHAPE, "gtts_voc_forward: bad shape B=%d T=%d", B, T);
+    if (!v || !packed || !mel || !wav || !workspace) return fail(GTTS_E_NULL, "gtts_voc_forward: null argument");
+    if (B <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_voc_forward: bad shape B=%d T=%d", B, T);
     const size_t need = gtts_voc_workspace_bytes(v, B, T);
-    if (workspace_bytes < need) return vfail(GTTS_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
     const unsigned char *blob = (const unsigned char *)packed;
     const size_t slot = need / 5;
@@ -332,9 +315,9 @@ extern "C" int gtts_voc_forward(const gtts_voc *v, const void *packed, const flo
     }
     // x = tanh(conv_post(leaky_relu(x)))  (:116-118; default slope 0.01)
     const int C = v->post_cin;
-    if (v->post_K != 7 || len % 4 != 0) return vfail(GTTS_E_CONFIG, "conv_post needs k = 7 and a multiple-of-4 length");
+    if (v->post_K != 7 || len % 4 != 0) return fail(GTTS_E_CONFIG, "conv_post needs k = 7 and a multiple-of-4 length");
     hipLaunchKernelGGL(conv_post_kernel, dim3((unsigned)((len / 4 + 255) / 256), B), dim3(256), (size_t)C * v->post_K * 4, st, cur,
                        (const float *)(blob + v->post_w_off), (const float *)(blob + v->post_b_off), wav, C, (int)len, v->post_K, 0.01f);
-    VCHK(hipGetLastError());
+    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }

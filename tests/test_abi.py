@@ -91,6 +91,28 @@ def test_conv_kernel_plan_option():
     assert copy.deepcopy(forced).conv_ws is True          # plans rebuild from their constructor arguments
 
 
+@pytest.mark.parametrize("make", [lambda S: S.Plan(), lambda S: S.Vocoder(), lambda S: S.Encoder("text"), lambda S: S.Encoder("mel"),
+                                  lambda S: S.PostNetPlan()], ids=["plan", "vocoder", "encoder-text", "encoder-mel", "postnet"])
+def test_handles_copy_and_pickle_by_rebuilding(make):
+    """Every native handle is host metadata: copy.deepcopy and a pickle round trip each give a distinct live handle of the same class,
+    built from the same constructor arguments, and dropping a copy leaves the original usable."""
+    import copy
+    import pickle
+    S = pkg()
+    h = make(S)
+    layout, nbytes = h.param_layout(), h.packed_bytes()
+    assert layout and nbytes > 0
+    for dup in (copy.deepcopy(h), pickle.loads(pickle.dumps(h))):
+        assert type(dup) is type(h) and dup is not h
+        assert dup._h.value and dup._h.value != h._h.value
+        assert dup._kw == h._kw
+        assert dup.param_layout() == layout and dup.packed_bytes() == nbytes
+        dup.__del__()                     # destroys the copy's native handle now, not whenever the collector runs
+        assert not dup._h
+        del dup
+        assert h._h.value and h.param_layout() == layout and h.packed_bytes() == nbytes
+
+
 def test_no_cpu_fallback():
     import torch
     S = pkg()
