@@ -13,6 +13,9 @@
 //           attn_fold   M_b = g * Wout . blockdiag(ctx^T) . Wq (fp32 VALU, tiny), written straight into the
 //                       packed bf16 hi/lo layout of the 1x1 MFMA convolution; bias_b = g * b
 //   pass 2  conv_mfma CONV_P1 with per-sample weights and EPI_ATTN (+ x): reads x once, writes once.
+//   An attention whose output has ONE reader and that reader is a Downsample (level 0: hiddens[0] is never popped) has no pass 2:
+//   attn_fold writes (I + M_b) composed into the Downsample's 3x3 weights instead, per sample, plus a border-aware bias table, and
+//   the Downsample (conv_mfma CONV_DN, EPI_DNFOLD) reads x itself -- the attention output is neither written nor read back.
 // Softmax quirks kept: over ALL h*w positions, no mask, no 1/sqrt(d) scaling, q not normalised.
 #include <cstring>
 #include "common.h"
@@ -707,19 +710,43 @@ hipError_t launch_attn_merge(const float *partials, float *ctxn, int B, int nrec
 
 // ------------------------------------------------------------------------------------------------ attn_fold
 // M[co][ci] = g * sum_{h,d} U[co][h,d] Wq[h*32+d][ci],  U[co][h,d] = sum_e Wout[co][h*32+e] ctx_h[d][e]
-// grid (C/8, B), 256 threads: a workgroup owns 8 output channels of one sample.  The 128-long (h,d) contraction is
-// split over 256 / min(C,256) thread groups (short dependent chains, many loads in flight -- the kernel is pure
-// latency) and combined through LDS in a fixed order.
+// grid (C/8, forms, B), 256 threads: a workgroup owns 8 output channels of one form of one sample.  The 128-long (h,d)
+// contraction is split over 256 / min(C,256) thread groups (short dependent chains, many loads in flight -- the kernel is
+// pure latency) and combined through LDS in a fixed order.
+// Forms.  The CONV_P1 form is M_b above, in the packed layout of the 1x1 convolution (pass 2).  The Downsample forms (ndn = 9,
+// one per tap (ky, kx)) exist where the attention's only reader is a Downsample: conv3x3s2(W, m (x + M_b x + b')) is a
+// convolution of m x with
+//     W'_b[co][ci][tap] = W[co][ci][tap] + sum_c W[co][c][tap] M_b[c][ci]
+//                       = W[co][ci][tap] + g * sum_{h,d} U_tap[co][h,d] Wq[h*32+d][ci],   U_tap from WO_tap = W_tap . Wout
+// WO_tap [9][C][128] depends on the checkpoint only and is composed once at pack time (attn_dn_precompose_kernel), so a tap's
+// form is the SAME computation as the 1x1 form with WO_tap in Wout's place -- every workgroup is independent of the others, no
+// form waits for M_b -- plus the fp32 W (kept beside the packed one: rebuilding it from hi + lo would round twice).  The bias
+// b' = g bout passes through the taps that fall inside the image and the mask: v[tap][co] = sum_c W[co][c][tap] bout[c] (pack
+// time), and the convolution's epilogue adds  sum_kx m(2 ox - 1 + kx) t_b[rowcase][kx][co]  with
+//     t_b[0][kx] = g (v[1][kx] + v[2][kx])            output row 0: tap row ky = 0 is above the image
+//     t_b[1][kx] = g ((v[0][kx] + v[1][kx]) + v[2][kx])   every other row (the input height is even: no row is lost below)
 constexpr int FOLD_CO = 8;
-__global__ __launch_bounds__(256) void attn_fold_kernel(const float *__restrict__ ctxn, const float *__restrict__ wq,
-                                                         const float *__restrict__ wout, const float *__restrict__ bout,
-                                                         const float *__restrict__ g, unsigned char *__restrict__ wpk,
-                                                         size_t wpk_bstride, float *__restrict__ biasb, int C, int MT,
-                                                         int nkg) {
+struct AttnFoldArgs {
+    const float *ctxn, *wq, *wout, *bout, *g;
+    unsigned char *wpk;          // CONV_P1 form [B][wpk_bstride bytes] + biasb [B][C]; nullptr: not produced
+    size_t wpk_bstride;
+    float *biasb;
+    int C, MT, nkg;              // (tile geometry of the 1x1 convolution)
+    int ndn;                     // 0, or 9: the Downsample forms are produced
+    const float *dn_w, *dn_wo, *dn_vw;      // Downsample weight [C][C][3][3]; WO [9][C][128]; v [9][C]   (fp32, blob)
+    unsigned char *dn_wpk;       // CONV_DN form [B][dn_bstride bytes]
+    size_t dn_bstride;
+    float *dn_btab;              // [B][2][3][C]
+    int dn_MT, dn_nkg;
+};
+__global__ __launch_bounds__(256) void attn_fold_kernel(const AttnFoldArgs a) {
     __shared__ float s_U[FOLD_CO][128];
     __shared__ float s_part[4][FOLD_CO][128];     // partial sums of j-groups 1..3 (only used when C <= 128)
-    const int co0 = blockIdx.x * FOLD_CO, b = blockIdx.y, tid = threadIdx.x;
-    const float *cb = ctxn + (size_t)b * 4096;
+    const int co0 = blockIdx.x * FOLD_CO, b = blockIdx.z, tid = threadIdx.x;
+    const int C = a.C;
+    const int tap = (int)blockIdx.y < a.ndn ? (int)blockIdx.y : -1;      // workgroup-uniform: Downsample tap ky * 3 + kx, or the 1x1 form
+    const float *wout = tap >= 0 ? a.dn_wo + (size_t)tap * C * 128 : a.wout;
+    const float *cb = a.ctxn + (size_t)b * 4096;
     {   // U: 8 x 128 outputs, 4 per thread, 32-long dot products of contiguous rows
         const int j = tid & 127, h = j >> 5, d = j & 31;
         const float4 *cx = reinterpret_cast<const float4 *>(cb + (h * 32 + d) * 32);
@@ -741,9 +768,13 @@ __global__ __launch_bounds__(256) void attn_fold_kernel(const float *__restrict_
         }
     }
     __syncthreads();
-    const float gv = g[0];
+    const float gv = a.g[0];
+    const int MT = tap >= 0 ? a.dn_MT : a.MT, nkg = tap >= 0 ? a.dn_nkg : a.nkg;
     const int ncot = (C + MT - 1) / MT;
-    __bf16 *wp = reinterpret_cast<__bf16 *>(wpk + (size_t)b * wpk_bstride);
+    __bf16 *wp = tap >= 0 ? reinterpret_cast<__bf16 *>(a.dn_wpk + (size_t)b * a.dn_bstride)
+                          : reinterpret_cast<__bf16 *>(a.wpk + (size_t)b * a.wpk_bstride);
+    const int ky = tap >= 0 ? tap / 3 : 0, kx = tap >= 0 ? tap - 3 * ky : 0;
+    const int nst = tap >= 0 ? 3 : 1, tps = nst;      // CONV_DN: stage = ky, three taps kx per stage; CONV_P1: one stage, one tap
     const int Cc = C < 256 ? C : 256;          // input channels handled per pass
     const int nj = 256 / Cc >= 4 ? 4 : (256 / Cc >= 2 ? 2 : 1);   // j-groups (C = 64: 4, 128: 2, >= 256: 1)
     const int jq = tid / Cc, cl = tid - jq * Cc;
@@ -753,7 +784,7 @@ __global__ __launch_bounds__(256) void attn_fold_kernel(const float *__restrict_
         float acc[FOLD_CO];
 #pragma unroll
         for (int r = 0; r < FOLD_CO; ++r) acc[r] = 0.f;
-        const float *qp = wq + (size_t)(active ? jq * jn : 0) * C + ci;
+        const float *qp = a.wq + (size_t)(active ? jq * jn : 0) * C + ci;
         for (int j0 = 0; j0 < (active ? jn : 0); j0 += 8) {
             float q[8];
 #pragma unroll
@@ -780,26 +811,75 @@ __global__ __launch_bounds__(256) void attn_fold_kernel(const float *__restrict_
 #pragma unroll
             for (int r = 0; r < FOLD_CO; ++r) {
                 const int co = co0 + r, cot = co / MT, m = co % MT;
-                const size_t blk = (size_t)chunk * ncot + cot;             // CONV_P1: one stage, one tap
-                const size_t e_hi = blk * ((size_t)MT * 16 * nkg) + ((size_t)(0 * nkg + kg) * MT + m) * 8 + i;
-                const size_t e_lo = blk * ((size_t)MT * 16 * nkg) + ((size_t)(1 * nkg + kg) * MT + m) * 8 + i;
+                const size_t blk = ((size_t)chunk * nst + ky) * ncot + cot;
+                const size_t blk_elems = (size_t)tps * MT * 16 * nkg;
+                const size_t e_hi = blk * blk_elems + ((size_t)((0 * tps + kx) * nkg + kg) * MT + m) * 8 + i;
+                const size_t e_lo = blk * blk_elems + ((size_t)((1 * tps + kx) * nkg + kg) * MT + m) * 8 + i;
+                const float v = tap >= 0 ? fmaf(acc[r], gv, a.dn_w[((size_t)co * C + ci) * 9 + tap]) : acc[r] * gv;
                 __bf16 hi, lo;
-                split_bf16(acc[r] * gv, hi, lo);
+                split_bf16(v, hi, lo);
                 wp[e_hi] = hi;
                 wp[e_lo] = lo;
             }
         }
     }
-    if (tid < FOLD_CO) biasb[(size_t)b * C + co0 + tid] = gv * bout[co0 + tid];
+    if (tap < 0 && tid < FOLD_CO) a.biasb[(size_t)b * C + co0 + tid] = gv * a.bout[co0 + tid];
+    if (tap == 0 && tid < FOLD_CO) {
+        const int co = co0 + tid;
+        float *t = a.dn_btab + (size_t)b * 6 * C + co;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float v0 = a.dn_vw[(size_t)(0 + k) * C + co], v1 = a.dn_vw[(size_t)(3 + k) * C + co], v2 = a.dn_vw[(size_t)(6 + k) * C + co];
+            t[(size_t)(0 + k) * C] = gv * (v1 + v2);
+            t[(size_t)(3 + k) * C] = gv * ((v0 + v1) + v2);
+        }
+    }
 }
 
 hipError_t launch_attn_fold(const float *ctxn, const float *wq, const float *wout, const float *bout, const float *g,
-                            unsigned char *wpk, size_t wpk_bstride, float *biasb, int B, int C, hipStream_t st) {
+                            unsigned char *wpk, size_t wpk_bstride, float *biasb, int B, int C, hipStream_t st,
+                            const AttnFoldDn *dn) {
     if (C % 16 != 0) return hipErrorInvalidValue;
     ConvGeom geom = conv_geom(CONV_P1, C, C);
     if (C % (16 * geom.kch) != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(attn_fold_kernel, dim3(C / FOLD_CO, B), dim3(256), 0, st, ctxn, wq, wout, bout, g, wpk,
-                       wpk_bstride, biasb, C, geom.MT, 2 * geom.kch);
+    if (wpk == nullptr && dn == nullptr) return hipErrorInvalidValue;
+    AttnFoldArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ctxn = ctxn; a.wq = wq; a.wout = wout; a.bout = bout; a.g = g;
+    a.wpk = wpk; a.wpk_bstride = wpk_bstride; a.biasb = biasb;
+    a.C = C; a.MT = geom.MT; a.nkg = 2 * geom.kch;
+    if (dn != nullptr) {
+        ConvGeom gd = conv_geom(CONV_DN, C, C);
+        if (C % (16 * gd.kch) != 0 || C % gd.MT != 0 || gd.nst != 3 || gd.tps != 3) return hipErrorInvalidValue;
+        if (dn->bstride < conv_packed_bytes(CONV_DN, C, C)) return hipErrorInvalidValue;
+        a.ndn = 9;
+        a.dn_w = dn->w; a.dn_wo = dn->wo; a.dn_vw = dn->vw;
+        a.dn_wpk = dn->wpk; a.dn_bstride = dn->bstride; a.dn_btab = dn->btab;
+        a.dn_MT = gd.MT; a.dn_nkg = 2 * gd.kch;
+    }
+    hipLaunchKernelGGL(attn_fold_kernel, dim3(C / FOLD_CO, a.ndn + (wpk != nullptr ? 1 : 0), B), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+// Pack time, once per checkpoint: WO[tap][co][j] = sum_c W[co][c][tap] Wout[c][j] and v[tap][co] = sum_c W[co][c][tap] bout[c]
+// (fp32, fixed order) for a Downsample that takes a folded attention (see attn_fold above).  grid (C, 9), 128 threads.
+__global__ __launch_bounds__(128) void attn_dn_precompose_kernel(const float *__restrict__ w, const float *__restrict__ wout,
+                                                                  const float *__restrict__ bout, float *__restrict__ wo,
+                                                                  float *__restrict__ vw, int C) {
+    const int co = blockIdx.x, tap = blockIdx.y, j = threadIdx.x;
+    const float *wr = w + (size_t)co * C * 9 + tap;
+    float acc = 0.f, accb = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float wv = wr[(size_t)c * 9];
+        acc = fmaf(wv, wout[(size_t)c * 128 + j], acc);
+        accb = fmaf(wv, bout[c], accb);
+    }
+    wo[((size_t)tap * C + co) * 128 + j] = acc;
+    if (j == 0) vw[(size_t)tap * C + co] = accb;
+}
+
+hipError_t launch_attn_dn_precompose(const float *w, const float *wout, const float *bout, float *wo, float *vw, int C, hipStream_t st) {
+    hipLaunchKernelGGL(attn_dn_precompose_kernel, dim3(C, 9), dim3(128), 0, st, w, wout, bout, wo, vw, C);
     return hipGetLastError();
 }
 

@@ -231,7 +231,9 @@ enum ConvEpi {
     EPI_PLAIN = 0,   // out = acc + bias
     EPI_STATS = 1,   // out = acc + bias, plus per-(sample,group) partial sums for GroupNorm
     EPI_TAIL = 2,    // out = acc + bias + Mish(GN(h_raw)) * mask      (ResnetBlock tail with res_conv, :78)
-    EPI_ATTN = 3     // out = acc + bias_b + x                          (Residual(Rezero(LinearAttention)))
+    EPI_ATTN = 3,    // out = acc + bias_b + x                          (Residual(Rezero(LinearAttention)))
+    EPI_DNFOLD = 4   // CONV_DN with a folded attention in its per-sample weights (attn.hip): out = acc + bias +
+                     //   sum_kx mask(2 ox - 1 + kx) btab_b[oy == 0 ? 0 : 1][kx][co]   (the attention's bias through the taps inside the image)
 };
 
 struct ConvArgs {
@@ -263,6 +265,7 @@ struct ConvArgs {
     const void *eh;         // EPI_TAIL: h_raw [B][cout][Hout][Wout]
     const float *esc, *esh; // EPI_TAIL: [B][cout]
     const void *eres;       // EPI_ATTN: residual [B][cout][Hout][Wout]
+    const float *btab;      // EPI_DNFOLD: [B][2][3][cout]
     int nsplit;             // 2: bf16x3 (hi/lo), 1: plain bf16
     int use_ws;             // plan option gtts_unet_cfg.conv_ws: eligible Block convolutions take conv_ws.hip
     const float *omask;     // EPI_PLAIN, conv_mfma.hip only: [B][Wout] column mask multiplied into the output (the data gradient

@@ -120,10 +120,11 @@ struct ConvCfg {
 
 static inline int conv_npar(int pro) { return pro == PRO_GN ? 3 : (pro == PRO_IGLU ? 5 : 0); }
 
-static inline size_t conv_smem_bytes(int npix, int nkg, int wblk16, int cin, int pro, int mt) {
+// epi_rows: per-output-channel epilogue rows in LDS (bias, EPI_TAIL scale / shift; EPI_DNFOLD: bias + the 2 x 3 bias table)
+static inline size_t conv_smem_bytes(int npix, int nkg, int wblk16, int cin, int pro, int mt, int epi_rows = 3) {
     size_t cpad = (size_t)((cin + 8 * nkg - 1) / (8 * nkg)) * 8 * nkg;
     return (size_t)npix * nkg * 16 * 2 + (size_t)wblk16 * 16 + (size_t)conv_npar(pro) * cpad * 4 + 4 * 2 * 4 * 2 * 4 +
-           (size_t)3 * mt * 4;
+           (size_t)epi_rows * mt * 4;
 }
 
 // FULLC = 1: cin is a multiple of 16 (and a concatenated input splits on a 16-channel boundary), so there is no
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : GTT
     float *s_par = reinterpret_cast<float *>(s_w + WBLK16);
     constexpr int NPAR = PRO == PRO_GN ? 3 : (PRO == PRO_IGLU ? 5 : 0);
     float *s_red = s_par + NPAR * cpad;                       // [4 waves][MF][4 octets][2]
-    float *s_epi = s_red + 4 * 2 * 4 * 2;                     // [3][MT]: bias, (EPI_TAIL) GN scale, shift
+    float *s_epi = s_red + 4 * 2 * 4 * 2;                     // [3][MT]: bias, (EPI_TAIL) GN scale, shift; EPI_DNFOLD: [7][MT] bias, table [2][3]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, kg_l = lane >> 5;
@@ -313,6 +314,10 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : GTT
         if (EPI == EPI_TAIL) {
             s_epi[MT + i] = a.esc[(size_t)b * a.cout + co];
             s_epi[2 * MT + i] = a.esh[(size_t)b * a.cout + co];
+        }
+        if (EPI == EPI_DNFOLD) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s_epi[(1 + k) * MT + i] = a.btab[((size_t)b * 6 + k) * a.cout + co];
         }
     }
 
@@ -578,6 +583,18 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : GTT
             float m_out = 0.f;
             if (EPI == EPI_TAIL) m_out = a.mask[(size_t)b * a.T + ((size_t)ox << a.lvl_out)];
             if (EPI == EPI_PLAIN && a.omask) m_out = a.omask[(size_t)b * a.Wout + ox];
+            // EPI_DNFOLD: mask at the three input columns under this output column (0 outside the image); row 0 has lost tap row 0
+            [[maybe_unused]] float mk[3] = {0.f, 0.f, 0.f};
+            [[maybe_unused]] const float *s_tab = s_epi + (oy == 0 ? 1 : 4) * MT;
+            if (EPI == EPI_DNFOLD) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int gx = 2 * ox - 1 + k;
+                    const bool in = gx >= 0 && gx < a.Win;
+                    const float mv = a.mask[(size_t)b * a.T + ((size_t)(in ? gx : 0) << a.lvl_in)];
+                    mk[k] = in ? mv : 0.f;
+                }
+            }
             const int voff = (oy * a.Wout + ox + 4 * kg_l * HWout) * AB;
 #pragma unroll
             for (int mi = 0; mi < MF; ++mi) {
@@ -602,6 +619,10 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : GTT
                         v += ex[rg];
                     } else if (EPI == EPI_PLAIN) {
                         if (a.omask) v *= m_out;
+                    } else if (EPI == EPI_DNFOLD) {
+                        v = fmaf(mk[0], s_tab[col], v);
+                        v = fmaf(mk[1], s_tab[MT + col], v);
+                        v = fmaf(mk[2], s_tab[2 * MT + col], v);
                     }
                     const int soff = (ch0 + mi * 32 + (rg & 3) + 8 * (rg >> 2)) * HWout * AB;
                     st_act<AT>(v, rs_out, voff, soff);
@@ -803,7 +824,7 @@ static hipError_t launch_cfg(const ConvArgs &a_in, hipStream_t st) {
     const size_t lim = (size_t)1 << 31;
     const size_t in_c = (size_t)(PRO == PRO_IGLU ? 2 * a.cin : std::max(a.c0, a.c1));
     if (in_c * a.Hin * a.Win * sizeof(AT) >= lim || (size_t)a.cout * a.Hout * a.Wout * sizeof(AT) >= lim) return hipErrorInvalidValue;
-    size_t smem = conv_smem_bytes(C::NPIX, C::NKG, C::WBLK16, a.cin, PRO, C::MT);
+    size_t smem = conv_smem_bytes(C::NPIX, C::NKG, C::WBLK16, a.cin, PRO, C::MT, EPI == EPI_DNFOLD ? 7 : 3);
     if (smem < (size_t)GTTS_LDS_MIN) smem = (size_t)GTTS_LDS_MIN;
     if (MODE == CONV_C3 && NSPLIT == 2 && (EPI == EPI_STATS || EPI == EPI_PLAIN) && smem < (size_t)GTTS_C3_LDS_MIN) smem = (size_t)GTTS_C3_LDS_MIN;
     // hipFuncSetAttribute is per device: remember the largest size set on each device (atomics: launches may come
@@ -862,7 +883,7 @@ int conv_nparts(int mode, int cout, int Hout, int Wout) {
 
 // (mode, tiling) x (prologue, epilogue) x precision -> template instance; must agree with conv_geom() in common.h.
 // Only the combinations the op program uses are instantiated:
-//   C3: (MASK | GN, STATS)   C7: (MASK | GN, STATS) | (MASK, PLAIN: training)   DN, UP: (MASK, PLAIN)   P1: (MASK, TAIL) | (PLAIN, ATTN) | (MASK, PLAIN: training)
+//   C3: (MASK | GN, STATS)   C7: (MASK | GN, STATS) | (MASK, PLAIN: training)   DN, UP: (MASK, PLAIN)   DN: (MASK, DNFOLD)   P1: (MASK, TAIL) | (PLAIN, ATTN) | (MASK, PLAIN: training)
 template <int MODE, int WM, int WN, int MF, int PRO, int EPI>
 static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
     const bool fullc = a.cin % 16 == 0 && (a.c1 == 0 || a.c0 % 16 == 0);
@@ -938,6 +959,11 @@ hipError_t launch_conv(int mode, const ConvArgs &a, hipStream_t st) {
             if (a.pro == PRO_GN) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_GN, EPI_STATS, 2, 1>(a, st);
             break;
         case CONV_DN:
+            if (a.pro == PRO_MASK && a.epi == EPI_DNFOLD) {      // per-sample weights with a folded attention (attn.hip): fp32 storage, bf16x3
+                if (a.w_bstride == 0 || a.btab == nullptr || a.act_bf16 || a.nsplit != 2 || a.cin % 16 != 0 || a.c1 != 0 || a.Hin != 2 * a.Hout) break;
+                return wide ? launch_cfg<CONV_DN, 2, 2, 2, 1, PRO_MASK, EPI_DNFOLD, 2, 1>(a, st)
+                            : launch_cfg<CONV_DN, 2, 2, 1, 1, PRO_MASK, EPI_DNFOLD, 2, 1>(a, st);
+            }
             if (a.pro != PRO_MASK || a.epi != EPI_PLAIN) break;
             return wide ? launch_prec<CONV_DN, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st)
                         : launch_prec<CONV_DN, 2, 2, 1, PRO_MASK, EPI_PLAIN>(a, st);

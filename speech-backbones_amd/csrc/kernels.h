@@ -124,8 +124,18 @@ hipError_t launch_attn_ctx(const void *x, const unsigned char *wkv, float *parti
                            hipStream_t st, int act_bf16 = 0, const AttnTail *tail = nullptr);
 hipError_t launch_attn_merge(const float *partials, float *ctxn, int B, int nrec, hipStream_t st);
 // wq [128][C], wout [C][128], bout [C], g [1] fp32 (reference layouts) -> per-sample packed 1x1 weights + bias
+// dn (nullable): the attention feeds one Downsample only -- the fold also writes that convolution's per-sample weights
+// (I + M_b composed into W, packed CONV_DN layout) and its bias table [B][2 row cases][3 kx][C]; wpk may then be nullptr (no 1x1 form)
+struct AttnFoldDn {
+    const float *w, *wo, *vw;   // Downsample weight [C][C][3][3], W_tap . Wout [9][C][128], W_tap . bout [9][C] (launch_attn_dn_precompose)
+    unsigned char *wpk;         // [B][bstride bytes]
+    size_t bstride;
+    float *btab;
+};
 hipError_t launch_attn_fold(const float *ctxn, const float *wq, const float *wout, const float *bout, const float *g,
-                            unsigned char *wpk, size_t wpk_bstride, float *biasb, int B, int C, hipStream_t st);
+                            unsigned char *wpk, size_t wpk_bstride, float *biasb, int B, int C, hipStream_t st,
+                            const AttnFoldDn *dn = nullptr);
+hipError_t launch_attn_dn_precompose(const float *w, const float *wout, const float *bout, float *wo, float *vw, int C, hipStream_t st);
 
 // ---- pack.hip
 // status / tag: range record of the f16 + fp8 format (mode CONV_C3 | 32), see pack.hip; nullptr: no record

@@ -73,7 +73,13 @@ struct Op {
     int use_ref;                   // conv / stats run on the reference mel geometry (ref_mask, T_ref)
     int has_tb;                    // PRO_IGLU: a time bias column is added (tb_off valid)
     int fused;                     // OP_TAILID: done by the following attention context pass (no launch); OP_ACTX: carries that tail
-                                   // (eh / esc / esh = the tail's GroupNorm inputs, eres = the block's input, src0 = the tail's output)
+                                   // (eh / esc / esh = the tail's GroupNorm inputs, eres = the block's input, src0 = the tail's output);
+                                   // OP_CONV (EPI_ATTN apply): folded into the Downsample ops[dn_op] that is its only reader (no launch)
+    // attention output folded into the Downsample's weights (attn.hip): the OP_AFOLD also writes the convolution's per-sample
+    // weights dn_wt and bias table dn_bt from the fp32 blob sections below; the OP_CONV (CONV_DN, EPI_DNFOLD) reads w_t / btab_t
+    int dn_op;                     // OP_AFOLD / the apply OP_CONV: index of that Downsample op, -1: none
+    int dn_wt, dn_bt, btab_t;
+    size_t dn_w32_off, dn_wo_off, dn_vw_off;
     std::string label;
 };
 
@@ -87,6 +93,9 @@ struct ParamDesc {
     size_t off2;     // to_qkv: fp32 copy of the q rows
     int cin, cout;
 };
+
+// blob sections of a Downsample that takes a folded attention: composed once per checkpoint by gtts_pack_weights
+struct FoldDnDesc { size_t w32_off, wo_off, vw_off, wout_off, bout_off; int C; };
 
 struct gtts_plan {
     gtts_unet_cfg cfg;
@@ -102,6 +111,7 @@ struct gtts_plan {
     size_t spk_w0, spk_b0, spk_w2, spk_b2;
     std::vector<Tensor> tensors;
     std::vector<Op> ops;
+    std::vector<FoldDnDesc> fold_dn;
     int t_x0, t_s, t_tb, t_final_raw, t_final_sc, t_final_sh;
     int t_xtref = -1, t_cond = -1;   // DiffVC: diffused reference mel [B,1,F,T_ref], condition vector [B,dim_cond]
     int t_ticket = -1;               // per-sample tickets of the fused GroupNorm finalize (zeroed once per call)
@@ -183,6 +193,8 @@ static Op blank_op(int kind, const std::string &label) {
     o.wkv_off = o.wq_off = o.wout_off = o.bout_off = o.g_off = 0; o.apart = o.ctxn = -1; o.use_ref = 0; o.has_tb = 0;
     o.gn_op = -1;
     o.fused = 0;
+    o.dn_op = o.dn_wt = o.dn_bt = o.btab_t = -1;
+    o.dn_w32_off = o.dn_wo_off = o.dn_vw_off = 0;
     o.label = label;
     return o;
 }
@@ -313,8 +325,9 @@ static void compute_liveness(gtts_plan *p) {
     };
     for (int i = 0; i < (int)p->ops.size(); ++i) {
         const Op &o = p->ops[i];
+        if (o.kind == OP_CONV && o.fused) continue;      // never launched: its output tensor gets no workspace
         const int ids[] = {o.src0, o.src1, o.sc, o.sh, o.w_t, o.bias_t, o.out, o.part, o.eh, o.esc, o.esh, o.eres,
-                           o.apart, o.ctxn};
+                           o.apart, o.ctxn, o.dn_wt, o.dn_bt, o.btab_t};
         for (int t : ids) touch(t, i);
         // A Block convolution with the GroupNorm finalize fused in writes the finalize's scale / shift DURING this op (the
         // sample that finishes first publishes while other workgroups still read this op's inputs): they are born here, not
@@ -540,6 +553,55 @@ extern "C" int gtts_plan_create(const gtts_unet_cfg *cfg, gtts_plan **out) {
             c.eh = t.eh; c.esc = t.esc; c.esh = t.esh; c.eres = t.src0;
         }
     }
+    // Attention output with ONE reader, a Downsample (level 0 in both architectures: hiddens[0] is never popped by the up path):
+    // y = (I + M_b) x + b' followed by a 3x3 stride-2 convolution is that convolution of x with per-sample weights, so the fold
+    // writes the Downsample's weights (attn.hip) and the apply pass -- one write and one read of the widest tensor of the network --
+    // is not run.  fp32 storage and the bf16x3 Downsample only.  keep_intermediates plans run the same folded Downsample and
+    // ALSO the apply, so that the attention output exists for inspection; both kinds of plan return the same bits.
+    // Widths measured: 64 (Grad-TTS, -2.6 % per sampler call) and 256 (DiffVC, -1.1 %: the per-sample weights grow with C^2, 2.4 MB
+    // per sample there); wider level-0 attentions than that stay unfolded (profiles/r08_fold_down_ab.txt).
+    constexpr int FOLD_DN_MAXC = 256;
+    if (p->cfg.precision == GTTS_PREC_BF16X3 || p->cfg.precision == GTTS_PREC_F16F8) {
+        for (size_t i = 1; i < p->ops.size(); ++i) {
+            Op &ap = p->ops[i], &fo = p->ops[i - 1];
+            if (ap.kind != OP_CONV || ap.epi != EPI_ATTN || fo.kind != OP_AFOLD || fo.w_t != ap.w_t) continue;
+            int readers = 0, dn = -1;
+            for (size_t j = 0; j < p->ops.size(); ++j) {
+                const Op &r = p->ops[j];
+                if (j == i || (r.src0 != ap.out && r.src1 != ap.out && r.eh != ap.out && r.eres != ap.out)) continue;
+                ++readers;
+                dn = (int)j;
+            }
+            if (readers != 1) continue;
+            Op &d = p->ops[dn];
+            const int C = ap.cout;
+            if (d.kind != OP_CONV || d.mode != CONV_DN || d.pro != PRO_MASK || d.epi != EPI_PLAIN || d.src0 != ap.out || d.c1 != 0 ||
+                d.c0 != C || d.cout != C || d.w_t >= 0 || C % 16 != 0 || C > FOLD_DN_MAXC)
+                continue;
+            int pi = -1;
+            for (size_t k = 0; k < p->params.size(); ++k)
+                if (p->params[k].pack == 2 && p->params[k].off == d.w_off) pi = (int)k;
+            if (pi < 0) continue;
+            FoldDnDesc fd;
+            fd.C = C; fd.wout_off = fo.wout_off; fd.bout_off = fo.bout_off;
+            fd.w32_off = p->blob_bytes; p->blob_bytes = align256(p->blob_bytes + (size_t)C * C * 9 * 4);
+            fd.wo_off = p->blob_bytes; p->blob_bytes = align256(p->blob_bytes + (size_t)9 * C * 128 * 4);
+            fd.vw_off = p->blob_bytes; p->blob_bytes = align256(p->blob_bytes + (size_t)9 * C * 4);
+            p->params[pi].off2 = fd.w32_off;             // gtts_pack_weights keeps the fp32 weight there
+            p->fold_dn.push_back(fd);
+            const int wt = add_tensor(p, d.label + ".wfold", TK_BYTES_PERB, 0, 0);
+            p->tensors[wt].bytes = align256(conv_packed_bytes(CONV_DN, C, C));
+            const int bt = add_tensor(p, d.label + ".bfold", TK_PERB, 6 * C, 0);
+            fo.dn_op = ap.dn_op = dn;
+            fo.dn_wt = wt; fo.dn_bt = bt;
+            fo.dn_w32_off = fd.w32_off; fo.dn_wo_off = fd.wo_off; fo.dn_vw_off = fd.vw_off;
+            d.src0 = ap.src0; d.w_t = wt; d.btab_t = bt; d.epi = EPI_DNFOLD;
+            if (!p->cfg.keep_intermediates) {
+                ap.fused = 1;
+                fo.w_t = fo.bias_t = -1;                 // no 1x1 form
+            }
+        }
+    }
     compute_liveness(p);
     *out = p;
     return GTTS_OK;
@@ -645,7 +707,10 @@ extern "C" int gtts_pack_weights(const gtts_plan *plan, const void *const *param
         switch (d.pack) {
             case 0: GTTS_HIPCHK(launch_copy_f32(src, (float *)(blob + d.off), n, st)); break;
             case 1: GTTS_HIPCHK(launch_pack_conv(CONV_C3, src, blob + d.off, d.cin, d.cout, st)); break;
-            case 2: GTTS_HIPCHK(launch_pack_conv(CONV_DN, src, blob + d.off, d.cin, d.cout, st)); break;
+            case 2:
+                GTTS_HIPCHK(launch_pack_conv(CONV_DN, src, blob + d.off, d.cin, d.cout, st));
+                if (d.off2 != 0) GTTS_HIPCHK(launch_copy_f32(src, (float *)(blob + d.off2), n, st));      // takes a folded attention (fold_dn)
+                break;
             case 3: GTTS_HIPCHK(launch_pack_conv(CONV_UP, src, blob + d.off, d.cin, d.cout, st)); break;
             case 7: GTTS_HIPCHK(launch_pack_conv(CONV_UP | 32, src, blob + d.off, d.cin, d.cout, st, (unsigned *)(blob + plan->status_off), (unsigned)i)); break;
             case 4: GTTS_HIPCHK(launch_pack_conv(CONV_P1, src, blob + d.off, d.cin, d.cout, st)); break;
@@ -656,6 +721,9 @@ extern "C" int gtts_pack_weights(const gtts_plan *plan, const void *const *param
                 break;
         }
     }
+    for (const FoldDnDesc &fd : plan->fold_dn)      // (after the loop: reads the fp32 copies of three parameters from the blob)
+        GTTS_HIPCHK(launch_attn_dn_precompose((const float *)(blob + fd.w32_off), (const float *)(blob + fd.wout_off), (const float *)(blob + fd.bout_off),
+                                              (float *)(blob + fd.wo_off), (float *)(blob + fd.vw_off), fd.C, st));
     if (plan->cfg.precision == GTTS_PREC_F16F8) {
         // Range contract of the f16 + fp8 format (include/gradtts_abi.h): a Block-convolution weight with |w| 2^S beyond the fp16
         // range cannot be represented (it was packed saturated, never inf).  The packer counted such weights on the device; this
@@ -852,6 +920,7 @@ static int run_ops(const RunCtx &c) {
         if (o.kind == OP_GNFIN && oi > 0 && p->ops[oi - 1].kind == OP_CONV && p->ops[oi - 1].gn_op == (int)oi && !p->ops[oi - 1].use_ref)
             continue;                               // done by the producing convolution's last workgroup (no launch)
         if (o.kind == OP_TAILID && o.fused) continue;   // done by the attention context pass that follows (no launch)
+        if (o.kind == OP_CONV && o.fused) continue;     // folded into the Downsample's weights (no launch)
         ProfScope prof_scope(p, c.st, (int)oi);
         switch (o.kind) {
             case OP_CONV: {
@@ -872,12 +941,16 @@ static int run_ops(const RunCtx &c) {
                 if (o.w_t >= 0) {
                     a.w = (const unsigned char *)tptr(c, o.w_t);
                     a.w_bstride = p->tensors[o.w_t].bytes;
+                } else {
+                    a.w = c.blob + o.w_off; a.w_bstride = 0;
+                }
+                if (o.bias_t >= 0) {
                     a.bias = tptr(c, o.bias_t);
                     a.bias_bstride = (size_t)o.cout;
                 } else {
-                    a.w = c.blob + o.w_off; a.w_bstride = 0;
                     a.bias = (const float *)(c.blob + o.b_off); a.bias_bstride = 0;
                 }
+                a.btab = tptr(c, o.btab_t);
                 a.cout = o.cout; a.epi = o.epi;
                 a.out = tptr(c, o.out);
                 a.partials = tptr(c, o.part);
@@ -973,11 +1046,18 @@ static int run_ops(const RunCtx &c) {
             case OP_AFOLD: {
                 if (skip_op_mask() & 2) break;
                 hipError_t e = hipSuccess;
+                AttnFoldDn dn;
+                if (o.dn_op >= 0) {
+                    dn.w = (const float *)(c.blob + o.dn_w32_off); dn.wo = (const float *)(c.blob + o.dn_wo_off);
+                    dn.vw = (const float *)(c.blob + o.dn_vw_off);
+                    dn.wpk = (unsigned char *)tptr(c, o.dn_wt); dn.bstride = p->tensors[o.dn_wt].bytes; dn.btab = tptr(c, o.dn_bt);
+                }
                 for (int rep = 0; rep < ((skip_op_mask() & 8) ? 2 : 1); ++rep)
                 e = launch_attn_fold(tptr(c, o.ctxn), (const float *)(c.blob + o.wq_off),
                                                 (const float *)(c.blob + o.wout_off), (const float *)(c.blob + o.bout_off),
                                                 (const float *)(c.blob + o.g_off), (unsigned char *)tptr(c, o.w_t),
-                                                p->tensors[o.w_t].bytes, tptr(c, o.bias_t), c.B, o.C, c.st);
+                                                o.w_t >= 0 ? p->tensors[o.w_t].bytes : 0, tptr(c, o.bias_t), c.B, o.C, c.st,
+                                                o.dn_op >= 0 ? &dn : nullptr);
                 if (e != hipSuccess) return fail(GTTS_E_HIP, "attn_fold %s: %s", o.label.c_str(), hipGetErrorString(e));
                 break;
             }
@@ -1511,6 +1591,10 @@ extern "C" int gtts_plan_op_info(const gtts_plan *plan, int i, int B, int T, con
                                             B, (int)Ho, (int)Wo, plan->cfg.groups,
                                             plan->cfg.precision == GTTS_PREC_F16F8 && conv_f16f8_ok(o.mode, o.c0, o.c1, o.cout, o.pro, o.epi, plan->cfg.conv_ws),
                                             plan->cfg.precision == GTTS_PREC_F16F8);
+                if (o.fused) {
+                    s_kernel = "(fused into " + plan->ops[o.dn_op].label + ")";
+                    fl = by = 0.0;
+                }
                 break;
             }
             case OP_GNFIN: s_kernel = "gtts::gn_finalize_kernel"; break;
@@ -1542,7 +1626,8 @@ extern "C" int gtts_plan_op_info(const gtts_plan *plan, int i, int B, int T, con
             case OP_REFPOOL: s_kernel = "gtts::ref_pool_kernel"; by = 8.0 * B * o.C * Hi * Wi; break;
             case OP_VCCOND: s_kernel = "gtts::vc_cond_kernel"; break;
             case OP_PREPVC: s_kernel = "gtts::prep_vc_kernel"; by = 4.0 * B * plan->cin0 * Hi * Wi; break;
-            case OP_AFOLD: s_kernel = "gtts::attn_fold_kernel"; fl = 2.0 * B * (o.C * 128.0 * 32 + (double)o.C * o.C * 128); break;
+            case OP_AFOLD: s_kernel = "gtts::attn_fold_kernel";      // (one 1x1 form and / or nine Downsample-tap forms)
+                fl = 2.0 * B * (o.C * 128.0 * 32 + (double)o.C * o.C * 128) * ((o.w_t >= 0 ? 1 : 0) + (o.dn_op >= 0 ? 9 : 0)); break;
         }
     }
     if (label) *label = s_label.c_str();
