@@ -453,6 +453,42 @@ size_t gtts_postnet_chan_dot_scratch_floats(int B, int C, int F, int T);
 int gtts_postnet_chan_dot(const float *a, const float *v, const float *mask, float *dot, float *sum, float *scratch, int B, int C, int F,
                           int T, gtts_stream_t stream);
 
+/* ---- ABI 6 (additive): log-mel front end, waveform -> the mel every other entry point takes in: mel_spectrogram(..., center=False) of
+ * Grad-TTS/hifi-gan/meldataset.py:51-74 (DiffVC's get_mel uses an identical copy) in one launch (csrc/mel.hip) ----------------------
+ * Each row of wav [B,L] is reflect-padded by p = (n_fft - hop_size) / 2 on both sides (needs L > p), cut into frames of n_fft samples at
+ * stride hop_size (T = (L + 2p - n_fft) / hop_size + 1; a tail shorter than a frame is dropped), windowed with the periodic Hann window
+ * of win_size samples (centred in the frame when win_size < n_fft, as torch.stft does), transformed (one-sided DFT, unnormalised),
+ * mag = sqrt(re^2 + im^2 + 1e-9), projected on librosa's default mel filterbank (slaney scale and normalisation, computed here in
+ * float64 and rounded to fp32) and compressed: out [B,num_mels,T] = log(max(W mag, 1e-5)).
+ * Supported (else GTTS_E_CONFIG): n_fft a power of two in [256, 2048], 1 <= win_size <= n_fft, 1 <= hop_size <= n_fft with
+ * n_fft - hop_size even, 1 <= num_mels <= 128, 0 <= fmin < fmax <= sampling_rate / 2.
+ * The handle is host metadata; gtts_mel_pack copies its tables (window, twiddles, filterbank: host float64 -> fp32) into the caller's
+ * blob of gtts_mel_packed_bytes bytes.  gtts_mel_forward takes no workspace and is a single kernel launch on `stream`.
+ * lengths (nullable, device int32 [B]): row b is the utterance wav[b, :lengths[b]] -- reflected about ITS ends -- and frames at or
+ * beyond gtts_mel_frames(lengths[b]) are written as 0 (the mel padding of the reference collate functions); a length outside (p, L] is
+ * clamped to L from above and yields an all-zero row from below.  A frame's value depends on its own n_fft samples alone, never on B
+ * or on its position in the batch. */
+typedef struct gtts_mel_cfg {
+    int n_fft;           /* 1024                                             */
+    int num_mels;        /* 80                                               */
+    int sampling_rate;   /* 22050                                            */
+    int hop_size;        /* 256                                              */
+    int win_size;        /* 1024                                             */
+    double fmin;         /* 0                                                */
+    double fmax;         /* 8000                                             */
+} gtts_mel_cfg;
+typedef struct gtts_mel gtts_mel;     /* host-side metadata only */
+int gtts_mel_create(const gtts_mel_cfg *cfg, gtts_mel **out);
+void gtts_mel_destroy(gtts_mel *mel);
+/* T for rows of L samples, or GTTS_E_SHAPE when L <= p or the padded row holds no whole frame */
+int gtts_mel_frames(const gtts_mel *mel, int L);
+size_t gtts_mel_packed_bytes(const gtts_mel *mel);
+int gtts_mel_pack(const gtts_mel *mel, void *packed, gtts_stream_t stream);
+/* the filterbank W [num_mels][n_fft / 2 + 1] as fp32 into HOST memory; touches no device */
+int gtts_mel_filterbank(const gtts_mel *mel, float *host_out);
+int gtts_mel_forward(const gtts_mel *mel, const void *packed, const float *wav, const int *lengths, float *out, int B, int L,
+                     gtts_stream_t stream);
+
 /* ---- debugging / tests: named intermediates of the last estimator call (keep_intermediates plans) ----- */
 int gtts_plan_num_tensors(const gtts_plan *plan);
 /* offset is in bytes into the workspace for the given (B,T); dims = {B,C,H,W}. */

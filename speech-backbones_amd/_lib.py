@@ -45,6 +45,11 @@ class VocCfg(ctypes.Structure):
                 ("resblock_dilations", (ctypes.c_int * 3) * 8), ("resblock_type", ctypes.c_int)]
 
 
+class MelCfg(ctypes.Structure):
+    _fields_ = [("n_fft", ctypes.c_int), ("num_mels", ctypes.c_int), ("sampling_rate", ctypes.c_int), ("hop_size", ctypes.c_int),
+                ("win_size", ctypes.c_int), ("fmin", ctypes.c_double), ("fmax", ctypes.c_double)]
+
+
 class PackItem(ctypes.Structure):           # gtts_pack_item
     _fields_ = [("w", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("kind", ctypes.c_int), ("cin", ctypes.c_int),
                 ("cout", ctypes.c_int), ("transposed", ctypes.c_int)]
@@ -199,6 +204,13 @@ def lib():
         L.gtts_postnet_chan_dot_scratch_floats.argtypes = [i, i, i, i]
         L.gtts_postnet_chan_dot_scratch_floats.restype = sz
         L.gtts_postnet_chan_dot.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
+        L.gtts_mel_create.argtypes = [ctypes.POINTER(MelCfg), ctypes.POINTER(vp)]
+        L.gtts_mel_destroy.argtypes, L.gtts_mel_destroy.restype = [vp], None
+        L.gtts_mel_frames.argtypes = [vp, i]
+        L.gtts_mel_packed_bytes.argtypes, L.gtts_mel_packed_bytes.restype = [vp], sz
+        L.gtts_mel_pack.argtypes = [vp, vp, vp]
+        L.gtts_mel_filterbank.argtypes = [vp, vp]
+        L.gtts_mel_forward.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
         if L.gtts_abi_version() != 6:
             raise RuntimeError("libgradtts_gfx950.so ABI version mismatch")
         _lib = L
@@ -743,6 +755,57 @@ class PostNetPlan(_Native):
         with torch.cuda.device(x.device):
             _check(lib().gtts_postnet_forward(self._h, _ptr(blob), _ptr(x), _ptr(mask), _ptr(out), _ptr(ws), ws.numel(), B, T,
                                               _stream()), "gtts_postnet_forward")
+        return out
+
+
+class MelPlan(_Native):
+    """Log-mel front end on the HIP kernel (csrc/mel.hip): mel_spectrogram(..., center=False) of Grad-TTS/hifi-gan/meldataset.py:51-74.
+    The handle has no parameters: its blob holds the window, the twiddles and the filterbank, computed on the host in float64."""
+    _family = "mel"
+
+    def __init__(self, n_fft=1024, num_mels=80, sampling_rate=22050, hop_size=256, win_size=1024, fmin=0.0, fmax=8000.0):
+        self.cfg = MelCfg(int(n_fft), int(num_mels), int(sampling_rate), int(hop_size), int(win_size), float(fmin), float(fmax))
+        self.n_fft, self.num_mels, self.hop_size = int(n_fft), int(num_mels), int(hop_size)
+        self.pad = (self.n_fft - self.hop_size) // 2
+        self._open(dict(n_fft=int(n_fft), num_mels=int(num_mels), sampling_rate=int(sampling_rate), hop_size=int(hop_size),
+                        win_size=int(win_size), fmin=float(fmin), fmax=float(fmax)), ctypes.byref(self.cfg))
+
+    def frames(self, L):
+        """T for rows of L samples; raises when L <= (n_fft - hop_size) / 2 (no reflection) or no whole frame fits."""
+        T = int(self._fn("frames")(self._h, int(L)))
+        if T < 0:
+            _check(T, "gtts_mel_frames")
+        return T
+
+    def filterbank(self):
+        """W [num_mels, n_fft / 2 + 1] fp32 on the CPU (a host call: no device is touched)."""
+        W = torch.empty((self.num_mels, self.n_fft // 2 + 1), dtype=torch.float32)
+        self._call("filterbank", self._h, _ptr(W))
+        return W
+
+    def pack(self, device):
+        blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
+        if not blob.is_cuda:
+            raise RuntimeError("the mel tables are packed for a HIP device (got %s)" % blob.device)
+        with torch.cuda.device(blob.device):
+            self._call("pack", self._h, _ptr(blob), _stream())
+            torch.cuda.current_stream().synchronize()
+        return blob
+
+    def forward(self, blob, y, lengths=None):
+        """y [B, L] -> log-mel [B, num_mels, frames(L)] in one launch; lengths: optional [B] ints on y's device -- row b is the
+        utterance y[b, :lengths[b]], frames beyond its own count are 0."""
+        y = _f32c(y, "y")
+        if y.dim() != 2:
+            raise RuntimeError("y must be [B, L] (got %s)" % (tuple(y.shape),))
+        B, L = y.shape
+        if lengths is not None:
+            if not torch.is_tensor(lengths) or lengths.device != y.device or lengths.numel() != B:
+                raise RuntimeError("lengths must be a [B] integer tensor on y's HIP device")
+            lengths = lengths.to(torch.int32).contiguous()
+        out = torch.empty((B, self.num_mels, self.frames(L)), dtype=torch.float32, device=y.device)
+        with _on(y.device):
+            self._call("forward", self._h, _ptr(blob), _ptr(y), _ptr(lengths), _ptr(out), B, L, _stream())
         return out
 
 

@@ -1,0 +1,159 @@
+"""GPU tests (-m gpu) of the log-mel front end kernel (csrc/mel.hip) through MelPlan and the drop-in hifi_gan/meldataset.py against the
+float64 restatement of the seven steps on the CPU (tests/mel_oracle.py).
+
+Bounds.  Parity: max-abs difference in log-mel <= 1e-3, the project's mel-scale bound (a wrong window, pad, frame origin, bin range
+or filter costs >= 1e-1).  Precision: with -s every parity case prints e_kernel and e_ref32 (the same recipe run in float32 torch on the
+CPU), both max-abs against float64; on noise, quiet and impulse e_kernel <= 4 e_ref32 + 2e-6 is asserted (headroom for a different
+butterfly order; two float32 ulps of the output's magnitude).  On speechlike the worst cell moves with the summation order, so the
+ratio is printed only.  No cell is left out of any comparison.  Batch independence, shift invariance and ragged rows: bit for bit."""
+import importlib
+import math
+
+import pytest
+import torch
+
+import mel_oracle as MO
+
+pytestmark = pytest.mark.gpu
+L37 = 256 * 37 + 100
+SHAPES = [("cfg1", L, B) for L in (385, 845, L37, 256 * 130) for B in (1, 2, 3)] + [("cfg2", 160 * 59 + 31, 2)]
+CFGS = {"cfg1": MO.CFG1, "cfg2": MO.CFG2}
+
+
+@pytest.fixture(scope="module")
+def S():
+    assert torch.cuda.is_available()
+    return importlib.import_module("speech-backbones_amd")
+
+
+@pytest.fixture(scope="module")
+def MD():
+    return importlib.import_module("speech-backbones_amd.hifi_gan.meldataset")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def run(S, dev):
+    """run(cfg, y, lengths=None): the kernel on y (a CPU tensor), plan and blob made once per configuration."""
+    made = {}
+
+    def go(cfg, y, lengths=None):
+        if cfg not in made:
+            plan = S.MelPlan(*cfg)
+            made[cfg] = (plan, plan.pack(dev))
+        plan, blob = made[cfg]
+        if lengths is not None:
+            lengths = torch.tensor(lengths, dtype=torch.int32, device=dev)
+        return plan.forward(blob, y.to(dev), lengths).cpu()
+    return go
+
+
+@pytest.mark.parametrize("tag,L,B", SHAPES)
+@pytest.mark.parametrize("name", MO.SIGNALS)
+def test_parity_with_the_float64_recipe(run, name, tag, L, B):
+    cfg = CFGS[tag]
+    ref, e32 = MO.reference(name, cfg, L)
+    ref, e_ref32 = ref[:B], float(e32[:B].max())
+    got = run(cfg, MO.signal(name, L, cfg[2])[:B])
+    assert got.shape == ref.shape and got.dtype == torch.float32 and bool(torch.isfinite(got).all())
+    e_kernel = float((got.double() - ref).abs().max())
+    print("\n%s L=%d B=%d %-10s e_kernel %.2e  e_ref32 %.2e  ratio %.2f" % (tag, L, B, name, e_kernel, e_ref32, e_kernel / max(e_ref32, 1e-30)))
+    assert e_kernel <= 1e-3
+    if name in ("noise", "quiet", "impulse"):
+        assert e_kernel <= 4 * e_ref32 + 2e-6
+    if name == "zeros":
+        assert float((got - torch.tensor(1e-5).log()).abs().max()) <= 1e-6
+    if tag == "cfg1" and name in ("speechlike", "noise"):
+        assert float(ref.min()) > math.log(1e-5)         # these signals leave no cell on the clip (quiet: a few in ten thousand)
+
+
+@pytest.mark.parametrize("cfg,L", [((256, 40, 16000, 64, 256, 0.0, 8000.0), 64 * 41 + 9),            # fewer butterflies than lanes
+                                   ((2048, 128, 44100, 512, 2048, 0.0, 22050.0), 512 * 19 + 77),     # every bin, the LDS limit
+                                   ((2048, 80, 22050, 512, 1200, 0.0, 8000.0), 512 * 19 + 77)],
+                         ids=["n256", "n2048-full", "n2048-win1200"])
+def test_the_other_transform_sizes(run, cfg, L):
+    """n_fft = 256 and 2048 are kernel instances of their own (pass structure, register and LDS footprint)."""
+    ref, e32 = MO.reference("noise", cfg, L)
+    got = run(cfg, MO.signal("noise", L, cfg[2]))
+    assert got.shape == ref.shape
+    e_kernel, e_ref32 = float((got.double() - ref).abs().max()), float(e32.max())
+    print("\nn_fft=%d L=%d noise e_kernel %.2e  e_ref32 %.2e" % (cfg[0], L, e_kernel, e_ref32))
+    assert e_kernel <= 1e-3 and e_kernel <= 4 * e_ref32 + 2e-6
+
+
+@pytest.mark.parametrize("tag,L", [("cfg1", L37), ("cfg1", 845), ("cfg2", 160 * 59 + 31)])
+@pytest.mark.parametrize("name", ["speechlike", "noise"])
+def test_rows_do_not_depend_on_the_batch(run, name, tag, L):
+    cfg = CFGS[tag]
+    y = MO.signal(name, L, cfg[2])
+    together = run(cfg, y)
+    for b in range(MO.ROWS):
+        assert torch.equal(together[b:b + 1], run(cfg, y[b:b + 1]))
+
+
+@pytest.mark.parametrize("name", ["speechlike", "noise"])
+def test_interior_frames_do_not_depend_on_their_position(run, name):
+    """Dropping five hops of samples moves every interior frame five places, into another slot of its tile, onto another wave and
+    into another workgroup: frames whose samples touch no reflection must not change by a bit."""
+    y = MO.signal(name, L37)
+    whole, shifted = run(MO.CFG1, y), run(MO.CFG1, y[:, 256 * 5:])
+    assert whole.shape[-1] == 37 and shifted.shape[-1] == 32
+    assert torch.equal(shifted[..., 2:-2], whole[..., 7:-2])
+
+
+def test_ragged_rows(run, MD, dev):
+    y = MO.signal("speechlike", L37)
+    lens = [L37, 845, 385]
+    got = run(MO.CFG1, y, lens)
+    assert tuple(got.shape) == (3, 80, 37)
+    for b, (n, T) in enumerate(zip(lens, (37, 3, 1))):
+        assert torch.equal(got[b:b + 1, :, :T], run(MO.CFG1, y[b:b + 1, :n]))
+        assert bool((got[b, :, T:] == 0).all())
+    for given in (lens, torch.tensor(lens), torch.tensor(lens, device=dev)):
+        mel, mel_lengths = MD.mel_spectrogram(y.to(dev), *MO.CFG1, y_lengths=given)
+        assert mel_lengths.tolist() == [37, 3, 1] and mel_lengths.dtype == torch.int64 and mel_lengths.device == mel.device
+        assert torch.equal(mel.cpu(), got)
+
+
+def test_drop_in_path_runs_the_kernel_and_caches_its_tables(S, MD, run, dev):
+    y = MO.signal("noise", L37)
+    want = run(MO.CFG1, y)
+    first = MD.mel_spectrogram(y.to(dev), *MO.CFG1)
+    assert first.is_cuda and torch.equal(first.cpu(), want)
+    key = [k for k in MD._blobs if k[1] == str(dev) and k[0][:5] == MO.CFG1[:5]]
+    assert len(key) == 1
+    plan, ptr = MD._plans[key[0][0]], MD._blobs[key[0]].data_ptr()
+    assert torch.equal(MD.mel_spectrogram(y.to(dev), *MO.CFG1, center=False).cpu(), want)
+    assert MD._plans[key[0][0]] is plan and MD._blobs[key[0]].data_ptr() == ptr
+    # inputs that are not contiguous float32: converted, never misread
+    strided = y.t().contiguous().to(dev).t()
+    assert not strided.is_contiguous()
+    assert torch.equal(MD.mel_spectrogram(strided, *MO.CFG1).cpu(), want)
+    assert torch.equal(MD.mel_spectrogram(y.to(dev)[:, ::2], *MO.CFG1).cpu(), run(MO.CFG1, y[:, ::2].contiguous()))
+    assert torch.equal(MD.mel_spectrogram(y.double().to(dev), *MO.CFG1).cpu(), want)
+    # center=True on a HIP tensor takes the torch recipe on the device
+    centred = MD.mel_spectrogram(y.to(dev), *MO.CFG1, center=True).cpu()
+    assert float((centred.double() - MO.recipe(y, MO.CFG1, center=True)).abs().max()) <= 1e-3
+
+
+def test_one_call_allocates_the_output_only(S, dev):
+    """gtts_mel_forward takes no workspace; the binding allocates the output and nothing else, not even transiently."""
+    plan = S.MelPlan(*MO.CFG1)
+    blob = plan.pack(dev)
+    y = MO.signal("noise", 256 * 130).to(dev)
+    plan.forward(blob, y)                                 # (first call: code object load)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    before = torch.cuda.memory_allocated(dev)
+    out = plan.forward(blob, y)
+    torch.cuda.synchronize()
+    out_bytes = (out.numel() * 4 + 511) // 512 * 512      # the caching allocator hands out multiples of 512 bytes
+    assert tuple(out.shape) == (3, 80, 130)
+    assert torch.cuda.memory_allocated(dev) - before == out_bytes
+    assert torch.cuda.max_memory_allocated(dev) - before == out_bytes
+    del out
+    assert torch.cuda.memory_allocated(dev) == before
