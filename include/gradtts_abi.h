@@ -489,6 +489,38 @@ int gtts_mel_filterbank(const gtts_mel *mel, float *host_out);
 int gtts_mel_forward(const gtts_mel *mel, const void *packed, const float *wav, const int *lengths, float *out, int B, int L,
                      gtts_stream_t stream);
 
+/* ---- ABI 6 (additive): DiffVC speaker encoder, the 256-d embedding `c` of DiffVC.forward (DiffVC/speaker_encoder/encoder/model.py:43-63,
+ * inference.py:150-151) on csrc/spk.hip ---------------------------------------------------------------------------------------------
+ * torch.nn.LSTM(n_mels -> hidden, layers, batch_first=True) with zero initial state (gate order i, f, g, o; c_t = s(f) c_{t-1} + s(i) tanh(g),
+ * h_t = s(o) tanh(c_t); both biases), then embeds = r / ||r||_2 with r = relu(W h_T + b) of the last layer -- no epsilon: an all-zero r
+ * gives a NaN row, as in the reference.  fp32 arithmetic throughout (v_mfma_f32_16x16x4_f32 = an fmaf chain, expf / tanhf).
+ * Sequences are addressed inside frames [U][T_total][n_mels] (fp32, contiguous) so that partial utterances are never stacked: sequence
+ * n in [0, U P) is rows (n % P) S ... (n % P) S + T - 1 of utterance n / P; P = 1, S = 0, T = T_total is the plain batched call.
+ * (P - 1) S + T > T_total is refused with GTTS_E_SHAPE before the device is touched, as is U P T * 4 hidden >= 2^31.
+ * Outputs: embeds [U P][embed]; hidden_out (nullable) [U P][hidden] = h_T of the last layer; utt_embeds (nullable) [U][embed] =
+ * m / ||m||_2 with m the mean of the utterance's P embeddings.  A sequence's result does not depend on U, P or its position.
+ * Supported (else GTTS_E_CONFIG): hidden = 256, n_mels a multiple of 4 in [4, 1024], 1 <= layers <= 8, 1 <= embed <= 4096.
+ * Parameters in the module's state_dict order: lstm.weight_ih_l{k}, lstm.weight_hh_l{k}, lstm.bias_ih_l{k}, lstm.bias_hh_l{k} per layer,
+ * then linear.weight, linear.bias (GTTS_E_PARAMS on a count mismatch).  Per layer one input-projection launch over all U P T rows and one
+ * persistent recurrence launch (a workgroup per 16 sequences, no workgroup waits on another), then the head: 2 layers + 1 (+ 1) launches. */
+typedef struct gtts_spk_cfg {
+    int n_mels;          /* 40  */
+    int hidden;          /* 256 */
+    int layers;          /* 3   */
+    int embed;           /* 256 */
+} gtts_spk_cfg;
+typedef struct gtts_spk gtts_spk;     /* host-side metadata only */
+int gtts_spk_create(const gtts_spk_cfg *cfg, gtts_spk **out);
+void gtts_spk_destroy(gtts_spk *spk);
+int gtts_spk_num_params(const gtts_spk *spk);
+int gtts_spk_param_info(const gtts_spk *spk, int i, const char **name, int *rank, int dims[4]);
+size_t gtts_spk_packed_bytes(const gtts_spk *spk);
+int gtts_spk_pack(const gtts_spk *spk, const void *const *param_ptrs, int n_params, void *packed, gtts_stream_t stream);
+/* bytes for N = U P sequences of T frames (0 for a shape gtts_spk_forward refuses) */
+size_t gtts_spk_workspace_bytes(const gtts_spk *spk, int N, int T);
+int gtts_spk_forward(const gtts_spk *spk, const void *packed, const float *frames, int U, int T_total, int P, int S, int T, float *embeds,
+                     float *hidden_out, float *utt_embeds, void *workspace, size_t workspace_bytes, gtts_stream_t stream);
+
 /* ---- debugging / tests: named intermediates of the last estimator call (keep_intermediates plans) ----- */
 int gtts_plan_num_tensors(const gtts_plan *plan);
 /* offset is in bytes into the workspace for the given (B,T); dims = {B,C,H,W}. */

@@ -50,6 +50,10 @@ class MelCfg(ctypes.Structure):
                 ("win_size", ctypes.c_int), ("fmin", ctypes.c_double), ("fmax", ctypes.c_double)]
 
 
+class SpkCfg(ctypes.Structure):
+    _fields_ = [("n_mels", ctypes.c_int), ("hidden", ctypes.c_int), ("layers", ctypes.c_int), ("embed", ctypes.c_int)]
+
+
 class PackItem(ctypes.Structure):           # gtts_pack_item
     _fields_ = [("w", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("kind", ctypes.c_int), ("cin", ctypes.c_int),
                 ("cout", ctypes.c_int), ("transposed", ctypes.c_int)]
@@ -80,9 +84,10 @@ def lib():
         vp, i, f, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
         L.gtts_abi_version.restype = i
         L.gtts_last_error.restype = ctypes.c_char_p
-        # the four handle families (_Native): create takes the family's configuration, gtts_pack_weights also the frequency table
+        # the handle families with parameters (_Native): create takes the family's configuration, gtts_pack_weights also the frequency table
         for fam, cfg, extra in (("plan", [ctypes.POINTER(UnetCfg)], [vp]), ("voc", [ctypes.POINTER(VocCfg)], []),
-                                ("enc", [ctypes.POINTER(EncCfg)], []), ("postnet", [i, i, i], [])):
+                                ("enc", [ctypes.POINTER(EncCfg)], []), ("postnet", [i, i, i], []),
+                                ("spk", [ctypes.POINTER(SpkCfg)], [])):
             fn = {op: getattr(L, _sym(fam, op)) for op in ("create", "destroy", "num_params", "param_info", "packed_bytes", "pack",
                                                             "workspace_bytes")}
             fn["create"].argtypes = cfg + [ctypes.POINTER(vp)]
@@ -211,6 +216,7 @@ def lib():
         L.gtts_mel_pack.argtypes = [vp, vp, vp]
         L.gtts_mel_filterbank.argtypes = [vp, vp]
         L.gtts_mel_forward.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
+        L.gtts_spk_forward.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, sz, vp]
         if L.gtts_abi_version() != 6:
             raise RuntimeError("libgradtts_gfx950.so ABI version mismatch")
         _lib = L
@@ -807,6 +813,41 @@ class MelPlan(_Native):
         with _on(y.device):
             self._call("forward", self._h, _ptr(blob), _ptr(y), _ptr(lengths), _ptr(out), B, L, _stream())
         return out
+
+
+class SpkPlan(_Native):
+    """DiffVC speaker encoder (DiffVC/speaker_encoder/encoder/model.py:43-63) on the HIP kernels (csrc/spk.hip): LSTM stack, Linear,
+    ReLU, L2 normalisation, and the mean + renormalisation over an utterance's partials."""
+    _family = "spk"
+
+    def __init__(self, n_mels=40, hidden=256, layers=3, embed=256):
+        self.cfg = SpkCfg(int(n_mels), int(hidden), int(layers), int(embed))
+        self.n_mels, self.hidden, self.layers, self.embed = int(n_mels), int(hidden), int(layers), int(embed)
+        self._open(dict(n_mels=int(n_mels), hidden=int(hidden), layers=int(layers), embed=int(embed)), ctypes.byref(self.cfg))
+
+    def forward(self, blob, frames, P=1, S=0, T=None, want_hidden=False, want_utt=False):
+        """frames [U, T_total, n_mels] -> embeds [U * P, embed]: sequence u * P + p is frames[u, p * S : p * S + T] (the slicing is load
+        addressing in the kernel; P = 1, S = 0, T = None: every row of frames is one sequence).  want_hidden: also h_T of the last
+        layer [U * P, hidden]; want_utt: also the normalised mean over each utterance's P embeddings [U, embed].  Returns embeds, or
+        (embeds[, hidden][, utt]) in that order."""
+        frames = _f32c(frames, "frames")
+        if frames.dim() != 3 or frames.shape[2] != self.n_mels:
+            raise RuntimeError("frames must be [U, T_total, %d] (got %s)" % (self.n_mels, tuple(frames.shape)))
+        U, T_total, _ = frames.shape
+        P, S = int(P), int(S)
+        T = T_total if T is None else int(T)
+        dev = frames.device
+        N = U * max(P, 0)
+        nbytes = self.workspace_bytes(N, T) if N > 0 and T > 0 else 0
+        ws = self._one_workspace((N, T, str(dev)), dev, lambda: max(nbytes, 256))
+        embeds = torch.empty((max(N, 0), self.embed), dtype=torch.float32, device=dev)
+        hidden = torch.empty((max(N, 0), self.hidden), dtype=torch.float32, device=dev) if want_hidden else None
+        utt = torch.empty((U, self.embed), dtype=torch.float32, device=dev) if want_utt else None
+        with _on(dev):
+            self._call("forward", self._h, _ptr(blob), _ptr(frames), U, T_total, P, S, T, _ptr(embeds), _ptr(hidden), _ptr(utt),
+                       _ptr(ws), ws.numel(), _stream())
+        out = [embeds] + ([hidden] if want_hidden else []) + ([utt] if want_utt else [])
+        return out[0] if len(out) == 1 else tuple(out)
 
 
 def euler_step(xt, mu, est, mask, beta_t, h, noise=None):

@@ -2,8 +2,9 @@
 tree and therefore state_dict keys: `encoder.encoder.*`, `encoder.postnet.*`, `decoder.estimator.*`).
 
 Inference on HIP tensors composes the three C-ABI paths of this package: MelEncoder (gtts_enc_forward, mode 1), PostNet
-(gtts_postnet_forward) and the decoder's sampler (gtts_vc_reverse_diffusion); the speaker encoder that produces `c` stays
-the caller's (DiffVC/inference.ipynb loads it separately).  Training methods compose the modules' autograd paths."""
+(gtts_postnet_forward) and the decoder's sampler (gtts_vc_reverse_diffusion).  The speaker embedding `c` is an input, as in the
+reference: DiffVC/inference.ipynb gets it from `speaker_encoder/encoder`, whose drop-in here is diffvc/speaker_encoder/encoder
+(gtts_spk_forward).  Training methods compose the modules' autograd paths."""
 import torch
 
 from .base import BaseModule
