@@ -22,7 +22,9 @@
 #include "kernels.h"
 
 // heads per workgroup of the per-head context kernel (C >= 128): see attn_ctx_kernel
-// (GTTS_ATTN_HPW: heads per workgroup of the C >= 128 context kernel -- kernels.h, shared with the kernel-name table of plan.hip)
+#ifndef GTTS_ATTN_HPW
+#define GTTS_ATTN_HPW 2
+#endif
 
 namespace gtts {
 
@@ -594,11 +596,27 @@ __global__ __launch_bounds__(256, 2) void attn_ctx64_kernel(const AttnCtxArgs a)
     }
 }
 
+// the leaves of launch_attn_ctx: launch one instance, or name it (common.h: launch or describe)
+template <int NSPLIT, typename AT, int TAIL>
+static hipError_t launch_ctx64(const AttnCtxArgs &a, dim3 grid, hipStream_t st, std::string *name) {
+    if (name) return kernel_name(name, "gtts::attn_ctx64_kernel", NSPLIT, act_name<AT>(), TAIL);
+    hipLaunchKernelGGL((attn_ctx64_kernel<NSPLIT, AT, TAIL>), grid, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+template <int NSPLIT, int FULLC, typename AT, int TAIL>
+static hipError_t launch_ctx(const AttnCtxArgs &a, int nslices, hipStream_t st, std::string *name) {
+    constexpr int HPW = GTTS_ATTN_HPW;
+    if (name) return kernel_name(name, "gtts::attn_ctx_kernel", NSPLIT, FULLC, act_name<AT>(), HPW, TAIL);
+    hipLaunchKernelGGL((attn_ctx_kernel<NSPLIT, FULLC, AT, HPW, TAIL>), dim3(nslices * (4 / HPW) * a.B), dim3(256 * HPW), 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_attn_ctx(const void *x, const unsigned char *wkv, float *partials, int B, int C, int HW, int nsplit,
-                           hipStream_t st, int act_bf16, const AttnTail *tail) {
+                           hipStream_t st, int act_bf16, const AttnTail *tail, std::string *name) {
     AttnGeom g = attn_geom(HW, C);
     if ((size_t)C * HW * 4 >= ((size_t)1 << 31)) return hipErrorInvalidValue;     // 32-bit offsets in the buffer descriptor
     if (tail != nullptr && (C % 32 != 0 || act_bf16)) return hipErrorInvalidValue;
+    if (act_bf16 && nsplit > 1) return hipErrorInvalidValue;
     AttnCtxArgs a;
     memset(&a, 0, sizeof(a));
     if (tail != nullptr) a.tail = *tail;
@@ -608,35 +626,14 @@ hipError_t launch_attn_ctx(const void *x, const unsigned char *wkv, float *parti
     if (attn_head_per_wave(C)) {
         static_assert(ATTN_KCH == 2, "attn_ctx64_kernel indexes the packed k|v blocks as 32-channel stages");
         const dim3 grid64(g.nslices * B);
-        if (act_bf16) {
-            if (nsplit > 1) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((attn_ctx64_kernel<1, __bf16>), grid64, dim3(256), 0, st, a);
-        } else if (tail != nullptr) {
-            if (nsplit > 1) hipLaunchKernelGGL((attn_ctx64_kernel<2, float, 1>), grid64, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((attn_ctx64_kernel<1, float, 1>), grid64, dim3(256), 0, st, a);
-        } else if (nsplit > 1) hipLaunchKernelGGL((attn_ctx64_kernel<2, float>), grid64, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((attn_ctx64_kernel<1, float>), grid64, dim3(256), 0, st, a);
-        return hipGetLastError();
+        if (act_bf16) return launch_ctx64<1, __bf16, 0>(a, grid64, st, name);
+        if (tail != nullptr) return nsplit > 1 ? launch_ctx64<2, float, 1>(a, grid64, st, name) : launch_ctx64<1, float, 1>(a, grid64, st, name);
+        return nsplit > 1 ? launch_ctx64<2, float, 0>(a, grid64, st, name) : launch_ctx64<1, float, 0>(a, grid64, st, name);
     }
-    constexpr int HPW = GTTS_ATTN_HPW;
-    const dim3 grid(g.nslices * (4 / HPW) * B), block(256 * HPW);
-    if (act_bf16) {
-        if (nsplit > 1) return hipErrorInvalidValue;
-        if (C % 32 == 0) hipLaunchKernelGGL((attn_ctx_kernel<1, 1, __bf16, HPW>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((attn_ctx_kernel<1, 0, __bf16, HPW>), grid, block, 0, st, a);
-        return hipGetLastError();
-    }
-    if (C % 32 == 0 && tail != nullptr) {
-        if (nsplit > 1) hipLaunchKernelGGL((attn_ctx_kernel<2, 1, float, HPW, 1>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((attn_ctx_kernel<1, 1, float, HPW, 1>), grid, block, 0, st, a);
-    } else if (C % 32 == 0) {
-        if (nsplit > 1) hipLaunchKernelGGL((attn_ctx_kernel<2, 1, float, HPW>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((attn_ctx_kernel<1, 1, float, HPW>), grid, block, 0, st, a);
-    } else {
-        if (nsplit > 1) hipLaunchKernelGGL((attn_ctx_kernel<2, 0, float, HPW>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((attn_ctx_kernel<1, 0, float, HPW>), grid, block, 0, st, a);
-    }
-    return hipGetLastError();
+    if (act_bf16) return C % 32 == 0 ? launch_ctx<1, 1, __bf16, 0>(a, g.nslices, st, name) : launch_ctx<1, 0, __bf16, 0>(a, g.nslices, st, name);
+    if (tail != nullptr) return nsplit > 1 ? launch_ctx<2, 1, float, 1>(a, g.nslices, st, name) : launch_ctx<1, 1, float, 1>(a, g.nslices, st, name);
+    if (C % 32 == 0) return nsplit > 1 ? launch_ctx<2, 1, float, 0>(a, g.nslices, st, name) : launch_ctx<1, 1, float, 0>(a, g.nslices, st, name);
+    return nsplit > 1 ? launch_ctx<2, 0, float, 0>(a, g.nslices, st, name) : launch_ctx<1, 0, float, 0>(a, g.nslices, st, name);
 }
 
 // ------------------------------------------------------------------------------------------------ attn_merge

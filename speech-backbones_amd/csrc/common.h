@@ -4,8 +4,28 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdlib.h>
+#include <string>
 
 namespace gtts {
+
+// ---------------------------------------------------------------------------------------------------
+// Launch or describe.  A launcher that chooses among template instances of a kernel takes a trailing `std::string *name`.
+// nullptr: it launches.  Otherwise it walks the same dispatch and the leaf that holds the template arguments stores the
+// instance's name as a demangler and rocprofv3 print it ("gtts::conv_mfma_kernel<0, 2, 2, 2, 1, 1, 1, 2, 1, float, 2, 0>") and
+// returns hipSuccess in place of the launch -- no HIP call, no read through a pointer argument (those may all be null).  That is
+// where gtts_plan_op_info (plan.hip) takes its kernel names from, on hosts without a GPU too; checks on shapes refuse on both sides.
+template <typename AT>
+constexpr const char *act_name() { return sizeof(AT) == 4 ? "float" : "__bf16"; }      // activation storage types only
+static inline void name_arg(std::string &s, int v) { s += std::to_string(v); }
+static inline void name_arg(std::string &s, const char *v) { s += v; }
+template <typename... TA>
+static hipError_t kernel_name(std::string *name, const char *kernel, TA... targs) {      // kernel<targs, ...>
+    *name = kernel;
+    [[maybe_unused]] const char *sep = "<";
+    ((*name += sep, name_arg(*name, targs), sep = ", "), ...);
+    if (sizeof...(TA) > 0) *name += ">";
+    return hipSuccess;
+}
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -316,18 +336,17 @@ static inline size_t conv_packed_bytes(int mode, int cin, int cout) {
     return phases * nchunk * g.nst * ncot * conv_wblock_bytes(g);
 }
 
-hipError_t launch_conv(int mode, const ConvArgs &a, hipStream_t st);
+hipError_t launch_conv(int mode, const ConvArgs &a, hipStream_t st, std::string *name = nullptr);
 // conv_ws.hip: the persistent wave-specialised Block convolution
 bool conv_ws_eligible(int mode, int c0, int c1, int cout, int pro, int epi, int nsplit, int f16f8 = 0);
 int conv_ws_nparts(int cout, int Hout, int Wout);      // GroupNorm partial slots per sample it writes (one per 32-frame x 5-row block)
 bool conv_ws_small(int cout, int groups, int Hout, int Wout, int B);   // the launch takes the three-wave workgroup form (same arithmetic)
-hipError_t launch_conv_ws(const ConvArgs &a, hipStream_t st);
+hipError_t launch_conv_ws(const ConvArgs &a, hipStream_t st, std::string *name = nullptr);
 // conv_up.hip: Upsample with the four output phases computed from one staged tile (fp32 storage, bf16x3)
 bool conv_up4_eligible(const ConvArgs &a);
 // GTTS_PREC_F16F8 plans: Upsample in the f16 + fp8 split (conv_up.hip); decides the packing of the layer's weights as well
 bool conv_up4_f16f8_ok(int cin, int cout);
-const char *conv_up4_f8_name();      // the instance launch_conv_up4 launches for such layers (per-op tables)
-hipError_t launch_conv_up4(const ConvArgs &a, hipStream_t st);
+hipError_t launch_conv_up4(const ConvArgs &a, hipStream_t st, std::string *name = nullptr);
 // Block convolutions that take the f16 + fp8 split when the plan's precision is GTTS_PREC_F16F8 (conv_mfma.hip): 3x3, whole
 // 32-channel chunks (a concatenated input splitting on one), mask / GroupNorm prologue, statistics epilogue, and an LDS
 // footprint that leaves two workgroups per CU.  Decides the packing of the layer's weights as well (pack.hip).

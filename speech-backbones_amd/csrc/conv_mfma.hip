@@ -807,7 +807,7 @@ __global__ __launch_bounds__(256, (PRO == PRO_IGLU || MODE == CONV_C7) ? 2 : GTT
 
 
 template <int MODE, int WM, int WN, int MF, int KCH, int PRO, int EPI, int NSPLIT, int FULLC, typename AT = float, int NF = 2>
-static hipError_t launch_cfg(const ConvArgs &a_in, hipStream_t st) {
+static hipError_t launch_cfg(const ConvArgs &a_in, hipStream_t st, std::string *name) {
     using C = ConvCfg<MODE, WM, WN, MF, KCH, NF>;
     ConvArgs a = a_in;
     a.nchunk = (a.cin + 16 * KCH - 1) / (16 * KCH);
@@ -824,6 +824,7 @@ static hipError_t launch_cfg(const ConvArgs &a_in, hipStream_t st) {
     const size_t lim = (size_t)1 << 31;
     const size_t in_c = (size_t)(PRO == PRO_IGLU ? 2 * a.cin : std::max(a.c0, a.c1));
     if (in_c * a.Hin * a.Win * sizeof(AT) >= lim || (size_t)a.cout * a.Hout * a.Wout * sizeof(AT) >= lim) return hipErrorInvalidValue;
+    if (name) return kernel_name(name, "gtts::conv_mfma_kernel", MODE, WM, WN, MF, KCH, PRO, EPI, NSPLIT, FULLC, act_name<AT>(), NF, 0);
     size_t smem = conv_smem_bytes(C::NPIX, C::NKG, C::WBLK16, a.cin, PRO, C::MT, EPI == EPI_DNFOLD ? 7 : 3);
     if (smem < (size_t)GTTS_LDS_MIN) smem = (size_t)GTTS_LDS_MIN;
     if (MODE == CONV_C3 && NSPLIT == 2 && (EPI == EPI_STATS || EPI == EPI_PLAIN) && smem < (size_t)GTTS_C3_LDS_MIN) smem = (size_t)GTTS_C3_LDS_MIN;
@@ -885,7 +886,7 @@ int conv_nparts(int mode, int cout, int Hout, int Wout) {
 // Only the combinations the op program uses are instantiated:
 //   C3: (MASK | GN, STATS)   C7: (MASK | GN, STATS) | (MASK, PLAIN: training)   DN, UP: (MASK, PLAIN)   DN: (MASK, DNFOLD)   P1: (MASK, TAIL) | (PLAIN, ATTN) | (MASK, PLAIN: training)
 template <int MODE, int WM, int WN, int MF, int PRO, int EPI>
-static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
+static hipError_t launch_prec(const ConvArgs &a, hipStream_t st, std::string *name) {
     const bool fullc = a.cin % 16 == 0 && (a.c1 == 0 || a.c0 % 16 == 0);
     if constexpr (MODE == CONV_C3 && EPI == EPI_STATS && (PRO == PRO_MASK || PRO == PRO_GN)) {
         // GTTS_PREC_F16F8: the layer's weights are packed in the f16 + fp8 format exactly when conv_f16f8_ok says so (plan.hip)
@@ -893,8 +894,8 @@ static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
             if (a.act_bf16 || a.nsplit != 2) return hipErrorInvalidValue;
             if constexpr (WM == 2) {      // (conv_f16f8_ok: 128-channel cout tiles only)
                 if (conv_small_tiles(MODE, a.cout, a.Hout, a.Wout, a.B))      // half-height tiles, as below
-                    return launch_cfg<MODE, 4, 1, 1, 2, PRO, EPI, 3, 1, float>(a, st);
-                return launch_cfg<MODE, WM, WN, MF, 2, PRO, EPI, 3, 1, float>(a, st);
+                    return launch_cfg<MODE, 4, 1, 1, 2, PRO, EPI, 3, 1, float>(a, st, name);
+                return launch_cfg<MODE, WM, WN, MF, 2, PRO, EPI, 3, 1, float>(a, st, name);
             }
             return hipErrorInvalidValue;
         }
@@ -902,8 +903,8 @@ static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
     if constexpr (MODE == CONV_C3 && PRO != PRO_IGLU) {
         // half-height tiles for small launches (conv_small_tiles): same cout tile, waves re-arranged to 32 channels x 2 rows
         if (fullc && !a.act_bf16 && a.nsplit > 1 && conv_small_tiles(MODE, a.cout, a.Hout, a.Wout, a.B)) {
-            if constexpr (WM == 2) return launch_cfg<MODE, 4, 1, 1, 1, PRO, EPI, 2, 1, float>(a, st);
-            else return launch_cfg<MODE, 2, 2, 1, 1, PRO, EPI, 2, 1, float>(a, st);
+            if constexpr (WM == 2) return launch_cfg<MODE, 4, 1, 1, 1, PRO, EPI, 2, 1, float>(a, st, name);
+            else return launch_cfg<MODE, 2, 2, 1, 1, PRO, EPI, 2, 1, float>(a, st, name);
         }
     }
     // ragged channel counts only occur on first layers (stacked input, 1-channel reference): PRO_MASK variants
@@ -912,78 +913,79 @@ static hipError_t launch_prec(const ConvArgs &a, hipStream_t st) {
         // bf16 storage (BASELINE config 3): single-pass bf16 MFMA only, Grad-TTS op set only (no InstanceNorm-GLU convs)
         if constexpr (PRO != PRO_IGLU && !(MODE == CONV_C3 && EPI == EPI_PLAIN)) {
             if (a.nsplit > 1) return hipErrorInvalidValue;
-            if (fullc) return launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 1, __bf16>(a, st);
-            if constexpr (ragged_ok) return launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 0, __bf16>(a, st);
+            if (fullc) return launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 1, __bf16>(a, st, name);
+            if constexpr (ragged_ok) return launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 0, __bf16>(a, st, name);
         }
         return hipErrorInvalidValue;
     }
     if (fullc)
-        return a.nsplit > 1 ? launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 2, 1>(a, st)
-                            : launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 1>(a, st);
+        return a.nsplit > 1 ? launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 2, 1>(a, st, name)
+                            : launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 1>(a, st, name);
     if constexpr (ragged_ok)
-        return a.nsplit > 1 ? launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 2, 0>(a, st)
-                            : launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 0>(a, st);
+        return a.nsplit > 1 ? launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 2, 0>(a, st, name)
+                            : launch_cfg<MODE, WM, WN, MF, 1, PRO, EPI, 1, 0>(a, st, name);
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_conv(int mode, const ConvArgs &a, hipStream_t st) {
+hipError_t launch_conv(int mode, const ConvArgs &a, hipStream_t st, std::string *name) {
     const bool wide = a.cout > 64;
     // Block convolutions on whole 16-channel chunks: the persistent wave-specialised kernel (conv_ws.hip)
-    if (a.use_ws && conv_ws_eligible(mode, a.c0, a.c1, a.cout, a.pro, a.epi, a.nsplit, a.f16f8)) return launch_conv_ws(a, st);
+    if (a.use_ws && conv_ws_eligible(mode, a.c0, a.c1, a.cout, a.pro, a.epi, a.nsplit, a.f16f8)) return launch_conv_ws(a, st, name);
     switch (mode) {
         case CONV_C3:
             if (a.epi == EPI_PLAIN) {          // DiffVC RefBlock convolutions (InstanceNorm statistics are a separate pass)
                 if (a.pro == PRO_MASK)
-                    return wide ? launch_prec<CONV_C3, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st)
-                                : launch_prec<CONV_C3, 1, 4, 2, PRO_MASK, EPI_PLAIN>(a, st);
+                    return wide ? launch_prec<CONV_C3, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st, name)
+                                : launch_prec<CONV_C3, 1, 4, 2, PRO_MASK, EPI_PLAIN>(a, st, name);
                 if (a.pro == PRO_IGLU)
-                    return wide ? launch_prec<CONV_C3, 2, 2, 2, PRO_IGLU, EPI_PLAIN>(a, st)
-                                : launch_prec<CONV_C3, 1, 4, 2, PRO_IGLU, EPI_PLAIN>(a, st);
+                    return wide ? launch_prec<CONV_C3, 2, 2, 2, PRO_IGLU, EPI_PLAIN>(a, st, name)
+                                : launch_prec<CONV_C3, 1, 4, 2, PRO_IGLU, EPI_PLAIN>(a, st, name);
                 break;
             }
             if (a.epi != EPI_STATS) break;
             if (a.pro == PRO_MASK)
-                return wide ? launch_prec<CONV_C3, 2, 2, 2, PRO_MASK, EPI_STATS>(a, st)
-                            : launch_prec<CONV_C3, 1, 4, 2, PRO_MASK, EPI_STATS>(a, st);
+                return wide ? launch_prec<CONV_C3, 2, 2, 2, PRO_MASK, EPI_STATS>(a, st, name)
+                            : launch_prec<CONV_C3, 1, 4, 2, PRO_MASK, EPI_STATS>(a, st, name);
             if (a.pro == PRO_GN)
-                return wide ? launch_prec<CONV_C3, 2, 2, 2, PRO_GN, EPI_STATS>(a, st)
-                            : launch_prec<CONV_C3, 1, 4, 2, PRO_GN, EPI_STATS>(a, st);
+                return wide ? launch_prec<CONV_C3, 2, 2, 2, PRO_GN, EPI_STATS>(a, st, name)
+                            : launch_prec<CONV_C3, 1, 4, 2, PRO_GN, EPI_STATS>(a, st, name);
             break;
         case CONV_C7:          // DiffVC PostNet Block (postnet.py:15-23): 64-cout tiles, fp32 storage, bf16x3
             if (a.act_bf16 || a.nsplit != 2 || a.cin % 16 != 0) break;
             // training (train.hip gtts_conv7x7_masked): raw output of x * mask (+ bias) for the autograd save, and the data
             // gradient (transposed weights, column mask in the epilogue)
-            if (a.epi == EPI_PLAIN && a.pro == PRO_MASK) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_MASK, EPI_PLAIN, 2, 1>(a, st);
+            if (a.epi == EPI_PLAIN && a.pro == PRO_MASK) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_MASK, EPI_PLAIN, 2, 1>(a, st, name);
             if (a.epi != EPI_STATS) break;
-            if (a.pro == PRO_MASK) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_MASK, EPI_STATS, 2, 1>(a, st);
-            if (a.pro == PRO_GN) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_GN, EPI_STATS, 2, 1>(a, st);
+            if (a.pro == PRO_MASK) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_MASK, EPI_STATS, 2, 1>(a, st, name);
+            if (a.pro == PRO_GN) return launch_cfg<CONV_C7, 1, 4, 2, 1, PRO_GN, EPI_STATS, 2, 1>(a, st, name);
             break;
         case CONV_DN:
             if (a.pro == PRO_MASK && a.epi == EPI_DNFOLD) {      // per-sample weights with a folded attention (attn.hip): fp32 storage, bf16x3
-                if (a.w_bstride == 0 || a.btab == nullptr || a.act_bf16 || a.nsplit != 2 || a.cin % 16 != 0 || a.c1 != 0 || a.Hin != 2 * a.Hout) break;
-                return wide ? launch_cfg<CONV_DN, 2, 2, 2, 1, PRO_MASK, EPI_DNFOLD, 2, 1>(a, st)
-                            : launch_cfg<CONV_DN, 2, 2, 1, 1, PRO_MASK, EPI_DNFOLD, 2, 1>(a, st);
+                // (the bias table is a pointer: checked when launching only -- a description carries none)
+                if (a.w_bstride == 0 || (a.btab == nullptr && !name) || a.act_bf16 || a.nsplit != 2 || a.cin % 16 != 0 || a.c1 != 0 || a.Hin != 2 * a.Hout) break;
+                return wide ? launch_cfg<CONV_DN, 2, 2, 2, 1, PRO_MASK, EPI_DNFOLD, 2, 1>(a, st, name)
+                            : launch_cfg<CONV_DN, 2, 2, 1, 1, PRO_MASK, EPI_DNFOLD, 2, 1>(a, st, name);
             }
             if (a.pro != PRO_MASK || a.epi != EPI_PLAIN) break;
-            return wide ? launch_prec<CONV_DN, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st)
-                        : launch_prec<CONV_DN, 2, 2, 1, PRO_MASK, EPI_PLAIN>(a, st);
+            return wide ? launch_prec<CONV_DN, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st, name)
+                        : launch_prec<CONV_DN, 2, 2, 1, PRO_MASK, EPI_PLAIN>(a, st, name);
         case CONV_UP:
             if (a.pro != PRO_MASK || a.epi != EPI_PLAIN) break;
-            if (conv_up4_eligible(a)) return launch_conv_up4(a, st);
+            if (conv_up4_eligible(a)) return launch_conv_up4(a, st, name);
             // a GTTS_PREC_F16F8 plan packed this layer's weights in the f16 + fp8 format: only conv_up.hip reads it -- fail, never misread
             if (a.f16f8 && conv_up4_f16f8_ok(a.cin, a.cout)) return hipErrorInvalidValue;
-            return wide ? launch_prec<CONV_UP, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st)
-                        : launch_prec<CONV_UP, 1, 4, 2, PRO_MASK, EPI_PLAIN>(a, st);
+            return wide ? launch_prec<CONV_UP, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st, name)
+                        : launch_prec<CONV_UP, 1, 4, 2, PRO_MASK, EPI_PLAIN>(a, st, name);
         case CONV_P1:
             if (a.pro == PRO_MASK && a.epi == EPI_PLAIN)        // training: res_conv / to_qkv / to_out and their data gradients (train.hip)
-                return wide ? launch_prec<CONV_P1, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st)
-                            : launch_prec<CONV_P1, 1, 4, 2, PRO_MASK, EPI_PLAIN>(a, st);
+                return wide ? launch_prec<CONV_P1, 2, 2, 2, PRO_MASK, EPI_PLAIN>(a, st, name)
+                            : launch_prec<CONV_P1, 1, 4, 2, PRO_MASK, EPI_PLAIN>(a, st, name);
             if (a.pro == PRO_MASK && a.epi == EPI_TAIL)
-                return wide ? launch_prec<CONV_P1, 2, 2, 2, PRO_MASK, EPI_TAIL>(a, st)
-                            : launch_prec<CONV_P1, 1, 4, 2, PRO_MASK, EPI_TAIL>(a, st);
+                return wide ? launch_prec<CONV_P1, 2, 2, 2, PRO_MASK, EPI_TAIL>(a, st, name)
+                            : launch_prec<CONV_P1, 1, 4, 2, PRO_MASK, EPI_TAIL>(a, st, name);
             if (a.pro == PRO_PLAIN && a.epi == EPI_ATTN)
-                return wide ? launch_prec<CONV_P1, 2, 2, 2, PRO_PLAIN, EPI_ATTN>(a, st)
-                            : launch_prec<CONV_P1, 1, 4, 2, PRO_PLAIN, EPI_ATTN>(a, st);
+                return wide ? launch_prec<CONV_P1, 2, 2, 2, PRO_PLAIN, EPI_ATTN>(a, st, name)
+                            : launch_prec<CONV_P1, 1, 4, 2, PRO_PLAIN, EPI_ATTN>(a, st, name);
             break;
     }
     return hipErrorInvalidValue;

@@ -477,9 +477,7 @@ bool conv_up4_f16f8_ok(int cin, int cout) {
     return cin % 32 == 0 && cin >= 32 && cout % 64 == 0 && (cout <= 64 || cout % 128 == 0);
 }
 
-const char *conv_up4_f8_name() { return "gtts::conv_up4_f8_kernel<1>"; }
-
-hipError_t launch_conv_up4(const ConvArgs &a_in, hipStream_t st) {
+hipError_t launch_conv_up4(const ConvArgs &a_in, hipStream_t st, std::string *name) {
     ConvArgs a = a_in;
     if (!conv_up4_eligible(a)) return hipErrorInvalidValue;
     a.tiles_x = (a.Win + 31) / 32;
@@ -491,6 +489,7 @@ hipError_t launch_conv_up4(const ConvArgs &a_in, hipStream_t st) {
         a.tiles_y = (a.Hin + 1) / 2;
         const long tiles = (long)a.B * a.tiles_x * a.tiles_y * (a.cout / 64);
         if (tiles > 0x7fffffffL) return hipErrorInvalidValue;
+        if (name) return kernel_name(name, "gtts::conv_up4_f8_kernel", 1);
         static std::atomic<int> n_cu[64];
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
@@ -501,6 +500,7 @@ hipError_t launch_conv_up4(const ConvArgs &a_in, hipStream_t st) {
         }
         hipLaunchKernelGGL(conv_up4_f8_kernel<1>, dim3((unsigned)std::min<long>(tiles, (long)cus * 2)), dim3(256), 0, st, a);
     } else {
+        if (name) return kernel_name(name, "gtts::conv_up4_kernel");
         hipLaunchKernelGGL(conv_up4_kernel, dim3((unsigned)grid), dim3(256), 0, st, a);
     }
     return hipGetLastError();

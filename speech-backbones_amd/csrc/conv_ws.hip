@@ -1011,7 +1011,7 @@ bool conv_ws_small(int cout, int groups, int Hout, int Wout, int B) {
 }
 
 template <int WM, int WN, int MF, int PRO, int NSPLIT, typename AT>
-static hipError_t launch_ws_ring(ConvArgs &a, hipStream_t st) {
+static hipError_t launch_ws_ring(ConvArgs &a, hipStream_t st, std::string *name) {
     constexpr int NF = 5;
     constexpr int NKG = NSPLIT == 3 ? 4 : 2, RING = NSPLIT == 3 ? 2 : 3, NPL = NSPLIT == 3 ? 2 : NSPLIT;
     using C = WsCfg<WM, WN, MF, NF, NKG>;
@@ -1024,6 +1024,9 @@ static hipError_t launch_ws_ring(ConvArgs &a, hipStream_t st) {
     const size_t lim = (size_t)1 << 31;
     if ((size_t)std::max(a.c0, a.c1) * a.Hin * a.Win * sizeof(AT) >= lim || (size_t)a.cout * a.Hout * a.Wout * sizeof(AT) >= lim)
         return hipErrorInvalidValue;
+    const size_t smem = ws_smem_bytes(C::NPIX, NPL, RING, a.cin, PRO, a.cout, MF, C::NCW, NKG);
+    if (smem > (size_t)160 * 1024) return hipErrorInvalidValue;      // (conv_ws_eligible keeps such layers on conv_mfma.hip)
+    if (name) return kernel_name(name, "gtts::conv3x3_ws_kernel", WM, WN, MF, NF, PRO, NSPLIT, act_name<AT>(), RING);
     static std::atomic<int> n_cu[64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
@@ -1032,8 +1035,6 @@ static hipError_t launch_ws_ring(ConvArgs &a, hipStream_t st) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
         n_cu[dev].store(cus, std::memory_order_relaxed);
     }
-    const size_t smem = ws_smem_bytes(C::NPIX, NPL, RING, a.cin, PRO, a.cout, MF, C::NCW, NKG);
-    if (smem > (size_t)160 * 1024) return hipErrorInvalidValue;      // (conv_ws_eligible keeps such layers on conv_mfma.hip)
     // persistent workgroups: one per CU for the eight-wave form; the three-wave form fits two per CU (registers: 8 waves)
     const int per_cu = C::NT >= 512 ? 1 : (int)std::min<size_t>(2, (size_t)160 * 1024 / smem);
     const long ntiles = (long)a.B * a.tiles_x * a.tiles_y * (a.cout / C::MT);
@@ -1052,22 +1053,22 @@ static hipError_t launch_ws_ring(ConvArgs &a, hipStream_t st) {
 }
 
 template <int PRO>
-static hipError_t launch_ws_pro(ConvArgs &a, hipStream_t st) {
+static hipError_t launch_ws_pro(ConvArgs &a, hipStream_t st, std::string *name) {
     if (a.act_bf16 || a.nsplit != 2) return hipErrorInvalidValue;
     if (a.f16f8) {
-        if (conv_ws_small(a.cout, a.groups, a.Hout, a.Wout, a.B)) return launch_ws_ring<1, 1, 1, PRO, 3, float>(a, st);
-        if (a.cout % 128 != 0) return launch_ws_ring<1, 2, 2, PRO, 3, float>(a, st);      // the 64-channel tile
-        return launch_ws_ring<2, 2, 2, PRO, 3, float>(a, st);
+        if (conv_ws_small(a.cout, a.groups, a.Hout, a.Wout, a.B)) return launch_ws_ring<1, 1, 1, PRO, 3, float>(a, st, name);
+        if (a.cout % 128 != 0) return launch_ws_ring<1, 2, 2, PRO, 3, float>(a, st, name);      // the 64-channel tile
+        return launch_ws_ring<2, 2, 2, PRO, 3, float>(a, st, name);
     }
-    if (conv_ws_small(a.cout, a.groups, a.Hout, a.Wout, a.B)) return launch_ws_ring<1, 1, 1, PRO, 2, float>(a, st);
-    return launch_ws_ring<2, 2, 2, PRO, 2, float>(a, st);
+    if (conv_ws_small(a.cout, a.groups, a.Hout, a.Wout, a.B)) return launch_ws_ring<1, 1, 1, PRO, 2, float>(a, st, name);
+    return launch_ws_ring<2, 2, 2, PRO, 2, float>(a, st, name);
 }
 
-hipError_t launch_conv_ws(const ConvArgs &a_in, hipStream_t st) {
+hipError_t launch_conv_ws(const ConvArgs &a_in, hipStream_t st, std::string *name) {
     ConvArgs a = a_in;
     if (!conv_ws_eligible(CONV_C3, a.c0, a.c1, a.cout, a.pro, a.epi, a.nsplit, a.f16f8)) return hipErrorInvalidValue;
     if (a.cin / (a.f16f8 ? 32 : 16) < 2) return hipErrorInvalidValue;
-    return a.pro == PRO_GN ? launch_ws_pro<PRO_GN>(a, st) : launch_ws_pro<PRO_MASK>(a, st);
+    return a.pro == PRO_GN ? launch_ws_pro<PRO_GN>(a, st, name) : launch_ws_pro<PRO_MASK>(a, st, name);
 }
 
 }  // namespace gtts

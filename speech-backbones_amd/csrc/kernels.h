@@ -38,8 +38,9 @@ struct VcStep {
     float sigma;
 };
 
+// (a trailing `std::string *name`: launch or describe, see common.h)
 hipError_t launch_prep_input(const float *mu, const float *x, const float *s, void *x0, int B, int F, int T,
-                             int nch, hipStream_t st, int act_bf16 = 0);
+                             int nch, hipStream_t st, int act_bf16 = 0, std::string *name = nullptr);
 hipError_t launch_spk_mlp(const float *spk, const float *w0, const float *b0, const float *w2, const float *b2,
                           float *s, int B, int E, int F, hipStream_t st);
 hipError_t launch_time_mlp(const float *t, const float *freq, float pe_scale, const unsigned char *blob,
@@ -47,14 +48,15 @@ hipError_t launch_time_mlp(const float *t, const float *freq, float pe_scale, co
 hipError_t launch_gn_finalize(const float *partials, int nparts, int groups, int C, int HW, const float *gamma,
                               const float *beta, float *sc, float *sh, int B, hipStream_t st);
 hipError_t launch_tail_identity(const void *h, const void *x, const float *sc, const float *sh, const float *mask,
-                                void *out, int B, int C, int H, int W, int T, int lvl, hipStream_t st, int act_bf16 = 0);
+                                void *out, int B, int C, int H, int W, int T, int lvl, hipStream_t st, int act_bf16 = 0,
+                                std::string *name = nullptr);
 hipError_t launch_euler_step(float *xt, const float *mu, const float *est, const float *mask, const float *noise,
                              float beta, float h, int B, int F, int T, hipStream_t st);
 hipError_t launch_mul_mask(const float *z, const float *mask, float *out, int B, int F, int T, hipStream_t st);
 hipError_t launch_final_euler(const void *raw, const float *sc, const float *sh, const float *w, const float *bias,
                               const float *mask, int B, int C, int F, int T, float *est_out, float *xt, const float *mu,
                               const float *noise, float beta, float h, hipStream_t st, const VcStep *vc = nullptr,
-                              int act_bf16 = 0);
+                              int act_bf16 = 0, std::string *name = nullptr);
 
 // ---- vc.hip  (DiffVC-only pieces: RefBlock statistics / pooling, condition MLP, input assembly)
 hipError_t launch_xt_ref(const float *ref, const float *mean_ref, const float *ref_mask, float *out, float w0, float w1,
@@ -77,11 +79,6 @@ bool conv_rowpair_stats(int mode, int cout, int Hout, int Wout);
 bool conv_small_tiles(int mode, int cout, int Hout, int Wout, int B);
 
 // ---- attn.hip  (LinearAttention, diffusion.py:82-100, folded: see attn.hip header)
-// heads per workgroup of attn_ctx_kernel (C >= 128): two heads share one staged x tile.  A build-time choice that appears in the
-// kernel's template arguments, hence in the names gtts_plan_op_info reports for the rocprofv3 / traffic.json joins.
-#ifndef GTTS_ATTN_HPW
-#define GTTS_ATTN_HPW 2
-#endif
 constexpr int ATTN_KCH = 2;                 // 16-channel chunks per LDS stage of the k/v projection
 constexpr int ATTN_REC = 32 + 32 + 32 * 32; // floats per partial record: m[32], Z[32], ctx[32][32]
 struct AttnGeom {
@@ -121,7 +118,7 @@ struct AttnTail {
     int W, T, lvl;
 };
 hipError_t launch_attn_ctx(const void *x, const unsigned char *wkv, float *partials, int B, int C, int HW, int nsplit,
-                           hipStream_t st, int act_bf16 = 0, const AttnTail *tail = nullptr);
+                           hipStream_t st, int act_bf16 = 0, const AttnTail *tail = nullptr, std::string *name = nullptr);
 hipError_t launch_attn_merge(const float *partials, float *ctxn, int B, int nrec, hipStream_t st);
 // wq [128][C], wout [C][128], bout [C], g [1] fp32 (reference layouts) -> per-sample packed 1x1 weights + bias
 // dn (nullable): the attention feeds one Downsample only -- the fold also writes that convolution's per-sample weights

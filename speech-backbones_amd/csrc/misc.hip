@@ -26,12 +26,17 @@ __global__ void prep_input_kernel(const float *__restrict__ mu, const float *__r
     x0[((size_t)b * nch + c) * F * T + i] = (AT)v;
 }
 
-hipError_t launch_prep_input(const float *mu, const float *x, const float *s, void *x0, int B, int F, int T,
-                             int nch, hipStream_t st, int act_bf16) {
-    dim3 grid((F * T + 255) / 256, nch, B);
-    if (act_bf16) hipLaunchKernelGGL(prep_input_kernel<__bf16>, grid, dim3(256), 0, st, mu, x, s, (__bf16 *)x0, F, T, nch);
-    else hipLaunchKernelGGL(prep_input_kernel<float>, grid, dim3(256), 0, st, mu, x, s, (float *)x0, F, T, nch);
+template <typename AT>
+static hipError_t launch_prep_input_t(const float *mu, const float *x, const float *s, void *x0, int B, int F, int T, int nch,
+                                      hipStream_t st, std::string *name) {
+    if (name) return kernel_name(name, "gtts::prep_input_kernel", act_name<AT>());
+    hipLaunchKernelGGL(prep_input_kernel<AT>, dim3((F * T + 255) / 256, nch, B), dim3(256), 0, st, mu, x, s, (AT *)x0, F, T, nch);
     return hipGetLastError();
+}
+hipError_t launch_prep_input(const float *mu, const float *x, const float *s, void *x0, int B, int F, int T,
+                             int nch, hipStream_t st, int act_bf16, std::string *name) {
+    return act_bf16 ? launch_prep_input_t<__bf16>(mu, x, s, x0, B, F, T, nch, st, name)
+                    : launch_prep_input_t<float>(mu, x, s, x0, B, F, T, nch, st, name);
 }
 
 // ------------------------------------------------------------------------------------------------ small MLPs
@@ -258,40 +263,37 @@ __global__ __launch_bounds__(256) void tail_identity_kernel(const AT *__restrict
     }
 }
 
+template <int VEC, typename AT, int ITEMS>
+static hipError_t launch_tail_items(const AT *h, const AT *x, const float *sc, const float *sh, const float *mask, AT *out, dim3 grid,
+                                    int C, int H, int W, int T, int lvl, hipStream_t st, std::string *name) {
+    if (name) return kernel_name(name, "gtts::tail_identity_kernel", VEC, act_name<AT>(), ITEMS);
+    hipLaunchKernelGGL((tail_identity_kernel<VEC, AT, ITEMS>), grid, dim3(256), 0, st, h, x, sc, sh, mask, out, C, H, W, T, lvl);
+    return hipGetLastError();
+}
 template <int VEC, typename AT>
-static void launch_tail_vec(const AT *h, const AT *x, const float *sc, const float *sh, const float *mask, AT *out, int B, int C,
-                            int H, int W, int T, int lvl, hipStream_t st) {
+static hipError_t launch_tail_vec(const AT *h, const AT *x, const float *sc, const float *sh, const float *mask, AT *out, int B, int C,
+                                  int H, int W, int T, int lvl, hipStream_t st, std::string *name) {
     const int per_plane = (H * W / VEC + 255) / 256;        // one-item blocks per (sample, channel) plane
-    if (per_plane >= 8) {
-        dim3 grid((per_plane + 3) / 4, C, B);
-        hipLaunchKernelGGL((tail_identity_kernel<VEC, AT, 4>), grid, dim3(256), 0, st, h, x, sc, sh, mask, out, C, H, W, T, lvl);
-    } else {
-        dim3 grid(per_plane, C, B);
-        hipLaunchKernelGGL((tail_identity_kernel<VEC, AT, 1>), grid, dim3(256), 0, st, h, x, sc, sh, mask, out, C, H, W, T, lvl);
+    if constexpr (VEC > 1) {      // (the scalar form takes one item per thread)
+        if (per_plane >= 8)
+            return launch_tail_items<VEC, AT, 4>(h, x, sc, sh, mask, out, dim3((per_plane + 3) / 4, C, B), C, H, W, T, lvl, st, name);
     }
+    return launch_tail_items<VEC, AT, 1>(h, x, sc, sh, mask, out, dim3(per_plane, C, B), C, H, W, T, lvl, st, name);
 }
 
 template <typename AT>
 static hipError_t launch_tail_identity_t(const AT *h, const AT *x, const float *sc, const float *sh, const float *mask,
-                                         AT *out, int B, int C, int H, int W, int T, int lvl, hipStream_t st) {
+                                         AT *out, int B, int C, int H, int W, int T, int lvl, hipStream_t st, std::string *name) {
     if constexpr (sizeof(AT) == 2) {
-        if (W % 8 == 0) {
-            launch_tail_vec<8, AT>(h, x, sc, sh, mask, out, B, C, H, W, T, lvl, st);
-            return hipGetLastError();
-        }
+        if (W % 8 == 0) return launch_tail_vec<8, AT>(h, x, sc, sh, mask, out, B, C, H, W, T, lvl, st, name);
     }
-    if (W % 4 == 0) {
-        launch_tail_vec<4, AT>(h, x, sc, sh, mask, out, B, C, H, W, T, lvl, st);
-    } else {
-        dim3 grid((H * W + 255) / 256, C, B);
-        hipLaunchKernelGGL((tail_identity_kernel<1, AT, 1>), grid, dim3(256), 0, st, h, x, sc, sh, mask, out, C, H, W, T, lvl);
-    }
-    return hipGetLastError();
+    if (W % 4 == 0) return launch_tail_vec<4, AT>(h, x, sc, sh, mask, out, B, C, H, W, T, lvl, st, name);
+    return launch_tail_vec<1, AT>(h, x, sc, sh, mask, out, B, C, H, W, T, lvl, st, name);
 }
 hipError_t launch_tail_identity(const void *h, const void *x, const float *sc, const float *sh, const float *mask,
-                                void *out, int B, int C, int H, int W, int T, int lvl, hipStream_t st, int act_bf16) {
-    if (act_bf16) return launch_tail_identity_t((const __bf16 *)h, (const __bf16 *)x, sc, sh, mask, (__bf16 *)out, B, C, H, W, T, lvl, st);
-    return launch_tail_identity_t((const float *)h, (const float *)x, sc, sh, mask, (float *)out, B, C, H, W, T, lvl, st);
+                                void *out, int B, int C, int H, int W, int T, int lvl, hipStream_t st, int act_bf16, std::string *name) {
+    if (act_bf16) return launch_tail_identity_t((const __bf16 *)h, (const __bf16 *)x, sc, sh, mask, (__bf16 *)out, B, C, H, W, T, lvl, st, name);
+    return launch_tail_identity_t((const float *)h, (const float *)x, sc, sh, mask, (float *)out, B, C, H, W, T, lvl, st, name);
 }
 
 // ------------------------------------------------------------------------------------------------ Euler update
@@ -417,25 +419,26 @@ __global__ void final_euler_kernel(const AT *__restrict__ raw, const float *__re
     }
 }
 
+template <typename AT, int VEC>
+static hipError_t launch_final_euler_t(const void *raw, const float *sc, const float *sh, const float *w, const float *bias,
+                                       const float *mask, int B, int C, int F, int T, float *est_out, float *xt, const float *mu,
+                                       const float *noise, float beta, float h, hipStream_t st, const VcStep &v, std::string *name) {
+    if (name) return kernel_name(name, "gtts::final_euler_kernel", act_name<AT>(), VEC);
+    hipLaunchKernelGGL((final_euler_kernel<AT, VEC>), dim3((F * T / VEC + 255) / 256, B), dim3(256), (size_t)3 * C * sizeof(float), st,
+                       (const AT *)raw, sc, sh, w, bias, mask, C, F, T, est_out, xt, mu, noise, beta, h, sqrtf(beta * h), v);
+    return hipGetLastError();
+}
 hipError_t launch_final_euler(const void *raw, const float *sc, const float *sh, const float *w, const float *bias,
                               const float *mask, int B, int C, int F, int T, float *est_out, float *xt, const float *mu,
-                              const float *noise, float beta, float h, hipStream_t st, const VcStep *vc, int act_bf16) {
-    dim3 grid((F * T + 255) / 256, B);
-    const float sq = sqrtf(beta * h);
+                              const float *noise, float beta, float h, hipStream_t st, const VcStep *vc, int act_bf16, std::string *name) {
     VcStep v;
     v.mode = 0; v.cm = v.k1 = v.bh = v.sigma = 0.f;
     if (vc) v = *vc;
-    if (act_bf16 && T % 4 == 0) {
-        dim3 grid4((F * T / 4 + 255) / 256, B);
-        hipLaunchKernelGGL((final_euler_kernel<__bf16, 4>), grid4, dim3(256), (size_t)3 * C * sizeof(float), st, (const __bf16 *)raw, sc, sh,
-                           w, bias, mask, C, F, T, est_out, xt, mu, noise, beta, h, sq, v);
-    } else if (act_bf16)
-        hipLaunchKernelGGL((final_euler_kernel<__bf16, 1>), grid, dim3(256), (size_t)3 * C * sizeof(float), st, (const __bf16 *)raw, sc, sh,
-                           w, bias, mask, C, F, T, est_out, xt, mu, noise, beta, h, sq, v);
-    else
-        hipLaunchKernelGGL((final_euler_kernel<float, 1>), grid, dim3(256), (size_t)3 * C * sizeof(float), st, (const float *)raw, sc, sh,
-                           w, bias, mask, C, F, T, est_out, xt, mu, noise, beta, h, sq, v);
-    return hipGetLastError();
+    if (act_bf16 && T % 4 == 0)
+        return launch_final_euler_t<__bf16, 4>(raw, sc, sh, w, bias, mask, B, C, F, T, est_out, xt, mu, noise, beta, h, st, v, name);
+    if (act_bf16)
+        return launch_final_euler_t<__bf16, 1>(raw, sc, sh, w, bias, mask, B, C, F, T, est_out, xt, mu, noise, beta, h, st, v, name);
+    return launch_final_euler_t<float, 1>(raw, sc, sh, w, bias, mask, B, C, F, T, est_out, xt, mu, noise, beta, h, st, v, name);
 }
 
 }  // namespace gtts

@@ -911,6 +911,31 @@ struct ProfScope {
 
 static inline float *tptr(const RunCtx &c, int id) { return id < 0 ? nullptr : (float *)(c.ws + c.p->offsets[id]); }
 
+// Everything of a convolution op's ConvArgs that follows from the op, the plan and (B, T, T_ref): channels, geometry, prologue /
+// epilogue, strides, precision and kernel options -- all that launch_conv's choice of a kernel instance reads.  run_ops adds the
+// pointers and launches; gtts_plan_op_info has launch_conv describe the same arguments (common.h: launch or describe).
+static ConvArgs conv_args(const gtts_plan *p, const Op &o, int B, int T, int Tr) {
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    const int F = p->cfg.n_feats, Tw = o.use_ref ? Tr : T;
+    a.c0 = o.c0; a.c1 = o.c1; a.cin = o.c0 + o.c1;
+    a.B = B;
+    a.Hin = F >> o.lvl_in; a.Win = Tw >> o.lvl_in;
+    a.Hout = F >> o.lvl_out; a.Wout = Tw >> o.lvl_out;
+    a.T = Tw; a.lvl_in = o.lvl_in; a.lvl_out = o.lvl_out;
+    a.pro = o.pro;
+    a.w_bstride = o.w_t >= 0 ? p->tensors[o.w_t].bytes : 0;       // per-sample weights / bias written by attn_fold
+    a.bias_bstride = o.bias_t >= 0 ? (size_t)o.cout : 0;
+    a.cout = o.cout; a.epi = o.epi;
+    a.nparts = conv_nparts(o.mode, o.cout, a.Hout, a.Wout);
+    a.groups = p->cfg.groups;
+    a.nsplit = plan_nsplit(p);
+    a.f16f8 = p->cfg.precision == GTTS_PREC_F16F8 ? 1 : 0;
+    a.use_ws = p->cfg.conv_ws;
+    a.act_bf16 = p->cfg.precision == GTTS_PREC_BF16_STORE ? 1 : 0;
+    return a;
+}
+
 static int run_ops(const RunCtx &c) {
     gtts_plan *p = c.p;
     const int F = p->cfg.n_feats, nsplit = plan_nsplit(p);
@@ -924,43 +949,19 @@ static int run_ops(const RunCtx &c) {
         ProfScope prof_scope(p, c.st, (int)oi);
         switch (o.kind) {
             case OP_CONV: {
-                ConvArgs a;
-                memset(&a, 0, sizeof(a));
+                ConvArgs a = conv_args(p, o, c.B, c.T, c.Tr);
                 a.src0 = tptr(c, o.src0);
                 a.src1 = o.src1 >= 0 ? tptr(c, o.src1) : a.src0;
-                a.c0 = o.c0; a.c1 = o.c1; a.cin = o.c0 + o.c1; a.nchunk = 0;
-                a.B = c.B;
-                const int Tw = o.use_ref ? c.Tr : c.T;
-                a.Hin = F >> o.lvl_in; a.Win = Tw >> o.lvl_in;
-                a.Hout = F >> o.lvl_out; a.Wout = Tw >> o.lvl_out;
-                a.mask = o.use_ref ? c.ref_mask : c.mask; a.T = Tw; a.lvl_in = o.lvl_in; a.lvl_out = o.lvl_out;
-                a.pro = o.pro;
+                a.mask = o.use_ref ? c.ref_mask : c.mask;
                 a.sc = tptr(c, o.sc); a.sh = tptr(c, o.sh);
                 a.tb = c.tb_row + o.tb_off; a.tb_stride = c.tb_bstride;
                 if (o.pro == PRO_IGLU && !o.has_tb) a.tb = nullptr;
-                if (o.w_t >= 0) {
-                    a.w = (const unsigned char *)tptr(c, o.w_t);
-                    a.w_bstride = p->tensors[o.w_t].bytes;
-                } else {
-                    a.w = c.blob + o.w_off; a.w_bstride = 0;
-                }
-                if (o.bias_t >= 0) {
-                    a.bias = tptr(c, o.bias_t);
-                    a.bias_bstride = (size_t)o.cout;
-                } else {
-                    a.bias = (const float *)(c.blob + o.b_off); a.bias_bstride = 0;
-                }
+                a.w = o.w_t >= 0 ? (const unsigned char *)tptr(c, o.w_t) : c.blob + o.w_off;
+                a.bias = o.bias_t >= 0 ? tptr(c, o.bias_t) : (const float *)(c.blob + o.b_off);
                 a.btab = tptr(c, o.btab_t);
-                a.cout = o.cout; a.epi = o.epi;
                 a.out = tptr(c, o.out);
                 a.partials = tptr(c, o.part);
-                a.nparts = conv_nparts(o.mode, o.cout, a.Hout, a.Wout);
-                a.groups = p->cfg.groups;
                 a.eh = tptr(c, o.eh); a.esc = tptr(c, o.esc); a.esh = tptr(c, o.esh); a.eres = tptr(c, o.eres);
-                a.nsplit = nsplit;
-                a.f16f8 = p->cfg.precision == GTTS_PREC_F16F8 ? 1 : 0;
-                a.use_ws = p->cfg.conv_ws;
-                a.act_bf16 = abf;
                 a.sat = c.sat;
                 if (o.epi == EPI_STATS && o.gn_op >= 0 && !o.use_ref) {          // GroupNorm finalize rides in the epilogue
                     const Op &gn = p->ops[o.gn_op];
@@ -1520,37 +1521,8 @@ extern "C" int gtts_log_prior(const float *mu_x, const float *y, float *log_prio
 }
 
 // ------------------------------------------------------------------------------------------------ measurement
-// the template instance launch_conv picks (conv_mfma.hip: launch_prec / launch_cfg), as rocprofv3 prints it
-static std::string conv_kernel_name(int mode, int cin, int cout, int pro, int epi, int nsplit, bool abf, bool small, bool ws, int B, int Ho,
-                                    int Wo, int groups, bool f8 = false, bool up_f8 = false) {
-    const bool wide = cout > 64;
-    if (ws) {      // conv_ws.hip (launch_ws_pro)
-        char wb[128];
-        const bool sm = conv_ws_small(cout, groups, Ho, Wo, B);
-        const int wm = sm ? 1 : (cout % 128 == 0 ? 2 : 1), wn = sm ? 1 : 2;       // (the f16 + fp8 64-channel tile: <1, 2, 2>)
-        snprintf(wb, sizeof wb, "gtts::conv3x3_ws_kernel<%d, %d, %d, 5, %d, %d, %s, %d>", wm, wn, sm ? 1 : 2, pro, f8 ? 3 : nsplit,
-                 abf ? "__bf16" : "float", f8 ? 2 : 3);
-        return wb;
-    }
-    if (mode == CONV_UP && nsplit == 2 && !abf && cin % 16 == 0 && pro == PRO_MASK && epi == EPI_PLAIN)      // conv_up.hip
-        return (up_f8 && conv_up4_f16f8_ok(cin, cout)) ? conv_up4_f8_name() : "gtts::conv_up4_kernel";
-    const int kch = conv_geom(mode, cin, cout, f8 ? 1 : 0).kch;
-    if (f8) nsplit = 3;
-    const bool fullc = cin % 16 == 0;
-    int wm, wn, mf;
-    if (mode == CONV_DN) { wm = 2; wn = 2; mf = wide ? 2 : 1; }
-    else if (wide) { wm = 2; wn = 2; mf = 2; }
-    else { wm = 1; wn = 4; mf = 2; }
-    if (small && mode == CONV_C3 && fullc && !abf && nsplit > 1 && pro != PRO_IGLU) {      // half-height tiles (conv_small_tiles)
-        mf = 1;
-        if (wide) { wm = 4; wn = 1; } else { wm = 2; wn = 2; }
-    }
-    char buf[128];
-    snprintf(buf, sizeof buf, "gtts::conv_mfma_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, %s, 2, 0>", mode, wm, wn, mf, kch, pro, epi, nsplit,
-             fullc ? 1 : 0, abf ? "__bf16" : "float");
-    return buf;
-}
-
+// Kernel names of the per-op table come from the launchers themselves: asked to describe instead of launch (common.h), each walks its
+// own dispatch with the op's shapes and options and no pointers.  A refusal means the plan holds an op no kernel instance takes.
 extern "C" int gtts_plan_num_ops(const gtts_plan *plan) { return plan ? (int)plan->ops.size() + XOP_COUNT : 0; }
 
 extern "C" int gtts_plan_op_info(const gtts_plan *plan, int i, int B, int T, const char **label, const char **kernel,
@@ -1562,15 +1534,18 @@ extern "C" int gtts_plan_op_info(const gtts_plan *plan, int i, int B, int T, con
     if (i < 0 || i >= n + XOP_COUNT) return fail(GTTS_E_SHAPE, "op index out of range");
     const double F = plan->cfg.n_feats;
     const double ab = plan->cfg.precision == GTTS_PREC_BF16_STORE ? 2.0 : 4.0;      // bytes per stored activation
-    const bool abf = plan->cfg.precision == GTTS_PREC_BF16_STORE;
+    const int abf = plan->cfg.precision == GTTS_PREC_BF16_STORE ? 1 : 0;
     double fl = 0, by = 0;
+    hipError_t e = hipSuccess;      // of the launcher asked for its kernel's name
     if (i >= n) {
         const double FT = F * T * B;
         switch (i - n) {
-            case XOP_PREP: s_label = "prep_input"; s_kernel = abf ? "gtts::prep_input_kernel<__bf16>" : "gtts::prep_input_kernel<float>"; by = (4.0 + ab) * FT * plan->cin0; break;
+            case XOP_PREP: s_label = "prep_input"; by = (4.0 + ab) * FT * plan->cin0;
+                e = launch_prep_input(nullptr, nullptr, nullptr, nullptr, B, (int)F, T, plan->cin0, nullptr, abf, &s_kernel); break;
             case XOP_TIME: s_label = "time_mlp"; s_kernel = "gtts::time_mlp_kernel"; break;
-            case XOP_FINAL: s_label = "final_conv+euler"; s_kernel = abf ? (T % 4 == 0 ? "gtts::final_euler_kernel<__bf16, 4>" : "gtts::final_euler_kernel<__bf16, 1>") : "gtts::final_euler_kernel<float, 1>";
-                fl = 2.0 * plan->cfg.dim * FT; by = FT * (ab * plan->cfg.dim + 16.0); break;
+            case XOP_FINAL: s_label = "final_conv+euler"; fl = 2.0 * plan->cfg.dim * FT; by = FT * (ab * plan->cfg.dim + 16.0);
+                e = launch_final_euler(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, plan->cfg.dim, (int)F, T, nullptr, nullptr, nullptr,
+                                       nullptr, 0.f, 0.f, nullptr, nullptr, abf, &s_kernel); break;
             case XOP_MULMASK: s_label = "xt=z*mask"; s_kernel = "gtts::mul_mask_kernel"; by = 8.0 * FT; break;
             case XOP_SPK: s_label = "spk_mlp"; s_kernel = "gtts::spk_mlp_kernel"; break;
         }
@@ -1585,39 +1560,25 @@ extern "C" int gtts_plan_op_info(const gtts_plan *plan, int i, int B, int T, con
                 fl = 2.0 * B * o.cout * cin * taps * Ho * Wo;
                 by = ab * B * (cin * Hi * Wi + o.cout * Ho * Wo);
                 if (o.epi == EPI_TAIL || o.epi == EPI_ATTN) by += ab * B * o.cout * Ho * Wo;
-                s_kernel = conv_kernel_name(o.mode, o.c0 + o.c1, o.cout, o.pro, o.epi, plan_nsplit(plan),
-                                            plan->cfg.precision == GTTS_PREC_BF16_STORE, conv_small_tiles(o.mode, o.cout, Ho, Wo, B),
-                                            plan->cfg.conv_ws && conv_ws_eligible(o.mode, o.c0, o.c1, o.cout, o.pro, o.epi, plan_nsplit(plan), plan->cfg.precision == GTTS_PREC_F16F8),
-                                            B, (int)Ho, (int)Wo, plan->cfg.groups,
-                                            plan->cfg.precision == GTTS_PREC_F16F8 && conv_f16f8_ok(o.mode, o.c0, o.c1, o.cout, o.pro, o.epi, plan->cfg.conv_ws),
-                                            plan->cfg.precision == GTTS_PREC_F16F8);
                 if (o.fused) {
                     s_kernel = "(fused into " + plan->ops[o.dn_op].label + ")";
                     fl = by = 0.0;
-                }
+                } else
+                    e = launch_conv(o.mode, conv_args(plan, o, B, T, T), nullptr, &s_kernel);
                 break;
             }
             case OP_GNFIN: s_kernel = "gtts::gn_finalize_kernel"; break;
             case OP_TAILID: {
-                // the instance launch_tail_identity picks (misc.hip): vector width by storage type / width, 4 items per thread on big planes
-                const int vec = (abf && (int)Wi % 8 == 0) ? 8 : ((int)Wi % 4 == 0 ? 4 : 1);
-                const int items = (vec > 1 && ((int)(Hi * Wi) / vec + 255) / 256 >= 8) ? 4 : 1;
-                char nb[96];
-                snprintf(nb, sizeof nb, "gtts::tail_identity_kernel<%d, %s, %d>", vec, abf ? "__bf16" : "float", items);
-                s_kernel = o.fused ? "(fused into the attention context pass)" : nb;
+                if (o.fused) s_kernel = "(fused into the attention context pass)";
+                else e = launch_tail_identity(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, o.C, (int)Hi, (int)Wi, T, o.lvl_in, nullptr,
+                                              abf, &s_kernel);
                 by = o.fused ? 0.0 : ab * B * o.C * Hi * Wi * 3;
                 break;
             }
             case OP_ACTX: {
-                char nb[96];
-                if (attn_head_per_wave(o.C) && o.fused)
-                    snprintf(nb, sizeof nb, "gtts::attn_ctx64_kernel<%d, float, 1>", plan_nsplit(plan));
-                else if (attn_head_per_wave(o.C))
-                    snprintf(nb, sizeof nb, "gtts::attn_ctx64_kernel<%d, %s, 0>", plan_nsplit(plan), abf ? "__bf16" : "float");
-                else
-                    snprintf(nb, sizeof nb, "gtts::attn_ctx_kernel<%d, %d, %s, %d, %d>", plan_nsplit(plan), o.C % 32 == 0 ? 1 : 0,
-                             abf ? "__bf16" : "float", GTTS_ATTN_HPW, o.fused ? 1 : 0);
-                s_kernel = nb;
+                const AttnTail tl{};      // (a fused tail: only its presence picks the instance)
+                e = launch_attn_ctx(nullptr, nullptr, nullptr, B, o.C, (int)(Hi * Wi), plan_nsplit(plan), nullptr, abf, o.fused ? &tl : nullptr,
+                                    &s_kernel);
                 fl = 2.0 * B * Hi * Wi * (256.0 * o.C + 128.0 * 32);
                 by = ab * B * o.C * Hi * Wi * (o.fused ? 3 : 1); break;      // (fused tail: block input + raw convolution output in, block output out)
             }
@@ -1630,6 +1591,7 @@ extern "C" int gtts_plan_op_info(const gtts_plan *plan, int i, int B, int T, con
                 fl = 2.0 * B * (o.C * 128.0 * 32 + (double)o.C * o.C * 128) * ((o.w_t >= 0 ? 1 : 0) + (o.dn_op >= 0 ? 9 : 0)); break;
         }
     }
+    if (e != hipSuccess) return fail(GTTS_E_CONFIG, "op %s: no kernel instance takes it at B=%d, T=%d", s_label.c_str(), B, T);
     if (label) *label = s_label.c_str();
     if (kernel) *kernel = s_kernel.c_str();
     if (flops) *flops = fl;
