@@ -247,16 +247,16 @@ __global__ __launch_bounds__(256 * HPW, HPW == 1 ? 2 : 1) void attn_ctx_kernel(c
         const float m_new = fmaxf(m_run, tmax);
         const float alpha = (m_run == NEG_INF) ? 0.f : __expf(m_run - m_new);
         const float msub = (m_new == NEG_INF) ? 0.f : m_new;
-        // p = exp(k - m) as one fma + v_exp_f32 per element: exp2(k * log2(e) - m * log2(e))
+        // p = exp2((k - m) * log2(e)): the reference point is exact (the maximum element gives 2^0 = 1 at any magnitude), and the
+        // records, alpha, the in-workgroup merge and attn_merge all share this m ("softmax reference point")
         constexpr float LOG2E = 1.44269504088896340736f;
-        const float ml2 = msub * LOG2E;
         float psum = 0.f;
         if (full) {
 #pragma unroll
             for (int pf = 0; pf < 2; ++pf)
 #pragma unroll
                 for (int rg = 0; rg < 16; ++rg) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[pf][0][rg], LOG2E, -ml2));
+                    const float p = __builtin_amdgcn_exp2f((acc[pf][0][rg] - msub) * LOG2E);
                     acc[pf][0][rg] = p;
                     psum += p;
                 }
@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256 * HPW, HPW == 1 ? 2 : 1) void attn_ctx_kernel(c
 #pragma unroll
                 for (int rg = 0; rg < 16; ++rg) {
                     const int n = nbase + pf * 32 + (rg & 3) + 8 * (rg >> 2);
-                    const float p = (n < a.HW) ? __builtin_amdgcn_exp2f(__builtin_fmaf(acc[pf][0][rg], LOG2E, -ml2)) : 0.f;
+                    const float p = (n < a.HW) ? __builtin_amdgcn_exp2f((acc[pf][0][rg] - msub) * LOG2E) : 0.f;
                     acc[pf][0][rg] = p;
                     psum += p;
                 }
@@ -527,15 +527,14 @@ __global__ __launch_bounds__(256, 2) void attn_ctx64_kernel(const AttnCtxArgs a)
         const float m_new = fmaxf(m_run, tmax);
         const float alpha = (m_run == NEG_INF) ? 0.f : __expf(m_run - m_new);
         const float msub = (m_new == NEG_INF) ? 0.f : m_new;
-        constexpr float LOG2E = 1.44269504088896340736f;
-        const float ml2 = msub * LOG2E;
+        constexpr float LOG2E = 1.44269504088896340736f;       // p = exp2((k - m) * log2(e)): see attn_ctx_kernel
         float psum = 0.f;
         if (full) {
 #pragma unroll
             for (int pf = 0; pf < 2; ++pf)
 #pragma unroll
                 for (int rg = 0; rg < 16; ++rg) {
-                    const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[pf][0][rg], LOG2E, -ml2));
+                    const float p = __builtin_amdgcn_exp2f((acc[pf][0][rg] - msub) * LOG2E);
                     acc[pf][0][rg] = p;
                     psum += p;
                 }
@@ -545,7 +544,7 @@ __global__ __launch_bounds__(256, 2) void attn_ctx64_kernel(const AttnCtxArgs a)
 #pragma unroll
                 for (int rg = 0; rg < 16; ++rg) {
                     const int n = nbase + pf * 32 + (rg & 3) + 8 * (rg >> 2);
-                    const float p = (n < a.HW) ? __builtin_amdgcn_exp2f(__builtin_fmaf(acc[pf][0][rg], LOG2E, -ml2)) : 0.f;
+                    const float p = (n < a.HW) ? __builtin_amdgcn_exp2f((acc[pf][0][rg] - msub) * LOG2E) : 0.f;
                     acc[pf][0][rg] = p;
                     psum += p;
                 }

@@ -11,9 +11,13 @@ Measured on MI355X (profiles/r08_fold_down_error.txt), max |err| / max |ref| of 
 own downs.0.2.out, worst region: folded 6.4e-6 (conv_mfma) / 5.9e-6 (f16f8 on conv_ws); the unfused path before the fold, same
 inputs: 7.9e-6 / 4.8e-6.  Against the oracle's tap: at most 3.3e-5.
 
-With g = 1.0 at all six attentions this state grows to 6e10 in the up path, and the estimator output of the ONE-FRAME utterance is
-not finite on the HIP path (the CPU oracle's is; the same before the fold, see the profile note): the checks below are the local
-ones at level 0, and the bit comparison of the two kinds of plan compares bit patterns and wants utterances 0 and 1 finite."""
+With g = 1.0 at all six attentions this state grows to 4.5e9 at the input of ups.1.2 in the ONE-FRAME utterance (branch 4.4e18) and
+stays inside fp32 (CPU oracle: final output max 7.9).  bf16x3: the estimator output of all three utterances is finite on the HIP
+path, since the context kernels take the softmax reference point exactly (tests/test_gpu_attention.py, profiles/attention_parity.txt).
+f16f8: a range limit of the format (tests/test_gpu_range.py, contract (b)).  The split's hi operand is fp16, and in the one-frame
+utterance the input of the 3x3 convolution of mid_block2.block1 (mid_attn.out, 1.5e6) is the first beyond 65504 -- the first
+non-finite tap of the f16f8 plan is mid_block2.b1.raw, on both convolution kernels (walk: profiles/attention_parity.txt) -- and the up path then reaches 4.4e18.  That utterance is not finite there, utterances 0 and 1 are, and Plan.range_status() must report the limit:
+events > 0 and max |x| = inf (non-finite GroupNorm statistics).  Both tests assert this per precision."""
 import importlib
 
 import numpy as np
@@ -69,6 +73,18 @@ def _forward(S, dev, case, prec, conv_ws, keep):
     return plan, out.cpu()
 
 
+def _check_finite(tag, plan, out, prec):
+    """The estimator output is finite (bf16x3: every utterance), or the format's range limit is on record (f16f8: module docstring)."""
+    fin = [bool(torch.isfinite(out[b]).all()) for b in range(B)]
+    ev, mx = plan.range_status()
+    print("%s | estimator output finite per utterance: %s, range_status: %d events, max |x| %g" % (tag, fin, ev, mx))
+    if prec == "f16f8":
+        assert fin[:2] == [True, True], fin
+        assert ev > 0 and mx == float("inf"), (ev, mx)
+    else:
+        assert fin == [True] * B, fin
+
+
 def _regions(lengths, Ho, Wo):
     """Boolean [B][Ho][Wo] maps: first output row; first and last output column; the two output columns on either side of each
     utterance end; everything else."""
@@ -118,16 +134,15 @@ def test_folded_downsample_local_and_oracle(S, dev, case, prec, conv_ws):
     assert e_att <= REL
     assert e_local <= REL, e_local
     assert e_oracle <= REL, e_oracle
-    fin = [bool(torch.isfinite(out[b]).all()) for b in range(B)]
-    print("%s | estimator output finite per utterance: %s" % (tag, fin))
+    _check_finite(tag, plan, out, prec)
 
 
 @kernels
 @precs
 def test_normal_and_keep_intermediates_plans_return_the_same_bits(S, dev, case, prec, conv_ws):
-    _, out_n = _forward(S, dev, case, prec, conv_ws, keep=False)
+    plan_n, out_n = _forward(S, dev, case, prec, conv_ws, keep=False)
     _, out_k = _forward(S, dev, case, prec, conv_ws, keep=True)
-    assert torch.isfinite(out_n[:2]).all()
+    _check_finite("%s %s" % (prec, "conv_ws" if conv_ws else "conv_mfma"), plan_n, out_n, prec)
     assert torch.equal(out_n.view(torch.int32), out_k.view(torch.int32))      # the same BITS (a NaN is not equal to itself)
 
 
