@@ -521,6 +521,51 @@ size_t gtts_spk_workspace_bytes(const gtts_spk *spk, int N, int T);
 int gtts_spk_forward(const gtts_spk *spk, const void *packed, const float *frames, int U, int T_total, int P, int S, int T, float *embeds,
                      float *hidden_out, float *utt_embeds, void *workspace, size_t workspace_bytes, gtts_stream_t stream);
 
+/* ---- ABI 6 (additive): Fast Griffin-Lim, log-mel -> waveform without a vocoder checkpoint: FastGL / PseudoInversion /
+ * InitialReconstruction of DiffVC/model/utils.py:42-110 on csrc/fgl.hip -------------------------------------------------------------
+ * K = n_fft / 2 + 1, w = the periodic Hann window of n_fft samples (win_length = n_fft), m = momentum, L = hop_size (T - 1).
+ *   c [B,K,T] = P exp(logmel), P [K][n_mels] the caller's pseudo-inverse of the mel filterbank (the library does no SVD); c may be
+ *   negative and is used as it is;  x0 = istft(c + 0i);  then n_iters times
+ *   s = stft(x),  a = s / sqrt(max(re^2 + im^2, 1e-8)),  x = istft(c (a + m (a - a_prev))),  a_prev = a   (a_prev = 0 at first).
+ * stft: center = True, reflect pad n_fft / 2 (needs L > n_fft / 2), one-sided, unnormalised.  istft: per-frame c2r transform scaled
+ * 1 / n_fft (imaginary parts of DC and Nyquist ignored), times w, overlap-added at stride hop_size, divided by the envelope
+ * sum_t w^2[j - t hop_size], n_fft / 2 trimmed from both ends.  fp32 throughout; tables host float64 -> fp32; no device sin / cos.
+ * Supported (else GTTS_E_CONFIG): n_fft a power of two in [256, 2048], 1 <= hop_size <= n_fft / 2 (the envelope is then positive
+ * everywhere after the trim), 1 <= n_mels <= 128, 0 <= momentum < 1.
+ * The handle is host metadata; gtts_fgl_pack copies its tables and the caller's HOST matrix into the caller's blob of
+ * gtts_fgl_packed_bytes bytes (it waits for the copy).  Every call takes a workspace of gtts_fgl_workspace_bytes(B, T) bytes.
+ * [B,K,T,2] is the memory of a torch complex64 [B,K,T].  Launches on `stream`: init = projection, first inverse transform, one that
+ * materialises x0; step = one transform launch + one that materialises x_out; forward = projection, first inverse transform, ONE
+ * launch per iteration, one that materialises wav -- between iterations x exists only as windowed inverse frames in the workspace,
+ * and launches are ordered by stream order alone (no workgroup waits for another, no cooperative launch).  No floating-point atomics:
+ * the at most ceil(n_fft / hop_size) overlapping frames of a sample are summed in ascending frame order, the mel projection in a
+ * fixed order.  gtts_fgl_forward(n_iters = n) equals gtts_fgl_init followed by n gtts_fgl_step bit for bit; n_iters = 0 returns x0.
+ * A row's result depends on that row's mel alone, never on B or on its position in the batch. */
+typedef struct gtts_fgl_cfg {
+    int n_fft;           /* 1024  */
+    int n_mels;          /* 80    */
+    int hop_size;        /* 256   */
+    double momentum;     /* 0.99  */
+} gtts_fgl_cfg;
+typedef struct gtts_fgl gtts_fgl;     /* host-side metadata only */
+int gtts_fgl_create(const gtts_fgl_cfg *cfg, gtts_fgl **out);
+void gtts_fgl_destroy(gtts_fgl *fgl);
+/* L = hop_size (T - 1) for mels of T frames, or GTTS_E_SHAPE when that is <= n_fft / 2 (the message names the smallest T) */
+int gtts_fgl_samples(const gtts_fgl *fgl, int T);
+size_t gtts_fgl_packed_bytes(const gtts_fgl *fgl);
+/* inv_basis_host: P [K][n_mels] fp32 in HOST memory */
+int gtts_fgl_pack(const gtts_fgl *fgl, const float *inv_basis_host, void *packed, gtts_stream_t stream);
+size_t gtts_fgl_workspace_bytes(const gtts_fgl *fgl, int B, int T);
+/* logmel [B,n_mels,T] -> c [B,K,T], x0 [B,L] */
+int gtts_fgl_init(const gtts_fgl *fgl, const void *packed, const float *logmel, float *c, float *x0, void *workspace,
+                  size_t workspace_bytes, int B, int T, gtts_stream_t stream);
+/* one iteration: c [B,K,T], x_in [B,L], a_prev [B,K,T,2] -> x_out [B,L], a [B,K,T,2] (x_out / a must not alias x_in / a_prev) */
+int gtts_fgl_step(const gtts_fgl *fgl, const void *packed, const float *c, const float *x_in, const float *a_prev, float *x_out, float *a,
+                  void *workspace, size_t workspace_bytes, int B, int T, gtts_stream_t stream);
+/* logmel [B,n_mels,T] -> wav [B,L] after n_iters >= 0 iterations */
+int gtts_fgl_forward(const gtts_fgl *fgl, const void *packed, const float *logmel, float *wav, void *workspace, size_t workspace_bytes,
+                     int B, int T, int n_iters, gtts_stream_t stream);
+
 /* ---- debugging / tests: named intermediates of the last estimator call (keep_intermediates plans) ----- */
 int gtts_plan_num_tensors(const gtts_plan *plan);
 /* offset is in bytes into the workspace for the given (B,T); dims = {B,C,H,W}. */

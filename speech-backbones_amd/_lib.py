@@ -50,6 +50,10 @@ class MelCfg(ctypes.Structure):
                 ("win_size", ctypes.c_int), ("fmin", ctypes.c_double), ("fmax", ctypes.c_double)]
 
 
+class FglCfg(ctypes.Structure):
+    _fields_ = [("n_fft", ctypes.c_int), ("n_mels", ctypes.c_int), ("hop_size", ctypes.c_int), ("momentum", ctypes.c_double)]
+
+
 class SpkCfg(ctypes.Structure):
     _fields_ = [("n_mels", ctypes.c_int), ("hidden", ctypes.c_int), ("layers", ctypes.c_int), ("embed", ctypes.c_int)]
 
@@ -216,6 +220,15 @@ def lib():
         L.gtts_mel_pack.argtypes = [vp, vp, vp]
         L.gtts_mel_filterbank.argtypes = [vp, vp]
         L.gtts_mel_forward.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
+        L.gtts_fgl_create.argtypes = [ctypes.POINTER(FglCfg), ctypes.POINTER(vp)]
+        L.gtts_fgl_destroy.argtypes, L.gtts_fgl_destroy.restype = [vp], None
+        L.gtts_fgl_samples.argtypes = [vp, i]
+        L.gtts_fgl_packed_bytes.argtypes, L.gtts_fgl_packed_bytes.restype = [vp], sz
+        L.gtts_fgl_pack.argtypes = [vp, vp, vp, vp]
+        L.gtts_fgl_workspace_bytes.argtypes, L.gtts_fgl_workspace_bytes.restype = [vp, i, i], sz
+        L.gtts_fgl_init.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, vp]
+        L.gtts_fgl_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
+        L.gtts_fgl_forward.argtypes = [vp, vp, vp, vp, vp, sz, i, i, i, vp]
         L.gtts_spk_forward.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, sz, vp]
         if L.gtts_abi_version() != 6:
             raise RuntimeError("libgradtts_gfx950.so ABI version mismatch")
@@ -813,6 +826,83 @@ class MelPlan(_Native):
         with _on(y.device):
             self._call("forward", self._h, _ptr(blob), _ptr(y), _ptr(lengths), _ptr(out), B, L, _stream())
         return out
+
+
+class FglPlan(_Native):
+    """Fast Griffin-Lim on the HIP kernels (csrc/fgl.hip): FastGL of DiffVC/model/utils.py:42-110, log-mel [B, n_mels, T] -> waveform
+    [B, hop_size (T - 1)].  The handle has no parameters of its own: its blob holds the window, the twiddles and the caller's
+    pseudo-inverse of the mel filterbank."""
+    _family = "fgl"
+
+    def __init__(self, n_fft=1024, n_mels=80, hop_size=256, momentum=0.99):
+        self.cfg = FglCfg(int(n_fft), int(n_mels), int(hop_size), float(momentum))
+        self.n_fft, self.n_mels, self.hop_size, self.momentum = int(n_fft), int(n_mels), int(hop_size), float(momentum)
+        self.bins = self.n_fft // 2 + 1
+        self._open(dict(n_fft=int(n_fft), n_mels=int(n_mels), hop_size=int(hop_size), momentum=float(momentum)), ctypes.byref(self.cfg))
+
+    def samples(self, T):
+        """L = hop_size (T - 1) for mels of T frames; raises when that is <= n_fft / 2 (no reflection), naming the smallest T."""
+        L = int(self._fn("samples")(self._h, int(T)))
+        if L < 0:
+            _check(L, "gtts_fgl_samples")
+        return L
+
+    def pack(self, inv_basis, device):
+        """inv_basis: the pseudo-inverse of the mel filterbank, [n_fft / 2 + 1, n_mels] (any device; it is read on the host)."""
+        P = inv_basis.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        if tuple(P.shape) != (self.bins, self.n_mels):
+            raise RuntimeError("inv_basis must be [%d, %d] (got %s)" % (self.bins, self.n_mels, tuple(P.shape)))
+        blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
+        if not blob.is_cuda:
+            raise RuntimeError("the Griffin-Lim tables are packed for a HIP device (got %s)" % blob.device)
+        with torch.cuda.device(blob.device):
+            self._call("pack", self._h, _ptr(P), _ptr(blob), _stream())
+        return blob
+
+    def _mel(self, s):
+        s = _f32c(s, "logmel")
+        if s.dim() != 3 or s.shape[1] != self.n_mels:
+            raise RuntimeError("logmel must be [B, %d, T] (got %s)" % (self.n_mels, tuple(s.shape)))
+        return s, int(s.shape[0]), int(s.shape[2]), self.samples(s.shape[2])
+
+    def init(self, blob, s):
+        """logmel [B, n_mels, T] -> (c [B, K, T], x0 [B, L])."""
+        s, B, T, L = self._mel(s)
+        ws = self.workspace(B, T, s.device)
+        c = torch.empty((B, self.bins, T), dtype=torch.float32, device=s.device)
+        x0 = torch.empty((B, L), dtype=torch.float32, device=s.device)
+        with _on(s.device):
+            self._call("init", self._h, _ptr(blob), _ptr(s), _ptr(c), _ptr(x0), _ptr(ws), ws.numel(), B, T, _stream())
+        return c, x0
+
+    def step(self, blob, c, x, a_prev):
+        """One iteration: c [B, K, T], x [B, L], a_prev complex64 [B, K, T] -> (x_out [B, L], a complex64 [B, K, T])."""
+        c, x = _f32c(c, "c"), _f32c(x, "x")
+        if c.dim() != 3 or c.shape[1] != self.bins:
+            raise RuntimeError("c must be [B, %d, T] (got %s)" % (self.bins, tuple(c.shape)))
+        B, _, T = c.shape
+        L = self.samples(T)
+        if tuple(x.shape) != (B, L):
+            raise RuntimeError("x must be [%d, %d] (got %s)" % (B, L, tuple(x.shape)))
+        if not a_prev.is_cuda or a_prev.dtype != torch.complex64 or tuple(a_prev.shape) != tuple(c.shape):
+            raise RuntimeError("a_prev must be a complex64 %s on the HIP device (got %s %s on %s)" %
+                               (tuple(c.shape), a_prev.dtype, tuple(a_prev.shape), a_prev.device))
+        a_prev = a_prev.contiguous()
+        ws = self.workspace(B, T, c.device)
+        x_out, a = torch.empty_like(x), torch.empty_like(a_prev)
+        with _on(c.device):
+            self._call("step", self._h, _ptr(blob), _ptr(c), _ptr(x), _ptr(a_prev), _ptr(x_out), _ptr(a), _ptr(ws), ws.numel(), B, T,
+                       _stream())
+        return x_out, a
+
+    def forward(self, blob, s, n_iters=32):
+        """logmel [B, n_mels, T] -> waveform [B, L] after n_iters iterations, one launch each (n_iters = 0: the initial reconstruction)."""
+        s, B, T, L = self._mel(s)
+        ws = self.workspace(B, T, s.device)
+        wav = torch.empty((B, L), dtype=torch.float32, device=s.device)
+        with _on(s.device):
+            self._call("forward", self._h, _ptr(blob), _ptr(s), _ptr(wav), _ptr(ws), ws.numel(), B, T, int(n_iters), _stream())
+        return wav
 
 
 class SpkPlan(_Native):

@@ -1,0 +1,229 @@
+"""GPU tests (-m gpu) of the Fast Griffin-Lim kernels (csrc/fgl.hip) through FglPlan and the drop-in FastGL of diffvc/model/utils.py
+against the recipe written out in float64 on the CPU (tests/fgl_oracle.py).  Run with -s: every case prints one row.
+
+Free-running waveforms cannot carry assertions: the phase s / |s| is ill-conditioned where |s| is small, so two float32 trajectories
+are 1e-4 apart after one iteration and 1e-1 after 32, as far from each other as from float64.  One step on GIVEN input is
+well-conditioned when it is checked in two halves, so the kernels are checked as
+  init       c against float64; x0 against the float64 istft of the kernel's own c;
+  analysis   a_k max(|s64|, 1e-4) against s64 = stft64 of the kernel's own input x_in, and |a_k| <= 1 + 1e-6, every cell;
+  synthesis  x_out against istft64(c (a_k + m (a_k - a_prev))) built from the kernel's own a_k;
+on the states (x, a_prev) the HIP path itself reached after 0, 1 and 15 iterations.  Every bound has the form
+  e_kernel <= 4 e_ref32 + 2 ulp32(max |reference|),
+e_ref32 being the same quantity for the float32 oracle on the same input: headroom for another butterfly and summation order, never a
+figure taken from the kernel.  forward(n) = init + n steps, batch independence and the module path are bit for bit.  The free-running
+case (T = 130, 32 iterations) asserts the spectral convergence only, |sc_kernel - sc_64| <= 1e-3 + 10 |sc_32 - sc_64|
+(tests/test_fgl_cpu.py shows that every mistake this is there for moves it by >= 3e-2), and prints the waveform distance."""
+import importlib
+import math
+
+import pytest
+import torch
+
+import fgl_oracle as FO
+import mel_oracle as MO
+
+pytestmark = pytest.mark.gpu
+CFG256 = (256, 40, 16000, 64)           # fewer butterflies than lanes
+CFG2048 = (2048, 80, 22050, 512)        # the largest transform: the LDS limit that needs the opt-in
+CFGS = {"cfgA": FO.CFGA, "cfgB": FO.CFGB, "n256": CFG256, "n2048": CFG2048}
+SHAPES = ([("cfgA", T, B) for T in (4, 5, 17, 37) for B in (1, 3)]            # 4: the smallest legal; 17: crosses a tile edge
+          + [("cfgB", FO.min_frames(FO.CFGB), 2), ("cfgB", 59, 2), ("n256", 21, 2), ("n2048", 19, 2)])
+NAMES = ("speechlike", "noise", "quiet")
+DEPTHS = (0, 1, 15)
+
+
+def ulp32(v):
+    return 2.0 ** (math.floor(math.log2(v)) - 23) if v > 0 else 0.0
+
+
+def c64_of(z):
+    return torch.complex(z.real.double(), z.imag.double())
+
+
+@pytest.fixture(scope="module")
+def S():
+    assert torch.cuda.is_available()
+    return importlib.import_module("speech-backbones_amd")
+
+
+@pytest.fixture(scope="module")
+def U():
+    return importlib.import_module("speech-backbones_amd.diffvc.model.utils")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def native(S, dev):
+    """native(cfg) -> (plan, blob), made once per configuration from the oracle's pseudo-inverse."""
+    made = {}
+
+    def go(cfg):
+        if cfg not in made:
+            plan = S.FglPlan(cfg[0], cfg[1], cfg[3], FO.MOMENTUM)
+            made[cfg] = (plan, plan.pack(FO.basis64(cfg)[1].float(), dev))
+        return made[cfg]
+    return go
+
+
+@pytest.fixture(scope="module")
+def states(native, dev):
+    """states(tag, name, T, B) -> {n: (c, x, a_prev) on the device} for n in DEPTHS: what the HIP path reached after n iterations."""
+    made = {}
+
+    def go(tag, name, T, B):
+        key = (tag, name, T, B)
+        if key not in made:
+            cfg = CFGS[tag]
+            plan, blob = native(cfg)
+            c, x = plan.init(blob, FO.logmel(name, cfg, T)[:B].to(dev))
+            a = torch.zeros(c.shape, dtype=torch.complex64, device=dev)
+            out = {}
+            for n in range(max(DEPTHS) + 1):
+                if n in DEPTHS:
+                    out[n] = (c, x, a)
+                x, a = plan.step(blob, c, x, a)
+            made[key] = out
+        return made[key]
+    return go
+
+
+@pytest.mark.parametrize("tag,T,B", SHAPES)
+@pytest.mark.parametrize("name", NAMES)
+def test_init_projection_and_first_inverse(native, dev, name, tag, T, B):
+    cfg = CFGS[tag]
+    plan, blob = native(cfg)
+    s = FO.logmel(name, cfg, T)[:B]
+    c_k, x0_k = plan.init(blob, s.to(dev))
+    c_k, x0_k = c_k.cpu(), x0_k.cpu()
+    assert tuple(c_k.shape) == (B, cfg[0] // 2 + 1, T) and tuple(x0_k.shape) == (B, cfg[3] * (T - 1))
+    assert c_k.dtype == torch.float32 and x0_k.dtype == torch.float32
+    c64 = FO.project(s, cfg)
+    e_ref = float((FO.project(s, cfg, torch.float32).double() - c64).abs().max())
+    e_k = float((c_k.double() - c64).abs().max())
+    zero = torch.zeros_like(c_k)
+    x64 = FO.istft(torch.complex(c_k.double(), zero.double()), cfg)
+    ex_ref = float((FO.istft(torch.complex(c_k, zero), cfg).double() - x64).abs().max())
+    ex_k = float((x0_k.double() - x64).abs().max())
+    print("\n%s T=%d B=%d %-10s c: e_kernel %.2e e_ref32 %.2e ratio %.2f | x0: e_kernel %.2e e_ref32 %.2e ratio %.2f" %
+          (tag, T, B, name, e_k, e_ref, e_k / max(e_ref, 1e-30), ex_k, ex_ref, ex_k / max(ex_ref, 1e-30)))
+    assert e_k <= 4 * e_ref + 2 * ulp32(float(c64.abs().max()))
+    assert ex_k <= 4 * ex_ref + 2 * ulp32(float(x64.abs().max()))
+
+
+@pytest.mark.parametrize("tag,T,B", SHAPES)
+@pytest.mark.parametrize("name", NAMES)
+def test_step_analysis_and_synthesis(native, states, name, tag, T, B):
+    cfg = CFGS[tag]
+    plan, blob = native(cfg)
+    for n in DEPTHS:
+        c, x_in, a_prev = states(tag, name, T, B)[n]
+        x_out, a_k = plan.step(blob, c, x_in, a_prev)
+        c, x_in, a_prev, x_out, a_k = c.cpu(), x_in.cpu(), a_prev.cpu(), x_out.cpu(), a_k.cpu()
+        assert a_k.dtype == torch.complex64 and a_k.shape == c.shape and x_out.shape == x_in.shape
+        # ---- analysis half
+        s64 = FO.stft(x_in, cfg)
+        floor = torch.clamp(s64.abs(), min=1e-4)
+        ea_k = float((c64_of(a_k) * floor - s64).abs().max())
+        ea_ref = float((c64_of(FO.phases(FO.stft(x_in, cfg, torch.float32))) * floor - s64).abs().max())
+        amax = float(c64_of(a_k).abs().max())
+        # ---- synthesis half, from the kernel's own phases
+        m = FO.MOMENTUM
+        a64, p64 = c64_of(a_k), c64_of(a_prev)
+        x64 = FO.istft(c.double() * (a64 + m * (a64 - p64)), cfg)
+        es_ref = float((FO.istft(c * (a_k + m * (a_k - a_prev)), cfg).double() - x64).abs().max())
+        es_k = float((x_out.double() - x64).abs().max())
+        print("\n%s T=%d B=%d %-10s after %2d: analysis e_kernel %.2e e_ref32 %.2e ratio %.2f max|a| %.8f | synthesis e_kernel %.2e "
+              "e_ref32 %.2e ratio %.2f" % (tag, T, B, name, n, ea_k, ea_ref, ea_k / max(ea_ref, 1e-30), amax, es_k, es_ref,
+                                           es_k / max(es_ref, 1e-30)))
+        assert bool(torch.isfinite(x_out).all()) and bool(torch.isfinite(torch.view_as_real(a_k)).all())
+        assert ea_k <= 4 * ea_ref + 2 * ulp32(float(s64.abs().max()))
+        assert amax <= 1 + 1e-6
+        assert es_k <= 4 * es_ref + 2 * ulp32(float(x64.abs().max()))
+
+
+@pytest.mark.parametrize("tag,T,B", SHAPES)
+def test_forward_is_init_followed_by_steps(native, dev, tag, T, B):
+    cfg = CFGS[tag]
+    plan, blob = native(cfg)
+    s = FO.logmel("speechlike", cfg, T)[:B].to(dev)
+    c, x = plan.init(blob, s)
+    a = torch.zeros(c.shape, dtype=torch.complex64, device=dev)
+    for n in range(33):
+        if n in (0, 1, 2, 32):
+            assert torch.equal(plan.forward(blob, s, n), x), n
+        x, a = plan.step(blob, c, x, a)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_free_running_spectral_convergence(U, dev, name):
+    cfg, T, B = FO.CFGA, 130, 2
+    s = FO.logmel(name, cfg, T)[:B]
+    g = U.FastGL(cfg[1], cfg[2], cfg[0], cfg[3]).to(dev)
+    got = g(s.to(dev))
+    assert got.is_cuda and got.dtype == torch.float32 and tuple(got.shape) == (B, 1, cfg[3] * (T - 1))
+    got = got.cpu()[:, 0]
+    assert bool(torch.isfinite(got).all())
+    c = FO.project(s, cfg)
+    x64, x32 = FO.run(s, cfg, 32), FO.run(s, cfg, 32, torch.float32)
+    sc_k, sc_64, sc_32 = (FO.spectral_convergence(x, c, cfg) for x in (got, x64, x32))
+    print("\ncfgA T=%d B=%d %-10s sc_kernel %.6f sc_64 %.6f sc_32 %.6f | waveform max-abs against float64: kernel %.2e, e_ref32 %.2e" %
+          (T, B, name, sc_k, sc_64, sc_32, float((got.double() - x64).abs().max()), float((x32.double() - x64).abs().max())))
+    assert abs(sc_k - sc_64) <= 1e-3 + 10 * abs(sc_32 - sc_64)
+
+
+@pytest.mark.parametrize("tag,T", [("cfgA", 4), ("cfgA", 37), ("cfgB", 59), ("n2048", 19)])
+def test_floor_mel_gives_a_finite_waveform(native, dev, tag, T):
+    cfg = CFGS[tag]
+    plan, blob = native(cfg)
+    out = plan.forward(blob, FO.logmel("floor", cfg, T).to(dev), 32)
+    assert tuple(out.shape) == (MO.ROWS, cfg[3] * (T - 1)) and bool(torch.isfinite(out).all())
+
+
+@pytest.mark.parametrize("tag,T", [("cfgA", 5), ("cfgA", 37), ("cfgB", 59), ("n256", 21)])
+@pytest.mark.parametrize("name", ["speechlike", "noise"])
+def test_rows_do_not_depend_on_the_batch_and_runs_repeat(native, dev, name, tag, T):
+    cfg = CFGS[tag]
+    plan, blob = native(cfg)
+    s = FO.logmel(name, cfg, T).to(dev)
+    together = plan.forward(blob, s, 32)
+    assert torch.equal(plan.forward(blob, s, 32), together)
+    for b in range(MO.ROWS):
+        assert torch.equal(plan.forward(blob, s[b:b + 1], 32), together[b:b + 1])
+    assert torch.equal(plan.forward(blob, s.flip(0), 32), together.flip(0))
+
+
+def test_the_module_runs_the_kernels_and_follows_its_matrix(S, U, native, dev):
+    cfg, T = FO.CFGA, 37
+    plan, blob = native(cfg)
+    s = FO.logmel("noise", cfg, T).to(dev)
+    g = U.FastGL(cfg[1], cfg[2], cfg[0], cfg[3]).cuda()
+    for n in (0, 3, 32):
+        assert torch.equal(g(s, n_iters=n), plan.forward(blob, s, n).unsqueeze(1))
+    assert torch.equal(g(s), plan.forward(blob, s, 32).unsqueeze(1))
+    key = ((cfg[0], cfg[1], cfg[3], 0.99), str(s.device))
+    held = U._blobs[key][2].data_ptr()
+    g(s, n_iters=1)
+    assert U._blobs[key][2].data_ptr() == held and U._plans[key[0]] is not None    # cached: nothing is packed again
+    # inputs that are not contiguous float32 on the kernel path: converted, never misread
+    strided = s.transpose(1, 2).contiguous().transpose(1, 2)
+    assert not strided.is_contiguous() and torch.equal(g(strided, n_iters=2), g(s, n_iters=2))
+    # a replaced pseudo-inverse is packed again and used
+    sd = {k: v.clone() for k, v in g.state_dict().items()}
+    sd["pi.mel_basis_inverse"] = sd["pi.mel_basis_inverse"] * 0.5
+    g.load_state_dict(sd, strict=True)
+    half = plan.pack(FO.basis64(cfg)[1].float() * 0.5, dev)
+    assert torch.equal(g(s, n_iters=2), plan.forward(half, s, 2).unsqueeze(1))
+    assert torch.equal(g(s, n_iters=0), 0.5 * plan.forward(blob, s, 0).unsqueeze(1))      # x0 is linear in the matrix; 0.5 is exact
+    # the sub-modules on their own, on the device
+    c = g.pi(s)
+    assert c.is_cuda and tuple(c.shape) == (MO.ROWS, 513, T) and tuple(g.ir(c).shape) == (MO.ROWS, 1, 256 * (T - 1))
+    # float64 on the device takes the torch recipe there
+    assert g(s.double(), n_iters=1).dtype == torch.float64
+    with pytest.raises(RuntimeError, match="smallest T is 4"):
+        g(s[:, :, :3])
+    with pytest.raises(RuntimeError, match="at least 4 frames"):
+        plan.forward(blob, s[:, :, :3].contiguous(), 1)
