@@ -566,6 +566,66 @@ int gtts_fgl_step(const gtts_fgl *fgl, const void *packed, const float *c, const
 int gtts_fgl_forward(const gtts_fgl *fgl, const void *packed, const float *logmel, float *wav, void *workspace, size_t workspace_bytes,
                      int B, int T, int n_iters, gtts_stream_t stream);
 
+/* ---- ABI 6 (additive): waveform front end of the DiffVC speaker encoder, waveform -> what gtts_spk_forward takes in: the batch functions of
+ * DiffVC/speaker_encoder/encoder/audio.py (preprocess_wav_batch :50-58, wav_to_mel_spectrogram_batch :76-89, normalize_volume_batch
+ * :101-114) on csrc/wav.hip -----------------------------------------------------------------------------------------------------------
+ * Resample = torchaudio.transforms.Resample(source_sr, sampling_rate) with its defaults (sinc_interp_hann): with g = gcd of the rates,
+ *   o = source_sr / g, n = sampling_rate / g, base = min(o, n) rolloff, w = ceil(lowpass_filter_width o / base), phase p in [0, n) and
+ *   tap j in [0, 2 w + o):  t = clamp((-p / n + (j - w) / o) base, -lpw, lpw),
+ *   k[p][j] = (base / o) cos^2(t pi / (2 lpw)) sinc(t)  (float64, rounded to fp32);  each row is zero-padded by w on the left and w + o
+ *   on the right;  out[q n + p] = sum_j k[p][j] xpad[q o + j], cut to gtts_wav_resampled_length(L) = ceil(n L / o) samples.  Taps on
+ *   the clamp (1e-49 in float64, 0 in fp32) are left out: gtts_wav_span taps per phase remain, summed in ascending j.
+ *   partials [B][gtts_wav_tiles(L')] receives the sum of out^2 over every tile of 1024 output samples.
+ * Normalise: change = target_dBFS - 10 log10(mean(x^2)); gain = 10^(change / 20) where change > 0 (mode 1, increase only) or change < 0
+ *   (mode 2, decrease only), else exactly 1 (mode 0: always); out = wav * gain (out may be wav).  An all-zero row gives 0 * inf = NaN
+ *   under mode 1 and stays 0 under modes 0 and 2 (the reference's 1 + mask (gain - 1) makes it NaN in every mode).  partials: the
+ *   resampler's tile sums of THIS wav, or NULL -- the same sums are then formed in workspace (gtts_wav_workspace_bytes(B, L) bytes) by
+ *   one more launch, and the result is the same bit for bit.
+ * Power mel: reflect pad n_fft / 2 (needs L > n_fft / 2), frames of n_fft samples at stride hop_size (T = gtts_wav_frames(L) = 1 + L /
+ *   hop_size), periodic Hann window of n_fft samples, one-sided DFT (unnormalised), re^2 + im^2, librosa's default mel filterbank
+ *   (slaney; float64 -> fp32): out [B,T,n_mels], frame-major.  No sqrt, no epsilon, no log.  One launch, no workspace.
+ * fp32 throughout, tables host float64 -> fp32 (gtts_wav_pack copies them into the caller's blob of gtts_wav_packed_bytes bytes), no
+ * floating-point atomics, every sum in a fixed order: a value depends on its own row alone, never on B or its position in the batch.
+ * Supported (else GTTS_E_CONFIG): o, n <= 1024; 1 <= lowpass_filter_width <= 64; 0 < rolloff <= 1; n_fft even in [64, 1024];
+ * 1 <= hop_size <= n_fft; 1 <= n_mels <= 128; 0 <= fmin < fmax <= sampling_rate / 2.  gtts_wav_resample on a handle with source_sr ==
+ * sampling_rate is GTTS_E_CONFIG.  Refused with GTTS_E_SHAPE before the device is touched: L < 1, L <= n_fft / 2 for the mel, B outside
+ * [1, 65535], B L, B L' or B T n_mels >= 2^31. */
+typedef struct gtts_wav_cfg {
+    int source_sr;              /* 22050 */
+    int sampling_rate;          /* 16000 */
+    int n_fft;                  /* 400   */
+    int hop_size;               /* 160   */
+    int n_mels;                 /* 40    */
+    int lowpass_filter_width;   /* 6     */
+    double rolloff;             /* 0.99  */
+    double fmin;                /* 0     */
+    double fmax;                /* 8000  */
+} gtts_wav_cfg;
+typedef struct gtts_wav gtts_wav;     /* host-side metadata only */
+int gtts_wav_create(const gtts_wav_cfg *cfg, gtts_wav **out);
+void gtts_wav_destroy(gtts_wav *wav);
+/* L' = ceil(n L / o), T = 1 + L / hop_size, tiles of 1024 samples in a row of L -- or GTTS_E_SHAPE */
+int gtts_wav_resampled_length(const gtts_wav *wav, int L);
+int gtts_wav_frames(const gtts_wav *wav, int L);
+int gtts_wav_tiles(const gtts_wav *wav, int L);
+/* host calls, no device is touched: taps kept per phase; first_host [n] = j of every phase's first kept tap, taps_host [n][span] (zeros
+ * behind a phase's last kept tap); the filterbank W [n_mels][n_fft / 2 + 1] */
+int gtts_wav_span(const gtts_wav *wav);
+int gtts_wav_taps(const gtts_wav *wav, int *first_host, float *taps_host);
+int gtts_wav_filterbank(const gtts_wav *wav, float *host_out);
+size_t gtts_wav_packed_bytes(const gtts_wav *wav);
+int gtts_wav_pack(const gtts_wav *wav, void *packed, gtts_stream_t stream);
+/* bytes gtts_wav_normalize needs without partials (0 for a shape it refuses) */
+size_t gtts_wav_workspace_bytes(const gtts_wav *wav, int B, int L);
+/* wav [B,L] -> out [B,L'], partials [B][gtts_wav_tiles(L')] */
+int gtts_wav_resample(const gtts_wav *wav, const void *packed, const float *in, float *out, float *partials, int B, int L,
+                      gtts_stream_t stream);
+/* in [B,L] -> out [B,L] (may alias in); partials [B][gtts_wav_tiles(L)] or NULL (then workspace) */
+int gtts_wav_normalize(const gtts_wav *wav, const float *in, const float *partials, double target_dBFS, int mode, float *out,
+                       void *workspace, size_t workspace_bytes, int B, int L, gtts_stream_t stream);
+/* in [B,L] -> out [B,T,n_mels] */
+int gtts_wav_powmel(const gtts_wav *wav, const void *packed, const float *in, float *out, int B, int L, gtts_stream_t stream);
+
 /* ---- debugging / tests: named intermediates of the last estimator call (keep_intermediates plans) ----- */
 int gtts_plan_num_tensors(const gtts_plan *plan);
 /* offset is in bytes into the workspace for the given (B,T); dims = {B,C,H,W}. */

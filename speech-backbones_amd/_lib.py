@@ -58,6 +58,12 @@ class SpkCfg(ctypes.Structure):
     _fields_ = [("n_mels", ctypes.c_int), ("hidden", ctypes.c_int), ("layers", ctypes.c_int), ("embed", ctypes.c_int)]
 
 
+class WavCfg(ctypes.Structure):
+    _fields_ = [("source_sr", ctypes.c_int), ("sampling_rate", ctypes.c_int), ("n_fft", ctypes.c_int), ("hop_size", ctypes.c_int),
+                ("n_mels", ctypes.c_int), ("lowpass_filter_width", ctypes.c_int), ("rolloff", ctypes.c_double),
+                ("fmin", ctypes.c_double), ("fmax", ctypes.c_double)]
+
+
 class PackItem(ctypes.Structure):           # gtts_pack_item
     _fields_ = [("w", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("kind", ctypes.c_int), ("cin", ctypes.c_int),
                 ("cout", ctypes.c_int), ("transposed", ctypes.c_int)]
@@ -230,6 +236,19 @@ def lib():
         L.gtts_fgl_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_fgl_forward.argtypes = [vp, vp, vp, vp, vp, sz, i, i, i, vp]
         L.gtts_spk_forward.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, sz, vp]
+        L.gtts_wav_create.argtypes = [ctypes.POINTER(WavCfg), ctypes.POINTER(vp)]
+        L.gtts_wav_destroy.argtypes, L.gtts_wav_destroy.restype = [vp], None
+        for op in ("resampled_length", "frames", "tiles"):
+            getattr(L, "gtts_wav_" + op).argtypes = [vp, i]
+        L.gtts_wav_span.argtypes = [vp]
+        L.gtts_wav_taps.argtypes = [vp, vp, vp]
+        L.gtts_wav_filterbank.argtypes = [vp, vp]
+        L.gtts_wav_packed_bytes.argtypes, L.gtts_wav_packed_bytes.restype = [vp], sz
+        L.gtts_wav_pack.argtypes = [vp, vp, vp]
+        L.gtts_wav_workspace_bytes.argtypes, L.gtts_wav_workspace_bytes.restype = [vp, i, i], sz
+        L.gtts_wav_resample.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
+        L.gtts_wav_normalize.argtypes = [vp, vp, vp, ctypes.c_double, i, vp, vp, sz, i, i, vp]
+        L.gtts_wav_powmel.argtypes = [vp, vp, vp, vp, i, i, vp]
         if L.gtts_abi_version() != 6:
             raise RuntimeError("libgradtts_gfx950.so ABI version mismatch")
         _lib = L
@@ -903,6 +922,107 @@ class FglPlan(_Native):
         with _on(s.device):
             self._call("forward", self._h, _ptr(blob), _ptr(s), _ptr(wav), _ptr(ws), ws.numel(), B, T, int(n_iters), _stream())
         return wav
+
+
+class WavPlan(_Native):
+    """Waveform front end of the DiffVC speaker encoder on the HIP kernels (csrc/wav.hip): the batch functions of
+    DiffVC/speaker_encoder/encoder/audio.py -- torchaudio's default Resample, normalize_volume_batch, the 40-band power mel
+    [B, T, n_mels] that SpkPlan.forward reads.  The handle has no parameters: its blob holds the resampling taps, the windowed DFT table
+    and the filterbank, computed on the host in float64."""
+    _family = "wav"
+
+    def __init__(self, source_sr=22050, sampling_rate=16000, n_fft=400, hop_size=160, n_mels=40, lowpass_filter_width=6, rolloff=0.99,
+                 fmin=0.0, fmax=8000.0):
+        kw = dict(source_sr=int(source_sr), sampling_rate=int(sampling_rate), n_fft=int(n_fft), hop_size=int(hop_size),
+                  n_mels=int(n_mels), lowpass_filter_width=int(lowpass_filter_width), rolloff=float(rolloff), fmin=float(fmin),
+                  fmax=float(fmax))
+        self.cfg = WavCfg(*kw.values())
+        self.source_sr, self.sampling_rate, self.n_fft, self.hop_size, self.n_mels = list(kw.values())[:5]
+        self._open(kw, ctypes.byref(self.cfg))
+
+    def _count(self, op, L):
+        v = int(self._fn(op)(self._h, int(L)))
+        if v < 0:
+            _check(v, _sym(self._family, op))
+        return v
+
+    def resampled_length(self, L):
+        """ceil(n L / o) for the reduced rates o -> n; raises on L < 1."""
+        return self._count("resampled_length", L)
+
+    def frames(self, L):
+        """T = 1 + L // hop_size; raises when L <= n_fft / 2 (no reflection)."""
+        return self._count("frames", L)
+
+    def tiles(self, L):
+        """Tile sums of squares per row of L samples (what resample leaves and normalize takes)."""
+        return self._count("tiles", L)
+
+    def taps(self):
+        """(first [n] int32, taps [n, span] fp32) on the CPU: the taps the kernel keeps of every phase (a host call)."""
+        n = self.sampling_rate // math.gcd(self.source_sr, self.sampling_rate)
+        first = torch.empty(n, dtype=torch.int32)
+        taps = torch.empty((n, int(self._fn("span")(self._h))), dtype=torch.float32)
+        self._call("taps", self._h, _ptr(first), _ptr(taps))
+        return first, taps
+
+    def filterbank(self):
+        """W [n_mels, n_fft / 2 + 1] fp32 on the CPU (a host call: no device is touched)."""
+        W = torch.empty((self.n_mels, self.n_fft // 2 + 1), dtype=torch.float32)
+        self._call("filterbank", self._h, _ptr(W))
+        return W
+
+    def pack(self, device):
+        blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
+        if not blob.is_cuda:
+            raise RuntimeError("the waveform front end's tables are packed for a HIP device (got %s)" % blob.device)
+        with torch.cuda.device(blob.device):
+            self._call("pack", self._h, _ptr(blob), _stream())
+            torch.cuda.current_stream().synchronize()
+        return blob
+
+    @staticmethod
+    def _rows(wavs):
+        wavs = _f32c(wavs, "wavs")
+        if wavs.dim() != 2:
+            raise RuntimeError("wavs must be [B, L] (got %s)" % (tuple(wavs.shape),))
+        return wavs, int(wavs.shape[0]), int(wavs.shape[1])
+
+    def resample(self, blob, wavs):
+        """wavs [B, L] at source_sr -> (out [B, resampled_length(L)] at sampling_rate, partials [B, tiles] for normalize); one launch."""
+        wavs, B, L = self._rows(wavs)
+        Lo = self.resampled_length(L)
+        out = torch.empty((B, Lo), dtype=torch.float32, device=wavs.device)
+        partials = torch.empty((B, self.tiles(Lo)), dtype=torch.float32, device=wavs.device)
+        with _on(wavs.device):
+            self._call("resample", self._h, _ptr(blob), _ptr(wavs), _ptr(out), _ptr(partials), B, L, _stream())
+        return out, partials
+
+    def normalize(self, blob, wavs, target_dBFS, increase_only=False, decrease_only=False, partials=None):
+        """normalize_volume_batch: wavs [B, L] -> [B, L].  partials: what resample returned beside THESE wavs (one launch); None: the
+        tile sums are formed first in the cached workspace (two launches, the same bits).  blob is not read (no table is needed)."""
+        if increase_only and decrease_only:
+            raise ValueError("Both increase only and decrease only are set")
+        wavs, B, L = self._rows(wavs)
+        ws = None
+        if partials is None:
+            ws = self._one_workspace((B, L, str(wavs.device)), wavs.device, lambda: max(self.workspace_bytes(B, L), 256))
+        elif (not partials.is_cuda or partials.dtype != torch.float32 or not partials.is_contiguous()
+              or tuple(partials.shape) != (B, self.tiles(L))):
+            raise RuntimeError("partials must be the fp32 [%d, %d] tensor resample returned beside these wavs" % (B, self.tiles(L)))
+        out = torch.empty_like(wavs)
+        with _on(wavs.device):
+            self._call("normalize", self._h, _ptr(wavs), _ptr(partials), float(target_dBFS), 1 if increase_only else 2 if decrease_only else 0,
+                       _ptr(out), _ptr(ws), 0 if ws is None else ws.numel(), B, L, _stream())
+        return out
+
+    def powmel(self, blob, wavs):
+        """wavs [B, L] at sampling_rate -> power mel [B, frames(L), n_mels] in one launch."""
+        wavs, B, L = self._rows(wavs)
+        out = torch.empty((B, self.frames(L), self.n_mels), dtype=torch.float32, device=wavs.device)
+        with _on(wavs.device):
+            self._call("powmel", self._h, _ptr(blob), _ptr(wavs), _ptr(out), B, L, _stream())
+        return out
 
 
 class SpkPlan(_Native):

@@ -1,5 +1,7 @@
 // kernels.h -- host-visible launchers of every kernel in libgradtts_gfx950 (internal header).
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 namespace gtts {
@@ -152,6 +154,10 @@ hipError_t launch_pack_attn_kv(const float *wqkv, unsigned char *dst, int C, hip
 hipError_t launch_wgrad_reduce(const float *part, const float *dbpart, float *dw, float *db, int cin, int cout, int nslice, int taps,
                                hipStream_t st);
 hipError_t launch_copy_f32(const float *src, float *dst, size_t n, hipStream_t st);
+
+// ---- mel.hip
+// librosa's default mel filterbank (slaney scale and normalisation), host float64 -> fp32 [n_mels][n_fft / 2 + 1]; mel.hip and wav.hip
+void slaney_filterbank(int sampling_rate, int n_fft, int n_mels, double fmin, double fmax, std::vector<float> &fb);
 
 // ---- glue.hip (generate_path + aligned prior mean + terminal sample: tts.py:84-94, utils.py:26-39)
 hipError_t launch_expand_alignment(const float *dur, const float *x_mask, const int *y_len, const float *mu_x,

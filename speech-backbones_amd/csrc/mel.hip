@@ -228,21 +228,27 @@ namespace {
 double hz_to_mel(double f) { return f < 1000.0 ? f / (200.0 / 3.0) : 15.0 + std::log(f / 1000.0) / (std::log(6.4) / 27.0); }
 double mel_to_hz(double m) { return m < 15.0 ? m * (200.0 / 3.0) : 1000.0 * std::exp((std::log(6.4) / 27.0) * (m - 15.0)); }
 
-void mel_filterbank(const gtts_mel_cfg &c, std::vector<float> &fb) {
-    const int nb = c.n_fft / 2 + 1, nm = c.num_mels;
+}  // namespace
+
+// librosa.filters.mel with its defaults (slaney scale, slaney area normalisation) in float64, rounded to fp32: fb [nm][n_fft / 2 + 1].
+// Edges and bin frequencies are formed as numpy.linspace forms them.  Shared with wav.hip.
+void gtts::slaney_filterbank(int sampling_rate, int n_fft, int nm, double fmin, double fmax, std::vector<float> &fb) {
+    const int nb = n_fft / 2 + 1;
     std::vector<double> f(nm + 2);
-    const double lo = hz_to_mel(c.fmin), hi = hz_to_mel(c.fmax), step = (hi - lo) / (nm + 1);
+    const double lo = hz_to_mel(fmin), hi = hz_to_mel(fmax), step = (hi - lo) / (nm + 1);
     for (int j = 0; j < nm + 2; ++j) f[j] = mel_to_hz(j == nm + 1 ? hi : lo + step * j);
-    const double fstep = (0.5 * c.sampling_rate) / (nb - 1);
+    const double fstep = (0.5 * sampling_rate) / (nb - 1);
     fb.assign((size_t)nm * nb, 0.f);
     for (int i = 0; i < nm; ++i)
         for (int k = 0; k < nb; ++k) {
-            const double fk = k == nb - 1 ? 0.5 * c.sampling_rate : fstep * k;
+            const double fk = k == nb - 1 ? 0.5 * sampling_rate : fstep * k;
             const double lower = (fk - f[i]) / (f[i + 1] - f[i]), upper = (f[i + 2] - fk) / (f[i + 2] - f[i + 1]);
             const double w = std::fmax(0.0, std::fmin(lower, upper)) * (2.0 / (f[i + 2] - f[i]));
             fb[(size_t)i * nb + k] = (float)w;
         }
 }
+
+namespace {
 
 template <int LOGN>
 hipError_t mel_launch(const MelArgs &a, size_t smem, hipStream_t st) {
@@ -278,7 +284,7 @@ extern "C" int gtts_mel_create(const gtts_mel_cfg *cfg, gtts_mel **out) {
     m->logn = logn;
     m->pad = (c.n_fft - c.hop_size) / 2;
     const int N = c.n_fft, M = N / 2, nb = M + 1;
-    mel_filterbank(c, m->fb);
+    slaney_filterbank(c.sampling_rate, c.n_fft, c.num_mels, c.fmin, c.fmax, m->fb);
     // rows: support [k0, k1) of every filter, its weights padded with zeros to whole chunks of four
     std::vector<int> rows(4 * (size_t)c.num_mels, 0);
     std::vector<float> wts;
