@@ -521,6 +521,41 @@ size_t gtts_spk_workspace_bytes(const gtts_spk *spk, int N, int T);
 int gtts_spk_forward(const gtts_spk *spk, const void *packed, const float *frames, int U, int T_total, int P, int S, int T, float *embeds,
                      float *hidden_out, float *utt_embeds, void *workspace, size_t workspace_bytes, gtts_stream_t stream);
 
+/* ---- ABI 6 (additive): training of the speaker encoder (DiffVC/speaker_encoder/encoder/train.py, model.py:35-137) on csrc/spk_train.hip --
+ * fp32 on the same MFMA; every reduction runs in a fixed order and nothing is accumulated with atomics: a call repeated gives the same bits.
+ * gtts_spktrain_forward is gtts_spk_forward (P = 1, S = 0, T = T_total; the blob of gtts_spk_pack) keeping what the backward needs in the
+ * caller's `saved` buffer of gtts_spktrain_saved_bytes(N, T) bytes: per layer the activated gates [N T][4 hidden], the cell states and the
+ * hidden sequence [N T][hidden] each, then h_T [N][hidden] and the head before its L2 norm [N][embed], every part rounded up to 256 bytes
+ * (layers 6 N T hidden 4 bytes and a little: 1 888 747 520 bytes at N = 640, T = 160).  Its embeds equal gtts_spk_forward's bit for bit.
+ * gtts_spktrain_backward takes d_embeds [N][embed], the same frames, the saved buffer (which it CONSUMES: the gate gradients are written over
+ * the gates, so one backward per forward), the blob of gtts_spktrain_pack (gtts_spktrain_packed_bytes bytes: W_hh^T and W_ih^T in MFMA
+ * fragment order, linear.weight; the same parameter pointers as gtts_spk_pack) and a workspace of gtts_spktrain_workspace_bytes(N, T)
+ * bytes, and writes one gradient per parameter through grads[i], i in gtts_spk_param_info order, each of the parameter's shape
+ * (bias_ih and bias_hh receive the same values).  There is no gradient for the frames.  Per layer, top down: one persistent recurrence
+ * launch (a workgroup per 16 sequences walking t = T - 1 ... 0; no workgroup waits on another), the data gradient dZ W_ih for the layer
+ * below, and the weight gradients dZ^T [X | H_prev] over slices of the N T rows (at least 256 rows a slice, at most 16 slices) added in
+ * ascending order.  Refused on the host before any launch: null arguments GTTS_E_NULL, a gradient count other than the parameter count
+ * GTTS_E_PARAMS, N or T < 1 or N T 4 hidden >= 2^31 GTTS_E_SHAPE, a short saved buffer or workspace GTTS_E_WORKSPACE; the three size
+ * functions return 0 for a null handle or a refused shape. */
+size_t gtts_spktrain_packed_bytes(const gtts_spk *spk);
+size_t gtts_spktrain_saved_bytes(const gtts_spk *spk, int N, int T);
+size_t gtts_spktrain_workspace_bytes(const gtts_spk *spk, int N, int T);
+int gtts_spktrain_pack(const gtts_spk *spk, const void *const *param_ptrs, int n_params, void *packed_train, gtts_stream_t stream);
+int gtts_spktrain_forward(const gtts_spk *spk, const void *packed, const float *frames, int N, int T, float *embeds, void *saved,
+                           size_t saved_bytes, gtts_stream_t stream);
+int gtts_spktrain_backward(const gtts_spk *spk, const void *packed_train, const float *frames, const float *d_embeds, void *saved,
+                      size_t saved_bytes, float *const *grads, int n_grads, void *workspace, size_t workspace_bytes, int N, int T,
+                      gtts_stream_t stream);
+/* GE2E loss of embeds [S][U][E] (model.py:65-126): inclusive centroids (mean over U, normalised), exclusive centroids ((sum - e) / (U - 1),
+ * normalised), sim[s u][j] = w <e_su, centroid_j> + b with the exclusive centroid of (s, u) where j = s, loss = the mean cross-entropy of
+ * the S U rows against their speaker.  w, b: device scalars.  Outputs: sim [S U][S], loss [1], and -- each nullable -- d_embeds [S][U][E],
+ * dw [1], db [1] for a loss gradient of 1.  No epsilon; U = 1 is not special-cased (0 / 0 = NaN, as in the reference).  One launch of one
+ * workgroup; workspace of gtts_ge2e_workspace_bytes(S, U, E) bytes (0 for a refused shape).  GTTS_E_SHAPE: S, U or E < 1, S > 1024, or
+ * S U max(S, E) >= 2^31. */
+size_t gtts_ge2e_workspace_bytes(int S, int U, int E);
+int gtts_ge2e_loss(const float *embeds, const float *w, const float *b, int S, int U, int E, float *sim, float *loss, float *d_embeds,
+                   float *dw, float *db, void *workspace, size_t workspace_bytes, gtts_stream_t stream);
+
 /* ---- ABI 6 (additive): Fast Griffin-Lim, log-mel -> waveform without a vocoder checkpoint: FastGL / PseudoInversion /
  * InitialReconstruction of DiffVC/model/utils.py:42-110 on csrc/fgl.hip -------------------------------------------------------------
  * K = n_fft / 2 + 1, w = the periodic Hann window of n_fft samples (win_length = n_fft), m = momentum, L = hop_size (T - 1).

@@ -236,6 +236,15 @@ def lib():
         L.gtts_fgl_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_fgl_forward.argtypes = [vp, vp, vp, vp, vp, sz, i, i, i, vp]
         L.gtts_spk_forward.argtypes = [vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, sz, vp]
+        L.gtts_spktrain_packed_bytes.argtypes, L.gtts_spktrain_packed_bytes.restype = [vp], sz
+        for op in ("saved_bytes", "workspace_bytes"):
+            fn = getattr(L, "gtts_spktrain_" + op)
+            fn.argtypes, fn.restype = [vp, i, i], sz
+        L.gtts_spktrain_pack.argtypes = [vp, ctypes.POINTER(vp), i, vp, vp]
+        L.gtts_spktrain_forward.argtypes = [vp, vp, vp, i, i, vp, vp, sz, vp]
+        L.gtts_spktrain_backward.argtypes = [vp, vp, vp, vp, vp, sz, ctypes.POINTER(vp), i, vp, sz, i, i, vp]
+        L.gtts_ge2e_workspace_bytes.argtypes, L.gtts_ge2e_workspace_bytes.restype = [i, i, i], sz
+        L.gtts_ge2e_loss.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, sz, vp]
         L.gtts_wav_create.argtypes = [ctypes.POINTER(WavCfg), ctypes.POINTER(vp)]
         L.gtts_wav_destroy.argtypes, L.gtts_wav_destroy.restype = [vp], None
         for op in ("resampled_length", "frames", "tiles"):
@@ -1058,6 +1067,91 @@ class SpkPlan(_Native):
                        _ptr(ws), ws.numel(), _stream())
         out = [embeds] + ([hidden] if want_hidden else []) + ([utt] if want_utt else [])
         return out[0] if len(out) == 1 else tuple(out)
+
+    # ---- training (csrc/spk_train.hip)
+    def pack_train(self, state, device):
+        """The weights in the orders the backward reads (W_hh^T and W_ih^T as MFMA fragments, linear.weight): a blob of its own beside
+        pack()'s, from the same state."""
+        keep, arr = self._params(state, device)
+        blob = torch.empty(int(lib().gtts_spktrain_packed_bytes(self._h)), dtype=torch.uint8, device=device)
+        with torch.cuda.device(blob.device):
+            _check(lib().gtts_spktrain_pack(self._h, arr, len(keep), _ptr(blob), _stream()), "gtts_spktrain_pack")
+            torch.cuda.current_stream().synchronize()     # sources in `keep` may be temporaries
+        return blob
+
+    def saved_bytes(self, N, T):
+        return int(lib().gtts_spktrain_saved_bytes(self._h, int(N), int(T)))
+
+    def train_workspace_bytes(self, N, T):
+        return int(lib().gtts_spktrain_workspace_bytes(self._h, int(N), int(T)))
+
+    def forward_train(self, blob, frames):
+        """frames [N, T, n_mels] -> (embeds [N, embed], saved): the embeddings of forward(), bit for bit, and the uint8 tensor of
+        saved_bytes(N, T) bytes that backward() takes (gates, cell states and hidden sequences of every layer, h_T, the head before
+        its norm).  No workspace: every intermediate is part of `saved`."""
+        frames = _f32c(frames, "frames")
+        if frames.dim() != 3 or frames.shape[2] != self.n_mels:
+            raise RuntimeError("frames must be [N, T, %d] (got %s)" % (self.n_mels, tuple(frames.shape)))
+        N, T, _ = frames.shape
+        dev = frames.device
+        embeds = torch.empty((N, self.embed), dtype=torch.float32, device=dev)
+        saved = torch.empty(max(self.saved_bytes(N, T) if N > 0 and T > 0 else 0, 256), dtype=torch.uint8, device=dev)
+        with _on(dev):
+            _check(lib().gtts_spktrain_forward(self._h, _ptr(blob), _ptr(frames), N, T, _ptr(embeds), _ptr(saved), saved.numel(),
+                                                _stream()), "gtts_spktrain_forward")
+        return embeds, saved
+
+    def backward(self, blob_train, frames, d_embeds, saved):
+        """The gradients of every parameter, in param_layout() order and of the parameters' shapes, for the upstream d_embeds [N, embed].
+        `saved` comes from forward_train on the same frames and is consumed (the gate gradients are written over the gates)."""
+        frames, d_embeds = _f32c(frames, "frames"), _f32c(d_embeds, "d_embeds")
+        N, T, _ = frames.shape
+        dev = frames.device
+        if tuple(d_embeds.shape) != (N, self.embed):
+            raise RuntimeError("d_embeds must be [%d, %d] (got %s)" % (N, self.embed, tuple(d_embeds.shape)))
+        grads = [torch.empty(shape, dtype=torch.float32, device=dev) for _, shape in self.param_layout()]
+        arr = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        nbytes = self.train_workspace_bytes(N, T) if N > 0 and T > 0 else 0
+        cache = self.__dict__.setdefault("_ws_train", {})      # beside forward()'s workspace: a training loop alternates the two
+        ws = cache.get((N, T, str(dev)))
+        if ws is None:
+            cache.clear()
+            ws = cache[(N, T, str(dev))] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        with _on(dev):
+            _check(lib().gtts_spktrain_backward(self._h, _ptr(blob_train), _ptr(frames), _ptr(d_embeds), _ptr(saved), saved.numel(), arr,
+                                           len(grads), _ptr(ws), ws.numel(), N, T, _stream()), "gtts_spktrain_backward")
+        return grads
+
+
+_GE2E_WS = {}       # the single live workspace of ge2e_loss: {(S, U, E, str(device)): uint8 tensor}
+
+
+def ge2e_loss(embeds, w, b, want_grad=True):
+    """GE2E similarity matrix, loss and gradient in one launch (csrc/spk_train.hip).  embeds [S, U, E], w and b one-element tensors on
+    the same HIP device -> (sim [S * U, S], loss [1], d_embeds [S, U, E], dw [1], db [1]) for a loss gradient of 1; with
+    want_grad=False the three gradients are None and their phases are skipped."""
+    embeds, w, b = _f32c(embeds, "embeds"), _f32c(w, "w"), _f32c(b, "b")
+    if embeds.dim() != 3:
+        raise RuntimeError("embeds must be [speakers, utterances, embed] (got %s)" % (tuple(embeds.shape),))
+    if w.numel() != 1 or b.numel() != 1 or w.device != embeds.device or b.device != embeds.device:
+        raise RuntimeError("w and b must be one-element tensors on %s" % embeds.device)
+    S, U, E = embeds.shape
+    dev = embeds.device
+    key = (S, U, E, str(dev))
+    ws = _GE2E_WS.get(key)
+    if ws is None:
+        _GE2E_WS.clear()
+        ws = torch.empty(max(int(lib().gtts_ge2e_workspace_bytes(S, U, E)), 256), dtype=torch.uint8, device=dev)
+        _GE2E_WS[key] = ws
+    sim = torch.empty((S * U, S), dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    d_embeds = torch.empty_like(embeds) if want_grad else None
+    dw = torch.empty(1, dtype=torch.float32, device=dev) if want_grad else None
+    db = torch.empty(1, dtype=torch.float32, device=dev) if want_grad else None
+    with _on(dev):
+        _check(lib().gtts_ge2e_loss(_ptr(embeds), _ptr(w), _ptr(b), S, U, E, _ptr(sim), _ptr(loss), _ptr(d_embeds), _ptr(dw), _ptr(db),
+                                    _ptr(ws), ws.numel(), _stream()), "gtts_ge2e_loss")
+    return sim, loss, d_embeds, dw, db
 
 
 def euler_step(xt, mu, est, mask, beta_t, h, noise=None):

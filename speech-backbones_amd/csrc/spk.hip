@@ -24,17 +24,9 @@
 #include "../../include/gradtts_abi.h"
 #include "common.h"
 #include "kernels.h"
+#include "spk.h"
 
 namespace gtts {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-constexpr int SPK_H = 256;          // hidden size the recurrence kernel is built for
-constexpr int SPK_G = 4 * SPK_H;    // gate rows
-constexpr int SPK_TILE = 16;        // sequences per workgroup (the MFMA's column count)
-constexpr int SPK_WAVES = 8;        // waves per recurrence workgroup; each owns SPK_H / SPK_WAVES = 32 hidden units (8 row tiles)
-constexpr int SPK_HS = SPK_H + 4;   // LDS row stride of h in floats: rows 16 bytes apart in the banks
-constexpr int SPK_KB = SPK_H / 16;  // 16-wide k blocks of the recurrent product
 
 // ---- weight packing: a [rows][K] row-major matrix -> MFMA A fragments.  Tile = 16 rows, k block = 16 columns; lane l of a fragment
 // holds the four values W[row0 + (l & 15)][16 kb + 4 (l >> 4) + j], j = 0..3 -- the A operand of the block's four k steps (the k order
@@ -65,15 +57,6 @@ __global__ void spk_pack_misc_kernel(const float *a, const float *b, float *dst,
 // ---- input projection: G [M][4H] = X [M][K] W_ih^T + bias, M = N * T rows.  Workgroup: 4 waves, wave w = rows 16 (4 bx + w) ... of M
 // against 8 row tiles (128 gate rows, blockIdx.y).  Computed transposed (A = W_ih fragment, B = X^T) so that a lane ends up with four
 // consecutive gate rows of ONE row of M: a 16-byte store.
-struct SpkProjArgs {
-    const float4 *wih;      // packed fragments [64 tiles][KB][64]
-    const float *bias;      // [4H] b_ih + b_hh
-    const float *x;         // layer 0: frames [U][T_total][K];  above: hseq [M][K]
-    float *G;               // [M][4H]
-    int M, T, K, KB;
-    int sliced, P, S, T_total;
-};
-
 __global__ __launch_bounds__(256) void spk_proj_kernel(SpkProjArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sq = lane & 15, q = lane >> 4;
     const int m = (blockIdx.x * 4 + wave) * 16 + sq;
@@ -114,17 +97,11 @@ __global__ __launch_bounds__(256) void spk_proj_kernel(SpkProjArgs a) {
     }
 }
 
-// ---- the recurrence of one layer
-struct SpkRecArgs {
-    const float4 *whh;      // packed fragments [16 unit groups][4 gates][SPK_KB][64]
-    const float *G;         // [N][T][4H]
-    float *hseq;            // [N][T][H] or nullptr (last layer)
-    float *hlast;           // [N][H] or nullptr
-    int N, T;
-};
-
+// ---- the recurrence of one layer.  SAVE (training forward, spk_train.hip): the activated gates overwrite G and c_t goes to a.C;
+// the arithmetic is the same, so both instances give the same bits.
 __device__ __forceinline__ float spk_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
+template <bool SAVE>
 __global__ __launch_bounds__(64 * SPK_WAVES) void spk_rec_kernel(SpkRecArgs a) {
     __shared__ __attribute__((aligned(16))) float hs[2][SPK_TILE][SPK_HS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sq = lane & 15, q = lane >> 4;
@@ -175,14 +152,24 @@ __global__ __launch_bounds__(64 * SPK_WAVES) void spk_rec_kernel(SpkRecArgs a) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             f32x4 h;
+            [[maybe_unused]] f32x4 act[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float gi = spk_sigmoid(acc[4 * u + 0][r]), gf = spk_sigmoid(acc[4 * u + 1][r]);
                 const float gg = tanhf(acc[4 * u + 2][r]), go = spk_sigmoid(acc[4 * u + 3][r]);
                 c[u][r] = fmaf(gf, c[u][r], gi * gg);
                 h[r] = go * tanhf(c[u][r]);
+                if constexpr (SAVE) { act[0][r] = gi; act[1][r] = gf; act[2][r] = gg; act[3][r] = go; }
             }
             const int unit = (wave * 2 + u) * 16 + q * 4;
+            if constexpr (SAVE) {
+                if (valid) {
+                    float *ga = a.G + (row + t) * SPK_G + unit;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4 *>(ga + k * SPK_H) = act[k];
+                    *reinterpret_cast<f32x4 *>(a.C + (row + t) * SPK_H + unit) = f32x4{c[u][0], c[u][1], c[u][2], c[u][3]};
+                }
+            }
             *reinterpret_cast<f32x4 *>(&hs[p ^ 1][sq][unit]) = h;
             if (valid) {
                 if (a.hseq) *reinterpret_cast<f32x4 *>(a.hseq + (row + t) * SPK_H + unit) = h;
@@ -208,7 +195,7 @@ __device__ __forceinline__ float spk_block_sum(float v, float *red) {
     return r;
 }
 
-__global__ __launch_bounds__(256) void spk_head_kernel(const float *hlast, const float *wt, const float *bias, float *embeds, int H, int E) {
+__global__ __launch_bounds__(256) void spk_head_kernel(const float *hlast, const float *wt, const float *bias, float *embeds, float *raw, int H, int E) {
     __shared__ float hsh[SPK_H];
     __shared__ float red[256];
     const int n = blockIdx.x, tid = threadIdx.x;
@@ -221,6 +208,7 @@ __global__ __launch_bounds__(256) void spk_head_kernel(const float *hlast, const
         for (int k = 0; k < H; ++k) acc = fmaf(wt[(size_t)k * E + j], hsh[k], acc);
         acc = fmaxf(acc + bias[j], 0.f);
         out[j] = acc;
+        if (raw) raw[(size_t)n * E + j] = acc;                          // training: the un-normalised head output
         ss = fmaf(acc, acc, ss);
     }
     const float norm = sqrtf(spk_block_sum(ss, red));
@@ -244,24 +232,25 @@ __global__ __launch_bounds__(256) void spk_utt_kernel(const float *embeds, float
     for (int j = tid; j < E; j += 256) out[j] = out[j] / norm;
 }
 
+// launchers shared with the training entry points (spk_train.hip)
+hipError_t spk_launch_proj(const SpkProjArgs &pa, hipStream_t st) {
+    hipLaunchKernelGGL(spk_proj_kernel, dim3((unsigned)((pa.M + 63) / 64), SPK_G / 128), dim3(256), 0, st, pa);
+    return hipGetLastError();
+}
+hipError_t spk_launch_rec(const SpkRecArgs &ra, bool save, hipStream_t st) {
+    const dim3 grid((unsigned)((ra.N + SPK_TILE - 1) / SPK_TILE)), block(64 * SPK_WAVES);
+    if (save) hipLaunchKernelGGL(spk_rec_kernel<true>, grid, block, 0, st, ra);
+    else hipLaunchKernelGGL(spk_rec_kernel<false>, grid, block, 0, st, ra);
+    return hipGetLastError();
+}
+hipError_t spk_launch_head(const float *hlast, const float *wt, const float *bias, float *embeds, float *raw, int N, int H, int E, hipStream_t st) {
+    hipLaunchKernelGGL(spk_head_kernel, dim3((unsigned)N), dim3(256), 0, st, hlast, wt, bias, embeds, raw, H, E);
+    return hipGetLastError();
+}
+
 }  // namespace gtts
 
 using namespace gtts;
-
-struct SpkParam {
-    std::string name;
-    int rank;
-    int dims[4];
-};
-
-// host-side metadata: configuration, state_dict layout, offsets into the packed blob
-struct gtts_spk {
-    gtts_spk_cfg cfg;
-    std::vector<SpkParam> params;
-    std::vector<int> kb;                        // k blocks of each layer's input projection
-    std::vector<size_t> off_wih, off_whh, off_bias;
-    size_t off_lin_wt, off_lin_b, blob_bytes;
-};
 
 extern "C" int gtts_spk_create(const gtts_spk_cfg *cfg, gtts_spk **out) {
     if (!cfg || !out) return fail(GTTS_E_NULL, "gtts_spk_create: null argument");
@@ -342,7 +331,7 @@ extern "C" int gtts_spk_pack(const gtts_spk *s, const void *const *ptrs, int n, 
 }
 
 // workspace: G [N T][4H], hseq [N T][H] (layers below the last), hlast [N][H]
-static bool spk_shape_ok(int N, int T) { return N >= 1 && T >= 1 && (size_t)N * (size_t)T * SPK_G < ((size_t)1 << 31); }
+bool gtts::spk_shape_ok(int N, int T) { return N >= 1 && T >= 1 && (size_t)N * (size_t)T * SPK_G < ((size_t)1 << 31); }
 static size_t spk_ws(const gtts_spk *s, int N, int T, size_t off[3]) {
     const size_t rows = (size_t)N * T;
     off[0] = 0;
@@ -382,18 +371,14 @@ extern "C" int gtts_spk_forward(const gtts_spk *s, const void *packed, const flo
         pa.x = l == 0 ? frames : hseq; pa.G = G;
         pa.M = M; pa.T = T; pa.K = l == 0 ? s->cfg.n_mels : H; pa.KB = s->kb[l];
         pa.sliced = l == 0; pa.P = P; pa.S = S; pa.T_total = T_total;
-        hipLaunchKernelGGL(spk_proj_kernel, dim3((unsigned)((M + 63) / 64), SPK_G / 128), dim3(256), 0, st, pa);
-        GTTS_HIPCHK(hipGetLastError());
+        GTTS_HIPCHK(spk_launch_proj(pa, st));
         SpkRecArgs ra;
-        ra.whh = (const float4 *)(blob + s->off_whh[l]); ra.G = G;
+        ra.whh = (const float4 *)(blob + s->off_whh[l]); ra.G = G; ra.C = nullptr;
         ra.hseq = l + 1 < L ? hseq : nullptr; ra.hlast = l + 1 == L ? hlast : nullptr;
         ra.N = N; ra.T = T;
-        hipLaunchKernelGGL(spk_rec_kernel, dim3((unsigned)((N + SPK_TILE - 1) / SPK_TILE)), dim3(64 * SPK_WAVES), 0, st, ra);
-        GTTS_HIPCHK(hipGetLastError());
+        GTTS_HIPCHK(spk_launch_rec(ra, false, st));
     }
-    hipLaunchKernelGGL(spk_head_kernel, dim3((unsigned)N), dim3(256), 0, st, (const float *)hlast, (const float *)(blob + s->off_lin_wt),
-                       (const float *)(blob + s->off_lin_b), embeds, H, E);
-    GTTS_HIPCHK(hipGetLastError());
+    GTTS_HIPCHK(spk_launch_head(hlast, (const float *)(blob + s->off_lin_wt), (const float *)(blob + s->off_lin_b), embeds, nullptr, N, H, E, st));
     if (utt_embeds) {
         hipLaunchKernelGGL(spk_utt_kernel, dim3((unsigned)U), dim3(256), 0, st, (const float *)embeds, utt_embeds, P, E);
         GTTS_HIPCHK(hipGetLastError());

@@ -1,0 +1,194 @@
+"""GPU tests (-m gpu) of the speaker encoder's training kernels (csrc/spk_train.hip) through SpkPlan.forward_train / backward, ge2e_loss
+and the drop-in diffvc/speaker_encoder/encoder/ge2e.py, against the float64 restatements of tests/ge2e_oracle.py.
+
+Bound on every tensor: e = max |got - g64| / max |g64| must satisfy e <= 4 e_ref32 + 2e-6 and e <= 1e-3, e_ref32 being the same recipe
+in float32 torch on the CPU -- factor, floor and cap of tests/test_gpu_spk.py on the normalised error.  similarity_bias.grad is
+analytically zero and is checked as |db| <= 1e-5.  With -s every (case, tensor) prints e, e_ref32 and their ratio.
+
+ReLU kink: the float64 oracle takes its ReLU mask from the HIP forward (embeds > 0); the two masks may differ only where the float64
+pre-activation lies within 1e-5 of zero (tests/test_ge2e_cpu.py proves at most 8 such units per case).
+
+Shapes of the encoder backward: (1, 1) is t = 0 alone (dW_hh = 0 exactly), (17, 160) crosses the sequence tile of 16, (40, 160) is three
+tiles; the weight gradient adds slices of max(256, ceil(N T / 16) rounded up to 16) rows of N T, so (1, 257) and (2, 129) are the two
+smallest shapes with more than one slice and a ragged last one (1 and 2 rows), and (40, 160) runs 16 full slices of 400."""
+import importlib
+
+import pytest
+import torch
+
+import ge2e_oracle as GO
+import spk_oracle as SO
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def S():
+    assert torch.cuda.is_available()
+    return importlib.import_module("speech-backbones_amd")
+
+
+@pytest.fixture(scope="module")
+def G():
+    return importlib.import_module("speech-backbones_amd.diffvc.speaker_encoder.encoder.ge2e")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def plans(S, dev):
+    """weights -> (plan, inference blob, training blob), made once per weight kind."""
+    made = {}
+
+    def get(weights):
+        if weights not in made:
+            plan = S.SpkPlan()
+            made[weights] = (plan, plan.pack(SO.state(weights), dev), plan.pack_train(SO.state(weights), dev))
+        return made[weights]
+    return get
+
+
+def _bounded(case, name, got, g64, e32):
+    assert bool(torch.isfinite(got).all()), (case, name)
+    if float(g64.abs().max()) == 0.0:                       # T = 1: h_{-1} = 0, so dW_hh is zero exactly and there is nothing to normalise by
+        assert float(got.abs().max()) == 0.0, (case, name)
+        print("%-34s %-20s exactly zero, as float64" % (case, name))
+        return
+    e = GO.err(got.cpu(), g64)
+    print("%-34s %-20s e %.2e  e_ref32 %.2e  ratio %.2f" % (case, name, e, e32, e / max(e32, 1e-30)))
+    assert e <= 4 * e32 + 2e-6 and e <= 1e-3, (case, name, e, e32)
+
+
+def _mask_from(embeds, pre64):
+    """The HIP forward's ReLU mask; it may differ from float64's only on units within 1e-5 of the kink."""
+    mask = embeds.detach().cpu() > 0
+    differs = mask != (pre64 > 0)
+    assert bool(GO.near_zero(pre64)[differs].all()), int(differs.sum())
+    return mask
+
+
+# ---- 1. the loss alone
+@pytest.mark.parametrize("S_,U", GO.GE2E_SHAPES)
+@pytest.mark.parametrize("kind", GO.KINDS)
+def test_ge2e_loss_and_gradient(S, G, dev, kind, S_, U):
+    g64, e32 = GO.ge2e_reference(kind, S_, U)
+    e = GO.embeddings(kind, S_, U).to(dev)
+    w, b = torch.tensor([GO.W0], device=dev), torch.tensor([GO.B0], device=dev)
+    sim, loss, d_embeds, dw, db = S.ge2e_loss(e, w, b)
+    assert tuple(sim.shape) == (S_ * U, S_) and tuple(d_embeds.shape) == (S_, U, 256) and loss.numel() == dw.numel() == db.numel() == 1
+    case = "ge2e %s %dx%d" % (kind, S_, U)
+    for name, got in (("sim", sim), ("loss", loss), ("d_embeds", d_embeds), ("dw", dw)):
+        _bounded(case, name, got, g64[name], e32[name])
+    assert abs(float(db)) <= 1e-5
+    # without the gradient outputs: the same matrix and loss
+    sim2, loss2, none1, none2, none3 = S.ge2e_loss(e, w, b, want_grad=False)
+    assert none1 is None and none2 is None and none3 is None and torch.equal(sim2, sim) and torch.equal(loss2, loss)
+    # the module on a HIP loss_device returns the kernel's values and routes its gradients
+    m = G.SpeakerEncoder("cpu", dev)
+    er = e.clone().requires_grad_(True)
+    mloss, eer = m.loss(er)
+    mloss.backward()
+    assert mloss.dim() == 0 and float(mloss) == float(loss) and 0.0 <= eer <= 1.0
+    assert eer == G.equal_error_rate(sim.cpu().numpy(), U)
+    assert torch.equal(m.similarity_matrix(e), sim.view(S_, U, S_))
+    assert torch.equal(er.grad, d_embeds) and torch.equal(m.similarity_weight.grad, dw) and torch.equal(m.similarity_bias.grad, db)
+    assert m.loss(e, want_eer=False)[1] is None
+
+
+# ---- 2. the encoder backward alone
+@pytest.mark.parametrize("N,T", GO.ENC_SHAPES)
+@pytest.mark.parametrize("inputs", SO.INPUTS)
+@pytest.mark.parametrize("weights", SO.WEIGHTS)
+def test_encoder_backward(plans, dev, weights, inputs, N, T):
+    plan, blob, blob_train = plans(weights)
+    x = SO.frames(inputs, N, T).to(dev)
+    embeds, saved = plan.forward_train(blob, x)
+    assert saved.numel() == plan.saved_bytes(N, T)
+    mask = _mask_from(embeds, GO.encoder_reference(weights, inputs, N, T)[2])
+    g64, e32, _ = GO.encoder_reference(weights, inputs, N, T, mask)
+    grads = plan.backward(blob_train, x, GO.upstream(N).to(dev), saved)
+    names = [n for n, _ in plan.param_layout()]
+    assert names == GO.PARAMS and [tuple(g.shape) for g in grads] == [tuple(g64[n].shape) for n in names]
+    case = "enc %s %s %dx%d" % (weights, inputs, N, T)
+    for n, g in zip(names, grads):
+        if T == 1 and "weight_hh" in n:
+            assert float(g.abs().max()) == 0.0 and float(g64[n].abs().max()) == 0.0      # h_{-1} = 0: exactly
+            continue
+        _bounded(case, n, g, g64[n], e32[n])
+    for l in range(3):
+        assert torch.equal(grads[4 * l + 2], grads[4 * l + 3])                             # bias_ih and bias_hh: the same values
+
+
+# ---- 3. the training forward
+def test_training_forward_equals_inference_and_backward_repeats(plans, dev):
+    plan, blob, blob_train = plans("default")
+    x = SO.frames("noise", 17, 160).to(dev)
+    d = GO.upstream(17).to(dev)
+    embeds, saved = plan.forward_train(blob, x)
+    assert torch.equal(embeds, plan.forward(blob, x))
+    first = plan.backward(blob_train, x, d, saved)
+    embeds2, saved2 = plan.forward_train(blob, x)
+    second = plan.backward(blob_train, x, d, saved2)
+    assert torch.equal(embeds2, embeds)
+    for a, b in zip(first, second):
+        assert torch.equal(a, b)
+
+
+# ---- 4. the whole step through the drop-in module
+@pytest.mark.parametrize("S_,U,T", GO.STEP_SHAPES)
+def test_whole_step_through_the_module(S, G, dev, S_, U, T):
+    m = G.SpeakerEncoder(dev, dev)
+    m.load_state_dict(dict(SO.state("trained"), similarity_weight=torch.tensor([GO.W0]), similarity_bias=torch.tensor([GO.B0])))
+    opt = torch.optim.Adam(m.parameters(), lr=1e-4)
+    x = SO.frames("noise", S_ * U, T).to(dev)
+    embeds = m(x)
+    assert embeds.requires_grad and tuple(embeds.shape) == (S_ * U, 256)
+    loss, _ = m.loss(embeds.view(S_, U, -1), want_eer=False)
+    loss.backward()
+    mask = _mask_from(embeds, GO.step_reference(S_, U, T)[2])
+    g64, e32, _, loss64 = GO.step_reference(S_, U, T, mask)
+    assert abs(float(loss) - float(loss64)) <= 1e-3 * abs(float(loss64))
+    case = "step %dx%dx%d" % (S_, U, T)
+    grads = dict((k, p.grad) for k, p in m.named_parameters())
+    assert len(grads) == 16 and all(g is not None for g in grads.values())
+    for k, g in grads.items():
+        if k == "similarity_bias":
+            assert abs(float(g)) <= 1e-5
+        else:
+            _bounded(case, k, g, g64[k], e32[k])
+    # one optimiser step: the next forward, with autograd and without, runs on the new weights
+    with torch.no_grad():
+        before = m(x)
+    assert torch.equal(before, embeds.detach())
+    m.do_gradient_ops()
+    opt.step()
+    with torch.no_grad():
+        after = m(x)
+    plan = S.SpkPlan()
+    fresh = plan.forward(plan.pack(dict(m.named_parameters()), dev), x)
+    assert not torch.equal(after, before) and torch.equal(after, fresh) and torch.equal(m(x).detach(), fresh)
+
+
+# ---- 5. memory
+def test_a_forward_backward_pair_allocates_outputs_and_saved_state_only(plans, dev):
+    """Beyond the packed blobs and the cached workspace: embeds, the saved state and the 14 gradients, nothing transient."""
+    plan, blob, blob_train = plans("default")
+    x = SO.frames("noise", 3, 7).to(dev)
+    d = GO.upstream(3).to(dev)
+    plan.backward(blob_train, x, d, plan.forward_train(blob, x)[1])          # (first call: code object load, workspace)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    before = torch.cuda.memory_allocated(dev)
+    embeds, saved = plan.forward_train(blob, x)
+    grads = plan.backward(blob_train, x, d, saved)
+    torch.cuda.synchronize()
+    rounded = lambda t: (t.numel() * t.element_size() + 511) // 512 * 512     # the caching allocator hands out multiples of 512 bytes
+    want = rounded(embeds) + rounded(saved) + sum(rounded(g) for g in grads)
+    assert saved.numel() == plan.saved_bytes(3, 7)
+    assert torch.cuda.memory_allocated(dev) - before == want
+    assert torch.cuda.max_memory_allocated(dev) - before == want
+    del embeds, saved, grads
+    assert torch.cuda.memory_allocated(dev) == before
