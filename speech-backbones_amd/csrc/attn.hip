@@ -696,8 +696,7 @@ hipError_t launch_attn_merge(const float *partials, float *ctxn, int B, int nrec
     const size_t smem = ((size_t)nrec * 32 + 1024 + 64) * sizeof(float);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     if (smem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&attn_merge_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        const hipError_t e = raise_dyn_lds<&attn_merge_kernel>(smem);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(attn_merge_kernel, dim3(4, B), dim3(1024), smem, st, partials, ctxn, nrec);

@@ -7,10 +7,10 @@
 // Prologue on load: LeakyReLU(slope) (slope 1 = identity, 0 = ReLU), then the [B][L] input mask.  Epilogue: bias, residual,
 // running-sum modes of the HiFi-GAN ResBlocks, output mask.  Layout [B][C][L] fp32, L fastest (coalesced along time).
 #pragma once
-#include <atomic>
 #include <type_traits>
 
 #include "common.h"
+#include "kernels.h"
 
 namespace gtts {
 
@@ -351,17 +351,10 @@ static hipError_t launch_c1_cfg(const C1Args &a, hipStream_t st) {
     const size_t smem = (size_t)2 * 2 * KCH * a.npx * 16 + (size_t)KCH * 2 * TPS * 2 * MT * 16;
     if ((size_t)2 * KCH * a.npx > (size_t)AITER * 256 || a.nchunk % KCH != 0) return hipErrorInvalidValue;
     // the attribute is per device and sticky: raise it once per (instance, device) to the largest image any layer needs
-    static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     constexpr size_t SMEM_MAX = (size_t)2 * 2 * (AITER * 128) * 16 + (size_t)KCH * 2 * TPS * 2 * MT * 16;
     if (smem > SMEM_MAX) return hipErrorInvalidValue;
-    if (!((attr_done.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv1d_mfma_kernel<WM, WN, MF, TPS, AITER, KCH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM_MAX);
-        if (e != hipSuccess) return e;
-        attr_done.fetch_or(1ull << dev, std::memory_order_relaxed);
-    }
+    const hipError_t e = raise_dyn_lds<&conv1d_mfma_kernel<WM, WN, MF, TPS, AITER, KCH>>(SMEM_MAX);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((conv1d_mfma_kernel<WM, WN, MF, TPS, AITER, KCH>), dim3((unsigned)(ncot * ntile * a.B)), dim3(256), smem, st, a);
     return hipGetLastError();
 }

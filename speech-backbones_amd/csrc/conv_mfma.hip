@@ -27,8 +27,8 @@
 //
 // Wave tile: (MF x 32) output channels x (2 rows x 32 columns) pixels; a workgroup is WM x WN waves.
 #include "common.h"
+#include "kernels.h"
 #include <algorithm>
-#include <atomic>
 
 // minimum waves per SIMD requested from the register allocator (= workgroups per CU with 4-wave workgroups)
 #ifndef GTTS_C3_WAVES
@@ -828,18 +828,8 @@ static hipError_t launch_cfg(const ConvArgs &a_in, hipStream_t st, std::string *
     size_t smem = conv_smem_bytes(C::NPIX, C::NKG, C::WBLK16, a.cin, PRO, C::MT, EPI == EPI_DNFOLD ? 7 : 3);
     if (smem < (size_t)GTTS_LDS_MIN) smem = (size_t)GTTS_LDS_MIN;
     if (MODE == CONV_C3 && NSPLIT == 2 && (EPI == EPI_STATS || EPI == EPI_PLAIN) && smem < (size_t)GTTS_C3_LDS_MIN) smem = (size_t)GTTS_C3_LDS_MIN;
-    // hipFuncSetAttribute is per device: remember the largest size set on each device (atomics: launches may come
-    // from several host threads; setting the attribute twice is harmless)
-    static std::atomic<size_t> attr_set[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (smem > attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(
-            reinterpret_cast<const void *>(&conv_mfma_kernel<MODE, WM, WN, MF, KCH, PRO, EPI, NSPLIT, FULLC, AT, NF, 0>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(smem, std::memory_order_relaxed);
-    }
+    const hipError_t e = raise_dyn_lds<&conv_mfma_kernel<MODE, WM, WN, MF, KCH, PRO, EPI, NSPLIT, FULLC, AT, NF, 0>>(smem);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((conv_mfma_kernel<MODE, WM, WN, MF, KCH, PRO, EPI, NSPLIT, FULLC, AT, NF, 0>), grid, dim3(256), smem, st, a);
     return hipGetLastError();
 }

@@ -1041,13 +1041,9 @@ static hipError_t launch_ws_ring(ConvArgs &a, hipStream_t st, std::string *name)
     // (Measured and not kept: persistent workgroups on half of the CUs per launch -- grid 128 with two sub-batch streams, so
     // that the other stream's kernels find free CUs: 7.45 vs 7.48 ms per call; the dispatcher fills the same CUs first.)
     const int grid = (int)std::min<long>(ntiles, (long)cus * per_cu);
-    auto kern = &conv3x3_ws_kernel<WM, WN, MF, NF, PRO, NSPLIT, AT, RING>;
-    static std::atomic<size_t> attr_set[64];
-    if (smem > attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(smem, std::memory_order_relaxed);
-    }
+    constexpr auto kern = &conv3x3_ws_kernel<WM, WN, MF, NF, PRO, NSPLIT, AT, RING>;
+    const hipError_t e = raise_dyn_lds<kern>(smem);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(C::NT), smem, st, a);
     return hipGetLastError();
 }

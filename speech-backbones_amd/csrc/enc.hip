@@ -536,12 +536,12 @@ extern "C" int gtts_enc_forward(const gtts_enc *e, const void *packed, const lon
         if (path == 16) {
             const size_t smem16 = att16_smem_bytes(dk, L);
             // 16 queries per workgroup, lanes along the keys (two workgroups per CU up to L ~ 1000)
-            GTTS_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&enc_attention16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem16));
+            GTTS_HIPCHK(raise_dyn_lds<&enc_attention16_kernel>(smem16));
             hipLaunchKernelGGL(enc_attention16_kernel, dim3((L + ATT16_QT - 1) / ATT16_QT, cf.n_heads, B), dim3(256), smem16, st, Q, K, V,
                                x_mask, ek, ev, A, C, L, cf.n_heads, win);
         } else {
             const size_t smem = (size_t)(ATT_QT * dk + ATT_QT * L) * 4;
-            GTTS_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&enc_attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            GTTS_HIPCHK(raise_dyn_lds<&enc_attention_kernel>(smem));
             hipLaunchKernelGGL(enc_attention_kernel, dim3((L + ATT_QT - 1) / ATT_QT, cf.n_heads, B), dim3(256), smem, st, Q, K, V, x_mask,
                                ek, ev, A, C, L, cf.n_heads, win);
         }

@@ -3,12 +3,12 @@
 //   n_iters times  s = stft(x),  a = s / sqrt(max(re^2 + im^2, 1e-8)),  x = istft(c (a + m (a - a_prev))),  a_prev = a  (a_prev = 0 first);
 //   stft / istft with center = True (reflect pad n_fft / 2), the periodic Hann window of n_fft samples, hop_size.
 // Launches: one projection, one first inverse transform, ONE per iteration, one that materialises x.  Layout of an iteration, as in
-// mel.hip: a workgroup of four waves owns a tile of FGL_TF = 16 consecutive frames of one row, a frame is transformed by one wave
+// mel.hip (the transform itself: spectral.h): a workgroup of four waves owns a tile of FGL_TF = 16 consecutive frames of one row, a frame is transformed by one wave
 // alone, in two bank-swizzled LDS buffers of that wave:
 //   * sample load: either from x [B][L] (gtts_fgl_step) or gathered from the previous launch's windowed inverse frames
 //     y [B][T][n_fft] as  x[j] = (sum_t y[t][p - t hop]) / (sum_t w^2[p - t hop]),  p = j + n_fft / 2,  t ascending (fgl_ola: the one
 //     definition the materialising kernel uses too, so x never has to exist between iterations); reflection is index arithmetic;
-//   * forward: n_fft real samples packed as n_fft / 2 complex points, Stockham autosort FFT (mel.hip's scheme), the real spectrum of
+//   * forward: n_fft real samples packed as n_fft / 2 complex points, Stockham autosort FFT (spectral.h), the real spectrum of
 //     bins k and n_fft / 2 - k together from Z[k] and Z[M - k]; ALL K bins are formed;
 //   * phase, momentum and magnitude on those two bins in registers; a is stored, s' never is;
 //   * inverse: the two bins are packed back into Z'[k], Z'[M - k], conjugated, the same FFT runs again (ifft(Z) = conj(fft(conj Z))),
@@ -18,7 +18,6 @@
 // Tables (window, w^2, twiddles) are computed on the host in float64 and rounded to fp32; there is no device sin / cos.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -26,6 +25,7 @@
 #include "../../include/gradtts_abi.h"
 #include "common.h"
 #include "kernels.h"
+#include "spectral.h"
 
 namespace gtts {
 
@@ -49,18 +49,6 @@ struct FglArgs {
     float mom;
 };
 
-__device__ __forceinline__ float2 fgl_cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-
-// (see mel.hip) orders the LDS traffic of one wave
-__device__ __forceinline__ void fgl_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// (see mel.hip) bank swizzle of a transform buffer
-__device__ __forceinline__ int fgl_at(int j) { return j ^ (5 * ((j >> 4) & 3)); }
-
 // Sample j of the overlap-added, envelope-normalised, trimmed signal of a row's windowed inverse frames y [T][n]: position p = j + n / 2
 // of the untrimmed signal is covered by the frames t with t hop <= p < t hop + n (at most ceil(n / hop)); they are summed in
 // ascending t.  The ONE definition of x: the iteration's sample load and the materialising kernel return the same bits.
@@ -76,47 +64,12 @@ __device__ __forceinline__ float fgl_ola(const float *y, const float *win2, int 
     return s / e;
 }
 
-// Stockham autosort FFT of M = 2^(LOGN-1) points (decimation in frequency, radix-4 passes and one radix-2 pass when LOGN - 1 is odd)
-// between the wave's two buffers; on return x holds the transform in natural order and y is free.  tw: the M-point twiddle table in
-// LDS.  (Held in registers per lane, as mel.hip does, the pass twiddles cost 48 VGPRs at n_fft = 1024 and 120 at 2048 and, with the
-// window, kept the kernel at one wave per SIMD; read from LDS it runs at three, at 2048 at two.)
+// The wave's FFT (spectral.h) with the M-point twiddle table `tw` read from LDS.  (Held in registers per lane, as mel.hip does, the
+// pass twiddles cost 48 VGPRs at n_fft = 1024 and 120 at 2048 and, with the window, kept the kernel at one wave per SIMD; read from
+// LDS it runs at three, at 2048 at two.)
 template <int LOGN>
 __device__ __forceinline__ void fgl_fft(float2 *&x, float2 *&y, const float2 *tw, int lane) {
-    constexpr int M = 1 << (LOGN - 1), Q = M / 4, RB = (Q + 63) / 64;
-    int s = 1;
-#pragma unroll
-    for (int n = M; n >= 4; n >>= 2) {
-#pragma unroll
-        for (int r = 0; r < RB; ++r) {
-            const int i = lane + 64 * r;              // butterfly i = q + s p
-            if (Q >= 64 || i < Q) {
-                const int q = i & (s - 1), ps = i - q;
-                const float2 v0 = x[fgl_at(i)], v1 = x[fgl_at(i + Q)], v2 = x[fgl_at(i + 2 * Q)], v3 = x[fgl_at(i + 3 * Q)];
-                const float2 apc = make_float2(v0.x + v2.x, v0.y + v2.y), amc = make_float2(v0.x - v2.x, v0.y - v2.y);
-                const float2 bpd = make_float2(v1.x + v3.x, v1.y + v3.y);
-                const float2 jbmd = make_float2(-(v1.y - v3.y), v1.x - v3.x);        // i (b - d)
-                const int o = q + 4 * ps;
-                y[fgl_at(o)] = make_float2(apc.x + bpd.x, apc.y + bpd.y);
-                y[fgl_at(o + s)] = fgl_cmul(make_float2(amc.x - jbmd.x, amc.y - jbmd.y), tw[ps]);
-                y[fgl_at(o + 2 * s)] = fgl_cmul(make_float2(apc.x - bpd.x, apc.y - bpd.y), tw[2 * ps]);
-                y[fgl_at(o + 3 * s)] = fgl_cmul(make_float2(amc.x + jbmd.x, amc.y + jbmd.y), tw[3 * ps]);
-            }
-        }
-        fgl_wave_sync();
-        float2 *tmp = x; x = y; y = tmp;
-        s <<= 2;
-    }
-    if ((LOGN - 1) & 1) {                 // the remaining length-2 transforms (s = M / 2)
-#pragma unroll
-        for (int r = 0; r < (M / 2 + 63) / 64; ++r) {
-            const int q = lane + 64 * r;
-            const float2 v0 = x[fgl_at(q)], v1 = x[fgl_at(q + M / 2)];
-            y[fgl_at(q)] = make_float2(v0.x + v1.x, v0.y + v1.y);
-            y[fgl_at(q + M / 2)] = make_float2(v0.x - v1.x, v0.y - v1.y);
-        }
-        fgl_wave_sync();
-        float2 *tmp = x; x = y; y = tmp;
-    }
+    stockham_fft<LOGN>(x, y, [tw](int, int, int ps, int m) { return tw[m * ps]; }, lane);
 }
 
 // s / sqrt(max(re^2 + im^2, 1e-8))
@@ -161,18 +114,14 @@ __global__ __launch_bounds__(64 * FGL_WAVES) void fgl_kernel(FglArgs a) {
             const int base = t * a.hop - N / 2;
 #pragma unroll 1
             for (int r = 0; r < R; ++r) {
-                int j0 = base + 2 * (lane + 64 * r), j1 = j0 + 1;
-                j0 = j0 < 0 ? -j0 : j0;
-                j1 = j1 < 0 ? -j1 : j1;
-                j0 = j0 >= a.L ? 2 * (a.L - 1) - j0 : j0;
-                j1 = j1 >= a.L ? 2 * (a.L - 1) - j1 : j1;
+                const int j = base + 2 * (lane + 64 * r), j0 = reflect_index(j, a.L), j1 = reflect_index(j + 1, a.L);
                 float v0, v1;
                 if (xrow) { v0 = xrow[j0]; v1 = xrow[j1]; }
                 else { v0 = fgl_ola(yrow, a.win2, j0, N, a.T, a.hop); v1 = fgl_ola(yrow, a.win2, j1, N, a.T, a.hop); }
                 const float2 w = win[lane + 64 * r];
-                x[fgl_at(lane + 64 * r)] = make_float2(v0 * w.x, v1 * w.y);
+                x[fft_at(lane + 64 * r)] = make_float2(v0 * w.x, v1 * w.y);
             }
-            fgl_wave_sync();
+            wave_lds_sync();
             fgl_fft<LOGN>(x, y, tw, lane);
         }
         // ---- bins k and M - k (k = 0: DC and Nyquist) from Z[k], Z[M - k]; phase, momentum, magnitude; packed back into y
@@ -183,12 +132,9 @@ __global__ __launch_bounds__(64 * FGL_WAVES) void fgl_kernel(FglArgs a) {
             float2 sk = make_float2(crow[(size_t)k * a.c_sk + (size_t)t * a.c_st], 0.f);
             float2 sm = make_float2(crow[(size_t)k2 * a.c_sk + (size_t)t * a.c_st], 0.f);
             if (!a.init) {
-                const float2 zk = x[fgl_at(k & (M - 1))], zm = x[fgl_at(k2 & (M - 1))];
-                const float er = 0.5f * (zk.x + zm.x), ei = 0.5f * (zk.y - zm.y);              // E = (Z[k] + conj Z[M-k]) / 2
-                const float orr = 0.5f * (zk.y + zm.y), oi = -0.5f * (zk.x - zm.x);            // O = -i (Z[k] - conj Z[M-k]) / 2
-                const float tr = w.x * orr - w.y * oi, ti = w.x * oi + w.y * orr;             // W^k O
-                const float2 ak = fgl_phase(make_float2(er + tr, ei + ti));                   // X[k] = E + W^k O
-                const float2 am = fgl_phase(make_float2(er - tr, -(ei - ti)));                // X[M-k] = conj(E - W^k O)
+                const RealSplit sp = real_split(x[fft_at(k & (M - 1))], x[fft_at(k2 & (M - 1))], w);
+                const float2 ak = fgl_phase(make_float2(sp.e.x + sp.wo.x, sp.e.y + sp.wo.y));         // X[k] = E + W^k O
+                const float2 am = fgl_phase(make_float2(sp.e.x - sp.wo.x, -(sp.e.y - sp.wo.y)));      // X[M-k] = conj(E - W^k O)
                 const size_t ik = (size_t)k * a.a_sk + (size_t)t * a.a_st, im = (size_t)k2 * a.a_sk + (size_t)t * a.a_st;
                 float2 pk = make_float2(0.f, 0.f), pm = pk;
                 if (prow) { pk = prow[ik]; pm = prow[im]; }
@@ -202,20 +148,20 @@ __global__ __launch_bounds__(64 * FGL_WAVES) void fgl_kernel(FglArgs a) {
             // (the factor 1 / 2 of both is in `scale`)
             const float epr = sk.x + sm.x, epi = sk.y - sm.y, dr = sk.x - sm.x, di = sk.y + sm.y;
             const float opr = dr * w.x + di * w.y, opi = di * w.x - dr * w.y;
-            y[fgl_at(k & (M - 1))] = make_float2(epr - opi, -(epi + opr));                    // conj Z'[k]
-            if (k != 0 && k2 != k) y[fgl_at(k2)] = make_float2(epr + opi, -(opr - epi));      // conj Z'[M-k]
+            y[fft_at(k & (M - 1))] = make_float2(epr - opi, -(epi + opr));                    // conj Z'[k]
+            if (k != 0 && k2 != k) y[fft_at(k2)] = make_float2(epr + opi, -(opr - epi));      // conj Z'[M-k]
         }
-        fgl_wave_sync();
+        wave_lds_sync();
         { float2 *tmp = x; x = y; y = tmp; }
         fgl_fft<LOGN>(x, y, tw, lane);
         // z[m] = conj(fft(conj Z'))[m] / N = x[2m] + i x[2m+1]; windowed, stored as frame t of y
         float2 *yo = reinterpret_cast<float2 *>(a.yout + ((size_t)b * a.T + t) * N);
 #pragma unroll 1
         for (int r = 0; r < R; ++r) {
-            const float2 z = x[fgl_at(lane + 64 * r)], w = win[lane + 64 * r];
+            const float2 z = x[fft_at(lane + 64 * r)], w = win[lane + 64 * r];
             yo[lane + 64 * r] = make_float2((z.x * scale) * w.x, (-z.y * scale) * w.y);
         }
-        fgl_wave_sync();                  // the next frame overwrites this wave's buffers
+        wave_lds_sync();                  // the next frame overwrites this wave's buffers
     }
 }
 
@@ -283,14 +229,8 @@ FglWs fgl_ws(const gtts_fgl *g, int B, int T) {
 
 template <int LOGN>
 hipError_t fgl_launch(const FglArgs &a, int B, size_t smem, hipStream_t st) {
-    static std::atomic<int> attr_set[64];        // hipFuncSetAttribute is per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (smem > 48 * 1024 && !attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fgl_kernel<LOGN>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(1, std::memory_order_relaxed);
-    }
+    const hipError_t e = raise_dyn_lds<&fgl_kernel<LOGN>>(smem);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fgl_kernel<LOGN>, dim3((unsigned)((a.T + FGL_TF - 1) / FGL_TF), (unsigned)B), dim3(64 * FGL_WAVES), smem, st, a);
     return hipGetLastError();
 }
@@ -363,14 +303,13 @@ extern "C" int gtts_fgl_create(const gtts_fgl_cfg *cfg, gtts_fgl **out) {
     g->image.assign(g->off_p, 0);
     float *win = reinterpret_cast<float *>(g->image.data() + g->off_win), *win2 = reinterpret_cast<float *>(g->image.data() + g->off_win2);
     float *twm = reinterpret_cast<float *>(g->image.data() + g->off_twm), *twn = reinterpret_cast<float *>(g->image.data() + g->off_twn);
-    const double two_pi = 6.283185307179586476925286766559;
     for (int n = 0; n < N; ++n) {
-        const double w = 0.5 - 0.5 * std::cos(two_pi * n / N);      // periodic Hann
+        const double w = hann_periodic(n, N);
         win[n] = (float)w;
         win2[n] = (float)(w * w);
     }
-    for (int k = 0; k < M; ++k) { twm[2 * k] = (float)std::cos(two_pi * k / M); twm[2 * k + 1] = (float)-std::sin(two_pi * k / M); }
-    for (int k = 0; k <= H; ++k) { twn[2 * k] = (float)std::cos(two_pi * k / N); twn[2 * k + 1] = (float)-std::sin(two_pi * k / N); }
+    fill_twiddles(twm, M, M);
+    fill_twiddles(twn, H + 1, N);
     g->smem = (size_t)M * 8 + (size_t)(H + 2) * 8 + (size_t)FGL_WAVES * 2 * M * 8;
     *out = g;
     return GTTS_OK;

@@ -70,8 +70,7 @@ hipError_t launch_expand_alignment(const float *dur, const float *x_mask, const 
     const size_t smem = ((size_t)tx + T) * 4;
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     if (smem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&expand_alignment_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        const hipError_t e = raise_dyn_lds<&expand_alignment_kernel>(smem);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(expand_alignment_kernel, dim3(B), dim3(256), smem, st, dur, x_mask, y_len, mu_x, noise, temperature,
@@ -124,8 +123,7 @@ hipError_t launch_log_prior(const float *mu_x, const float *y, float *out, int B
     const size_t smem = (size_t)F * 80 * sizeof(float);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     if (smem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&log_prior_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        const hipError_t e = raise_dyn_lds<&log_prior_kernel>(smem);
         if (e != hipSuccess) return e;
     }
     const float cst = (float)(-0.5 * 1.8378770664093453 * (double)F);     // -0.5 * log(2 pi) * n_feats

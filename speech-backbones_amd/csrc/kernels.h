@@ -1,5 +1,6 @@
 // kernels.h -- host-visible launchers of every kernel in libgradtts_gfx950 (internal header).
 #pragma once
+#include <atomic>
 #include <vector>
 
 #include "common.h"
@@ -17,6 +18,20 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // blob and workspace sections start on 256-byte boundaries
 static inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+// Raises the dynamic-LDS cap of kernel K (its address: every kernel instance has its own record) to `bytes` on the current device,
+// unless it is already that high.  The attribute is per device and sticky, so the record is the largest size set on each device
+// (atomics: launches may come from several host threads; setting the attribute twice is harmless).  Returns HIP's error unchanged.
+template <auto K>
+hipError_t raise_dyn_lds(size_t bytes) {
+    static std::atomic<size_t> cap[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (bytes <= cap[dev].load(std::memory_order_relaxed)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) cap[dev].store(bytes, std::memory_order_relaxed);
+    return e;
+}
 
 // ---- misc.hip
 struct TimeMlpDesc {
@@ -154,10 +169,6 @@ hipError_t launch_pack_attn_kv(const float *wqkv, unsigned char *dst, int C, hip
 hipError_t launch_wgrad_reduce(const float *part, const float *dbpart, float *dw, float *db, int cin, int cout, int nslice, int taps,
                                hipStream_t st);
 hipError_t launch_copy_f32(const float *src, float *dst, size_t n, hipStream_t st);
-
-// ---- mel.hip
-// librosa's default mel filterbank (slaney scale and normalisation), host float64 -> fp32 [n_mels][n_fft / 2 + 1]; mel.hip and wav.hip
-void slaney_filterbank(int sampling_rate, int n_fft, int n_mels, double fmin, double fmax, std::vector<float> &fb);
 
 // ---- glue.hip (generate_path + aligned prior mean + terminal sample: tts.py:84-94, utils.py:26-39)
 hipError_t launch_expand_alignment(const float *dur, const float *x_mask, const int *y_len, const float *mu_x,

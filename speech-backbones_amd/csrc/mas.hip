@@ -222,15 +222,7 @@ template <int R, int TY>
 static hipError_t launch_mas_wave(const float *value, const float *mask, const int *t_x, const int *t_y, int *path,
                                   unsigned char *scratch, int b, int tx, int ty, hipStream_t st) {
     const size_t smem = (size_t)2 * TY * (64 * R + 4) * sizeof(float);
-    static bool attr_done[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mas_wave_kernel<R, TY>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) { (void)hipGetLastError(); return hipErrorNotSupported; }      // the ONE failure the caller may answer with the other kernel
-        attr_done[dev] = true;
-    }
+    if (raise_dyn_lds<&mas_wave_kernel<R, TY>>(smem) != hipSuccess) { (void)hipGetLastError(); return hipErrorNotSupported; }      // the ONE failure the caller may answer with the other kernel
     hipLaunchKernelGGL((mas_wave_kernel<R, TY>), dim3(b), dim3(256), smem, st, value, mask, t_x, t_y, path,
                        reinterpret_cast<unsigned short *>(scratch), tx, ty);
     return hipGetLastError();
@@ -257,8 +249,7 @@ hipError_t launch_mas(const float *value, const float *mask, const int *t_x, con
     const size_t smem = (size_t)2 * tx * sizeof(float);
     if (smem > 160 * 1024) return hipErrorInvalidValue;
     if (smem > 48 * 1024) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mas_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem);
+        e = raise_dyn_lds<&mas_kernel>(smem);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(mas_kernel, dim3(b), dim3(256), smem, st, value, mask, t_x, t_y, path, scratch, tx, ty);

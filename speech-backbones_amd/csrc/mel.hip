@@ -17,7 +17,6 @@
 // A frame's value depends on its own n_fft samples and the tables alone: not on B, its place in the tile, or the grid.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -25,6 +24,7 @@
 #include "../../include/gradtts_abi.h"
 #include "common.h"
 #include "kernels.h"
+#include "spectral.h"
 
 namespace gtts {
 
@@ -43,27 +43,11 @@ struct MelArgs {
     int B, L, T, hop, pad, num_mels, kmax, kstride, nw;
 };
 
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-
 // frames of a row of `len` samples (0 when the row cannot be reflected or holds no whole frame)
 __host__ __device__ inline int mel_frames_of(int len, int n_fft, int hop, int pad) {
     if (len <= pad || len + 2 * pad < n_fft) return 0;
     return (len + 2 * pad - n_fft) / hop + 1;
 }
-
-// Orders the LDS traffic of ONE wave: a wave's LDS instructions execute in issue order, so a value written by one lane is there for
-// any lane of the same wave that reads it later; this only keeps the compiler from moving accesses across the point.  The four waves
-// of a workgroup transform their frames without waiting for one another.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Where point j of a transform buffer lives.  The radix-4 passes with stride 1 and 4 store with 16 consecutive lanes 4 and 16 points
-// apart: on the 32 banks of a ds_write_b64 lane group that is a 4-way conflict.  XOR-ing bits 4-5 of j into bits 0-1 and 2-3 spreads
-// both patterns over all banks and keeps contiguous runs of 16 points contiguous (a permutation inside each run).
-__device__ __forceinline__ int mel_at(int j) { return j ^ (5 * ((j >> 4) & 3)); }
 
 template <int LOGN>
 __global__ __launch_bounds__(64 * MEL_WAVES) void mel_kernel(MelArgs a) {
@@ -98,12 +82,8 @@ __global__ __launch_bounds__(64 * MEL_WAVES) void mel_kernel(MelArgs a) {
         for (int r = 0; r < R; ++r) {
             z[r] = make_float2(0.f, 0.f);
             if (t < Tb) {
-                int j0 = base + 2 * (lane + 64 * r), j1 = j0 + 1;
-                j0 = j0 < 0 ? -j0 : j0;
-                j1 = j1 < 0 ? -j1 : j1;
-                j0 = j0 >= len ? 2 * (len - 1) - j0 : j0;
-                j1 = j1 >= len ? 2 * (len - 1) - j1 : j1;
-                z[r] = make_float2(row[j0], row[j1]);
+                const int j0 = base + 2 * (lane + 64 * r);
+                z[r] = make_float2(row[reflect_index(j0, len)], row[reflect_index(j0 + 1, len)]);
             }
         }
     };
@@ -134,54 +114,18 @@ __global__ __launch_bounds__(64 * MEL_WAVES) void mel_kernel(MelArgs a) {
 #pragma unroll 1
     for (int f = wave; f < MEL_TF; f += MEL_WAVES) {
 #pragma unroll
-        for (int r = 0; r < R; ++r) A[mel_at(lane + 64 * r)] = make_float2(z[r].x * win[r].x, z[r].y * win[r].y);
+        for (int r = 0; r < R; ++r) A[fft_at(lane + 64 * r)] = make_float2(z[r].x * win[r].x, z[r].y * win[r].y);
         if (f + MEL_WAVES < MEL_TF) load_frame(f + MEL_WAVES, z);        // the next frame's samples travel while this one is transformed
         wave_lds_sync();
-        // ---- Stockham autosort FFT of M points (decimation in frequency): sub-transform length n, stride s = M / n
         float2 *x = A, *y = Bf;
-        int s = 1, pi = 0;
-#pragma unroll
-        for (int n = M; n >= 4; n >>= 2, ++pi) {
-#pragma unroll
-            for (int r = 0; r < (Q + 63) / 64; ++r) {
-                const int i = lane + 64 * r;              // butterfly i = q + s p
-                if (Q >= 64 || i < Q) {
-                    const int q = i & (s - 1), ps = i - q;            // ps = p s: the index of e^{-2 pi i p / n} in the M-point table (twr)
-                    const float2 v0 = x[mel_at(i)], v1 = x[mel_at(i + Q)], v2 = x[mel_at(i + 2 * Q)], v3 = x[mel_at(i + 3 * Q)];
-                    const float2 apc = make_float2(v0.x + v2.x, v0.y + v2.y), amc = make_float2(v0.x - v2.x, v0.y - v2.y);
-                    const float2 bpd = make_float2(v1.x + v3.x, v1.y + v3.y);
-                    const float2 jbmd = make_float2(-(v1.y - v3.y), v1.x - v3.x);        // i (b - d)
-                    const int o = q + 4 * ps;
-                    y[mel_at(o)] = make_float2(apc.x + bpd.x, apc.y + bpd.y);
-                    y[mel_at(o + s)] = cmul(make_float2(amc.x - jbmd.x, amc.y - jbmd.y), twr[pi][r][0]);
-                    y[mel_at(o + 2 * s)] = cmul(make_float2(apc.x - bpd.x, apc.y - bpd.y), twr[pi][r][1]);
-                    y[mel_at(o + 3 * s)] = cmul(make_float2(amc.x + jbmd.x, amc.y + jbmd.y), twr[pi][r][2]);
-                }
-            }
-            wave_lds_sync();
-            float2 *tmp = x; x = y; y = tmp;
-            s <<= 2;
-        }
-        if ((LOGN - 1) & 1) {             // the remaining length-2 transforms (s = M / 2)
-#pragma unroll
-            for (int r = 0; r < (M / 2 + 63) / 64; ++r) {
-                const int q = lane + 64 * r;
-                const float2 v0 = x[mel_at(q)], v1 = x[mel_at(q + M / 2)];
-                y[mel_at(q)] = make_float2(v0.x + v1.x, v0.y + v1.y);
-                y[mel_at(q + M / 2)] = make_float2(v0.x - v1.x, v0.y - v1.y);
-            }
-            wave_lds_sync();
-            float2 *tmp = x; x = y; y = tmp;
-        }
+        stockham_fft<LOGN>(x, y, [&](int pass, int r, int, int m) { return twr[pass][r][m - 1]; }, lane);
         // ---- real spectrum from the packed transform, magnitude; bins [kmax, kmax + 3) are the zero pad of the last row's chunk
         float *mg = mag + f * a.kstride;
         for (int k = lane; k < a.kmax + 3; k += 64) {
             float v = 0.f;
             if (k < a.kmax) {
-                const float2 zk = x[mel_at(k & (M - 1))], zm = x[mel_at((M - k) & (M - 1))], w = twn[k];
-                const float er = 0.5f * (zk.x + zm.x), ei = 0.5f * (zk.y - zm.y);
-                const float orr = 0.5f * (zk.y + zm.y), oi = -0.5f * (zk.x - zm.x);
-                const float re = er + (w.x * orr - w.y * oi), im = ei + (w.x * oi + w.y * orr);
+                const RealSplit sp = real_split(x[fft_at(k & (M - 1))], x[fft_at((M - k) & (M - 1))], twn[k]);
+                const float re = sp.e.x + sp.wo.x, im = sp.e.y + sp.wo.y;        // X[k] = E + W^k O
                 v = sqrtf(re * re + im * im + 1e-9f);
             }
             mg[k] = v;
@@ -224,42 +168,10 @@ struct gtts_mel {
 
 namespace {
 
-// slaney mel scale (librosa htk = False): linear below 1000 Hz, logarithmic above
-double hz_to_mel(double f) { return f < 1000.0 ? f / (200.0 / 3.0) : 15.0 + std::log(f / 1000.0) / (std::log(6.4) / 27.0); }
-double mel_to_hz(double m) { return m < 15.0 ? m * (200.0 / 3.0) : 1000.0 * std::exp((std::log(6.4) / 27.0) * (m - 15.0)); }
-
-}  // namespace
-
-// librosa.filters.mel with its defaults (slaney scale, slaney area normalisation) in float64, rounded to fp32: fb [nm][n_fft / 2 + 1].
-// Edges and bin frequencies are formed as numpy.linspace forms them.  Shared with wav.hip.
-void gtts::slaney_filterbank(int sampling_rate, int n_fft, int nm, double fmin, double fmax, std::vector<float> &fb) {
-    const int nb = n_fft / 2 + 1;
-    std::vector<double> f(nm + 2);
-    const double lo = hz_to_mel(fmin), hi = hz_to_mel(fmax), step = (hi - lo) / (nm + 1);
-    for (int j = 0; j < nm + 2; ++j) f[j] = mel_to_hz(j == nm + 1 ? hi : lo + step * j);
-    const double fstep = (0.5 * sampling_rate) / (nb - 1);
-    fb.assign((size_t)nm * nb, 0.f);
-    for (int i = 0; i < nm; ++i)
-        for (int k = 0; k < nb; ++k) {
-            const double fk = k == nb - 1 ? 0.5 * sampling_rate : fstep * k;
-            const double lower = (fk - f[i]) / (f[i + 1] - f[i]), upper = (f[i + 2] - fk) / (f[i + 2] - f[i + 1]);
-            const double w = std::fmax(0.0, std::fmin(lower, upper)) * (2.0 / (f[i + 2] - f[i]));
-            fb[(size_t)i * nb + k] = (float)w;
-        }
-}
-
-namespace {
-
 template <int LOGN>
 hipError_t mel_launch(const MelArgs &a, size_t smem, hipStream_t st) {
-    static std::atomic<int> attr_set[64];        // hipFuncSetAttribute is per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (smem > 48 * 1024 && !attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&mel_kernel<LOGN>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(1, std::memory_order_relaxed);
-    }
+    const hipError_t e = raise_dyn_lds<&mel_kernel<LOGN>>(smem);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(mel_kernel<LOGN>, dim3((unsigned)((a.T + MEL_TF - 1) / MEL_TF), (unsigned)a.B), dim3(64 * MEL_WAVES), smem, st, a);
     return hipGetLastError();
 }
@@ -285,21 +197,12 @@ extern "C" int gtts_mel_create(const gtts_mel_cfg *cfg, gtts_mel **out) {
     m->pad = (c.n_fft - c.hop_size) / 2;
     const int N = c.n_fft, M = N / 2, nb = M + 1;
     slaney_filterbank(c.sampling_rate, c.n_fft, c.num_mels, c.fmin, c.fmax, m->fb);
-    // rows: support [k0, k1) of every filter, its weights padded with zeros to whole chunks of four
-    std::vector<int> rows(4 * (size_t)c.num_mels, 0);
+    // rows: support [k0, k1) of every filter, its weights padded with zeros to whole chunks of four (an empty filter: no chunk, the
+    // cell is log(1e-5))
+    std::vector<int> rows;
     std::vector<float> wts;
-    m->kmax = 1;
-    for (int i = 0; i < c.num_mels; ++i) {
-        int k0 = nb, k1 = 0;
-        for (int k = 0; k < nb; ++k)
-            if (m->fb[(size_t)i * nb + k] != 0.f) { k0 = k < k0 ? k : k0; k1 = k + 1; }
-        if (k1 == 0) k0 = 0;              // an empty filter: no chunk, the cell is log(1e-5)
-        const int nch = (k1 - k0 + 3) / 4;
-        rows[4 * i] = k0; rows[4 * i + 1] = nch; rows[4 * i + 2] = (int)wts.size();
-        for (int k = k0; k < k0 + 4 * nch; ++k) wts.push_back(k < k1 ? m->fb[(size_t)i * nb + k] : 0.f);
-        if (k1 > m->kmax) m->kmax = k1;
-    }
-    if (wts.empty()) wts.assign(4, 0.f);
+    m->kmax = filter_supports(m->fb, c.num_mels, nb, 4, rows, wts);
+    if (m->kmax < 1) m->kmax = 1;
     m->nw = (int)wts.size();
     m->kstride = (m->kmax + 3) | 1;       // every row's last chunk stays inside its frame's magnitudes; odd: frames on different banks
     m->off_win = 0;
@@ -310,11 +213,10 @@ extern "C" int gtts_mel_create(const gtts_mel_cfg *cfg, gtts_mel **out) {
     m->image.assign(m->off_wts + align256(wts.size() * 4), 0);
     float *win = reinterpret_cast<float *>(m->image.data() + m->off_win);
     float *twm = reinterpret_cast<float *>(m->image.data() + m->off_twm), *twn = reinterpret_cast<float *>(m->image.data() + m->off_twn);
-    const double two_pi = 6.283185307179586476925286766559;
     const int left = (N - c.win_size) / 2;
-    for (int n = 0; n < c.win_size; ++n) win[left + n] = (float)(0.5 - 0.5 * std::cos(two_pi * n / c.win_size));      // periodic Hann
-    for (int k = 0; k < M; ++k) { twm[2 * k] = (float)std::cos(two_pi * k / M); twm[2 * k + 1] = (float)-std::sin(two_pi * k / M); }
-    for (int k = 0; k < nb; ++k) { twn[2 * k] = (float)std::cos(two_pi * k / N); twn[2 * k + 1] = (float)-std::sin(two_pi * k / N); }
+    for (int n = 0; n < c.win_size; ++n) win[left + n] = (float)hann_periodic(n, c.win_size);
+    fill_twiddles(twm, M, M);
+    fill_twiddles(twn, nb, N);
     memcpy(m->image.data() + m->off_rows, rows.data(), rows.size() * 4);
     memcpy(m->image.data() + m->off_wts, wts.data(), wts.size() * 4);
     m->smem = (size_t)M * 8 + (size_t)(M + 2) * 8 + (size_t)MEL_WAVES * 2 * M * 8 + (size_t)((MEL_TF * m->kstride + 3) & ~3) * 4 + (size_t)c.num_mels * 16 + (size_t)m->nw * 4;

@@ -681,7 +681,7 @@ extern "C" int gtts_spktrain_backward(const gtts_spk *s, const void *packed_trai
     hipLaunchKernelGGL(spk_lin_wgrad_kernel, dim3((unsigned)E), dim3(256), 0, st, (const float *)dpre, hlast, grads[4 * L], grads[4 * L + 1], N, H, E);
     GTTS_HIPCHK(hipGetLastError());
     const size_t lds = (size_t)2 * SPK_TILE * SPK_ZS * 4;
-    GTTS_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&spk_rec_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GTTS_HIPCHK(raise_dyn_lds<&spk_rec_bwd_kernel>(lds));
     for (int l = L - 1; l >= 0; --l) {
         float *A = (float *)(sb + sv.A[l]);
         SpkRecBwdArgs ra;

@@ -16,7 +16,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 
 #include "../../include/gradtts_abi.h"
 #include "common.h"
@@ -465,13 +464,7 @@ extern "C" int gtts_conv3x3_wgrad_tiled2(const float *x, const float *x1, int c0
     a.dbpart = db ? a.part + (size_t)a.nslice * tiles * (9 * 64 * 64) : nullptr;
     hipStream_t st = (hipStream_t)stream;
     constexpr size_t smem = (size_t)2 * (2 * 64 * DY_STRIDE + 2 * 64 * X_STRIDE) * 16;      // two buffers
-    static std::atomic<int> attr_set[64];        // hipFuncSetAttribute is per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev].load(std::memory_order_relaxed)) {
-        GTTS_HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_wgrad2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set[dev].store(1, std::memory_order_relaxed);
-    }
+    GTTS_HIPCHK(raise_dyn_lds<&conv3x3_wgrad2_kernel>(smem));
     hipLaunchKernelGGL(conv3x3_wgrad2_kernel, dim3((unsigned)(tiles * a.nslice)), dim3(512), smem, st, a);
     GTTS_HIPCHK(hipGetLastError());
     const size_t total = (size_t)tiles * (9 * 64 * 64) + (db ? (size_t)cout : 0);

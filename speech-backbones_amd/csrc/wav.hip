@@ -19,7 +19,6 @@
 // fixed order, and an MFMA column is a frame: an output depends on its own samples and the tables, never on B, its place or the grid.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -27,6 +26,7 @@
 #include "../../include/gradtts_abi.h"
 #include "common.h"
 #include "kernels.h"
+#include "spectral.h"
 
 namespace gtts {
 
@@ -151,9 +151,7 @@ __global__ __launch_bounds__(256) void wav_powmel_kernel(WavMelArgs a) {
     float *xs = wts + a.nw;                                                   // [span + span / 32 + 1]
     const int span = (WAV_TF - 1) * a.hop + a.n_fft, i0 = t0 * a.hop - a.pad;
     for (int j = tid; j < span; j += 256) {
-        int i = i0 + j;
-        i = i < 0 ? -i : i;                                                   // (L > pad: one reflection is enough for a frame of the row)
-        i = i >= a.L ? 2 * (a.L - 1) - i : i;
+        const int i = reflect_index(i0 + j, a.L);                             // (L > pad: one reflection is enough for a frame of the row)
         xs[j + (j >> 5)] = (i >= 0 && i < a.L) ? x[i] : 0.f;                  // (still outside: a frame behind the row's last)
     }
     lds_barrier();
@@ -240,14 +238,8 @@ namespace {
 int gcd_int(int a, int b) { return b == 0 ? a : gcd_int(b, a % b); }
 
 hipError_t powmel_launch(const WavMelArgs &a, int B, size_t smem, hipStream_t st) {
-    static std::atomic<int> attr_set[64];        // hipFuncSetAttribute is per device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (smem > 48 * 1024 && !attr_set[dev].load(std::memory_order_relaxed)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&wav_powmel_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set[dev].store(1, std::memory_order_relaxed);
-    }
+    const hipError_t e = raise_dyn_lds<&wav_powmel_kernel>(smem);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wav_powmel_kernel, dim3((unsigned)((a.T + WAV_TF - 1) / WAV_TF), (unsigned)B), dim3(256), smem, st, a);
     return hipGetLastError();
 }
@@ -310,17 +302,9 @@ extern "C" int gtts_wav_create(const gtts_wav_cfg *cfg, gtts_wav **out) {
     // ---- power mel: filterbank rows as contiguous supports, the windowed one-sided DFT table as MFMA A fragments
     const int N = c.n_fft, nb = N / 2 + 1;
     slaney_filterbank(c.sampling_rate, N, c.n_mels, c.fmin, c.fmax, m->fb);
-    std::vector<int> rows(4 * (size_t)c.n_mels, 0);
+    std::vector<int> rows;
     std::vector<float> wts;
-    for (int i = 0; i < c.n_mels; ++i) {
-        int k0 = nb, k1 = 0;
-        for (int k = 0; k < nb; ++k)
-            if (m->fb[(size_t)i * nb + k] != 0.f) { k0 = k < k0 ? k : k0; k1 = k + 1; }
-        if (k1 == 0) k0 = 0;              // an empty filter: the cell is 0
-        rows[4 * i] = k0; rows[4 * i + 1] = k1 - k0; rows[4 * i + 2] = (int)wts.size();
-        for (int k = k0; k < k1; ++k) wts.push_back(m->fb[(size_t)i * nb + k]);
-    }
-    if (wts.empty()) wts.push_back(0.f);
+    filter_supports(m->fb, c.n_mels, nb, 1, rows, wts);        // (an empty filter: the cell is 0)
     m->nw = (int)wts.size();
     m->KB = (N + 15) / 16;
     m->ntl = (nb + 7) / 8;
@@ -343,7 +327,7 @@ extern "C" int gtts_wav_create(const gtts_wav_cfg *cfg, gtts_wav **out) {
                     const int r = lane & 15, bin = 8 * tl + r / 2, k = 16 * kb + 4 * (lane >> 4) + j;
                     double v = 0.0;
                     if (bin < nb && k < N) {
-                        const double hann = 0.5 - 0.5 * std::cos(2.0 * pi * k / N);                     // periodic Hann
+                        const double hann = hann_periodic(k, N);
                         const double ang = 2.0 * pi * (double)(((long long)bin * k) % N) / N;
                         v = (r & 1) ? -hann * std::sin(ang) : hann * std::cos(ang);
                     }

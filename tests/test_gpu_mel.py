@@ -85,6 +85,20 @@ def test_the_other_transform_sizes(run, cfg, L):
     assert e_kernel <= 1e-3 and e_kernel <= 4 * e_ref32 + 2e-6
 
 
+def test_a_larger_plan_after_a_smaller_one_on_the_same_kernel_instance(run):
+    """Two plans of one kernel instance (n_fft = 1024) on one device, the smaller LDS image first (few bins below fmax = 2000: 47 KB),
+    then every bin under 128 bands (over 80 KB): the launch path has to raise the instance's dynamic-LDS cap for each plan that
+    outgrows the last one (twice when this test runs alone), not only for the first."""
+    L = 256 * 5 + 9
+    for cfg in ((1024, 20, 22050, 256, 1024, 0.0, 2000.0), (1024, 128, 22050, 256, 1024, 0.0, 11025.0)):
+        ref, e32 = MO.reference("noise", cfg, L)
+        got = run(cfg, MO.signal("noise", L, cfg[2])[:2])
+        assert got.shape == ref[:2].shape
+        e_kernel, e_ref32 = float((got.double() - ref[:2]).abs().max()), float(e32[:2].max())
+        print("\nnum_mels=%d fmax=%g L=%d noise e_kernel %.2e  e_ref32 %.2e" % (cfg[1], cfg[6], L, e_kernel, e_ref32))
+        assert e_kernel <= 1e-3 and e_kernel <= 4 * e_ref32 + 2e-6
+
+
 @pytest.mark.parametrize("tag,L", [("cfg1", L37), ("cfg1", 845), ("cfg2", 160 * 59 + 31)])
 @pytest.mark.parametrize("name", ["speechlike", "noise"])
 def test_rows_do_not_depend_on_the_batch(run, name, tag, L):
