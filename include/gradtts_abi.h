@@ -661,6 +661,30 @@ int gtts_wav_normalize(const gtts_wav *wav, const float *in, const float *partia
 /* in [B,L] -> out [B,T,n_mels] */
 int gtts_wav_powmel(const gtts_wav *wav, const void *packed, const float *in, float *out, int B, int L, gtts_stream_t stream);
 
+/* ---- ABI 6 (additive): one layer of the shared 1-D convolution kernel (csrc/conv1d.h), the kernel behind every dense layer of the
+ * HiFi-GAN generator and of both encoders -- the entry its per-layer tests drive; the models reach the same launcher -----------------
+ *   mode 0  Conv1d(cin, cout, K, dilation, padding = (K - 1) / 2 * dilation): K odd, S = 1; weight [cout][cin][K]
+ *   mode 1  ConvTranspose1d(cin, cout, K = 2 S, stride S, padding S / 2): S a power of two >= 2, dilation 1; weight [cin][cout][K]
+ *   out[b][co][q] = ((sum W * (leaky_relu(x, slope) * in_mask) + bias[co]) + res), then accmode 1: accsrc + v, 2: (accsrc + v) / div,
+ *   then * out_mask.  x [B][cin][Lin], out / res / accsrc [B][cout][Lin * S], in_mask [B][Lin], out_mask [B][Lin * S], bias [cout]; res,
+ *   accsrc (accmode 0), in_mask and out_mask may be NULL; slope 1 = identity, 0 = ReLU.  fp32 storage, split-bf16 MFMAs, fp32 accumulate.
+ * Any cin >= 1 (a last chunk of fewer than 16 channels is staged with zeros).  Refused with GTTS_E_CONFIG at create: K above 12 taps,
+ * an even Conv1d kernel, K != 2 S or S not a power of two for mode 1, (K - 1) * dilation above 256 for cout * S >= 128 and above 128
+ * below.  Refused with GTTS_E_SHAPE by forward / instance, on the host, before anything is launched: B or Lin < 1, a sample of
+ * cout * Lin * S * 4 >= 2^31 or ceil(cin / 16) * 16 * Lin * 4 >= 2^31 bytes. */
+typedef struct gtts_conv1d gtts_conv1d;     /* host-side metadata only */
+int gtts_conv1d_create(int mode, int cin, int cout, int K, int dilation, int S, gtts_conv1d **out);
+void gtts_conv1d_destroy(gtts_conv1d *op);
+size_t gtts_conv1d_packed_bytes(const gtts_conv1d *op);
+int gtts_conv1d_pack(const gtts_conv1d *op, const float *weight, void *packed, gtts_stream_t stream);
+int gtts_conv1d_forward(const gtts_conv1d *op, const void *packed, const float *bias, const float *x, float *out, const float *res,
+                        const float *accsrc, int accmode, float div, float slope, const float *in_mask, const float *out_mask, int B,
+                        int Lin, gtts_stream_t stream);
+/* host only: what forward would launch for this shape -- info = {row tile MT (128 / 64 / 32), taps per weight stage (3 / 4), staging
+ * depth AITER (2 / 3), 16-channel chunks per step KCH (1 / 2), epilogue (0 buffer descriptors, 1 ConvTranspose1d 16-byte stores,
+ * 2 ConvTranspose1d two 8-byte stores, 3 generic pointer path)}, from the launcher's own selection. */
+int gtts_conv1d_instance(const gtts_conv1d *op, int B, int Lin, int has_res, int accmode, int has_out_mask, int info[5]);
+
 /* ---- debugging / tests: named intermediates of the last estimator call (keep_intermediates plans) ----- */
 int gtts_plan_num_tensors(const gtts_plan *plan);
 /* offset is in bytes into the workspace for the given (B,T); dims = {B,C,H,W}. */

@@ -174,6 +174,12 @@ def lib():
         L.gtts_enc_attention_path.argtypes = [vp, i]
         L.gtts_enc_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_postnet_forward.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, vp]
+        L.gtts_conv1d_create.argtypes = [i, i, i, i, i, i, ctypes.POINTER(vp)]
+        L.gtts_conv1d_destroy.argtypes, L.gtts_conv1d_destroy.restype = [vp], None
+        L.gtts_conv1d_packed_bytes.argtypes, L.gtts_conv1d_packed_bytes.restype = [vp], sz
+        L.gtts_conv1d_pack.argtypes = [vp, vp, vp, vp]
+        L.gtts_conv1d_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, f, f, vp, vp, i, i, vp]
+        L.gtts_conv1d_instance.argtypes = [vp, i, i, i, i, i, ctypes.POINTER(i * 5)]
         L.gtts_voc_hop.argtypes = [vp]
         L.gtts_voc_forward.argtypes = [vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_plan_num_tensors.argtypes = [vp]
@@ -737,6 +743,64 @@ class Vocoder(_Native):
             _check(lib().gtts_voc_forward(self._h, _ptr(blob), _ptr(mel), _ptr(wav), _ptr(ws), ws.numel(), B, T, _stream()),
                    "gtts_voc_forward")
         return wav
+
+
+class Conv1dOp(_Native):
+    """One layer of the shared 1-D convolution kernel (csrc/conv1d.h) -- the kernel of every dense layer of the vocoder and of both
+    encoders -- for its per-layer tests.  mode 0: Conv1d(cin, cout, K, dilation, 'same' padding); mode 1: ConvTranspose1d(cin, cout,
+    K = 2 S, stride S, padding S / 2).  The handle has no parameters of its own: pack() takes the reference module's weight."""
+    _family = "conv1d"
+
+    def __init__(self, mode, cin, cout, K, dilation=1, S=1):
+        self.mode, self.cin, self.cout, self.K, self.S = int(mode), int(cin), int(cout), int(K), int(S)
+        kw = dict(mode=int(mode), cin=int(cin), cout=int(cout), K=int(K), dilation=int(dilation), S=int(S))
+        self._open(kw, *[kw[k] for k in ("mode", "cin", "cout", "K", "dilation", "S")])
+
+    def instance(self, B, Lin, res=False, accmode=0, out_mask=False):
+        """(MT, TPS, AITER, KCH, epilogue) of the kernel instance forward() launches at this shape (a host call; epilogue 0: buffer
+        descriptors, 1 / 2: ConvTranspose1d 16-byte / two 8-byte stores, 3: generic); raises where forward() would refuse."""
+        info = (ctypes.c_int * 5)()
+        self._call("instance", self._h, int(B), int(Lin), int(bool(res)), int(accmode), int(bool(out_mask)), ctypes.byref(info))
+        return tuple(info)
+
+    def pack(self, weight, device):
+        """weight: Conv1d [cout, cin, K] / ConvTranspose1d [cin, cout, K]."""
+        want = (self.cout, self.cin, self.K) if self.mode == 0 else (self.cin, self.cout, self.K)
+        if tuple(weight.shape) != want:
+            raise RuntimeError("weight has shape %s, expected %s" % (tuple(weight.shape), want))
+        w = weight.detach().to(device=device, dtype=torch.float32).contiguous()
+        if not w.is_cuda:
+            raise RuntimeError("the weights are packed for a HIP device (got %s)" % w.device)
+        blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=w.device)
+        with torch.cuda.device(w.device):
+            self._call("pack", self._h, _ptr(w), _ptr(blob), _stream())
+            torch.cuda.current_stream().synchronize()
+        return blob
+
+    def forward(self, blob, bias, x, out=None, res=None, accsrc=None, accmode=0, div=1.0, slope=1.0, in_mask=None, out_mask=None):
+        """x [B, cin, Lin] -> [B, cout, Lin * S] (written into `out` when given).  Every tensor must be contiguous fp32 on x's HIP
+        device: views into larger allocations are passed as they are, nothing is copied."""
+        if not x.is_cuda:
+            raise RuntimeError("x must live on a HIP device (got %s); there is no CPU fallback" % x.device)
+        B, cin, Lin = x.shape
+        if cin != self.cin:
+            raise RuntimeError("expected %d input channels, got %d" % (self.cin, cin))
+        if out is None:
+            out = torch.empty((B, self.cout, Lin * self.S), dtype=torch.float32, device=x.device)
+        shapes = {"bias": (self.cout,), "out": (B, self.cout, Lin * self.S), "res": (B, self.cout, Lin * self.S),
+                  "accsrc": (B, self.cout, Lin * self.S), "in_mask": (B, Lin), "out_mask": (B, Lin * self.S)}
+        given = {"x": x, "bias": bias, "out": out, "res": res, "accsrc": accsrc, "in_mask": in_mask, "out_mask": out_mask}
+        for name, t in given.items():
+            if t is None:
+                continue
+            if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("%s must be a contiguous fp32 tensor on %s" % (name, x.device))
+            if name in shapes and tuple(t.shape) != shapes[name]:
+                raise RuntimeError("%s has shape %s, expected %s" % (name, tuple(t.shape), shapes[name]))
+        with _on(x.device):
+            self._call("forward", self._h, _ptr(blob), _ptr(bias), _ptr(x), _ptr(out), _ptr(res), _ptr(accsrc), int(accmode), float(div),
+                       float(slope), _ptr(in_mask), _ptr(out_mask), B, Lin, _stream())
+        return out
 
 
 class Encoder(_Native):

@@ -34,6 +34,18 @@ struct C1Args {
     const float *out_mask;   // [B][Lin * S] multiplied into the result, or nullptr
 };
 
+// Epilogue of a launch (the same for every workgroup; the kernel and the host's description of a launch share this one decision):
+//   BUFFER   plain convolution on whole row tiles: residual, running sum and output through buffer descriptors
+//   UP16/UP8 ConvTranspose1d on whole row tiles with nothing fused behind the bias: 16-byte (S >= 4) / two 8-byte (S == 2) stores
+//   GENERIC  everything else (a partial last row tile, a ConvTranspose1d with a residual, running sum or output mask): pointer path
+enum C1Epilogue { C1_EPI_BUFFER = 0, C1_EPI_UP16 = 1, C1_EPI_UP8 = 2, C1_EPI_GENERIC = 3 };
+__host__ __device__ inline int c1_epilogue(const C1Args &a, int MT) {
+    if ((a.cout * a.S) % MT != 0) return C1_EPI_GENERIC;
+    if (a.S == 1) return C1_EPI_BUFFER;
+    if (!a.res && a.accmode == 0 && !a.out_mask) return a.ls >= 2 ? C1_EPI_UP16 : C1_EPI_UP8;
+    return C1_EPI_GENERIC;
+}
+
 // Occupancy by tile: the 32- and 64-row tiles (HiFi-GAN's last two stages, the encoders' small layers) are bandwidth /
 // latency bound -- a workgroup's whole life is a handful of dependent memory round trips -- and want many workgroups per CU;
 // the 128-row tile is MFMA-bound and keeps the deeper (two chunks ahead) activation prefetch instead.
@@ -88,10 +100,14 @@ __global__ __launch_bounds__(256, (WM * MF == 1) ? 4 : (WM * MF == 2 ? 3 : GTTS_
     // Activations are prefetched TWO chunks ahead into two statically indexed register sets: a 1-D convolution has only
     // `taps` MFMA groups per chunk (a third of the 3x3 kernel's), so one chunk of MFMAs does not cover an HBM round trip.
     float araw2[PF2 ? 2 : 1][AITER][8];
-    // Buffer loads (the launcher requires cin % 16 == 0 -- every layer of the vocoder and the encoders -- and a sample below
-    // 2 GB): per-lane byte offset of (first channel of the item's 8-group, position), out-of-range items point past the
-    // descriptor and read 0, the chunk / channel offset rides in an SGPR -- no 64-bit VALU address arithmetic and no exec-mask
-    // branch per load (plain pointer loads under a validity select compile to one s_cbranch_execz per element)
+    // Buffer loads (the launcher requires a sample below 2 GB, counted in whole 16-channel chunks): per-lane byte offset of (first
+    // channel of the item's 8-group, position), out-of-range items point past the descriptor and read 0, the chunk / channel offset
+    // rides in an SGPR -- no 64-bit VALU address arithmetic and no exec-mask branch per load (plain pointer loads under a validity
+    // select compile to one s_cbranch_execz per element).  cin need NOT be a multiple of 16 (HiFi-GAN configurations below 16
+    // channels, n_mels % 16 != 0): the pad channels of the last chunk have per-lane + SGPR offset >= cin * Lin * 4, and on gfx950 the
+    // range check of a raw buffer access counts the SGPR offset in -- they read 0 whatever follows the sample in memory, which the
+    // zero weights they meet need (NaN * 0 = NaN).  LLVM documents soffset as excluded from the check, so this is measured, not
+    // promised: tests/test_gpu_conv1d.py runs such layers between NaN-filled margins.
     const int xbytes = a.cin * a.Lin * 4;
     const unsigned long long xaddr = reinterpret_cast<unsigned long long>(xb);
     const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(
@@ -219,7 +235,8 @@ __global__ __launch_bounds__(256, (WM * MF == 1) ? 4 : (WM * MF == 2 ? 3 : GTTS_
             const int m = cot * MT + m0 + mi * 32 + (rg & 3) + 8 * (rg >> 2) + 4 * kgl;
             bv[mi][rg] = a.bias[min(m, M - 1) >> a.ls];
         }
-    if (a.S == 1 && M % MT == 0) {
+    const int epi = c1_epilogue(a, MT);
+    if (epi == C1_EPI_BUFFER) {
         // Plain convolutions on whole row tiles (every ResBlock / encoder layer): residual, running sum and output go through
         // buffer descriptors of this sample's tensors -- per-lane byte offset = (the lane's 4-row sub-block, position), the row
         // offset of each of the 16 x MF values in an SGPR -- so the 64 (x 3 arrays) accesses of a lane need no 64-bit VALU address
@@ -272,7 +289,7 @@ __global__ __launch_bounds__(256, (WM * MF == 1) ? 4 : (WM * MF == 2 ? 3 : GTTS_
         }
         return;
     }
-    if (a.S >= 2 && M % MT == 0 && !a.res && a.accmode == 0 && !a.out_mask) {
+    if (epi == C1_EPI_UP16 || epi == C1_EPI_UP8) {
         // ConvTranspose1d (every upsampling layer): the four consecutive rows (rg & 3) of a C/D fragment are four consecutive
         // output phases of one channel (S >= 4) or two phases of two adjacent channels (S == 2): one 16-byte / two 8-byte
         // buffer stores per lane instead of four scalar stores with 64-bit address arithmetic each.
@@ -296,7 +313,7 @@ __global__ __launch_bounds__(256, (WM * MF == 1) ? 4 : (WM * MF == 2 ? 3 : GTTS_
                     float v[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] = acc[mi][ni][4 * g + i] + bv[mi][4 * g + i];
-                    if (a.ls >= 2) {
+                    if (epi == C1_EPI_UP16) {
                         const int co = m4 >> a.ls, r0 = m4 & (a.S - 1);
                         const int voff = ok ? (co * Lout + qs + r0) * 4 : tbytes;
                         u32x4 pk;
@@ -369,27 +386,39 @@ static C1Geom c1_geom(int M, int ntap_real) {
     return g;
 }
 
-template <int TPS>
-static hipError_t launch_c1_t(const C1Args &a, hipStream_t st) {
-    const int M = a.cout * a.S;
-    const C1Geom g = c1_geom(M, TPS == 3 ? 3 : 4);
+// The instance a launch runs: one of the nine compiled ones, AITER = 0 when none holds the layer's halo (2 * KCH * npx staging items
+// must fit AITER * 256).  launch_c1_t dispatches on exactly this, and gtts_conv1d_instance reports it.
+struct C1Inst { int MT, TPS, AITER, KCH, epilogue; };
+static inline C1Inst c1_instance(const C1Args &a, int tps) {
+    const C1Geom g = c1_geom(a.cout * a.S, tps == 3 ? 3 : 4);
+    C1Inst r = {g.MT, tps, 0, 1, c1_epilogue(a, g.MT)};
     const int aiter = (2 * a.npx + 255) / 256;
-    if constexpr (TPS == 3) {
-        // three-tap layers on the 128-row tile: 32 channels per step when the channel count allows it (see the kernel comment)
-        if (g.MT == 128 && a.nchunk % 2 == 0 && a.cin % 32 == 0) {
-            const int aiter2 = (4 * a.npx + 255) / 256;
-            if (aiter2 <= 3) return launch_c1_cfg<2, 2, 2, 3, 3, 2>(a, st);
-        }
-    }
-    if (g.MT == 128) {
-        if (aiter <= 2) return launch_c1_cfg<2, 2, 2, TPS, 2>(a, st);
-        if (aiter == 3) return launch_c1_cfg<2, 2, 2, TPS, 3>(a, st);
-    } else if (g.MT == 64) {
-        if (aiter <= 3) return launch_c1_cfg<1, 4, 2, TPS, 3>(a, st);
+    // three-tap layers on the 128-row tile: 32 channels per step when the channel count allows it (see the kernel comment)
+    if (tps == 3 && g.MT == 128 && a.nchunk % 2 == 0 && a.cin % 32 == 0 && (4 * a.npx + 255) / 256 <= 3) {
+        r.AITER = 3;
+        r.KCH = 2;
+    } else if (g.MT == 128) {
+        r.AITER = aiter <= 2 ? 2 : (aiter == 3 ? 3 : 0);
     } else {
-        if (aiter <= 3) return launch_c1_cfg<1, 4, 1, TPS, 3>(a, st);
+        r.AITER = aiter <= 3 ? 3 : 0;
     }
+    return r;
+}
+
+template <int TPS>
+static hipError_t launch_c1_t(const C1Args &a, const C1Inst &r, hipStream_t st) {
+    if constexpr (TPS == 3) {
+        if (r.KCH == 2) return launch_c1_cfg<2, 2, 2, 3, 3, 2>(a, st);
+    }
+    if (r.MT == 128 && r.AITER == 2) return launch_c1_cfg<2, 2, 2, TPS, 2>(a, st);
+    if (r.MT == 128 && r.AITER == 3) return launch_c1_cfg<2, 2, 2, TPS, 3>(a, st);
+    if (r.MT == 64 && r.AITER == 3) return launch_c1_cfg<1, 4, 2, TPS, 3>(a, st);
+    if (r.MT == 32 && r.AITER == 3) return launch_c1_cfg<1, 4, 1, TPS, 3>(a, st);
     return hipErrorInvalidValue;
+}
+// launch a planned call (conv1d_plan below filled a's geometry and chose r)
+static inline hipError_t launch_c1(const C1Args &a, const C1Inst &r, hipStream_t st) {
+    return r.TPS == 3 ? launch_c1_t<3>(a, r, st) : launch_c1_t<4>(a, r, st);
 }
 
 // ---- weight packer: reference layouts -> [chunk][stage][cot][split][tap][kg][MT][8] bf16 (hi, lo)
@@ -453,10 +482,23 @@ static inline size_t conv1d_packed_bytes(int mode, int cin, int cout, int K, int
     return nchunk * nst * ncot * (size_t)2 * g.tps * 2 * g.MT * 16;
 }
 
-// fill the geometry fields of a[] for a Conv1d (mode 0: kernel K, dilation dil) or a ConvTranspose1d (mode 1) and launch
-static inline hipError_t launch_conv1d(C1Args a, int mode, int K, int dil, hipStream_t st) {
+// Why a call is refused (host side, before anything is launched)
+enum C1Refusal { C1_OK = 0, C1_E_TAPS, C1_E_STRIDE, C1_E_SIZE, C1_E_HALO };
+static inline const char *c1_refusal_text(int r) {
+    switch (r) {
+    case C1_E_TAPS: return "more taps than the kernel's offset table holds (C1_MAXTAP = 12)";
+    case C1_E_STRIDE: return "the stride must be a power of two";
+    case C1_E_SIZE: return "a sample's input (in whole 16-channel chunks) or output reaches 2^31 bytes";
+    case C1_E_HALO: return "halo too wide: no kernel instance stages the tile plus (k - 1) * dilation positions";
+    default: return "ok";
+    }
+}
+// The one place that knows the geometry: fills the geometry fields of a (nchunk, nst, toff, halo_lo, npx, ls) for a Conv1d (mode 0:
+// kernel K, dilation dil) or a ConvTranspose1d (mode 1), checks everything the kernel's 32-bit arithmetic relies on and picks the
+// instance.  Host arithmetic only -- a's pointers are looked at (null or not: the epilogue), never through.
+static inline int conv1d_plan(C1Args &a, int mode, int K, int dil, C1Inst *inst) {
     const int real = mode == 0 ? K : 3;
-    if (real > C1_MAXTAP) return hipErrorInvalidValue;
+    if (real < 1 || real > C1_MAXTAP) return C1_E_TAPS;
     const C1Geom g = c1_geom(a.cout * a.S, real);
     a.nchunk = (a.cin + 15) / 16;
     a.nst = (real + g.tps - 1) / g.tps;
@@ -470,12 +512,20 @@ static inline hipError_t launch_conv1d(C1Args a, int mode, int K, int dil, hipSt
     a.halo_lo = -lo;
     a.npx = g.NT + hi - lo;
     a.ls = 0;
+    if (a.S < 1 || a.S > 1024) return C1_E_STRIDE;
     while ((1 << a.ls) < a.S) ++a.ls;
-    if ((1 << a.ls) != a.S) return hipErrorInvalidValue;
-    // (the buffer-descriptor epilogues address a sample's OUTPUT with 32-bit byte offsets: cout * Lout * 4 bytes, Lout = Lin * S)
-    if ((size_t)a.cout * a.Lin * a.S * 4 >= ((size_t)1 << 31)) return hipErrorInvalidValue;
-    if (a.cin % 16 != 0 || (size_t)a.cin * a.Lin * 4 >= ((size_t)1 << 31)) return hipErrorInvalidValue;   // buffer-load staging
-    return g.tps == 3 ? launch_c1_t<3>(a, st) : launch_c1_t<4>(a, st);
+    if ((1 << a.ls) != a.S) return C1_E_STRIDE;
+    // (the buffer-descriptor epilogues address a sample's OUTPUT with 32-bit byte offsets: cout * Lout * 4 bytes, Lout = Lin * S;
+    //  the buffer-load staging a sample's INPUT, its SGPR channel offset running to the end of the last 16-channel chunk)
+    if ((size_t)a.cout * a.Lin * a.S * 4 >= ((size_t)1 << 31)) return C1_E_SIZE;
+    if ((size_t)a.nchunk * 16 * a.Lin * 4 >= ((size_t)1 << 31)) return C1_E_SIZE;
+    *inst = c1_instance(a, g.tps);
+    return inst->AITER ? C1_OK : C1_E_HALO;
+}
+static inline hipError_t launch_conv1d(C1Args a, int mode, int K, int dil, hipStream_t st) {
+    C1Inst inst;
+    if (conv1d_plan(a, mode, K, dil, &inst) != C1_OK) return hipErrorInvalidValue;
+    return launch_c1(a, inst, st);
 }
 
 }  // namespace gtts

@@ -67,10 +67,7 @@ struct VocLayer {
     std::string name;
     int mode;              // 0 Conv1d, 1 ConvTranspose1d
     int cin, cout, K, dil, S, pad;
-    int ntap, nst, tps, MT;
-    int toff[C1_MAXTAP];
-    int halo_lo, halo_hi;
-    size_t w_off, b_off;   // blob offsets (packed weights, fp32 bias)
+    size_t w_off, b_off;   // blob offsets (packed weights, fp32 bias); tiling, taps and halo are conv1d.h's business
 };
 struct gtts_voc {
     gtts_voc_cfg cfg;
@@ -86,22 +83,8 @@ struct gtts_voc {
 static int voc_add_layer(gtts_voc *v, const std::string &name, int mode, int cin, int cout, int K, int dil, int S, int pad) {
     VocLayer L;
     L.name = name; L.mode = mode; L.cin = cin; L.cout = cout; L.K = K; L.dil = dil; L.S = S; L.pad = pad;
-    const int real = mode == 0 ? K : 3;
-    const C1Geom g = c1_geom(cout * S, real);
-    L.tps = g.tps; L.MT = g.MT;
-    L.nst = (real + g.tps - 1) / g.tps;
-    L.ntap = L.nst * g.tps;
-    int lo = 0, hi = 0;
-    for (int t = 0; t < C1_MAXTAP; ++t) L.toff[t] = 0;
-    for (int t = 0; t < real; ++t) {
-        L.toff[t] = mode == 0 ? (t - (K - 1) / 2) * dil : t - 1;
-        lo = std::min(lo, L.toff[t]);
-        hi = std::max(hi, L.toff[t]);
-    }
-    L.halo_lo = -lo; L.halo_hi = hi;
-    const size_t nchunk = (cin + 15) / 16, ncot = ((size_t)cout * S + g.MT - 1) / g.MT;
     L.w_off = v->blob_bytes;
-    v->blob_bytes = align256(v->blob_bytes + nchunk * L.nst * ncot * (size_t)2 * g.tps * 2 * g.MT * 16);
+    v->blob_bytes = align256(v->blob_bytes + conv1d_packed_bytes(mode, cin, cout, K, S));
     L.b_off = v->blob_bytes;
     v->blob_bytes = align256(v->blob_bytes + (size_t)cout * 4);
     v->layers.push_back(L);
@@ -150,7 +133,7 @@ extern "C" int gtts_voc_create(const gtts_voc_cfg *cfg, gtts_voc **out) {
                 }
             }
             for (int id : ids)
-                if (v->layers[id].halo_lo + v->layers[id].halo_hi > 128) { delete v; return fail(GTTS_E_CONFIG, "receptive field too wide"); }
+                if ((v->layers[id].K - 1) * v->layers[id].dil > 128) { delete v; return fail(GTTS_E_CONFIG, "receptive field too wide"); }
             v->rb.back().push_back(ids);
         }
     }
@@ -201,12 +184,7 @@ extern "C" int gtts_voc_pack(const gtts_voc *v, const void *const *ptrs, int n_p
         const VocLayer &L = v->layers[li];
         const float *w = (const float *)ptrs[2 * li], *bb = (const float *)ptrs[2 * li + 1];
         if (!w || !bb) return fail(GTTS_E_NULL, "parameter of %s is null", L.name.c_str());
-        const int nchunk = (L.cin + 15) / 16, ncot = (L.cout * L.S + L.MT - 1) / L.MT;
-        const size_t total = (size_t)nchunk * L.nst * ncot * L.tps * 2 * L.MT * 8;
-        hipLaunchKernelGGL(pack_conv1d_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w,
-                           reinterpret_cast<__bf16 *>(blob + L.w_off), L.mode, L.cin, L.cout, L.K, L.S, L.pad, L.MT, L.nst, L.tps,
-                           nchunk, ncot, total);
-        GTTS_HIPCHK(hipGetLastError());
+        GTTS_HIPCHK(launch_pack_conv1d(w, blob + L.w_off, L.mode, L.cin, L.cout, L.K, L.S, L.pad, st));
         GTTS_HIPCHK(hipMemcpyAsync(blob + L.b_off, bb, (size_t)L.cout * 4, hipMemcpyDeviceToDevice, st));
     }
     if (!ptrs[2 * n] || !ptrs[2 * n + 1]) return fail(GTTS_E_NULL, "conv_post parameter is null");
@@ -237,41 +215,37 @@ extern "C" int gtts_voc_hop(const gtts_voc *v) {
     return hop;
 }
 
+// One layer of the walk below.  dry: plan only -- geometry, size checks and the choice of instance (conv1d_plan, host arithmetic) --
+// so that gtts_voc_forward can refuse a shape before its first launch; else plan and launch.
 static int voc_run_layer(const gtts_voc *v, const unsigned char *blob, int li, const float *x, float *out, const float *res,
-                         const float *accsrc, int accmode, float slope, int B, int Lin, hipStream_t st) {
+                         const float *accsrc, int accmode, float slope, int B, int Lin, hipStream_t st, bool dry) {
     const VocLayer &L = v->layers[li];
-    C1Args a;
+    C1Args a = {};
     a.x = x; a.out = out; a.res = res; a.accsrc = accsrc; a.w = blob + L.w_off; a.bias = (const float *)(blob + L.b_off);
     a.B = B; a.cin = L.cin; a.cout = L.cout; a.Lin = Lin; a.S = L.S;
-    a.nchunk = (L.cin + 15) / 16; a.nst = L.nst;
-    for (int t = 0; t < C1_MAXTAP; ++t) a.toff[t] = L.toff[t];
-    a.halo_lo = L.halo_lo;
-    const C1Geom g = c1_geom(L.cout * L.S, L.mode == 0 ? L.K : 3);
-    a.npx = g.NT + L.halo_lo + L.halo_hi;
     a.slope = slope; a.accmode = accmode; a.div = (float)v->cfg.n_kernels;
     a.in_mask = nullptr; a.out_mask = nullptr;
-    a.ls = 0;
-    while ((1 << a.ls) < L.S) ++a.ls;
-    if ((size_t)L.cout * Lin * L.S >= ((size_t)1 << 31)) return fail(GTTS_E_SHAPE, "%s: tensor too large", L.name.c_str());
-    const hipError_t e = L.tps == 3 ? launch_c1_t<3>(a, st) : launch_c1_t<4>(a, st);
+    C1Inst inst;
+    const int r = conv1d_plan(a, L.mode, L.K, L.dil, &inst);
+    if (r != C1_OK)
+        return fail(r == C1_E_SIZE ? GTTS_E_SHAPE : GTTS_E_CONFIG, "%s (B %d, %d -> %d channels, %d positions in): %s", L.name.c_str(), B,
+                    L.cin, L.cout, Lin, c1_refusal_text(r));
+    if (dry) return GTTS_OK;
+    const hipError_t e = launch_c1(a, inst, st);
     if (e != hipSuccess) return fail(GTTS_E_HIP, "conv1d %s: %s", L.name.c_str(), hipGetErrorString(e));
     return GTTS_OK;
 }
 
-// Generator.forward (models.py:103-120): mel [B, n_mels, T] -> wav [B, 1, T * hop]
-extern "C" int gtts_voc_forward(const gtts_voc *v, const void *packed, const float *mel, float *wav, void *workspace,
-                                size_t workspace_bytes, int B, int T, gtts_stream_t stream) {
-    if (!v || !packed || !mel || !wav || !workspace) return fail(GTTS_E_NULL, "gtts_voc_forward: null argument");
-    if (B <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_voc_forward: bad shape B=%d T=%d", B, T);
-    const size_t need = gtts_voc_workspace_bytes(v, B, T);
-    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    hipStream_t st = (hipStream_t)stream;
+// Generator.forward (models.py:103-120): mel [B, n_mels, T] -> wav [B, 1, T * hop].  The layers of one call in launch order;
+// dry: every layer is planned and nothing is launched (no HIP call at all)
+static int voc_walk(const gtts_voc *v, const void *packed, const float *mel, float *wav, void *workspace, size_t need, int B, int T,
+                    hipStream_t st, bool dry) {
     const unsigned char *blob = (const unsigned char *)packed;
     const size_t slot = need / 5;
     float *buf[5];
     for (int i = 0; i < 5; ++i) buf[i] = (float *)((unsigned char *)workspace + i * slot);
     const float LR = 0.1f;                                        // LRELU_SLOPE (models.py:10)
-    int rc = voc_run_layer(v, blob, v->pre, mel, buf[0], nullptr, nullptr, 0, 1.0f, B, T, st);     // conv_pre (:104)
+    int rc = voc_run_layer(v, blob, v->pre, mel, buf[0], nullptr, nullptr, 0, 1.0f, B, T, st, dry);     // conv_pre (:104)
     if (rc) return rc;
     float *cur = buf[0];                                          // stage input
     size_t len = (size_t)T;
@@ -282,7 +256,7 @@ extern "C" int gtts_voc_forward(const gtts_voc *v, const void *packed, const flo
         for (int k = 0, j = 0; k < 5; ++k) if (buf[k] != cur) w4[j++] = buf[k];
         float *X = w4[0], *T1 = w4[1], *R = w4[2], *XS = w4[3];
         // x = ups[i](leaky_relu(x, 0.1))  (:105-106).  From stage 1 on `cur` holds the ResBlock mean already.
-        rc = voc_run_layer(v, blob, v->ups[i], cur, X, nullptr, nullptr, 0, LR, B, (int)len, st);
+        rc = voc_run_layer(v, blob, v->ups[i], cur, X, nullptr, nullptr, 0, LR, B, (int)len, st, dry);
         if (rc) return rc;
         len *= v->cfg.upsample_rates[i];
         for (int j = 0; j < nk; ++j) {
@@ -293,11 +267,11 @@ extern "C" int gtts_voc_forward(const gtts_voc *v, const void *packed, const flo
                 // ResBlock1 (:37-44): three times  xt = c2(lrelu(c1(lrelu(x))));  x = xt + x
                 for (int d = 0; d < 3; ++d) {
                     const float *xin = d == 0 ? X : R;
-                    rc = voc_run_layer(v, blob, ids[d], xin, T1, nullptr, nullptr, 0, LR, B, (int)len, st);
+                    rc = voc_run_layer(v, blob, ids[d], xin, T1, nullptr, nullptr, 0, LR, B, (int)len, st, dry);
                     if (rc) return rc;
                     const bool last = d == 2;
                     rc = voc_run_layer(v, blob, ids[3 + d], T1, last ? XS : R, xin, last && accmode ? XS : nullptr,
-                                       last ? accmode : 0, LR, B, (int)len, st);
+                                       last ? accmode : 0, LR, B, (int)len, st, dry);
                     if (rc) return rc;
                 }
             } else {
@@ -306,7 +280,7 @@ extern "C" int gtts_voc_forward(const gtts_voc *v, const void *packed, const flo
                     const float *xin = d == 0 ? X : R;
                     const bool last = d == 1;
                     rc = voc_run_layer(v, blob, ids[d], xin, last ? XS : R, xin, last && accmode ? XS : nullptr,
-                                       last ? accmode : 0, LR, B, (int)len, st);
+                                       last ? accmode : 0, LR, B, (int)len, st, dry);
                     if (rc) return rc;
                 }
             }
@@ -316,8 +290,20 @@ extern "C" int gtts_voc_forward(const gtts_voc *v, const void *packed, const flo
     // x = tanh(conv_post(leaky_relu(x)))  (:116-118; default slope 0.01)
     const int C = v->post_cin;
     if (v->post_K != 7 || len % 4 != 0) return fail(GTTS_E_CONFIG, "conv_post needs k = 7 and a multiple-of-4 length");
+    if (dry) return GTTS_OK;
     hipLaunchKernelGGL(conv_post_kernel, dim3((unsigned)((len / 4 + 255) / 256), B), dim3(256), (size_t)C * v->post_K * 4, st, cur,
                        (const float *)(blob + v->post_w_off), (const float *)(blob + v->post_b_off), wav, C, (int)len, v->post_K, 0.01f);
     GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
+}
+
+extern "C" int gtts_voc_forward(const gtts_voc *v, const void *packed, const float *mel, float *wav, void *workspace,
+                                size_t workspace_bytes, int B, int T, gtts_stream_t stream) {
+    if (!v || !packed || !mel || !wav || !workspace) return fail(GTTS_E_NULL, "gtts_voc_forward: null argument");
+    if (B <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_voc_forward: bad shape B=%d T=%d", B, T);
+    const size_t need = gtts_voc_workspace_bytes(v, B, T);
+    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    // every layer's geometry and size first: a refused shape has launched nothing
+    const int rc = voc_walk(v, packed, mel, wav, workspace, need, B, T, (hipStream_t)stream, true);
+    return rc ? rc : voc_walk(v, packed, mel, wav, workspace, need, B, T, (hipStream_t)stream, false);
 }

@@ -59,6 +59,35 @@ def test_vocoder_matches_oracle_odd_shapes(S, dev, B, T):
     assert float((wav - ref).abs().max()) <= 1e-4
 
 
+@pytest.mark.parametrize("B,T", [(2, 5), (1, 1)])
+def test_vocoder_does_not_depend_on_what_the_workspace_holds(S, dev, B, T):
+    """SMALL runs its last stage at 4 channels: the staged 16-channel chunk has 12 pad channels, whose addresses lie in the next
+    sample, the next workspace slot or past the workspace.  They meet zero weights, so they must be READ as zero -- NaN * 0 = NaN.
+    The workspace Vocoder.forward itself uses (the cached tensor) is filled with NaN bit patterns, then with zeros: finite, within
+    the bounds of this file, and the same bits both times.  (Measured: the MI355X counts the SGPR offset of a buffer load into its
+    range check and the pad channels do read 0 -- shown between NaN margins by the cin % 16 != 0 cases of tests/test_gpu_conv1d.py.
+    Here the slots behind a 4-channel tensor hold live finite tensors by the last stage, so this test guards the property for the
+    vocoder as a whole rather than the mechanism: DESIGN section 4.6.1.)"""
+    cfg = H.SMALL
+    sd = H.make_state(cfg, seed=5, gain=1.0)
+    mel = H.make_mel(B, T, seed=T)
+    ref = H.generator_forward(sd, cfg, mel)
+    voc = S.Vocoder(**cfg)
+    blob = voc.pack(sd, dev)
+    ws = voc.workspace(B, T, dev)
+    ws.view(torch.int32).fill_(-1)                       # 0xffffffff: a NaN in every fp32 slot
+    wav_nan = voc.forward(blob, mel.to(dev)).cpu()
+    assert voc.workspace(B, T, dev) is ws                # forward() ran in the tensor that was filled
+    print("B %d T %d, NaN workspace: finite %s, max|err| %.2e" % (B, T, bool(torch.isfinite(wav_nan).all()),
+                                                                  float((wav_nan - ref).abs().max())))
+    assert bool(torch.isfinite(wav_nan).all())
+    assert relerr(wav_nan, ref) <= REL and float((wav_nan - ref).abs().max()) <= 1e-4
+    ws.zero_()
+    wav_zero = voc.forward(blob, mel.to(dev)).cpu()
+    assert voc.workspace(B, T, dev) is ws
+    assert torch.equal(wav_nan, wav_zero)
+
+
 def test_vocoder_v1_full_length_properties(S, dev):
     """The shape inference.py feeds it at the bench size (80 x 1024 frames -> 262 144 samples), V1 width: finite, in
     (-1, 1), run-to-run bit-identical, batch entries independent; one utterance against the CPU oracle (~10 s)."""
