@@ -278,6 +278,30 @@ int gtts_enc_attention_path(const gtts_enc *enc, int L);
  * mode 1: mel [B,n_feats,L], x_mask -> mu [B,n_feats,L] (the encoded mel); ids / logw are ignored. */
 int gtts_enc_forward(const gtts_enc *enc, const void *packed, const long long *ids, const float *mel, const float *x_mask,
                      float *mu, float *logw, void *workspace, size_t workspace_bytes, int B, int L, gtts_stream_t stream);
+/* ---- ABI 6 (additive): the encoders' two fp32 VALU ops as calls of their own -- the entries their per-op tests drive;
+ * gtts_enc_forward reaches its kernels through the same two launch functions.  All tensors fp32, contiguous, t fastest.
+ *
+ * gtts_enc_layernorm: LayerNorm over the channel axis per position (text_encoder.py:12-27: biased variance, two passes):
+ *   out[b][c][t] = relu_out?( (v - mean_c v) * rsqrt(var_c v + eps) * gamma[c] + beta[c] ) * out_mask[b][t],
+ *   v = relu_in?(a[b][c][t]) * a_mask[b][t] + bres[b][c][t].   a, bres, out [B][C][L]; gamma, beta [C]; a_mask, out_mask [B][L];
+ *   bres, a_mask and out_mask may be NULL (no residual / no mask); out must not overlap an input.
+ *   GTTS_E_NULL: a, gamma, beta or out NULL; GTTS_E_SHAPE: B, C or L < 1 or B > 65535; GTTS_E_CONFIG: eps <= 0.
+ *
+ * gtts_enc_attention: MultiHeadAttention.attention (text_encoder.py:145-175), self-attention with a relative window:
+ *   q, k, v, out [B][C][L] (head h = channels [h dk, (h + 1) dk), dk = C / n_heads), mask [B][L] (0 / 1: a score whose query or key is
+ *   masked is -1e4 before the softmax), emb_rel_k, emb_rel_v [2 window + 1][dk] shared by all heads.  window 0: no relative terms,
+ *   the two embedding pointers are not read and may be NULL.  path 0: the kernel gtts_enc_forward would run
+ *   (gtts_enc_attention_path_for); 16 / 8: that kernel.  Refused on the host before the device is touched:
+ *   GTTS_E_NULL (a required pointer), GTTS_E_SHAPE (B or L < 1, B or n_heads > 65535, L beyond the 160 KB of LDS of the kernel asked
+ *   for -- or of both under path 0), GTTS_E_CONFIG (C % n_heads, window < 0, a path other than 0 / 8 / 16, path 16 with dk % 4 != 0 or
+ *   window > 7). */
+int gtts_enc_layernorm(const float *a, const float *bres, const float *gamma, const float *beta, const float *a_mask,
+                       const float *out_mask, float *out, int B, int C, int L, float eps, int relu_in, int relu_out, gtts_stream_t stream);
+int gtts_enc_attention(const float *q, const float *k, const float *v, const float *mask, const float *emb_rel_k,
+                       const float *emb_rel_v, float *out, int B, int C, int L, int n_heads, int window, int path, gtts_stream_t stream);
+/* host only, no encoder handle: gtts_enc_attention_path for an encoder of these channels, heads and window at length L (0 also for
+ * channels, n_heads < 1, channels % n_heads != 0 or window < 0) */
+int gtts_enc_attention_path_for(int channels, int n_heads, int window, int L);
 
 /* ---- DiffVC PostNet (DiffVC/model/postnet.py:40-53; the last stage of the "average voice" encoder, vc.py:33-41):
  * x [B,n_feats,T], mask [B,T] -> out [B,n_feats,T].  dim % 64 == 0, 8 GroupNorm groups.  Parameter names are the module's

@@ -19,12 +19,24 @@ def sequence_mask(length, max_length=None):
     return torch.arange(int(max_length), dtype=length.dtype).unsqueeze(0) < length.unsqueeze(1)
 
 
-def layer_norm(sd, p, x, eps=1e-4):
-    """LayerNorm.forward, text_encoder.py:20-27 (over dim 1, biased variance)."""
+def layer_norm(sd, p, x, eps=1e-4, bres=None, a_mask=None, out_mask=None, relu_in=False, relu_out=False):
+    """LayerNorm.forward, text_encoder.py:20-27 (over dim 1, biased variance), with the prologues and epilogues its call sites put
+    around it:  relu_out?(LN(relu_in?(x) * a_mask + bres)) * out_mask   (masks [b, 1, t]; all off = the module alone)."""
+    if relu_in:
+        x = torch.relu(x)
+    if a_mask is not None:
+        x = x * a_mask
+    if bres is not None:
+        x = x + bres
     mean = torch.mean(x, 1, keepdim=True)
     var = torch.mean((x - mean) ** 2, 1, keepdim=True)
     x = (x - mean) * torch.rsqrt(var + eps)
-    return x * sd[p + "gamma"].view(1, -1, 1) + sd[p + "beta"].view(1, -1, 1)
+    x = x * sd[p + "gamma"].view(1, -1, 1) + sd[p + "beta"].view(1, -1, 1)
+    if relu_out:
+        x = torch.relu(x)
+    if out_mask is not None:
+        x = x * out_mask
+    return x
 
 
 def conv(sd, p, x, k):
@@ -67,9 +79,10 @@ def _abs_to_rel(x):
     return flat.view(b, h, l, 2 * l)[:, :, :, 1:]
 
 
-def attention(sd, p, x, attn_mask, n_heads, window):
-    """MultiHeadAttention.forward / attention, text_encoder.py:136-175 (self-attention, relative window)."""
-    q, k, v = conv(sd, p + "conv_q.", x, 1), conv(sd, p + "conv_k.", x, 1), conv(sd, p + "conv_v.", x, 1)
+def attention_core(q, k, v, attn_mask, ek, ev, n_heads, window):
+    """MultiHeadAttention.attention, text_encoder.py:145-175 (self-attention, relative window): q, k, v [b, d, t] as the three
+    convolutions leave them, attn_mask [b, 1, t, t], ek / ev = emb_rel_k / emb_rel_v [1, 2w+1, dk] (unused without a window)
+    -> [b, d, t], in the dtype of its arguments."""
     b, d, t = k.shape
     dk = d // n_heads
     q = q.view(b, n_heads, dk, t).transpose(2, 3)
@@ -77,16 +90,22 @@ def attention(sd, p, x, attn_mask, n_heads, window):
     v = v.view(b, n_heads, dk, t).transpose(2, 3)
     scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(dk)
     if window:
-        ek = _rel_embeddings(sd[p + "emb_rel_k"], t, window)
+        ek = _rel_embeddings(ek, t, window)
         rel = torch.matmul(q, ek.unsqueeze(0).transpose(-2, -1))
         scores = scores + _rel_to_abs(rel) / math.sqrt(dk)
     scores = scores.masked_fill(attn_mask == 0, -1e4)
     pa = F.softmax(scores, dim=-1)
     out = torch.matmul(pa, v)
     if window:
-        ev = _rel_embeddings(sd[p + "emb_rel_v"], t, window)
+        ev = _rel_embeddings(ev, t, window)
         out = out + torch.matmul(_abs_to_rel(pa), ev.unsqueeze(0))
-    out = out.transpose(2, 3).contiguous().view(b, d, t)
+    return out.transpose(2, 3).contiguous().view(b, d, t)
+
+
+def attention(sd, p, x, attn_mask, n_heads, window):
+    """MultiHeadAttention.forward, text_encoder.py:136-143: the three 1x1 convolutions, attention_core, conv_o."""
+    q, k, v = conv(sd, p + "conv_q.", x, 1), conv(sd, p + "conv_k.", x, 1), conv(sd, p + "conv_v.", x, 1)
+    out = attention_core(q, k, v, attn_mask, sd.get(p + "emb_rel_k"), sd.get(p + "emb_rel_v"), n_heads, window)
     return conv(sd, p + "conv_o.", out, 1)
 
 

@@ -6,6 +6,6 @@ The drop-in `model` package (same class names / signatures / state_dict as Grad-
 ``inference.py`` / ``train.py`` pick it up as ``from model import GradTTS``.
 """
 from . import _lib  # noqa: F401
-from ._lib import Plan, Vocoder, Encoder, Conv1dOp, PostNetPlan, MelPlan, WavPlan, FglPlan, SpkPlan, PREC_BF16, PREC_BF16_STORE, PREC_BF16X3, PREC_F16F8, RangeError, euler_step, mas_maximum_path, ge2e_loss  # noqa: F401
+from ._lib import Plan, Vocoder, Encoder, Conv1dOp, PostNetPlan, MelPlan, WavPlan, FglPlan, SpkPlan, PREC_BF16, PREC_BF16_STORE, PREC_BF16X3, PREC_F16F8, RangeError, euler_step, mas_maximum_path, ge2e_loss, enc_layernorm, enc_attention, enc_attention_path  # noqa: F401
 
 __all__ = ["Plan", "Vocoder", "Encoder", "Conv1dOp", "PostNetPlan", "MelPlan", "WavPlan", "FglPlan", "SpkPlan", "PREC_BF16", "PREC_BF16_STORE", "PREC_BF16X3", "PREC_F16F8", "RangeError", "euler_step", "mas_maximum_path", "ge2e_loss"]

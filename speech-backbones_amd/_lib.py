@@ -173,6 +173,9 @@ def lib():
         L.gtts_gn_mish_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.gtts_enc_attention_path.argtypes = [vp, i]
         L.gtts_enc_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
+        L.gtts_enc_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, f, i, i, vp]
+        L.gtts_enc_attention.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
+        L.gtts_enc_attention_path_for.argtypes = [i, i, i, i]
         L.gtts_postnet_forward.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_conv1d_create.argtypes = [i, i, i, i, i, i, ctypes.POINTER(vp)]
         L.gtts_conv1d_destroy.argtypes, L.gtts_conv1d_destroy.restype = [vp], None
@@ -845,6 +848,58 @@ class Encoder(_Native):
             _check(lib().gtts_enc_forward(self._h, _ptr(blob), _ptr(ids), _ptr(mel), _ptr(m), _ptr(mu), _ptr(logw), _ptr(ws),
                                           ws.numel(), B, L, _stream()), "gtts_enc_forward")
         return (mu, logw) if self.mode == "text" else mu
+
+
+def _enc_op_tensors(given, shapes, dev):
+    """The stand-alone encoder ops take views into larger allocations as they are: nothing is converted or copied."""
+    for name, t in given.items():
+        if t is None:
+            continue
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("%s must be a contiguous fp32 tensor on %s" % (name, dev))
+        if tuple(t.shape) != shapes[name]:
+            raise RuntimeError("%s has shape %s, expected %s" % (name, tuple(t.shape), shapes[name]))
+
+
+def enc_attention_path(channels, n_heads, window, L):
+    """Which attention kernel an encoder of these channels, heads and window runs at length L (16, 8, or 0: refused) -- a host
+    call, the decision of Encoder.attention_path without a handle."""
+    return int(lib().gtts_enc_attention_path_for(int(channels), int(n_heads), int(window or 0), int(L)))
+
+
+def enc_layernorm(a, gamma, beta, bres=None, a_mask=None, out_mask=None, eps=1e-4, relu_in=False, relu_out=False, out=None):
+    """The encoders' LayerNorm kernel on its own: relu_out?(LN_c(relu_in?(a) * a_mask + bres)) * out_mask.  a, bres [B,C,L]; gamma,
+    beta [C]; masks [B,L]; written into `out` when given.  The launch gtts_enc_forward makes, for the per-op tests."""
+    if not a.is_cuda:
+        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % a.device)
+    B, C, L = a.shape
+    if out is None:
+        out = torch.empty((B, C, L), dtype=torch.float32, device=a.device)
+    _enc_op_tensors(dict(a=a, bres=bres, gamma=gamma, beta=beta, a_mask=a_mask, out_mask=out_mask, out=out),
+                    dict(a=(B, C, L), bres=(B, C, L), gamma=(C,), beta=(C,), a_mask=(B, L), out_mask=(B, L), out=(B, C, L)), a.device)
+    with _on(a.device):
+        _check(lib().gtts_enc_layernorm(_ptr(a), _ptr(bres), _ptr(gamma), _ptr(beta), _ptr(a_mask), _ptr(out_mask), _ptr(out), B, C, L,
+                                        float(eps), int(bool(relu_in)), int(bool(relu_out)), _stream()), "gtts_enc_layernorm")
+    return out
+
+
+def enc_attention(q, k, v, mask, emb_rel_k=None, emb_rel_v=None, n_heads=2, window=0, path=0, out=None):
+    """The encoders' windowed relative-position attention kernel on its own: q, k, v [B,C,L], mask [B,L], emb_rel_k / emb_rel_v
+    [2 window + 1, C / n_heads] (window 0: none) -> [B,C,L].  path 0: the kernel Encoder.forward would run; 16 / 8: that kernel
+    (refused where it cannot serve the shape).  The launch gtts_enc_forward makes, for the per-op tests."""
+    if not q.is_cuda:
+        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % q.device)
+    B, C, L = q.shape
+    window = int(window or 0)
+    if out is None:
+        out = torch.empty((B, C, L), dtype=torch.float32, device=q.device)
+    rel = (2 * window + 1, C // max(int(n_heads), 1))
+    _enc_op_tensors(dict(q=q, k=k, v=v, mask=mask, emb_rel_k=emb_rel_k, emb_rel_v=emb_rel_v, out=out),
+                    dict(q=(B, C, L), k=(B, C, L), v=(B, C, L), mask=(B, L), emb_rel_k=rel, emb_rel_v=rel, out=(B, C, L)), q.device)
+    with _on(q.device):
+        _check(lib().gtts_enc_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(emb_rel_k), _ptr(emb_rel_v), _ptr(out), B, C, L,
+                                        int(n_heads), window, int(path), _stream()), "gtts_enc_attention")
+    return out
 
 
 class PostNetPlan(_Native):

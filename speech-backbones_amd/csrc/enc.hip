@@ -426,14 +426,78 @@ extern "C" int gtts_enc_pack(const gtts_enc *e, const void *const *ptrs, int n_p
 //    8: 8 * dk + 8 * L
 // The one place this is decided: gtts_enc_forward dispatches and refuses by it, gtts_enc_attention_path reports it.
 constexpr size_t ATT_LDS_LIMIT = (size_t)160 * 1024;
-static int enc_attention_path(const gtts_enc_cfg &cf, int L) {
-    if (L <= 0) return 0;
-    const int dk = cf.channels / cf.n_heads;
-    if (att16_smem_bytes(dk, L) <= ATT_LDS_LIMIT && dk % 4 == 0 && cf.window_size <= 7) return 16;
-    if (((size_t)ATT_QT * dk + (size_t)ATT_QT * L) * sizeof(float) <= ATT_LDS_LIMIT) return 8;
+static inline size_t att8_smem_bytes(int dk, int L) { return ((size_t)ATT_QT * dk + (size_t)ATT_QT * L) * sizeof(float); }
+static int enc_attention_path(int channels, int n_heads, int window, int L) {
+    if (L <= 0 || channels <= 0 || n_heads <= 0 || channels % n_heads || window < 0) return 0;
+    const int dk = channels / n_heads;
+    if (att16_smem_bytes(dk, L) <= ATT_LDS_LIMIT && dk % 4 == 0 && window <= 7) return 16;
+    if (att8_smem_bytes(dk, L) <= ATT_LDS_LIMIT) return 8;
     return 0;
 }
-extern "C" int gtts_enc_attention_path(const gtts_enc *e, int L) { return e ? enc_attention_path(e->cfg, L) : 0; }
+extern "C" int gtts_enc_attention_path(const gtts_enc *e, int L) {
+    return e ? enc_attention_path(e->cfg.channels, e->cfg.n_heads, e->cfg.window_size, L) : 0;
+}
+extern "C" int gtts_enc_attention_path_for(int channels, int n_heads, int window, int L) {
+    return enc_attention_path(channels, n_heads, window, L);
+}
+
+// ---- the two fp32 VALU ops as launches of their own: gtts_enc_forward reaches its kernels through these two functions and the
+// stand-alone entry points below are the same two functions behind argument checks, so a per-op test runs the encoder's own launches.
+static int enc_launch_layernorm(const float *a, const float *bres, const float *gamma, const float *beta, const float *a_mask,
+                                const float *out_mask, float *out, int B, int C, int L, float eps, int relu_in, int relu_out,
+                                hipStream_t st) {
+    hipLaunchKernelGGL(enc_layernorm_kernel, dim3((L + 15) / 16, B), dim3(256), 0, st, a, bres, gamma, beta, a_mask, out_mask, out, C, L,
+                       eps, relu_in ? 1 : 0, relu_out ? 1 : 0);
+    GTTS_HIPCHK(hipGetLastError());
+    return GTTS_OK;
+}
+// path: 0 = enc_attention_path's choice, 16 / 8 = that kernel.  Everything that can be refused is refused here, on the host, before
+// the first HIP call.  window 0: no relative embeddings (the kernels take win = -1 for that).
+static int enc_launch_attention(const float *q, const float *k, const float *v, const float *mask, const float *ek, const float *ev,
+                                float *out, int B, int C, int L, int heads, int window, int path, hipStream_t st) {
+    if (B <= 0 || L <= 0) return fail(GTTS_E_SHAPE, "attention: bad shape B=%d L=%d", B, L);
+    if (C <= 0 || heads <= 0 || C % heads || window < 0) return fail(GTTS_E_CONFIG, "attention: unsupported channels=%d n_heads=%d window=%d", C, heads, window);
+    if (path != 0 && path != 8 && path != 16) return fail(GTTS_E_CONFIG, "attention: path must be 0, 8 or 16 (got %d)", path);
+    if (B > 65535 || heads > 65535) return fail(GTTS_E_SHAPE, "attention: B=%d / n_heads=%d exceed the launch grid", B, heads);
+    const int dk = C / heads;
+    if (path == 16 && (dk % 4 || window > 7))
+        return fail(GTTS_E_CONFIG, "the 16-query attention kernel needs channels / n_heads %% 4 == 0 and a window of at most 7 (got %d, %d)", dk, window);
+    if (path == 16 && att16_smem_bytes(dk, L) > ATT_LDS_LIMIT)
+        return fail(GTTS_E_SHAPE, "sequence too long for the 16-query attention kernel (%d)", L);
+    if (path == 0) path = enc_attention_path(C, heads, window, L);
+    if (!path || (path == 8 && att8_smem_bytes(dk, L) > ATT_LDS_LIMIT))
+        return fail(GTTS_E_SHAPE, "sequence too long for the attention kernel (%d)", L);
+    const int win = window > 0 ? window : -1;
+    if (path == 16) {
+        const size_t smem16 = att16_smem_bytes(dk, L);
+        // 16 queries per workgroup, lanes along the keys (two workgroups per CU up to L ~ 1000)
+        GTTS_HIPCHK(raise_dyn_lds<&enc_attention16_kernel>(smem16));
+        hipLaunchKernelGGL(enc_attention16_kernel, dim3((L + ATT16_QT - 1) / ATT16_QT, heads, B), dim3(256), smem16, st, q, k, v, mask, ek,
+                           ev, out, C, L, heads, win);
+    } else {
+        const size_t smem = att8_smem_bytes(dk, L);
+        GTTS_HIPCHK(raise_dyn_lds<&enc_attention_kernel>(smem));
+        hipLaunchKernelGGL(enc_attention_kernel, dim3((L + ATT_QT - 1) / ATT_QT, heads, B), dim3(256), smem, st, q, k, v, mask, ek, ev, out,
+                           C, L, heads, win);
+    }
+    GTTS_HIPCHK(hipGetLastError());
+    return GTTS_OK;
+}
+extern "C" int gtts_enc_layernorm(const float *a, const float *bres, const float *gamma, const float *beta, const float *a_mask,
+                                  const float *out_mask, float *out, int B, int C, int L, float eps, int relu_in, int relu_out,
+                                  gtts_stream_t stream) {
+    if (!a || !gamma || !beta || !out) return fail(GTTS_E_NULL, "gtts_enc_layernorm: null argument");
+    if (B <= 0 || C <= 0 || L <= 0 || B > 65535) return fail(GTTS_E_SHAPE, "gtts_enc_layernorm: bad shape B=%d C=%d L=%d", B, C, L);
+    if (!(eps > 0.f)) return fail(GTTS_E_CONFIG, "gtts_enc_layernorm: eps must be positive");
+    return enc_launch_layernorm(a, bres, gamma, beta, a_mask, out_mask, out, B, C, L, eps, relu_in, relu_out, (hipStream_t)stream);
+}
+extern "C" int gtts_enc_attention(const float *q, const float *k, const float *v, const float *mask, const float *emb_rel_k,
+                                  const float *emb_rel_v, float *out, int B, int C, int L, int n_heads, int window, int path,
+                                  gtts_stream_t stream) {
+    if (!q || !k || !v || !mask || !out) return fail(GTTS_E_NULL, "gtts_enc_attention: null argument");
+    if (window > 0 && (!emb_rel_k || !emb_rel_v)) return fail(GTTS_E_NULL, "gtts_enc_attention: a window needs emb_rel_k and emb_rel_v");
+    return enc_launch_attention(q, k, v, mask, emb_rel_k, emb_rel_v, out, B, C, L, n_heads, window, path, (hipStream_t)stream);
+}
 
 // workspace: X, Y, Z (C channels), Q, K, V, A (C channels), H (max(filter, filter_dp) channels)
 static size_t enc_slot(const gtts_enc *e, int B, int L, int ch) { return align256((size_t)B * ch * L * 4); }
@@ -476,10 +540,7 @@ static int enc_ln(const EncRun &r, const std::string &name, const float *a, cons
                   bool relu_in, bool relu_out) {
     const float *g = bp(r, name + ".gamma"), *b = bp(r, name + ".beta");
     if (!g || !b) return fail(GTTS_E_CONFIG, "encoder has no layer %s", name.c_str());
-    hipLaunchKernelGGL(enc_layernorm_kernel, dim3((r.L + 15) / 16, r.B), dim3(256), 0, r.st, a, bres, g, b, a_mask ? r.mask : nullptr,
-                       (const float *)nullptr, out, C, r.L, 1e-4f, relu_in ? 1 : 0, relu_out ? 1 : 0);
-    GTTS_HIPCHK(hipGetLastError());
-    return GTTS_OK;
+    return enc_launch_layernorm(a, bres, g, b, a_mask ? r.mask : nullptr, nullptr, out, r.B, C, r.L, 1e-4f, relu_in, relu_out, r.st);
 }
 
 // TextEncoder.forward (text_encoder.py:310-326) / MelEncoder.forward (DiffVC encoder.py:279-284).
@@ -492,8 +553,8 @@ extern "C" int gtts_enc_forward(const gtts_enc *e, const void *packed, const lon
     if (cf.mode == 0 && (!ids || !logw)) return fail(GTTS_E_NULL, "TextEncoder needs ids and logw");
     if (cf.mode == 1 && !mel) return fail(GTTS_E_NULL, "MelEncoder needs mel");
     if (workspace_bytes < gtts_enc_workspace_bytes(e, B, L)) return fail(GTTS_E_WORKSPACE, "workspace too small");
-    const int C = cf.channels, dk = C / cf.n_heads;
-    const int path = enc_attention_path(cf, L);
+    const int C = cf.channels;
+    const int path = enc_attention_path(cf.channels, cf.n_heads, cf.window_size, L);
     if (!path) return fail(GTTS_E_SHAPE, "sequence too long for the attention kernel (%d)", L);
     hipStream_t st = (hipStream_t)stream;
     EncRun r{e, (const unsigned char *)packed, x_mask, B, L, st};
@@ -532,20 +593,7 @@ extern "C" int gtts_enc_forward(const gtts_enc *e, const void *packed, const lon
         if ((rc = enc_conv(r, p + "conv_k", x, K, true, false, nullptr, false))) return rc;
         if ((rc = enc_conv(r, p + "conv_v", x, V, true, false, nullptr, false))) return rc;
         const float *ek = bp(r, p + "emb_rel_k"), *ev = bp(r, p + "emb_rel_v");
-        const int win = cf.window_size > 0 ? cf.window_size : -1;
-        if (path == 16) {
-            const size_t smem16 = att16_smem_bytes(dk, L);
-            // 16 queries per workgroup, lanes along the keys (two workgroups per CU up to L ~ 1000)
-            GTTS_HIPCHK(raise_dyn_lds<&enc_attention16_kernel>(smem16));
-            hipLaunchKernelGGL(enc_attention16_kernel, dim3((L + ATT16_QT - 1) / ATT16_QT, cf.n_heads, B), dim3(256), smem16, st, Q, K, V,
-                               x_mask, ek, ev, A, C, L, cf.n_heads, win);
-        } else {
-            const size_t smem = (size_t)(ATT_QT * dk + ATT_QT * L) * 4;
-            GTTS_HIPCHK(raise_dyn_lds<&enc_attention_kernel>(smem));
-            hipLaunchKernelGGL(enc_attention_kernel, dim3((L + ATT_QT - 1) / ATT_QT, cf.n_heads, B), dim3(256), smem, st, Q, K, V, x_mask,
-                               ek, ev, A, C, L, cf.n_heads, win);
-        }
-        GTTS_HIPCHK(hipGetLastError());
+        if ((rc = enc_launch_attention(Q, K, V, x_mask, ek, ev, A, B, C, L, cf.n_heads, cf.window_size, path, st))) return rc;
         if ((rc = enc_conv(r, p + "conv_o", A, Z, false, false, nullptr, false))) return rc;
         snprintf(nm, sizeof nm, "encoder.norm_layers_1.%d", i);
         if ((rc = enc_ln(r, nm, x, Z, t1, C, true, false, false))) return rc;                          // LN(x * mask + y)

@@ -5,8 +5,9 @@ gtts_enc_attention_path reports the decision gtts_enc_forward dispatches by (one
 cases of tests/test_gpu_utterance_shapes.py read which kernel ran from the library.  Here the hand-over and the limit are derived
 from the documented LDS sizes (include/gradtts_abi.h) and the library must agree at every length around them.
 
-Every gtts_enc_forward call below is made with fake non-null addresses and MUST return before anything is dereferenced or launched:
-each is written against the guard it exercises (a call that passed every guard would launch kernels on those addresses)."""
+Every gtts_enc_forward / gtts_enc_layernorm / gtts_enc_attention call below is made with fake non-null addresses and MUST return
+before anything is dereferenced or launched: each is written against the guard it exercises (a call that passed every guard would
+launch kernels on those addresses)."""
 import ctypes
 import os
 
@@ -156,3 +157,81 @@ def test_create_refusals(S):
         lib.gtts_enc_destroy(h)
     with pytest.raises(RuntimeError):
         S.Encoder("text", window_size=-1)
+
+
+# ------------------------------------------------------------------------------ the stand-alone ops: gtts_enc_layernorm / gtts_enc_attention
+def test_attention_path_for_is_the_handle_query_without_a_handle(S):
+    lib = S._lib.lib()
+    for C, heads, window in ((192, 2, 4), (192, 2, 7), (192, 2, 8), (192, 2, 0), (80, 8, 4), (96, 4, 4), (144, 8, 3), (48, 1, 5), (96, 1, 4),
+                             (4, 1, 4), (32, 8, 4)):
+        enc = S.Encoder("mel", 0, 80, C, 4 * C, 0, heads, 1, 3, window)
+        dk = C // heads
+        last8 = (LDS // 4 - 8 * dk) // 8
+        for L in list(range(1, 200)) + [1024, 2432, 2433, 2500, last8 - 1, last8, last8 + 1, 1 << 20]:
+            got = S.enc_attention_path(C, heads, window, L)
+            assert got == enc.attention_path(L) == expected_path(C, heads, window, L), (C, heads, window, L, got)
+    assert S.enc_attention_path(96, 1, 4, 2432) == 16 and S.enc_attention_path(96, 1, 4, 2433) == 8
+    assert S.enc_attention_path(96, 1, 4, 5024) == 8 and S.enc_attention_path(96, 1, 4, 5025) == 0
+    for bad in ((0, 1, 4, 10), (-192, 2, 4, 10), (192, 0, 4, 10), (192, -2, 4, 10), (100, 3, 4, 10), (192, 2, -1, 10), (192, 2, 4, 0),
+                (192, 2, 4, -3)):
+        assert lib.gtts_enc_attention_path_for(*bad) == 0, bad
+
+
+def test_layernorm_refuses_before_launching(S):
+    lib = S._lib.lib()
+    a, bres, gamma, beta, am, om, out = _fake(7)
+
+    def ln(a=a, bres=bres, gamma=gamma, beta=beta, am=am, om=om, out=out, B=2, C=20, L=17, eps=1e-4):
+        return lib.gtts_enc_layernorm(a, bres, gamma, beta, am, om, out, B, C, L, eps, 0, 0, None)
+    for kw in (dict(a=None), dict(gamma=None), dict(beta=None), dict(out=None)):
+        assert ln(**kw) == E_NULL, kw
+        assert b"gtts_enc_layernorm" in lib.gtts_last_error()
+    # bres and the two masks are optional: without them the call gets as far as the shape check
+    for kw in (dict(bres=None), dict(am=None), dict(om=None), dict(bres=None, am=None, om=None)):
+        assert ln(B=0, **kw) == E_SHAPE, kw
+    for kw in (dict(B=0), dict(B=-1), dict(C=0), dict(C=-20), dict(L=0), dict(L=-17), dict(B=65536)):
+        assert ln(**kw) == E_SHAPE, kw
+        assert b"bad shape" in lib.gtts_last_error()
+    for eps in (0.0, -1e-4, float("nan")):
+        assert ln(eps=eps) == E_CONFIG, eps
+    assert ln(a=None, B=0, eps=0.0) == E_NULL                       # pointers first, then the shape, then eps
+    assert ln(B=0, eps=0.0) == E_SHAPE
+
+
+def test_attention_refuses_before_launching(S):
+    lib = S._lib.lib()
+    q, k, v, mask, ek, ev, out = _fake(7)
+
+    def att(q=q, k=k, v=v, mask=mask, ek=ek, ev=ev, out=out, B=2, C=192, L=100, heads=2, window=4, path=0):
+        return lib.gtts_enc_attention(q, k, v, mask, ek, ev, out, B, C, L, heads, window, path, None)
+    for kw in (dict(q=None), dict(k=None), dict(v=None), dict(mask=None), dict(out=None), dict(ek=None), dict(ev=None)):
+        assert att(**kw) == E_NULL, kw
+        assert b"gtts_enc_attention" in lib.gtts_last_error()
+    # window 0 takes no embeddings: with both null the call gets as far as the length check
+    assert att(ek=None, ev=None, window=0, L=5025) == E_SHAPE
+    assert b"too long" in lib.gtts_last_error()
+    for kw in (dict(B=0), dict(B=-2), dict(L=0), dict(L=-100), dict(B=65536), dict(C=65536 * 4, heads=65536)):
+        assert att(**kw) == E_SHAPE, kw
+    for kw in (dict(C=0), dict(C=-192), dict(heads=0), dict(heads=-2), dict(C=100, heads=3), dict(window=-1), dict(path=7), dict(path=-8),
+               dict(path=1), dict(path=32)):
+        assert att(**kw) == E_CONFIG, kw
+    # a forced 16 where enc_attention_path's conditions do not hold: the head width, the window, the LDS
+    assert att(C=80, heads=8, path=16) == E_CONFIG and b"16-query" in lib.gtts_last_error()          # dk = 10
+    assert att(window=8, path=16) == E_CONFIG and b"16-query" in lib.gtts_last_error()
+    assert att(C=96, heads=1, L=2433, path=16) == E_SHAPE and b"16-query" in lib.gtts_last_error()
+    assert att(L=2433, path=16) == E_SHAPE
+    # either kernel past its 160 KB, and the dispatch's own choice past both
+    for path in (0, 8, 16):
+        assert att(C=96, heads=1, L=5025, path=path) == E_SHAPE, path
+        assert b"too long" in lib.gtts_last_error()
+    assert att(C=96, heads=1, L=1 << 30, path=8) == E_SHAPE
+    assert att(C=80, heads=8, L=(LDS // 4 - 8 * 10) // 8 + 1, path=8) == E_SHAPE
+
+
+def test_stand_alone_ops_have_no_cpu_fallback(S):
+    import torch
+    x = torch.zeros(1, 4, 8)
+    with pytest.raises(RuntimeError, match="HIP tensors"):
+        S.enc_layernorm(x, torch.ones(4), torch.zeros(4))
+    with pytest.raises(RuntimeError, match="HIP tensors"):
+        S.enc_attention(x, x, x, torch.ones(1, 8), n_heads=1, window=0)
