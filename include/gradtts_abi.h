@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define GTTS_ABI_VERSION 6
+#define GTTS_ABI_VERSION 7
 
 enum {
     GTTS_OK = 0,
@@ -318,7 +318,7 @@ int gtts_postnet_forward(const gtts_postnet *pn, const void *packed, const float
                          void *workspace, size_t workspace_bytes, int B, int T, gtts_stream_t stream);
 
 /* ---- training hot path, first kernels (Grad-TTS/train.py:105-119; Grad-TTS/model/diffusion.py:244-252,281-294) --------
- * The host (model/_train_ops.py) wraps these and the ABI-3 entry points further down in torch.autograd.Function; autograd only
+ * The host (model/_train_ops.py) wraps these and the entry points further down in torch.autograd.Function; autograd only
  * sequences them (and adds gradient accumulations). */
 /* Diffusion.forward_diffusion: xt = (x0 d + mu (1-d) + z sqrt(1 - e^{-cum})) mask, z_masked = z mask; d = e^{-cum/2},
  * cum = beta_min t + (beta_max - beta_min) t^2 / 2 per sample; x0, mu, z, xt, z_masked [B,F,T], mask [B,T], t [B]. */
@@ -329,48 +329,40 @@ int gtts_diffusion_noising(const float *x0, const float *mu, const float *z, con
 size_t gtts_score_loss_partials(int B, int F, int T);
 int gtts_score_loss(const float *eps, const float *z_masked, const float *t, float beta_min, float beta_max, float inv_denom,
                     float *partials, float *grad_eps, int B, int F, int T, gtts_stream_t stream);
-/* Block's convolution for training: y = Conv2d_3x3(x * mask) + bias with weights packed by gtts_conv3x3_pack (transposed = 0);
- * the data gradient is the same call on dy with weights packed transposed = 1 (cin / cout swapped), an all-ones mask and a
- * zero bias; the weight / bias gradient is gtts_conv3x3_wgrad (dw, db are overwritten).  x [B,cin,H,W], mask [B,W]. */
+/* Block's convolution for training: y = Conv2d_3x3(x * mask) + bias with weights packed by gtts_conv3x3_pack (transposed = 0).
+ * x [B,cin,H,W], mask [B,W] (columns), y [B,cout,H,W]; cout 64 or a multiple of 128.
+ * x1 (nullable) / c0: the input is the channel concatenation of x [B,c0,H,W] and x1 [B,cin-c0,H,W], read in place (torch.cat of the
+ * up path, diffusion.py:166); c0 a multiple of 16 here, of 64 in the weight gradient.  Without x1, c0 is ignored.
+ * omask (nullable): [B,W] column mask multiplied into the output.  The data gradient is this call on dy with weights packed
+ * transposed = 1 (cin / cout swapped), an all-ones mask, a zero bias and the forward mask as omask. */
 size_t gtts_conv3x3_packed_bytes(int cin, int cout);
 int gtts_conv3x3_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream);
-int gtts_conv3x3_masked(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B, int cin,
-                        int cout, int H, int W, gtts_stream_t stream);
-int gtts_conv3x3_wgrad(const float *x, const float *mask, const float *dy, float *dw, float *db, int B, int cin, int cout, int H,
-                       int W, gtts_stream_t stream);
-
-/* The same weight / bias gradient as an LDS-tiled, deterministic reduction (no atomics): cin and cout multiples of 64;
- * workspace: gtts_conv3x3_wgrad_workspace_bytes(...) bytes of device memory (per-slice partial tiles).  The kernel addresses a
- * call's tensors with 32-bit byte offsets: B * max(cin, cout) * H * W < 2^29 (GTTS_E_SHAPE), as for gtts_conv1x1_wgrad. */
+int gtts_conv3x3_masked(const float *x, const float *x1, int c0, const float *mask, const float *omask, const void *packed,
+                        const float *bias, float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream);
+/* Its weight / bias gradient dw [cout][cin][3][3], db [cout] (nullable), both overwritten: an LDS-tiled reduction in a fixed order
+ * (no atomics); cin and cout multiples of 64.  workspace: gtts_conv3x3_wgrad_workspace_bytes(...) bytes of device memory (per-slice
+ * partial tiles).  The kernel addresses a call's tensors with 32-bit byte offsets: B * max(cin, cout) * H * W < 2^29 (GTTS_E_SHAPE),
+ * as for gtts_conv1x1_wgrad. */
 size_t gtts_conv3x3_wgrad_workspace_bytes(int B, int cin, int cout, int H, int W);
-int gtts_conv3x3_wgrad_tiled(const float *x, const float *mask, const float *dy, float *dw, float *db, void *workspace,
-                             size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream);
+int gtts_conv3x3_wgrad(const float *x, const float *x1, int c0, const float *mask, const float *dy, float *dw, float *db,
+                       void *workspace, size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream);
 
-/* Block's GroupNorm + Mish + mask for training (Grad-TTS/model/diffusion.py:53-58,13-15): out = Mish(GroupNorm(y)) * mask.
- * y, out [B,C,H,W]; gamma, beta [C]; mask [B,W] (columns).  stats: gtts_gn_mish_stats_floats(B, groups) floats, 8-byte aligned;
- * its first [B][groups][2] = (mean, 1/sqrt(var + eps)) are written by the forward call (the rest is its reduction scratch) and
- * read by the backward call, which overwrites dy [B,C,H,W], dgamma [C], dbeta [C];
- * scratch: gtts_gn_mish_scratch_bytes(B, C) bytes of device memory. */
+/* Block's GroupNorm + Mish + mask for training (Grad-TTS/model/diffusion.py:53-58,13-15), with ResnetBlock's time term (:75-76):
+ * out = Mish(GroupNorm(y)) * mask + tb[b,c].  y, out [B,C,H,W]; gamma, beta [C]; mask [B,W] (columns); tb [B][C] (nullable: no term).
+ * stats: gtts_gn_mish_stats_floats(B, groups) floats, 8-byte aligned; its first [B][groups][2] = (mean, 1/sqrt(var + eps)) are
+ * written by the forward call (the rest is its reduction scratch) and read by the backward call, which overwrites dy [B,C,H,W],
+ * dgamma [C], dbeta [C] and dtb [B][C] (nullable); scratch: gtts_gn_mish_scratch_bytes(B, C) bytes of device memory. */
 size_t gtts_gn_mish_stats_floats(int B, int groups);
-int gtts_gn_mish_forward(const float *y, const float *gamma, const float *beta, const float *mask, float *out, float *stats,
-                         int B, int C, int H, int W, int groups, float eps, gtts_stream_t stream);
+int gtts_gn_mish_forward(const float *y, const float *gamma, const float *beta, const float *mask, const float *tb, float *out,
+                         float *stats, int B, int C, int H, int W, int groups, float eps, gtts_stream_t stream);
 size_t gtts_gn_mish_scratch_bytes(int B, int C);
 int gtts_gn_mish_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *mask,
-                          const float *stats, float *dy, float *dgamma, float *dbeta, void *scratch, int B, int C, int H, int W,
-                          int groups, gtts_stream_t stream);
+                          const float *stats, float *dy, float *dgamma, float *dbeta, float *dtb, void *scratch, int B, int C, int H,
+                          int W, int groups, gtts_stream_t stream);
 
-/* ---- training hot path, the rest of the score network (ABI 3; Grad-TTS/model/diffusion.py:19-108,140-176) ----------------
+/* ---- training hot path, the rest of the score network (Grad-TTS/model/diffusion.py:19-108,140-176) -----------------------
  * Every tensor-sized op of Diffusion.compute_loss's forward and backward (Upsample's gradients run as stride-1 3x3 operations
  * over gtts_space_to_depth2 planes: no MIOpen / rocBLAS kernel is left in the step). */
-/* Block's convolution on a channel concatenation read in place (torch.cat of the up path, diffusion.py:166): x [B,c0,H,W],
- * x1 [B,cin-c0,H,W] (nullptr: one source, c0 ignored); c0 a multiple of 16 (forward) / 64 (weight gradient). */
-int gtts_conv3x3_masked2(const float *x, const float *x1, int c0, const float *mask, const void *packed, const float *bias, float *y,
-                         int B, int cin, int cout, int H, int W, gtts_stream_t stream);
-/* the same with a column mask on the OUTPUT (omask [B][W], nullable): the data gradient of a masked convolution in one pass */
-int gtts_conv3x3_masked3(const float *x, const float *x1, int c0, const float *mask, const float *omask, const void *packed,
-                         const float *bias, float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream);
-int gtts_conv3x3_wgrad_tiled2(const float *x, const float *x1, int c0, const float *mask, const float *dy, float *dw, float *db,
-                              void *workspace, size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream);
 /* 1x1 convolutions (res_conv, to_qkv, to_out: diffusion.py:70,87-88): y = Conv2d_1x1(x * mask) + bias; the data gradient is the
  * same call on dy with weights packed transposed = 1 (the mask then applies to dy: columns do not mix); weight gradient
  * dw [cout][cin], db [cout] (nullable); mask [B,W] (nullable in the weight gradient).  cin, cout multiples of 64. */
@@ -406,12 +398,6 @@ int gtts_zero_insert2(const float *in, float *out, int B, int C, int h, int w, g
 /* out [B,4C,h,w] = the four stride-2 phases of in [B,C,2h,2w], channel block (pr * 2 + pc) = rows 2y + 1 - pr, columns 2x + 1 - pc:
  * Upsample's data / weight gradient are the 3x3 stride-1 convolution / weight gradient over these planes. */
 int gtts_space_to_depth2(const float *in, float *out, int B, int C, int h, int w, gtts_stream_t stream);
-/* GroupNorm + Mish + mask with ResnetBlock's time term: out = Mish(GroupNorm(y)) * mask + tb[b,c] (tb, dtb [B][C], nullable). */
-int gtts_gn_mish_forward_tb(const float *y, const float *gamma, const float *beta, const float *mask, const float *tb, float *out,
-                            float *stats, int B, int C, int H, int W, int groups, float eps, gtts_stream_t stream);
-int gtts_gn_mish_backward_tb(const float *dout, const float *y, const float *gamma, const float *beta, const float *mask,
-                             const float *stats, float *dy, float *dgamma, float *dbeta, float *dtb, void *scratch, int B, int C,
-                             int H, int W, int groups, gtts_stream_t stream);
 /* LinearAttention between its two 1x1 convolutions (diffusion.py:90-100): qkv [B][384][N] -> out [B][128][N]; ctx [B][4][32][32]
  * and stat [B][4][32][2] (softmax row maximum, reciprocal sum) are kept for the backward call, which writes dqkv [B][384][N];
  * dctx [B][4][32][32], rdot [B][4][32]: outputs used as scratch; scratch: gtts_attn_train_scratch_floats(B, N) floats. */

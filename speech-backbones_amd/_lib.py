@@ -126,11 +126,10 @@ def lib():
         L.gtts_conv3x3_packed_bytes.argtypes = [i, i]
         L.gtts_conv3x3_packed_bytes.restype = sz
         L.gtts_conv3x3_pack.argtypes = [vp, vp, i, i, i, vp]
-        L.gtts_conv3x3_masked.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
-        L.gtts_conv3x3_wgrad.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp]
+        L.gtts_conv3x3_masked.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.gtts_conv3x3_wgrad_workspace_bytes.argtypes = [i, i, i, i, i]
         L.gtts_conv3x3_wgrad_workspace_bytes.restype = sz
-        L.gtts_conv3x3_wgrad_tiled.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
+        L.gtts_conv3x3_wgrad.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
         L.gtts_conv1x1_packed_bytes.argtypes = [i, i]
         L.gtts_conv1x1_packed_bytes.restype = sz
         L.gtts_conv1x1_pack.argtypes = [vp, vp, i, i, i, vp]
@@ -138,15 +137,10 @@ def lib():
         L.gtts_conv1x1_wgrad_workspace_bytes.argtypes = [i, i, i, i, i]
         L.gtts_conv1x1_wgrad_workspace_bytes.restype = sz
         L.gtts_conv1x1_wgrad.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
-        L.gtts_conv3x3_masked2.argtypes = [vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, vp]
-        L.gtts_conv3x3_masked3.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
-        L.gtts_conv3x3_wgrad_tiled2.argtypes = [vp, vp, i, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
         L.gtts_conv_resample_packed_bytes.argtypes = [i, i, i]
         L.gtts_conv_resample_packed_bytes.restype = sz
         L.gtts_conv_resample_pack.argtypes = [vp, vp, i, i, i, vp]
         L.gtts_conv_resample.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
-        L.gtts_gn_mish_forward_tb.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, vp]
-        L.gtts_gn_mish_backward_tb.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.gtts_add_masked.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp]
         L.gtts_conv_wgrad_small_scratch_floats.argtypes = [i, i, i, i]
         L.gtts_conv_wgrad_small_scratch_floats.restype = sz
@@ -165,12 +159,12 @@ def lib():
         L.gtts_rezero_scratch_bytes.argtypes = [sz]
         L.gtts_rezero_scratch_bytes.restype = sz
         L.gtts_rezero_backward.argtypes = [vp, vp, vp, vp, vp, vp, sz, vp]
-        L.gtts_gn_mish_forward.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, vp]
+        L.gtts_gn_mish_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, f, vp]
         L.gtts_gn_mish_stats_floats.argtypes = [i, i]
         L.gtts_gn_mish_stats_floats.restype = sz
         L.gtts_gn_mish_scratch_bytes.argtypes = [i, i]
         L.gtts_gn_mish_scratch_bytes.restype = sz
-        L.gtts_gn_mish_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
+        L.gtts_gn_mish_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
         L.gtts_enc_attention_path.argtypes = [vp, i]
         L.gtts_enc_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_enc_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, f, i, i, vp]
@@ -267,7 +261,7 @@ def lib():
         L.gtts_wav_resample.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
         L.gtts_wav_normalize.argtypes = [vp, vp, vp, ctypes.c_double, i, vp, vp, sz, i, i, vp]
         L.gtts_wav_powmel.argtypes = [vp, vp, vp, vp, i, i, vp]
-        if L.gtts_abi_version() != 6:
+        if L.gtts_abi_version() != 7:
             raise RuntimeError("libgradtts_gfx950.so ABI version mismatch")
         _lib = L
         return _lib
@@ -1354,6 +1348,18 @@ def clear_packed_cache():
     _PACKED.clear()
 
 
+# kind -> (family of gtts_<family>_packed_bytes / gtts_<family>_pack, `up` of the resampling family (None: the family takes
+# `transposed` there), gtts_pack_item.kind (None: not part of the batched pack)).  "dn" Downsample forward, "up" Upsample forward,
+# "dn_T" Downsample's data gradient.
+_PACK_KINDS = {"3x3": ("conv3x3", None, 0), "1x1": ("conv1x1", None, 1), "7x7": ("conv7x7", None, None),
+               "dn": ("conv_resample", 0, 2), "up": ("conv_resample", 1, 3), "dn_T": ("conv_resample", 1, 4)}
+
+
+def _packed_nbytes(kind, cin, cout):
+    family, up, _ = _PACK_KINDS[kind]
+    return int(getattr(lib(), "gtts_%s_packed_bytes" % family)(int(cin), int(cout), *(() if up is None else (up,))))
+
+
 def _packed_weight(weight, cin, cout, transposed, kind):
     """Packed (fragment-order, bf16 hi / lo) copy of a convolution weight, cached per Parameter OBJECT and version: the entry is
     valid only while the very same tensor object is alive and unmodified (an optimizer step bumps `_version`; a data pointer
@@ -1363,19 +1369,13 @@ def _packed_weight(weight, cin, cout, transposed, kind):
     if (hit is not None and hit[0]() is weight and hit[1] == int(weight._version) and hit[2] == _PACK_GEN and
             hit[3].device == weight.device):
         return hit[3]
-    L = lib()
-    if kind in ("3x3", "1x1", "7x7"):
-        nbytes, pack = {"3x3": (L.gtts_conv3x3_packed_bytes, L.gtts_conv3x3_pack), "1x1": (L.gtts_conv1x1_packed_bytes, L.gtts_conv1x1_pack),
-                        "7x7": (L.gtts_conv7x7_packed_bytes, L.gtts_conv7x7_pack)}[kind]
-        packed = torch.empty(int(nbytes(cin, cout)), dtype=torch.uint8, device=weight.device)
-        _check(pack(_ptr(weight), _ptr(packed), cin, cout, 1 if transposed else 0, _stream()), "gtts_conv%s_pack" % kind)
-    else:
-        # "dn" Downsample forward, "up" Upsample forward, "dn_T" Downsample's data gradient: an Upsample of dy with the forward
-        # weight [cout][cin][3][3] zero-padded to [.][.][4][4] (ConvTranspose2d layout: [in = cout][out = cin])
-        up = 0 if kind == "dn" else 1
-        src = torch.nn.functional.pad(weight, (0, 1, 0, 1)).contiguous() if kind == "dn_T" else weight
-        packed = torch.empty(int(L.gtts_conv_resample_packed_bytes(cin, cout, up)), dtype=torch.uint8, device=weight.device)
-        _check(L.gtts_conv_resample_pack(_ptr(src), _ptr(packed), cin, cout, up, _stream()), "gtts_conv_resample_pack")
+    family, up, _ = _PACK_KINDS[kind]
+    # "dn_T": an Upsample of dy with the forward weight [cout][cin][3][3] zero-padded to [.][.][4][4] (ConvTranspose2d layout:
+    # [in = cout][out = cin])
+    src = torch.nn.functional.pad(weight, (0, 1, 0, 1)).contiguous() if kind == "dn_T" else weight
+    packed = torch.empty(_packed_nbytes(kind, cin, cout), dtype=torch.uint8, device=weight.device)
+    _check(getattr(lib(), "gtts_%s_pack" % family)(_ptr(src), _ptr(packed), cin, cout, (1 if transposed else 0) if up is None else up,
+                                                   _stream()), "gtts_%s_pack" % family)
     if len(_PACKED) >= 512:          # (two entries per convolution: ~100 for the Grad-TTS U-Net); dead entries go with the sweep
         for k in [k for k, v in _PACKED.items() if v[0]() is None]:
             del _PACKED[k]
@@ -1383,9 +1383,6 @@ def _packed_weight(weight, cin, cout, transposed, kind):
             _PACKED.clear()
     _PACKED[key] = (weakref.ref(weight), int(weight._version), _PACK_GEN, packed)
     return packed
-
-
-_KIND_CODE = {"3x3": 0, "1x1": 1, "dn": 2, "up": 3, "dn_T": 4}
 
 
 class PackSpecs(list):
@@ -1402,16 +1399,10 @@ def _build_pack_plan(specs, dev, sig):
     blobs = []
     with _on(dev):
         for k, (w, ci, co, t, kind) in enumerate(specs):
-            if kind == "3x3":
-                nb = L.gtts_conv3x3_packed_bytes(int(ci), int(co))
-            elif kind == "1x1":
-                nb = L.gtts_conv1x1_packed_bytes(int(ci), int(co))
-            else:
-                nb = L.gtts_conv_resample_packed_bytes(int(ci), int(co), 0 if kind == "dn" else 1)
-            blob = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+            blob = torch.empty(_packed_nbytes(kind, ci, co), dtype=torch.uint8, device=dev)
             blobs.append(blob)
             items[k].w, items[k].packed = w.data_ptr(), blob.data_ptr()
-            items[k].kind, items[k].cin, items[k].cout, items[k].transposed = _KIND_CODE[kind], int(ci), int(co), 1 if t else 0
+            items[k].kind, items[k].cin, items[k].cout, items[k].transposed = _PACK_KINDS[kind][2], int(ci), int(co), 1 if t else 0
         nbytes = int(L.gtts_pack_batch_desc_bytes(n))
         host = (ctypes.c_ubyte * nbytes)()
         grid = ctypes.c_int(0)
@@ -1455,57 +1446,86 @@ def _const(device, kind, *shape):
     return v
 
 
-def _conv3x3_run(x, mask_cols, weight, bias, transposed, x1=None, out_mask=None):
+# kind -> (kernel size, the entry points take a second source x1 / c0, the forward entry point takes an output mask, the names of
+# the forward / data-gradient entry point, of the weight gradient and of its workspace size)
+_CONV_KINDS = {kind: (ksize, two, om, "gtts_conv%s_masked" % kind, "gtts_conv%s_wgrad" % kind, "gtts_conv%s_wgrad_workspace_bytes" % kind)
+               for kind, ksize, two, om in (("3x3", 3, True, True), ("7x7", 7, False, True), ("1x1", 1, False, False))}
+
+
+def _conv_run(kind, x, mask_cols, weight, bias, transposed, x1=None, out_mask=None):
+    _, two, om, name, _, _ = _CONV_KINDS[kind]
     B, c0, H, W = x.shape
     cin = c0 + (int(x1.shape[1]) if x1 is not None else 0)
     cout = weight.shape[1] if transposed else weight.shape[0]
-    L = lib()
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    src = (_ptr(x), _ptr(x1), c0, _ptr(mask_cols)) if two else (_ptr(x), _ptr(mask_cols))
     with _on(x.device):
-        packed = _packed_weight(weight, cin, cout, transposed, "3x3")
-        _check(L.gtts_conv3x3_masked3(_ptr(x), _ptr(x1), c0, _ptr(mask_cols), _ptr(out_mask), _ptr(packed), _ptr(bias), _ptr(y), B, cin,
-                                      cout, H, W, _stream()), "gtts_conv3x3_masked")
+        packed = _packed_weight(weight, cin, cout, transposed, kind)
+        _check(getattr(lib(), name)(*src, *((_ptr(out_mask),) if om else ()), _ptr(packed), _ptr(bias), _ptr(y), B, cin, cout, H, W,
+                                    _stream()), name)
     return y
+
+
+def _conv_dgrad(kind, dy, weight, mask_cols):
+    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
+    B, cout, H, W = dy.shape
+    return _conv_run(kind, dy, _const(dy.device, "ones", B, W), weight, _const(dy.device, "zeros", int(weight.shape[1])), True,
+                     out_mask=_f32c(mask_cols, "mask"))
+
+
+def _tiled_wgrad(kind, x, mask_cols, dy, x1=None, want_bias=True):
+    """(dW [cout,cin,k,k], db [cout] or None) by the kind's LDS-tiled deterministic reduction (train_wgrad.hip, train_wgrad7.hip)."""
+    ksize, two, _, _, name, ws_name = _CONV_KINDS[kind]
+    B, c0, H, W = x.shape
+    cin = c0 + (int(x1.shape[1]) if x1 is not None else 0)
+    cout = int(dy.shape[1])
+    dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=x.device)
+    db = torch.empty((cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    src = (_ptr(x), _ptr(x1), c0) if two else (_ptr(x),)
+    with _on(x.device):
+        L = lib()
+        nws = int(getattr(L, ws_name)(B, cin, cout, H, W))
+        ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+        _check(getattr(L, name)(*src, _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws, B, cin, cout, H, W, _stream()), name)
+    return dw, db
+
+
+def _wgrad_small(x, mask_cols, dy, ksize, want_bias=True):
+    """The first layer's weight gradient (cin 2 or 3: its own kernel)."""
+    B, cin, H, W = x.shape
+    cout = int(dy.shape[1])
+    dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=x.device)
+    db = torch.empty((cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    with _on(x.device):
+        scratch = torch.empty(int(lib().gtts_conv_wgrad_small_scratch_floats(B, cin, cout, ksize)), dtype=torch.float32, device=x.device)
+        _check(lib().gtts_conv_wgrad_small(_ptr(x), _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(scratch), B, cin, cout, H, W, ksize,
+                                           _stream()), "gtts_conv_wgrad_small")
+    return dw, db
 
 
 def conv3x3_masked(x, mask_cols, weight, bias, x1=None):
     """Conv2d_3x3(cat(x, x1) * mask) + bias (Block.forward, diffusion.py:56-57; the concatenation of the up path, :166, is read in
     place): x [B,c0,H,W], x1 [B,c1,H,W] or None, mask_cols [B,W], weight [cout,c0+c1,3,3]."""
     x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
-    return _conv3x3_run(x, mask_cols, weight, bias, False, _f32c(x1, "x1"))
+    return _conv_run("3x3", x, mask_cols, weight, bias, False, _f32c(x1, "x1"))
 
 
 def conv3x3_dgrad(dy, weight, mask_cols=None):
     """Gradient of conv3x3_masked w.r.t. (x * mask): a 3x3 convolution of dy with the transposed, flipped weights; with
     mask_cols [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue)."""
-    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
-    B, cout, H, W = dy.shape
-    return _conv3x3_run(dy, _const(dy.device, "ones", B, W), weight, _const(dy.device, "zeros", int(weight.shape[1])), True,
-                        out_mask=_f32c(mask_cols, "mask"))
+    return _conv_dgrad("3x3", dy, weight, mask_cols)
 
 
 def conv3x3_wgrad(x, mask_cols, dy, x1=None):
     """(dW [cout,cin,3,3], db [cout]) of conv3x3_masked (x1: second source of a concatenated input, c0 a multiple of 64)."""
     x, mask_cols, dy, x1 = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy"), _f32c(x1, "x1")
-    B, c0, H, W = x.shape
-    cin = c0 + (int(x1.shape[1]) if x1 is not None else 0)
-    cout = dy.shape[1]
-    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=x.device)
-    db = torch.empty((cout,), dtype=torch.float32, device=x.device)
-    with _on(x.device):
-        if cin in (2, 3) and x1 is None:
-            _wgrad_small(x, mask_cols, dy, dw, db, 3)
-        elif cin % 64 == 0 and cout % 64 == 0:       # LDS-tiled deterministic reduction (train_wgrad.hip)
-            nws = int(lib().gtts_conv3x3_wgrad_workspace_bytes(B, cin, cout, H, W))
-            ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-            _check(lib().gtts_conv3x3_wgrad_tiled2(_ptr(x), _ptr(x1), c0, _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws,
-                                                   B, cin, cout, H, W, _stream()), "gtts_conv3x3_wgrad_tiled")
-        else:
-            if x1 is not None:
-                x = torch.cat((x, x1), 1)
-            _check(lib().gtts_conv3x3_wgrad(_ptr(x), _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), B, cin, cout, H, W, _stream()),
-                   "gtts_conv3x3_wgrad")
-    return dw, db
+    cin, cout = int(x.shape[1]) + (int(x1.shape[1]) if x1 is not None else 0), int(dy.shape[1])
+    if cin in (2, 3) and x1 is None:
+        return _wgrad_small(x, mask_cols, dy, 3)
+    if cin % 64 or cout % 64:
+        raise ValueError("conv3x3_wgrad: cin and cout must be multiples of 64, or cin 2 or 3 from one source (got cin %d, cout %d)"
+                         % (cin, cout))
+    return _tiled_wgrad("3x3", x, mask_cols, dy, x1)
 
 
 def conv7x7_supported(cin, cout, need_dgrad=True, shape=None):
@@ -1516,47 +1536,22 @@ def conv7x7_supported(cin, cout, need_dgrad=True, shape=None):
     return int(cin) > 0 and int(cout) > 0 and int(cin) % 64 == 0 and int(cout) % 64 == 0
 
 
-def _conv7x7_run(x, mask_cols, weight, bias, transposed, out_mask=None):
-    B, cin, H, W = x.shape
-    cout = weight.shape[1] if transposed else weight.shape[0]
-    L = lib()
-    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    with _on(x.device):
-        packed = _packed_weight(weight, cin, cout, transposed, "7x7")
-        _check(L.gtts_conv7x7_masked(_ptr(x), _ptr(mask_cols), _ptr(out_mask), _ptr(packed), _ptr(bias), _ptr(y), B, cin, cout, H, W,
-                                     _stream()), "gtts_conv7x7_masked")
-    return y
-
-
 def conv7x7_masked(x, mask_cols, weight, bias):
     """Conv2d_7x7(x * mask, padding 3) + bias (PostNet Block, DiffVC/model/postnet.py:21-23): x [B,cin,H,W], mask_cols [B,W],
     weight [cout,cin,7,7]."""
     x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
-    return _conv7x7_run(x, mask_cols, weight, bias, False)
+    return _conv_run("7x7", x, mask_cols, weight, bias, False)
 
 
 def conv7x7_dgrad(dy, weight, mask_cols=None):
     """Gradient of conv7x7_masked w.r.t. (x * mask): a 7x7 convolution of dy with the transposed, flipped weights; with mask_cols
     [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue)."""
-    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
-    B, cout, H, W = dy.shape
-    return _conv7x7_run(dy, _const(dy.device, "ones", B, W), weight, _const(dy.device, "zeros", int(weight.shape[1])), True,
-                        out_mask=_f32c(mask_cols, "mask"))
+    return _conv_dgrad("7x7", dy, weight, mask_cols)
 
 
 def conv7x7_wgrad(x, mask_cols, dy):
     """(dW [cout,cin,7,7], db [cout]) of conv7x7_masked (train_wgrad7.hip: deterministic split-bf16 MFMA reduction)."""
-    x, mask_cols, dy = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy")
-    B, cin, H, W = x.shape
-    cout = int(dy.shape[1])
-    dw = torch.empty((cout, cin, 7, 7), dtype=torch.float32, device=x.device)
-    db = torch.empty((cout,), dtype=torch.float32, device=x.device)
-    with _on(x.device):
-        nws = int(lib().gtts_conv7x7_wgrad_workspace_bytes(B, cin, cout, H, W))
-        ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-        _check(lib().gtts_conv7x7_wgrad(_ptr(x), _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws, B, cin, cout, H, W, _stream()),
-               "gtts_conv7x7_wgrad")
-    return dw, db
+    return _tiled_wgrad("7x7", _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy"))
 
 
 def postnet_expand(x, mask, w, bias=None):
@@ -1606,17 +1601,6 @@ def conv1x1_supported(cin, cout, need_dgrad=True, shape=None):
     return _tiles(cout) and cin % 64 == 0 and (_tiles(cin) or not need_dgrad)
 
 
-def _conv1x1_run(x, mask_cols, weight, bias, transposed):
-    B, cin, H, W = x.shape
-    cout = weight.shape[1] if transposed else weight.shape[0]
-    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    with _on(x.device):
-        packed = _packed_weight(weight, cin, cout, transposed, "1x1")
-        _check(lib().gtts_conv1x1_masked(_ptr(x), _ptr(mask_cols), _ptr(packed), _ptr(bias), _ptr(y), B, cin, cout, H, W, _stream()),
-               "gtts_conv1x1_masked")
-    return y
-
-
 def conv1x1_masked(x, mask_cols, weight, bias):
     """Conv2d_1x1(x * mask) + bias (res_conv / to_qkv / to_out, diffusion.py:70,87-88): x [B,cin,H,W], mask_cols [B,W] or None,
     weight [cout,cin,1,1], bias [cout] or None."""
@@ -1624,7 +1608,7 @@ def conv1x1_masked(x, mask_cols, weight, bias):
     B, W = int(x.shape[0]), int(x.shape[3])
     mask_cols = _const(x.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
     bias = _const(x.device, "zeros", int(weight.shape[0])) if bias is None else _f32c(bias, "bias")
-    return _conv1x1_run(x, mask_cols, weight, bias, False)
+    return _conv_run("1x1", x, mask_cols, weight, bias, False)
 
 
 def conv1x1_dgrad(dy, weight, mask_cols=None):
@@ -1632,35 +1616,15 @@ def conv1x1_dgrad(dy, weight, mask_cols=None):
     dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
     B, W = int(dy.shape[0]), int(dy.shape[3])
     mask_cols = _const(dy.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
-    return _conv1x1_run(dy, mask_cols, weight, _const(dy.device, "zeros", int(weight.shape[1])), True)
-
-
-def _wgrad_small(x, mask_cols, dy, dw, db, ksize):
-    B, cin, H, W = x.shape
-    cout = int(dy.shape[1])
-    scratch = torch.empty(int(lib().gtts_conv_wgrad_small_scratch_floats(B, cin, cout, ksize)), dtype=torch.float32, device=x.device)
-    _check(lib().gtts_conv_wgrad_small(_ptr(x), _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(scratch), B, cin, cout, H, W, ksize,
-                                       _stream()), "gtts_conv_wgrad_small")
+    return _conv_run("1x1", dy, mask_cols, weight, _const(dy.device, "zeros", int(weight.shape[1])), True)
 
 
 def conv1x1_wgrad(x, mask_cols, dy, want_bias=True):
     """(dW [cout,cin,1,1], db [cout] or None) of conv1x1_masked."""
-    x, dy = _f32c(x, "x"), _f32c(dy, "dy")
-    B, cin, H, W = x.shape
-    cout = int(dy.shape[1])
-    dw = torch.empty((cout, cin, 1, 1), dtype=torch.float32, device=x.device)
-    db = torch.empty((cout,), dtype=torch.float32, device=x.device) if want_bias else None
-    if cin in (2, 3):
-        with _on(x.device):
-            _wgrad_small(x, _const(x.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask"), dy, dw, db, 1)
-        return dw, db
-    with _on(x.device):
-        nws = int(lib().gtts_conv1x1_wgrad_workspace_bytes(B, cin, cout, H, W))
-        ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-        _check(lib().gtts_conv1x1_wgrad(_ptr(x), _ptr(_f32c(mask_cols, "mask")) if mask_cols is not None else None, _ptr(dy), _ptr(dw),
-                                        _ptr(db) if db is not None else None, _ptr(ws), nws, B, cin, cout, H, W, _stream()),
-               "gtts_conv1x1_wgrad")
-    return dw, db
+    x, mask_cols, dy = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy")
+    if x.shape[1] in (2, 3):
+        return _wgrad_small(x, _const(x.device, "ones", int(x.shape[0]), int(x.shape[3])) if mask_cols is None else mask_cols, dy, 1, want_bias)
+    return _tiled_wgrad("1x1", x, mask_cols, dy, want_bias=want_bias)
 
 
 def add_masked(a, b, mask_cols, channels=None):
@@ -1811,8 +1775,8 @@ def gn_mish_forward(y, gamma, beta, mask_cols, groups, eps, tb=None):
     out = torch.empty_like(y)
     stats = torch.empty(int(lib().gtts_gn_mish_stats_floats(B, int(groups))), dtype=torch.float32, device=y.device)
     with _on(y.device):
-        _check(lib().gtts_gn_mish_forward_tb(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(mask_cols), _ptr(tb), _ptr(out), _ptr(stats), B, C,
-                                             H, W, int(groups), float(eps), _stream()), "gtts_gn_mish_forward")
+        _check(lib().gtts_gn_mish_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(mask_cols), _ptr(tb), _ptr(out), _ptr(stats), B, C,
+                                          H, W, int(groups), float(eps), _stream()), "gtts_gn_mish_forward")
     return out, stats
 
 
@@ -1826,9 +1790,9 @@ def gn_mish_backward(dout, y, gamma, beta, mask_cols, stats, groups, want_dtb=Fa
     dtb = torch.empty((B, C), dtype=torch.float32, device=y.device) if want_dtb else None
     scratch = torch.empty(int(lib().gtts_gn_mish_scratch_bytes(B, C)), dtype=torch.uint8, device=y.device)
     with _on(y.device):
-        _check(lib().gtts_gn_mish_backward_tb(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")),
-                                              _ptr(_f32c(mask_cols, "mask")), _ptr(stats), _ptr(dy), _ptr(dg), _ptr(db), _ptr(dtb),
-                                              _ptr(scratch), B, C, H, W, int(groups), _stream()), "gtts_gn_mish_backward")
+        _check(lib().gtts_gn_mish_backward(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")),
+                                           _ptr(_f32c(mask_cols, "mask")), _ptr(stats), _ptr(dy), _ptr(dg), _ptr(db), _ptr(dtb),
+                                           _ptr(scratch), B, C, H, W, int(groups), _stream()), "gtts_gn_mish_backward")
     return (dy, dg, db, dtb) if want_dtb else (dy, dg, db)
 
 

@@ -3,6 +3,7 @@
 #include <atomic>
 #include <vector>
 
+#include "../../include/gradtts_abi.h"
 #include "common.h"
 
 namespace gtts {
@@ -168,6 +169,21 @@ hipError_t launch_pack_attn_kv(const float *wqkv, unsigned char *dst, int C, hip
 // (+ bias partials [nslice][cout]) -- the second pass of every tiled weight gradient (3x3, 1x1, and train_wgrad7.hip's 7x7)
 hipError_t launch_wgrad_reduce(const float *part, const float *dbpart, float *dw, float *db, int cin, int cout, int nslice, int taps,
                                hipStream_t st);
+// The common end of the tiled weight-gradient entry points (gtts_conv3x3_wgrad, gtts_conv1x1_wgrad, gtts_conv7x7_wgrad), after their
+// argument checks and *_geometry: refuses a workspace below `need` (the entry's own *_wgrad_workspace_bytes), places the partial tiles
+// at its start and, with db, the bias partials behind them, runs launch(a, tiles) -- the entry's kernel -- and then the reduction.
+template <class Args, class Launch>
+int wgrad_finish(const char *fn, Args &a, int taps, void *workspace, size_t workspace_bytes, size_t need, float *dw, float *db,
+                 hipStream_t st, Launch launch) {
+    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "%s: workspace too small: need %zu bytes, got %zu", fn, need, workspace_bytes);
+    const int tiles = (a.cin / 64) * (a.cout / 64);
+    a.part = (float *)workspace;
+    a.dbpart = db ? a.part + (size_t)a.nslice * tiles * taps * (64 * 64) : nullptr;
+    hipError_t e = launch(a, tiles);
+    if (e == hipSuccess) e = launch_wgrad_reduce(a.part, a.dbpart, dw, db, a.cin, a.cout, a.nslice, taps, st);
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return GTTS_OK;
+}
 hipError_t launch_copy_f32(const float *src, float *dst, size_t n, hipStream_t st);
 
 // ---- glue.hip (generate_path + aligned prior mean + terminal sample: tts.py:84-94, utils.py:26-39)

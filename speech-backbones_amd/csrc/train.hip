@@ -3,14 +3,14 @@
 //
 //   gtts_diffusion_noising   forward_diffusion (diffusion.py:244-252): xt = (x0 e^{-c/2} + mu (1 - e^{-c/2}) + z sqrt(1 - e^{-c})) mask
 //   gtts_score_loss          loss_t (diffusion.py:281-288): sum((eps sqrt(1 - e^{-c}) + z)^2) / (sum(mask) F) and d loss / d eps
-//   gtts_conv3x3_masked      y = Conv2d_3x3(x * mask) + bias      (Block.forward, diffusion.py:56-57) on the inference MFMA kernel
-//   gtts_conv3x3_dgrad       d loss / d (x * mask) = Conv2d_3x3(dy, W^T flipped): the same kernel with repacked weights
-//   gtts_conv3x3_wgrad       dW[co][ci][ky][kx] = sum_{b,y,x} dy[b,co,y,x] (x mask)[b,ci,y+ky-1,x+kx-1], db = sum dy:
-//                            an MFMA reduction over PIXELS (the K dimension is the frame axis, contiguous in NCHW, so both
-//                            operands are read straight from HBM as 8-pixel runs per lane -- no LDS, no barriers);
-//                            split-bf16 (3 MFMAs per product, fp32 accumulate), partial sums combined with fp32 atomics.
-// The 3x3 convolutions are 84 % of the U-Net's FLOPs forward and (twice that) backward; GroupNorm / Mish / attention
-// backward stay PyTorch autograd for now (model/_train_ops.py wraps these entry points in torch.autograd.Function).
+//   gtts_conv3x3_masked      y = Conv2d_3x3(x * mask) + bias      (Block.forward, diffusion.py:56-57) on the inference MFMA kernel;
+//                            the data gradient Conv2d_3x3(dy, W^T flipped) [* mask] is the same call with weights packed transposed
+//   gtts_conv7x7_masked, gtts_conv1x1_masked, gtts_conv_resample     the same launch setup (conv_train_launch) on the 7x7, 1x1 and
+//                            Downsample / Upsample inference kernels, and gtts_*_pack / gtts_pack_batch, which pack their weights
+// The weight gradients are fixed-order MFMA reductions over pixels in train_wgrad.hip and train_wgrad7.hip; GroupNorm + Mish, the
+// attention core and the elementwise ops of the step are train_norm.hip, train_attn.hip and train_elem.hip.  Every tensor-sized op
+// of the step, forward and backward, is a kernel of this library: model/_train_ops.py wraps the entry points in
+// torch.autograd.Function, and autograd only sequences them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -65,124 +65,6 @@ __global__ void score_loss_kernel(const float *__restrict__ eps, const float *__
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// ------------------------------------------------------------------------------------------------ weight gradient
-// One wave owns a 32 (cout) x 32 (cin) x 9 (taps) tile of dW and a slice of the pixel blocks (b, y, 16 consecutive x).
-// MFMA 32x32x16: A[m = co][k = pixel] from dy, B[n = ci][k = pixel] from x * mask shifted by the tap; lane (l31, kg) holds
-// the 8 consecutive pixels x0 + 8 kg .. + 7 of its channel, read as two 16-byte loads.
-struct WgradArgs {
-    const float *x;        // [B][cin][H][W]
-    const float *mask;     // [B][W] or nullptr
-    const float *dy;       // [B][cout][H][W]
-    float *dw;             // [cout][cin][3][3]  (zeroed by the caller; fp32 atomics)
-    float *db;             // [cout] or nullptr
-    int B, cin, cout, H, W;
-    int nblk;              // B * H * ceil(W / 16)
-    int nslice;            // pixel slices (waves) per (co tile, ci tile)
-};
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {        // (lo half = a, hi half = b), RNE
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    bf16x2 v;
-    v[0] = (__bf16)a;
-    v[1] = (__bf16)b;
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float bf16_hi_part(float x) { return (float)(__bf16)x; }
-
-__global__ __launch_bounds__(256, 2) void conv3x3_wgrad_kernel(const WgradArgs a) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l31 = lane & 31, kg = lane >> 5;
-    const int ncit = a.cin / 32, ncot = a.cout / 32;
-    const int gw = blockIdx.x * 4 + wave;                  // global wave id
-    const int tile = gw % (ncit * ncot), slice = gw / (ncit * ncot);
-    if (slice >= a.nslice) return;
-    const int co0 = (tile / ncit) * 32, ci0 = (tile % ncit) * 32;
-    const int xb16 = (a.W + 15) / 16;
-    const size_t HW = (size_t)a.H * a.W;
-
-    f32x16 acc[3][3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[ky][kx][r] = 0.f;
-    float bsum = 0.f;
-
-    const int per = (a.nblk + a.nslice - 1) / a.nslice;
-    const int blk0 = slice * per, blk1 = min(a.nblk, blk0 + per);
-    for (int blk = blk0; blk < blk1; ++blk) {
-        const int xb = blk % xb16;
-        const int y = (blk / xb16) % a.H;
-        const int b = blk / (xb16 * a.H);
-        const int px0 = xb * 16 + 8 * kg;                   // first pixel of this lane's run
-        // ---- A: dy[b][co0 + l31][y][px0 .. px0 + 7]
-        float av[8];
-        {
-            const float *p = a.dy + ((size_t)b * a.cout + co0 + l31) * HW + (size_t)y * a.W + px0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) av[i] = (px0 + i < a.W) ? p[i] : 0.f;
-        }
-        u32x4 ah, al;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float h0 = bf16_hi_part(av[2 * i]), h1 = bf16_hi_part(av[2 * i + 1]);
-            ah[i] = pack_bf16(av[2 * i], av[2 * i + 1]);
-            al[i] = pack_bf16(av[2 * i] - h0, av[2 * i + 1] - h1);
-            bsum += av[2 * i] + av[2 * i + 1];
-        }
-        const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah), Al = __builtin_bit_cast(bf16x8, al);
-        // ---- B: rows y-1, y, y+1 of (x * mask)[b][ci0 + l31], pixels px0 - 1 .. px0 + 8
-        const float *xrow = a.x + ((size_t)b * a.cin + ci0 + l31) * HW;
-        const float *mrow = a.mask ? a.mask + (size_t)b * a.W : nullptr;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int yy = y + ky - 1;
-            float v[10];
-            const bool rowok = yy >= 0 && yy < a.H;
-#pragma unroll
-            for (int i = 0; i < 10; ++i) {
-                const int px = px0 - 1 + i;
-                const bool ok = rowok && px >= 0 && px < a.W;
-                float t = ok ? xrow[(size_t)(rowok ? yy : 0) * a.W + (ok ? px : 0)] : 0.f;
-                if (mrow) t *= ok ? mrow[px] : 0.f;
-                v[i] = t;
-            }
-            float lo[10];
-#pragma unroll
-            for (int i = 0; i < 10; ++i) lo[i] = v[i] - bf16_hi_part(v[i]);
-            // kx = 0: elements 0..7, kx = 1: 1..8, kx = 2: 2..9 of v[]
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                u32x4 bh, bl;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    bh[i] = pack_bf16(v[kx + 2 * i], v[kx + 2 * i + 1]);
-                    bl[i] = pack_bf16(lo[kx + 2 * i], lo[kx + 2 * i + 1]);
-                }
-                const bf16x8 Bh = __builtin_bit_cast(bf16x8, bh), Bl = __builtin_bit_cast(bf16x8, bl);
-                acc[ky][kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc[ky][kx], 0, 0, 0);
-                acc[ky][kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc[ky][kx], 0, 0, 0);
-                acc[ky][kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[ky][kx], 0, 0, 0);
-            }
-        }
-    }
-    // ---- combine: D[m = co][n = ci]; lane (l31 = ci, kg) holds rows (rg&3) + 8 (rg>>2) + 4 kg
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-            for (int rg = 0; rg < 16; ++rg) {
-                const int co = co0 + (rg & 3) + 8 * (rg >> 2) + 4 * kg;
-                atomicAdd(a.dw + (((size_t)co * a.cin + ci0 + l31) * 3 + ky) * 3 + kx, acc[ky][kx][rg]);
-            }
-    if (a.db && ci0 == 0) {
-        bsum += __shfl_xor(bsum, 32, 64);                   // the two 8-pixel halves of the run
-        if (kg == 0) atomicAdd(a.db + co0 + l31, bsum);
-    }
-}
-
 }  // namespace gtts
 
 using namespace gtts;
@@ -212,19 +94,49 @@ extern "C" int gtts_score_loss(const float *eps, const float *z_masked, const fl
     return GTTS_OK;
 }
 
-extern "C" size_t gtts_conv3x3_packed_bytes(int cin, int cout) {
-    if (cin <= 0 || cout <= 0) return 0;
-    return align256(conv_packed_bytes(CONV_C3, cin, cout));
+// ---- the launch setup of every forward / data-gradient convolution of the training path: the inference kernel of `mode` with the
+// mask prologue (mask [B][Win] on the input columns) and the plain epilogue, one weight and bias for the whole batch.  x1 (nullable):
+// the input is the channel concatenation of x [B,c0,..] and x1 [B,cin-c0,..], read in place; omask (nullable): [B][Wout] column mask
+// multiplied into the output.  `fn`: the entry point, for the error text.  The callers have validated every argument.
+static int conv_train_launch(int mode, const char *fn, const float *x, const float *x1, int c0, const float *mask, const float *omask,
+                             const void *packed, const float *bias, float *y, int B, int cin, int cout, int Hin, int Win, int Hout,
+                             int Wout, gtts_stream_t stream) {
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src0 = x; a.src1 = x1 ? x1 : x; a.c0 = x1 ? c0 : cin; a.c1 = x1 ? cin - c0 : 0; a.cin = cin;
+    a.B = B; a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout;
+    a.mask = mask; a.T = Win; a.lvl_in = a.lvl_out = 0;
+    a.pro = PRO_MASK; a.epi = EPI_PLAIN;
+    a.w = (const unsigned char *)packed; a.w_bstride = 0;
+    a.bias = bias; a.bias_bstride = 0;
+    a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
+    a.omask = omask;
+    const hipError_t e = launch_conv(mode, a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GTTS_E_HIP, "%s (cin %d, cout %d): %s", fn, cin, cout, hipGetErrorString(e));
+    return GTTS_OK;
 }
 
-// transposed != 0: w is the FORWARD weight [cin_of_this_conv... i.e. forward cout][forward cin = cout of this conv][3][3] and
-// is packed transposed with flipped taps (the data-gradient convolution)
-extern "C" int gtts_conv3x3_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream) {
-    if (!w || !packed) return fail(GTTS_E_NULL, "gtts_conv3x3_pack: null argument");
-    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv3x3_pack: bad shape");
-    // cin / cout are those of the convolution being packed (for the data gradient: cin = forward cout, cout = forward cin)
-    GTTS_HIPCHK(launch_pack_conv(transposed ? CONV_C3 + 16 : CONV_C3, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
+// ---- weight packing: gtts_<kind>_packed_bytes is the aligned blob size of the kind's CONV_* mode, gtts_<kind>_pack this call.  cin /
+// cout are those of the convolution being packed; mode + 16 packs the FORWARD weight [forward cout = cin][forward cin = cout][k][k]
+// transposed with flipped taps (the data-gradient convolution).  chan: cin and cout must be multiples of it (GTTS_E_CONFIG).
+static size_t train_packed_bytes(int mode, int cin, int cout, int chan = 1) {
+    if (cin <= 0 || cout <= 0 || cin % chan || cout % chan) return 0;
+    return align256(conv_packed_bytes(mode, cin, cout));
+}
+
+static int train_pack(int mode, const char *fn, const float *w, void *packed, int cin, int cout, gtts_stream_t stream, int chan = 1) {
+    if (!w || !packed) return fail(GTTS_E_NULL, "%s: null argument", fn);
+    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "%s: bad shape", fn);
+    if (cin % chan || cout % chan) return fail(GTTS_E_CONFIG, "%s: cin and cout must be multiples of %d (got %d, %d)", fn, chan, cin, cout);
+    GTTS_HIPCHK(launch_pack_conv(mode, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
     return GTTS_OK;
+}
+
+// ---- 3x3 convolutions (Block: diffusion.py:56-57): the weight gradient is gtts_conv3x3_wgrad (train_wgrad.hip)
+extern "C" size_t gtts_conv3x3_packed_bytes(int cin, int cout) { return train_packed_bytes(CONV_C3, cin, cout); }
+
+extern "C" int gtts_conv3x3_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream) {
+    return train_pack(transposed ? CONV_C3 + 16 : CONV_C3, "gtts_conv3x3_pack", w, packed, cin, cout, stream);
 }
 
 // y = Conv2d_3x3(x * mask, packed W) + bias; x [B,cin,H,W], mask [B,W] (columns), y [B,cout,H,W].  cout % 64 == 0 (128 above 64).
@@ -232,39 +144,17 @@ extern "C" int gtts_conv3x3_pack(const float *w, void *packed, int cin, int cout
 // in place (torch.cat of the up path, diffusion.py:166)
 // omask (nullable): [B][W] column mask multiplied into the output -- the data gradient of a masked convolution is
 // conv(dy; transposed weights) * mask, and the mask rides in the epilogue instead of a second pass over dx
-extern "C" int gtts_conv3x3_masked3(const float *x, const float *x1, int c0, const float *mask, const float *omask, const void *packed,
-                                    const float *bias, float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
+extern "C" int gtts_conv3x3_masked(const float *x, const float *x1, int c0, const float *mask, const float *omask, const void *packed,
+                                   const float *bias, float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
     if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv3x3_masked: null argument");
     if (x1 && (c0 <= 0 || c0 >= cin || c0 % 16)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: c0 must be a multiple of 16 inside (0, cin) (got %d of %d)", c0, cin);
     if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: bad shape");
     if (cout % (cout > 64 ? 128 : 64) != 0) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: cout must be 64 or a multiple of 128 (got %d)", cout);
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = x; a.src1 = x1 ? x1 : x; a.c0 = x1 ? c0 : cin; a.c1 = x1 ? cin - c0 : 0; a.cin = cin;
-    a.B = B; a.Hin = a.Hout = H; a.Win = a.Wout = W;
-    a.mask = mask; a.T = W; a.lvl_in = a.lvl_out = 0;
-    a.pro = PRO_MASK; a.epi = EPI_PLAIN;
-    a.w = (const unsigned char *)packed; a.w_bstride = 0;
-    a.bias = bias; a.bias_bstride = 0;
-    a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
-    a.omask = omask;
-    const hipError_t e = launch_conv(CONV_C3, a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv3x3 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
-    return GTTS_OK;
+    return conv_train_launch(CONV_C3, "gtts_conv3x3_masked", x, x1, c0, mask, omask, packed, bias, y, B, cin, cout, H, W, H, W, stream);
 }
 
-extern "C" int gtts_conv3x3_masked2(const float *x, const float *x1, int c0, const float *mask, const void *packed, const float *bias,
-                                    float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
-    return gtts_conv3x3_masked3(x, x1, c0, mask, nullptr, packed, bias, y, B, cin, cout, H, W, stream);
-}
-
-extern "C" int gtts_conv3x3_masked(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B,
-                                   int cin, int cout, int H, int W, gtts_stream_t stream) {
-    return gtts_conv3x3_masked3(x, nullptr, 0, mask, nullptr, packed, bias, y, B, cin, cout, H, W, stream);
-}
-
-// ---- 7x7 convolutions of the training path (DiffVC PostNet Block, DiffVC/model/postnet.py:15-23): forward and data gradient on
-// the inference CONV_C7 kernel (mask prologue, plain epilogue); the weight gradient is gtts_conv7x7_wgrad (train_wgrad7.hip).
+// ---- 7x7 convolutions (DiffVC PostNet Block, DiffVC/model/postnet.py:15-23) on the inference CONV_C7 kernel; the weight gradient is
+// gtts_conv7x7_wgrad (train_wgrad7.hip).
 // Channel counts are multiples of 64 (GTTS_E_CONFIG otherwise: the kernel's 64-cout tile and the weight gradient's 64 x 64 tile);
 // every tensor of a call must stay below 2^31 bytes (GTTS_E_SHAPE): the kernels address it with 32-bit byte offsets.
 static int conv7x7_check(const char *fn, int B, int cin, int cout, int H, int W) {
@@ -274,19 +164,10 @@ static int conv7x7_check(const char *fn, int B, int cin, int cout, int H, int W)
     return GTTS_OK;
 }
 
-extern "C" size_t gtts_conv7x7_packed_bytes(int cin, int cout) {
-    if (cin <= 0 || cout <= 0 || cin % 64 || cout % 64) return 0;
-    return align256(conv_packed_bytes(CONV_C7, cin, cout));
-}
+extern "C" size_t gtts_conv7x7_packed_bytes(int cin, int cout) { return train_packed_bytes(CONV_C7, cin, cout, 64); }
 
-// transposed != 0: w is the FORWARD weight [forward cout = cin of this conv][forward cin = cout of this conv][7][7], packed
-// transposed with flipped taps (the data-gradient convolution)
 extern "C" int gtts_conv7x7_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream) {
-    if (!w || !packed) return fail(GTTS_E_NULL, "gtts_conv7x7_pack: null argument");
-    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv7x7_pack: bad shape");
-    if (cin % 64 || cout % 64) return fail(GTTS_E_CONFIG, "gtts_conv7x7_pack: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
-    GTTS_HIPCHK(launch_pack_conv(transposed ? CONV_C7 + 16 : CONV_C7, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
-    return GTTS_OK;
+    return train_pack(transposed ? CONV_C7 + 16 : CONV_C7, "gtts_conv7x7_pack", w, packed, cin, cout, stream, 64);
 }
 
 // y = Conv2d_7x7(x * mask, packed W, padding 3) + bias; x [B,cin,H,W], mask [B,W] (columns), bias [cout], y [B,cout,H,W];
@@ -296,34 +177,15 @@ extern "C" int gtts_conv7x7_masked(const float *x, const float *mask, const floa
     if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv7x7_masked: null argument");
     const int rc = conv7x7_check("gtts_conv7x7_masked", B, cin, cout, H, W);
     if (rc != GTTS_OK) return rc;
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = x; a.src1 = x; a.c0 = cin; a.c1 = 0; a.cin = cin;
-    a.B = B; a.Hin = a.Hout = H; a.Win = a.Wout = W;
-    a.mask = mask; a.T = W; a.lvl_in = a.lvl_out = 0;
-    a.pro = PRO_MASK; a.epi = EPI_PLAIN;
-    a.w = (const unsigned char *)packed; a.w_bstride = 0;
-    a.bias = bias; a.bias_bstride = 0;
-    a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
-    a.omask = omask;
-    const hipError_t e = launch_conv(CONV_C7, a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv7x7 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
-    return GTTS_OK;
+    return conv_train_launch(CONV_C7, "gtts_conv7x7_masked", x, nullptr, 0, mask, omask, packed, bias, y, B, cin, cout, H, W, H, W, stream);
 }
 
-// ---- 1x1 convolutions of the training path (res_conv, to_qkv, to_out: diffusion.py:70,87-88): forward and data gradient on
-// the inference CONV_P1 kernel (mask prologue, plain epilogue); the weight gradient is gtts_conv1x1_wgrad (train_wgrad.hip)
-extern "C" size_t gtts_conv1x1_packed_bytes(int cin, int cout) {
-    if (cin <= 0 || cout <= 0) return 0;
-    return align256(conv_packed_bytes(CONV_P1, cin, cout));
-}
+// ---- 1x1 convolutions (res_conv, to_qkv, to_out: diffusion.py:70,87-88) on the inference CONV_P1 kernel; the weight gradient is
+// gtts_conv1x1_wgrad (train_wgrad.hip)
+extern "C" size_t gtts_conv1x1_packed_bytes(int cin, int cout) { return train_packed_bytes(CONV_P1, cin, cout); }
 
-// transposed != 0: w is the FORWARD weight [forward cout = cin of this conv][forward cin = cout of this conv]
 extern "C" int gtts_conv1x1_pack(const float *w, void *packed, int cin, int cout, int transposed, gtts_stream_t stream) {
-    if (!w || !packed) return fail(GTTS_E_NULL, "gtts_conv1x1_pack: null argument");
-    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv1x1_pack: bad shape");
-    GTTS_HIPCHK(launch_pack_conv(transposed ? CONV_P1 + 16 : CONV_P1, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
-    return GTTS_OK;
+    return train_pack(transposed ? CONV_P1 + 16 : CONV_P1, "gtts_conv1x1_pack", w, packed, cin, cout, stream);
 }
 
 // y = Conv2d_1x1(x * mask, packed W) + bias; x [B,cin,H,W], mask [B,W] (columns), bias [cout], y [B,cout,H,W]
@@ -332,18 +194,7 @@ extern "C" int gtts_conv1x1_masked(const float *x, const float *mask, const void
     if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv1x1_masked: null argument");
     if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv1x1_masked: bad shape");
     if (cout % (cout > 64 ? 128 : 64) != 0) return fail(GTTS_E_SHAPE, "gtts_conv1x1_masked: cout must be 64 or a multiple of 128 (got %d)", cout);
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = x; a.src1 = x; a.c0 = cin; a.c1 = 0; a.cin = cin;
-    a.B = B; a.Hin = a.Hout = H; a.Win = a.Wout = W;
-    a.mask = mask; a.T = W; a.lvl_in = a.lvl_out = 0;
-    a.pro = PRO_MASK; a.epi = EPI_PLAIN;
-    a.w = (const unsigned char *)packed; a.w_bstride = 0;
-    a.bias = bias; a.bias_bstride = 0;
-    a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
-    const hipError_t e = launch_conv(CONV_P1, a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv1x1 (cin %d, cout %d): %s", cin, cout, hipGetErrorString(e));
-    return GTTS_OK;
+    return conv_train_launch(CONV_P1, "gtts_conv1x1_masked", x, nullptr, 0, mask, nullptr, packed, bias, y, B, cin, cout, H, W, H, W, stream);
 }
 
 // ---- Downsample (Conv2d 3x3, stride 2, pad 1: diffusion.py:28-34) and Upsample (ConvTranspose2d 4x4, stride 2, pad 1:
@@ -351,16 +202,22 @@ extern "C" int gtts_conv1x1_masked(const float *x, const float *mask, const void
 // up = 1: w [cin][cout][4][4] (ConvTranspose2d layout), y [B,cout,2H,2W].  The data gradient of Downsample IS an Upsample call:
 // a transposed 3x3 stride-2 convolution is the 4x4 one whose fourth kernel row and column are zero (same index map
 // y = 2 oy - 1 + ky), so the host packs the zero-padded forward weight with up = 1.
-extern "C" size_t gtts_conv_resample_packed_bytes(int cin, int cout, int up) {
-    if (cin <= 0 || cout <= 0) return 0;
-    return align256(conv_packed_bytes(up ? CONV_UP : CONV_DN, cin, cout));
-}
+extern "C" size_t gtts_conv_resample_packed_bytes(int cin, int cout, int up) { return train_packed_bytes(up ? CONV_UP : CONV_DN, cin, cout); }
 
 extern "C" int gtts_conv_resample_pack(const float *w, void *packed, int cin, int cout, int up, gtts_stream_t stream) {
-    if (!w || !packed) return fail(GTTS_E_NULL, "gtts_conv_resample_pack: null argument");
-    if (cin <= 0 || cout <= 0) return fail(GTTS_E_SHAPE, "gtts_conv_resample_pack: bad shape");
-    GTTS_HIPCHK(launch_pack_conv(up ? CONV_UP : CONV_DN, w, (unsigned char *)packed, cin, cout, (hipStream_t)stream));
-    return GTTS_OK;
+    return train_pack(up ? CONV_UP : CONV_DN, "gtts_conv_resample_pack", w, packed, cin, cout, stream);
+}
+
+// y = conv(x * mask) + bias; x [B,cin,H,W], mask [B,W] (columns of the INPUT).  H and W even for up = 0.
+extern "C" int gtts_conv_resample(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B, int cin,
+                                  int cout, int H, int W, int up, gtts_stream_t stream) {
+    if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv_resample: null argument");
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv_resample: bad shape");
+    if (!up && ((H | W) & 1)) return fail(GTTS_E_SHAPE, "gtts_conv_resample: Downsample needs even H and W (got %d x %d)", H, W);
+    if (cin % 16 != 0 || cout % (cout > 64 ? 128 : 64) != 0)
+        return fail(GTTS_E_SHAPE, "gtts_conv_resample: cin must be a multiple of 16 and cout 64 or a multiple of 128 (got %d, %d)", cin, cout);
+    return conv_train_launch(up ? CONV_UP : CONV_DN, up ? "gtts_conv_resample (up)" : "gtts_conv_resample (down)", x, nullptr, 0, mask, nullptr,
+                             packed, bias, y, B, cin, cout, H, W, up ? 2 * H : H / 2, up ? 2 * W : W / 2, stream);
 }
 
 // ---- all weight packs of a training step in one launch (ABI 4) ----------------------------------------------------------
@@ -398,51 +255,5 @@ extern "C" int gtts_pack_batch(const void *desc_dev, int n, int grid_x, gtts_str
     if (!desc_dev) return fail(GTTS_E_NULL, "gtts_pack_batch: null argument");
     if (n <= 0 || grid_x <= 0) return fail(GTTS_E_SHAPE, "gtts_pack_batch: bad sizes");
     GTTS_HIPCHK(launch_pack_batch(reinterpret_cast<const PackDesc *>(desc_dev), n, grid_x, (hipStream_t)stream));
-    return GTTS_OK;
-}
-
-// y = conv(x * mask) + bias; x [B,cin,H,W], mask [B,W] (columns of the INPUT).  H and W even for up = 0.
-extern "C" int gtts_conv_resample(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B, int cin,
-                                  int cout, int H, int W, int up, gtts_stream_t stream) {
-    if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv_resample: null argument");
-    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv_resample: bad shape");
-    if (!up && ((H | W) & 1)) return fail(GTTS_E_SHAPE, "gtts_conv_resample: Downsample needs even H and W (got %d x %d)", H, W);
-    if (cin % 16 != 0 || cout % (cout > 64 ? 128 : 64) != 0)
-        return fail(GTTS_E_SHAPE, "gtts_conv_resample: cin must be a multiple of 16 and cout 64 or a multiple of 128 (got %d, %d)", cin, cout);
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = x; a.src1 = x; a.c0 = cin; a.c1 = 0; a.cin = cin;
-    a.B = B; a.Hin = H; a.Win = W;
-    a.Hout = up ? 2 * H : H / 2; a.Wout = up ? 2 * W : W / 2;
-    a.mask = mask; a.T = W; a.lvl_in = 0; a.lvl_out = 0;
-    a.pro = PRO_MASK; a.epi = EPI_PLAIN;
-    a.w = (const unsigned char *)packed; a.w_bstride = 0;
-    a.bias = bias; a.bias_bstride = 0;
-    a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
-    const hipError_t e = launch_conv(up ? CONV_UP : CONV_DN, a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(GTTS_E_HIP, "conv resample (cin %d, cout %d, up %d): %s", cin, cout, up, hipGetErrorString(e));
-    return GTTS_OK;
-}
-
-extern "C" int gtts_conv3x3_wgrad(const float *x, const float *mask, const float *dy, float *dw, float *db, int B, int cin, int cout,
-                                  int H, int W, gtts_stream_t stream) {
-    if (!x || !dy || !dw) return fail(GTTS_E_NULL, "gtts_conv3x3_wgrad: null argument");
-    if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 32 || cout % 32)
-        return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad: cin and cout must be multiples of 32 (got %d, %d)", cin, cout);
-    hipStream_t st = (hipStream_t)stream;
-    GTTS_HIPCHK(hipMemsetAsync(dw, 0, (size_t)cout * cin * 9 * 4, st));
-    if (db) GTTS_HIPCHK(hipMemsetAsync(db, 0, (size_t)cout * 4, st));
-    WgradArgs a;
-    a.x = x; a.mask = mask; a.dy = dy; a.dw = dw; a.db = db;
-    a.B = B; a.cin = cin; a.cout = cout; a.H = H; a.W = W;
-    a.nblk = B * H * ((W + 15) / 16);
-    const int tiles = (cin / 32) * (cout / 32);
-    // ~8 waves per SIMD-pair worth of work across the chip, at least 8 pixel blocks per wave
-    int nslice = (256 * 8 * 4 + tiles - 1) / tiles;
-    nslice = std::max(1, std::min(nslice, (a.nblk + 7) / 8));
-    a.nslice = nslice;
-    const long long waves = (long long)tiles * nslice;
-    hipLaunchKernelGGL(conv3x3_wgrad_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, a);
-    GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }

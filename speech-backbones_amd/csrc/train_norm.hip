@@ -1,7 +1,7 @@
 // train_norm.hip -- Block's GroupNorm + Mish + mask for the training hot path (second stage).
 //
-//   forward   out = Mish(GroupNorm_8(y)) * mask                     Grad-TTS/model/diffusion.py:53-58 (Block), :13-15 (Mish)
-//   backward  dy, dgamma, dbeta from d out                          (what autograd derives for those lines)
+//   forward   out = Mish(GroupNorm_8(y)) * mask [+ tb[b,c]]         Grad-TTS/model/diffusion.py:53-58 (Block), :13-15 (Mish), :75-76 (time term)
+//   backward  dy, dgamma, dbeta [, dtb] from d out                  (what autograd derives for those lines)
 //
 // GroupNorm statistics span the whole H x W plane of the group's channels, masked frames included, exactly like
 // torch.nn.GroupNorm on the padded batch (eps 1e-5, biased variance).  Everything here is bound by HBM:
@@ -213,9 +213,8 @@ static int norm_shape_ok(int B, int C, int H, int W, int groups) {
 }
 
 // tb (nullable): [B][C] bias added after the mask (ResnetBlock's time embedding term, diffusion.py:75-76)
-extern "C" int gtts_gn_mish_forward_tb(const float *y, const float *gamma, const float *beta, const float *mask, const float *tb,
-                                       float *out, float *stats, int B, int C, int H, int W, int groups, float eps,
-                                       gtts_stream_t stream) {
+extern "C" int gtts_gn_mish_forward(const float *y, const float *gamma, const float *beta, const float *mask, const float *tb,
+                                    float *out, float *stats, int B, int C, int H, int W, int groups, float eps, gtts_stream_t stream) {
     if (!y || !gamma || !beta || !mask || !out || !stats) return fail(GTTS_E_NULL, "gtts_gn_mish_forward: null argument");
     if (!norm_shape_ok(B, C, H, W, groups)) return fail(GTTS_E_SHAPE, "gtts_gn_mish_forward: bad shape B=%d C=%d H=%d W=%d groups=%d", B, C, H, W, groups);
     const int HW = H * W, cpg = C / groups;
@@ -231,11 +230,6 @@ extern "C" int gtts_gn_mish_forward_tb(const float *y, const float *gamma, const
     return GTTS_OK;
 }
 
-extern "C" int gtts_gn_mish_forward(const float *y, const float *gamma, const float *beta, const float *mask, float *out,
-                                    float *stats, int B, int C, int H, int W, int groups, float eps, gtts_stream_t stream) {
-    return gtts_gn_mish_forward_tb(y, gamma, beta, mask, nullptr, out, stats, B, C, H, W, groups, eps, stream);
-}
-
 extern "C" size_t gtts_gn_mish_stats_floats(int B, int groups) {
     return B > 0 && groups > 0 ? (size_t)B * groups * 2 + (size_t)B * groups * GN_SPLIT * 4 : 0;
 }
@@ -243,9 +237,9 @@ extern "C" size_t gtts_gn_mish_stats_floats(int B, int groups) {
 extern "C" size_t gtts_gn_mish_scratch_bytes(int B, int C) { return B > 0 && C > 0 ? (size_t)B * C * 2 * 4 * 2 : 0; }
 
 // dtb (nullable): [B][C] gradient of the time bias
-extern "C" int gtts_gn_mish_backward_tb(const float *dout, const float *y, const float *gamma, const float *beta, const float *mask,
-                                        const float *stats, float *dy, float *dgamma, float *dbeta, float *dtb, void *scratch, int B,
-                                        int C, int H, int W, int groups, gtts_stream_t stream) {
+extern "C" int gtts_gn_mish_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *mask,
+                                     const float *stats, float *dy, float *dgamma, float *dbeta, float *dtb, void *scratch, int B,
+                                     int C, int H, int W, int groups, gtts_stream_t stream) {
     if (!dout || !y || !gamma || !beta || !mask || !stats || !dy || !dgamma || !dbeta || !scratch)
         return fail(GTTS_E_NULL, "gtts_gn_mish_backward: null argument");
     if (!norm_shape_ok(B, C, H, W, groups)) return fail(GTTS_E_SHAPE, "gtts_gn_mish_backward: bad shape B=%d C=%d H=%d W=%d groups=%d", B, C, H, W, groups);
@@ -262,10 +256,4 @@ extern "C" int gtts_gn_mish_backward_tb(const float *dout, const float *y, const
                        dy, C, HW, W, cpg);
     GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
-}
-
-extern "C" int gtts_gn_mish_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *mask,
-                                     const float *stats, float *dy, float *dgamma, float *dbeta, void *scratch, int B, int C, int H,
-                                     int W, int groups, gtts_stream_t stream) {
-    return gtts_gn_mish_backward_tb(dout, y, gamma, beta, mask, stats, dy, dgamma, dbeta, nullptr, scratch, B, C, H, W, groups, stream);
 }

@@ -446,32 +446,27 @@ extern "C" size_t gtts_conv3x3_wgrad_workspace_bytes(int B, int cin, int cout, i
     return ((size_t)a.nslice * (cin / 64) * (cout / 64) * (9 * 64 * 64) + (size_t)a.nslice * cout) * sizeof(float);
 }
 
+// dw [cout][cin][3][3], db [cout] (or null) of y = Conv2d_3x3(x * mask) + bias; both are overwritten
 // x1 (nullable) / c0: the input is the channel concatenation of x [B,c0,H,W] and x1 [B,cin-c0,H,W] (c0 a multiple of 64)
-extern "C" int gtts_conv3x3_wgrad_tiled2(const float *x, const float *x1, int c0, const float *mask, const float *dy, float *dw, float *db,
-                                         void *workspace, size_t workspace_bytes, int B, int cin, int cout, int H, int W,
-                                         gtts_stream_t stream) {
-    if (!x || !mask || !dy || !dw || !workspace) return fail(GTTS_E_NULL, "gtts_conv3x3_wgrad_tiled: null argument");
-    if (x1 && (c0 <= 0 || c0 >= cin || c0 % 64)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: c0 must be a multiple of 64 inside (0, cin) (got %d of %d)", c0, cin);
+extern "C" int gtts_conv3x3_wgrad(const float *x, const float *x1, int c0, const float *mask, const float *dy, float *dw, float *db,
+                                  void *workspace, size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
+    if (!x || !mask || !dy || !dw || !workspace) return fail(GTTS_E_NULL, "gtts_conv3x3_wgrad: null argument");
+    if (x1 && (c0 <= 0 || c0 >= cin || c0 % 64)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad: c0 must be a multiple of 64 inside (0, cin) (got %d of %d)", c0, cin);
     if (B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 64 || cout % 64)
-        return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
-    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad_tiled: tensor too large");
+        return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad: cin and cout must be multiples of 64 (got %d, %d)", cin, cout);
+    if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_wgrad: tensor too large");
     Wgrad2Args a;
     wgrad2_geometry(B, cin, cout, H, W, a);
-    const size_t need = gtts_conv3x3_wgrad_workspace_bytes(B, cin, cout, H, W);
-    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "gtts_conv3x3_wgrad_tiled: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    const int tiles = (cin / 64) * (cout / 64);
-    a.x = x; a.x1 = x1; a.c0 = x1 ? c0 : cin; a.mask = mask; a.dy = dy; a.part = (float *)workspace;
-    a.dbpart = db ? a.part + (size_t)a.nslice * tiles * (9 * 64 * 64) : nullptr;
+    a.x = x; a.x1 = x1; a.c0 = x1 ? c0 : cin; a.mask = mask; a.dy = dy;
     hipStream_t st = (hipStream_t)stream;
-    constexpr size_t smem = (size_t)2 * (2 * 64 * DY_STRIDE + 2 * 64 * X_STRIDE) * 16;      // two buffers
-    GTTS_HIPCHK(raise_dyn_lds<&conv3x3_wgrad2_kernel>(smem));
-    hipLaunchKernelGGL(conv3x3_wgrad2_kernel, dim3((unsigned)(tiles * a.nslice)), dim3(512), smem, st, a);
-    GTTS_HIPCHK(hipGetLastError());
-    const size_t total = (size_t)tiles * (9 * 64 * 64) + (db ? (size_t)cout : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, a.part, a.dbpart, dw, db, cin, cout,
-                       a.nslice, 9);
-    GTTS_HIPCHK(hipGetLastError());
-    return GTTS_OK;
+    return wgrad_finish("gtts_conv3x3_wgrad", a, 9, workspace, workspace_bytes, gtts_conv3x3_wgrad_workspace_bytes(B, cin, cout, H, W), dw, db, st,
+                        [st](const Wgrad2Args &a, int tiles) {
+                            constexpr size_t smem = (size_t)2 * (2 * 64 * DY_STRIDE + 2 * 64 * X_STRIDE) * 16;      // two buffers
+                            const hipError_t e = raise_dyn_lds<&conv3x3_wgrad2_kernel>(smem);
+                            if (e != hipSuccess) return e;
+                            hipLaunchKernelGGL(conv3x3_wgrad2_kernel, dim3((unsigned)(tiles * a.nslice)), dim3(512), smem, st, a);
+                            return hipGetLastError();
+                        });
 }
 
 extern "C" size_t gtts_conv1x1_wgrad_workspace_bytes(int B, int cin, int cout, int H, int W) {
@@ -490,22 +485,11 @@ extern "C" int gtts_conv1x1_wgrad(const float *x, const float *mask, const float
     if ((size_t)B * std::max(cin, cout) * H * W >= ((size_t)1 << 29)) return fail(GTTS_E_SHAPE, "gtts_conv1x1_wgrad: tensor too large");
     Wgrad1Args a;
     wgrad1_geometry(B, cin, cout, H * W, W, a);
-    const size_t need = gtts_conv1x1_wgrad_workspace_bytes(B, cin, cout, H, W);
-    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "gtts_conv1x1_wgrad: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    const int tiles = (cin / 64) * (cout / 64);
-    a.x = x; a.mask = mask; a.dy = dy; a.part = (float *)workspace;
-    a.dbpart = db ? a.part + (size_t)a.nslice * tiles * (64 * 64) : nullptr;
+    a.x = x; a.mask = mask; a.dy = dy;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(conv1x1_wgrad_kernel, dim3((unsigned)(tiles * a.nslice)), dim3(256), 0, st, a);
-    GTTS_HIPCHK(hipGetLastError());
-    const size_t total = (size_t)tiles * (64 * 64) + (db ? (size_t)cout : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 31) / 32)), dim3(256), 0, st, a.part, a.dbpart, dw, db, cin, cout,
-                       a.nslice, 1);
-    GTTS_HIPCHK(hipGetLastError());
-    return GTTS_OK;
-}
-
-extern "C" int gtts_conv3x3_wgrad_tiled(const float *x, const float *mask, const float *dy, float *dw, float *db, void *workspace,
-                                        size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
-    return gtts_conv3x3_wgrad_tiled2(x, nullptr, 0, mask, dy, dw, db, workspace, workspace_bytes, B, cin, cout, H, W, stream);
+    return wgrad_finish("gtts_conv1x1_wgrad", a, 1, workspace, workspace_bytes, gtts_conv1x1_wgrad_workspace_bytes(B, cin, cout, H, W), dw, db, st,
+                        [st](const Wgrad1Args &a, int tiles) {
+                            hipLaunchKernelGGL(conv1x1_wgrad_kernel, dim3((unsigned)(tiles * a.nslice)), dim3(256), 0, st, a);
+                            return hipGetLastError();
+                        });
 }

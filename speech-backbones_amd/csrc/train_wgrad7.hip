@@ -278,15 +278,11 @@ extern "C" int gtts_conv7x7_wgrad(const float *x, const float *mask, const float
         return fail(GTTS_E_SHAPE, "gtts_conv7x7_wgrad: tensor too large for 32-bit offsets");
     Wgrad7Args a;
     wgrad7_geometry(B, cin, cout, H, W, a);
-    const size_t need = gtts_conv7x7_wgrad_workspace_bytes(B, cin, cout, H, W);
-    if (workspace_bytes < need) return fail(GTTS_E_WORKSPACE, "gtts_conv7x7_wgrad: workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    const int tiles = (cin / 64) * (cout / 64);
-    a.x = x; a.mask = mask; a.dy = dy; a.part = (float *)workspace;
-    a.dbpart = db ? a.part + (size_t)a.nslice * tiles * (49 * 64 * 64) : nullptr;
+    a.x = x; a.mask = mask; a.dy = dy;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(conv7x7_wgrad_kernel, dim3((unsigned)(tiles * 7 * a.nslice)), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = launch_wgrad_reduce(a.part, a.dbpart, dw, db, cin, cout, a.nslice, 49, st);
-    if (e != hipSuccess) return fail(GTTS_E_HIP, "gtts_conv7x7_wgrad: %s", hipGetErrorString(e));
-    return GTTS_OK;
+    return wgrad_finish("gtts_conv7x7_wgrad", a, 49, workspace, workspace_bytes, gtts_conv7x7_wgrad_workspace_bytes(B, cin, cout, H, W), dw, db, st,
+                        [st](const Wgrad7Args &a, int tiles) {
+                            hipLaunchKernelGGL(conv7x7_wgrad_kernel, dim3((unsigned)(tiles * 7 * a.nslice)), dim3(256), 0, st, a);
+                            return hipGetLastError();
+                        });
 }

@@ -24,6 +24,7 @@ def test_header_symbols_are_exported():
     declared = _declared()
     assert len(declared) >= 15
     assert set(declared) <= exported, sorted(set(declared) - exported)
+    assert exported - set(declared) == {"gtts_debug_mas_force_sweep"}     # (a test hook of mas.hip; anything else undeclared is a stray export)
     lib = ctypes.CDLL(S._lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name)
@@ -128,7 +129,7 @@ def test_abi_contract_surface():
     compiled into the product library (no GTTS_SKIP_OPS / trace entry points)."""
     S = pkg()
     L = S._lib.lib()
-    assert L.gtts_abi_version() == 6
+    assert L.gtts_abi_version() == 7
     p = S.Plan(streams=0)
     assert L.gtts_plan_set_streams(p._h, None, 0) == 0
     assert L.gtts_plan_set_streams(p._h, None, 3) != 0            # null stream array

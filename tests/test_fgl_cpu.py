@@ -39,7 +39,7 @@ def test_fgl_symbols_are_exported_and_the_abi_version_stays():
     header = open(os.path.join(ROOT, "include", "gradtts_abi.h")).read()
     for name in want:
         assert re.search(r"\b%s\(" % name, header), name
-    assert S._lib.lib().gtts_abi_version() == 6
+    assert S._lib.lib().gtts_abi_version() == 7
     assert S.FglPlan is S._lib.FglPlan and "FglPlan" in S.__all__
 
 

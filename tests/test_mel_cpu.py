@@ -27,7 +27,7 @@ def test_mel_symbols_are_exported_and_the_abi_version_stays():
     exported = set(re.findall(r"\bT (gtts_mel_[a-z_0-9]+)", out))
     assert exported >= {"gtts_mel_create", "gtts_mel_destroy", "gtts_mel_frames", "gtts_mel_packed_bytes", "gtts_mel_pack",
                         "gtts_mel_filterbank", "gtts_mel_forward"}
-    assert S._lib.lib().gtts_abi_version() == 6
+    assert S._lib.lib().gtts_abi_version() == 7
 
 
 def test_frames_and_configuration_checks():

@@ -32,7 +32,7 @@ def test_new_symbols_declared_and_exported(L):
     for name in NEW:
         assert name in declared, name
         assert name in exported, name
-    assert L.gtts_abi_version() == 6
+    assert L.gtts_abi_version() == 7
 
 
 def _fake(n=1):

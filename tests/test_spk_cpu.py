@@ -36,7 +36,7 @@ def test_spk_symbols_are_exported_and_the_abi_version_stays():
                         "gtts_spk_pack", "gtts_spk_workspace_bytes", "gtts_spk_forward"}
     header = open(os.path.join(ROOT, "include", "gradtts_abi.h")).read()
     assert exported == set(re.findall(r"\b(gtts_spk_[a-z_0-9]+)\s*\(", header))
-    assert S._lib.lib().gtts_abi_version() == 6
+    assert S._lib.lib().gtts_abi_version() == 7
 
 
 def test_plan_layout_and_refusals_touch_no_device():

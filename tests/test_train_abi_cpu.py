@@ -38,7 +38,7 @@ def _each_null(call, args, required):
 
 def test_conv3x3_masked_validates(L):
     x, x1, m, om, p, b, y = _fake(7)
-    f = L.gtts_conv3x3_masked3
+    f = L.gtts_conv3x3_masked
     good = (x, None, 0, m, om, p, b, y, 2, 64, 64, 80, 44, None)
     _each_null(f, good, (0, 3, 5, 6, 7))                                    # x, mask, packed, bias, y (x1 and omask are optional)
     for c0 in (0, -16, 128, 144, 24):                                       # two sources: c0 a multiple of 16 inside (0, cin)
@@ -47,13 +47,11 @@ def test_conv3x3_masked_validates(L):
         assert f(x, None, 0, m, om, p, b, y, B, cin, cout, H, W, None) == E_SHAPE
     for cout in (32, 96, 192, 320):                                         # cout is 64 or a multiple of 128
         assert f(x, None, 0, m, om, p, b, y, 2, 64, cout, 80, 44, None) == E_SHAPE, cout
-    assert L.gtts_conv3x3_masked(None, m, p, b, y, 2, 64, 64, 80, 44, None) == E_NULL
-    assert L.gtts_conv3x3_masked2(x, x1, 8, m, p, b, y, 2, 128, 64, 80, 44, None) == E_SHAPE
 
 
-def test_conv3x3_wgrad_tiled_validates(L):
+def test_conv3x3_wgrad_validates(L):
     x, x1, m, dy, dw, db, ws = _fake(7)
-    f = L.gtts_conv3x3_wgrad_tiled2
+    f = L.gtts_conv3x3_wgrad
     nws = L.gtts_conv3x3_wgrad_workspace_bytes(2, 128, 64, 80, 44)
     assert nws > 0
     good = (x, None, 0, m, dy, dw, db, ws, nws, 2, 128, 64, 80, 44, None)
@@ -68,11 +66,17 @@ def test_conv3x3_wgrad_tiled_validates(L):
                                (2, 96, 64, 80, 44), (2, 64, 32, 80, 44), (2, 3, 64, 80, 44)):
         assert f(x, None, 0, m, dy, dw, db, ws, nws, B, cin, cout, H, W, None) == E_SHAPE, (B, cin, cout, H, W)
     assert f(x, None, 0, m, dy, dw, db, ws, 0, 2, 128, 64, 80, 44, None) == E_WORKSPACE
-    g = L.gtts_conv3x3_wgrad_tiled                                          # the one-source spelling forwards to the same guards
-    assert g(None, m, dy, dw, db, ws, nws, 2, 128, 64, 80, 44, None) == E_NULL
-    assert g(x, m, dy, dw, db, ws, nws, 2, 128, 96, 80, 44, None) == E_SHAPE
-    assert g(x, m, dy, dw, db, ws, nws - 4, 2, 128, 64, 80, 44, None) == E_WORKSPACE
+    assert f(x, None, 0, m, dy, dw, db, ws, nws - 4, 2, 128, 64, 80, 44, None) == E_WORKSPACE
     assert b"workspace too small" in L.gtts_last_error()
+
+
+def test_superseded_spellings_are_gone(L):
+    """One exported name per op: the suffixed spellings that the full-signature entry points replaced are not in the library."""
+    for name, suffixes in (("gtts_conv3x3_masked", ("2", "3")), ("gtts_conv3x3_wgrad", ("_tiled", "_tiled2")),
+                           ("gtts_gn_mish_forward", ("_tb",)), ("gtts_gn_mish_backward", ("_tb",))):
+        assert hasattr(L, name), name
+        for suffix in suffixes:
+            assert not hasattr(L, name + suffix), name + suffix
 
 
 def test_conv1x1_masked_and_wgrad_validate(L):
@@ -124,7 +128,7 @@ def test_attention_core_validates(L):
 
 def test_gn_mish_validates(L):
     y, ga, be, m, tb, out, st, dout, dy, dg, db, dtb, scr = _fake(13)
-    f, g = L.gtts_gn_mish_forward_tb, L.gtts_gn_mish_backward_tb
+    f, g = L.gtts_gn_mish_forward, L.gtts_gn_mish_backward
     _each_null(f, (y, ga, be, m, tb, out, st, 2, 64, 80, 44, 8, 1e-5, None), (0, 1, 2, 3, 5, 6))          # (tb optional)
     _each_null(g, (dout, y, ga, be, m, st, dy, dg, db, dtb, scr, 2, 64, 80, 44, 8, None), (0, 1, 2, 3, 4, 5, 6, 7, 8, 10))   # (dtb optional)
     bad = ((0, 64, 80, 44, 8), (2, 0, 80, 44, 8), (2, 64, 0, 44, 8), (2, 64, 80, -1, 8), (2, 64, 80, 44, 0), (2, 64, 80, 44, -8),
@@ -132,8 +136,6 @@ def test_gn_mish_validates(L):
     for B, C, H, W, groups in bad:
         assert f(y, ga, be, m, None, out, st, B, C, H, W, groups, 1e-5, None) == E_SHAPE, (B, C, H, W, groups)
         assert g(dout, y, ga, be, m, st, dy, dg, db, None, scr, B, C, H, W, groups, None) == E_SHAPE, (B, C, H, W, groups)
-    assert L.gtts_gn_mish_forward(None, ga, be, m, out, st, 2, 64, 80, 44, 8, 1e-5, None) == E_NULL
-    assert L.gtts_gn_mish_backward(dout, y, ga, be, m, st, dy, dg, db, scr, 2, 64, 80, 44, 3, None) == E_SHAPE
     assert L.gtts_gn_mish_stats_floats(0, 8) == 0 and L.gtts_gn_mish_stats_floats(2, 0) == 0
     assert L.gtts_gn_mish_stats_floats(16, 8) >= 16 * 8 * 2                 # the (mean, rstd) pairs, then reduction scratch
     assert L.gtts_gn_mish_scratch_bytes(0, 64) == 0 and L.gtts_gn_mish_scratch_bytes(2, -1) == 0
@@ -203,10 +205,9 @@ def test_c_size_guard_agrees_with_python_gate(L, kind):
         assert supported(cin, cout, need_dgrad=True), (kind, cin, cout)     # (so it is the size, not the channel counts, that decides)
         # workspace_bytes = 0: a shape the size guard lets through stops at the workspace check, one step before the launch
         if kind == "3x3":
-            rc = [L.gtts_conv3x3_wgrad_tiled2(x, None, 0, m, dy, dw, db, ws, 0, B, cin, cout, H, W, None),
-                  L.gtts_conv3x3_wgrad_tiled(x, m, dy, dw, db, ws, 0, B, cin, cout, H, W, None)]
+            rc = [L.gtts_conv3x3_wgrad(x, None, 0, m, dy, dw, db, ws, 0, B, cin, cout, H, W, None)]
             if cin >= 128:
-                rc.append(L.gtts_conv3x3_wgrad_tiled2(x, x1, 64, m, dy, dw, db, ws, 0, B, cin, cout, H, W, None))
+                rc.append(L.gtts_conv3x3_wgrad(x, x1, 64, m, dy, dw, db, ws, 0, B, cin, cout, H, W, None))
         elif kind == "1x1":
             rc = [L.gtts_conv1x1_wgrad(x, m, dy, dw, db, ws, 0, B, cin, cout, H, W, None),
                   L.gtts_conv1x1_wgrad(x, None, dy, dw, None, ws, 0, B, cin, cout, H, W, None)]

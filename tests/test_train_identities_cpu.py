@@ -29,7 +29,7 @@ def test_downsample_data_gradient_is_an_upsample_with_zero_padded_kernel():
 
 def test_downsample_weight_gradient_is_the_stride1_one_against_zero_inserted_dy():
     """dW of the stride-2 convolution == dW of the stride-1 3x3 convolution whose output gradient is dy at the even positions and
-    zero elsewhere (gtts_zero_insert2 + gtts_conv3x3_wgrad_tiled)."""
+    zero elsewhere (gtts_zero_insert2 + gtts_conv3x3_wgrad)."""
     torch.manual_seed(1)
     x = torch.randn(2, 3, 8, 12)
     w = torch.randn(5, 3, 3, 3, requires_grad=True)

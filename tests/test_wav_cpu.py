@@ -55,7 +55,7 @@ def test_wav_symbols_are_exported_and_the_abi_version_stays():
     exported = set(re.findall(r"\bT (gtts_wav_[a-z_0-9]+)", out))
     assert exported >= {"gtts_wav_" + op for op in ("create", "destroy", "resampled_length", "frames", "tiles", "span", "taps", "filterbank",
                                                     "packed_bytes", "pack", "workspace_bytes", "resample", "normalize", "powmel")}
-    assert S._lib.lib().gtts_abi_version() == 6
+    assert S._lib.lib().gtts_abi_version() == 7
     assert S.WavPlan is S._lib.WavPlan and S.WavPlan._family == "wav"
 
 
