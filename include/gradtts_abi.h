@@ -303,6 +303,45 @@ int gtts_enc_attention(const float *q, const float *k, const float *v, const flo
  * channels, n_heads < 1, channels % n_heads != 0 or window < 0) */
 int gtts_enc_attention_path_for(int channels, int n_heads, int window, int L);
 
+/* ---- ABI 7 (additive): TRAINING of the same two ops (csrc/enc_train.hip) -- the attention core forward with dropout and its backward,
+ * and the backward of gtts_enc_layernorm (whose forward under autograd is gtts_enc_layernorm itself).  All tensors fp32, contiguous,
+ * t fastest, on `stream`; nothing L x L is kept between forward and backward, no floating-point atomics: the same inputs give the
+ * same bits.  Every refusal below happens on the host before the device is touched.
+ *
+ * gtts_enc_attention_train_ok (host only): 1 where the three training kernels hold the shape in 160 KB of LDS, else 0 (also for
+ *   channels, n_heads < 1, channels % n_heads != 0, window < 0, L < 1).  With dk = channels / n_heads, R = 2 window + 1 (0 without a
+ *   window) and LP = roundup(L, 64), in floats:   forward 16 dk + 16 R + 16 LP + 16;   query-tiled backward 16 dk + 16 R + 16 LP + 32;
+ *   key-tiled backward 288 dk + 32 R + 2112 (no L).  dk <= 96 with window <= 7: every L <= 2432 (the defaults, dk 96 and window 4: 2432 is the last).
+ *
+ * gtts_enc_attention_train_forward: gtts_enc_attention's semantics (q, k, v, out [B][C][L], mask [B][L], emb_rel_k / emb_rel_v
+ *   [2 window + 1][dk]; window 0: both may be NULL) plus
+ *   drop  [B][H][L][L] or NULL: multiplier (0 or 1 / (1 - p)) applied to the probabilities after the softmax;
+ *   stat  [B][H][L][2], written: per query row the score maximum and the reciprocal of its exponential sum.
+ * gtts_enc_attention_train_backward: dout [B][C][L] -> dq, dk, dv [B][C][L], dek, dev [2 window + 1][dk] (window 0: may be NULL, not
+ *   written), from the forward's inputs, `drop` and `stat`;  scratch of gtts_enc_attention_train_scratch_bytes(B, C, L, n_heads, window)
+ *   bytes (0 for a refused shape).  A score that was replaced by -1e4 passes no gradient; rows of padded queries still reach dv.
+ *   GTTS_E_NULL (a required pointer), GTTS_E_SHAPE (B or L < 1, B or n_heads > 65535, L beyond gtts_enc_attention_train_ok),
+ *   GTTS_E_CONFIG (C % n_heads, window < 0, a head width / window no length fits). */
+int gtts_enc_attention_train_ok(int channels, int n_heads, int window, int L);
+size_t gtts_enc_attention_train_scratch_bytes(int B, int C, int L, int n_heads, int window);
+int gtts_enc_attention_train_forward(const float *q, const float *k, const float *v, const float *mask, const float *emb_rel_k,
+                                     const float *emb_rel_v, const float *drop, float *out, float *stat, int B, int C, int L, int n_heads,
+                                     int window, gtts_stream_t stream);
+int gtts_enc_attention_train_backward(const float *q, const float *k, const float *v, const float *mask, const float *emb_rel_k,
+                                      const float *emb_rel_v, const float *drop, const float *stat, const float *dout, float *dq, float *dk,
+                                      float *dv, float *dek, float *dev, void *scratch, int B, int C, int L, int n_heads, int window,
+                                      gtts_stream_t stream);
+/* gtts_enc_layernorm_backward: gradients of  out = relu_out?(LN_c(relu_in?(a) * a_mask + bres)) * out_mask  (gtts_enc_layernorm) from
+ *   dout [B][C][L]: da [B][C][L], dbres [B][C][L] (written only when bres is given), dgamma, dbeta [C].  Mean and rstd are recomputed from
+ *   the inputs in two passes; ReLU' (0) = 0; beta is read only to recompute the sign under relu_out; dgamma / dbeta are per-workgroup
+ *   partials (scratch: gtts_enc_layernorm_backward_scratch_floats(B, C, L) floats, 0 for a refused shape) folded in a fixed order.
+ *   GTTS_E_NULL: dout, a, gamma, beta, da, dgamma, dbeta or scratch NULL, bres without dbres; GTTS_E_SHAPE: B, C or L < 1 or
+ *   B > 65535; GTTS_E_CONFIG: eps <= 0. */
+size_t gtts_enc_layernorm_backward_scratch_floats(int B, int C, int L);
+int gtts_enc_layernorm_backward(const float *dout, const float *a, const float *bres, const float *gamma, const float *beta,
+                                const float *a_mask, const float *out_mask, float *da, float *dbres, float *dgamma, float *dbeta,
+                                float *scratch, int B, int C, int L, float eps, int relu_in, int relu_out, gtts_stream_t stream);
+
 /* ---- DiffVC PostNet (DiffVC/model/postnet.py:40-53; the last stage of the "average voice" encoder, vc.py:33-41):
  * x [B,n_feats,T], mask [B,T] -> out [B,n_feats,T].  dim % 64 == 0, 8 GroupNorm groups.  Parameter names are the module's
  * state_dict keys (`init_conv.weight`, `res_block.block1.block.0.weight` [dim,dim,7,7], ...). */

@@ -170,6 +170,12 @@ def lib():
         L.gtts_enc_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, f, i, i, vp]
         L.gtts_enc_attention.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.gtts_enc_attention_path_for.argtypes = [i, i, i, i]
+        L.gtts_enc_attention_train_ok.argtypes = [i, i, i, i]
+        L.gtts_enc_attention_train_scratch_bytes.argtypes, L.gtts_enc_attention_train_scratch_bytes.restype = [i, i, i, i, i], sz
+        L.gtts_enc_attention_train_forward.argtypes = [vp] * 9 + [i] * 5 + [vp]
+        L.gtts_enc_attention_train_backward.argtypes = [vp] * 15 + [i] * 5 + [vp]
+        L.gtts_enc_layernorm_backward_scratch_floats.argtypes, L.gtts_enc_layernorm_backward_scratch_floats.restype = [i, i, i], sz
+        L.gtts_enc_layernorm_backward.argtypes = [vp] * 12 + [i, i, i, f, i, i, vp]
         L.gtts_postnet_forward.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_conv1d_create.argtypes = [i, i, i, i, i, i, ctypes.POINTER(vp)]
         L.gtts_conv1d_destroy.argtypes, L.gtts_conv1d_destroy.restype = [vp], None
@@ -894,6 +900,89 @@ def enc_attention(q, k, v, mask, emb_rel_k=None, emb_rel_v=None, n_heads=2, wind
         _check(lib().gtts_enc_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(emb_rel_k), _ptr(emb_rel_v), _ptr(out), B, C, L,
                                         int(n_heads), window, int(path), _stream()), "gtts_enc_attention")
     return out
+
+
+# ---- training of the two ops (csrc/enc_train.hip)
+def enc_attention_train_ok(channels, n_heads, window, L):
+    """Whether the training attention kernels hold this shape (a host call): 1 / 0."""
+    return int(lib().gtts_enc_attention_train_ok(int(channels), int(n_heads), int(window or 0), int(L)))
+
+
+def _att_train_shapes(q, n_heads, window):
+    B, C, L = q.shape
+    H = max(int(n_heads), 1)
+    rel = (2 * window + 1, C // H)
+    return B, C, L, H, dict(q=(B, C, L), k=(B, C, L), v=(B, C, L), mask=(B, L), emb_rel_k=rel, emb_rel_v=rel, drop=(B, H, L, L),
+                            out=(B, C, L), stat=(B, H, L, 2), dout=(B, C, L), dq=(B, C, L), dk=(B, C, L), dv=(B, C, L), dek=rel, dev=rel)
+
+
+def enc_attention_train_forward(q, k, v, mask, emb_rel_k=None, emb_rel_v=None, drop=None, n_heads=2, window=0, out=None, stat=None):
+    """enc_attention for training: `drop` [B,H,L,L] (0 or 1 / (1 - p)) multiplies the probabilities after the softmax; returns
+    (out [B,C,L], stat [B,H,L,2]: each query row's score maximum and reciprocal exponential sum, what the backward recomputes from)."""
+    if not q.is_cuda:
+        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % q.device)
+    window = int(window or 0)
+    B, C, L, H, shapes = _att_train_shapes(q, n_heads, window)
+    if out is None:
+        out = torch.empty((B, C, L), dtype=torch.float32, device=q.device)
+    if stat is None:
+        stat = torch.empty((B, H, L, 2), dtype=torch.float32, device=q.device)
+    _enc_op_tensors(dict(q=q, k=k, v=v, mask=mask, emb_rel_k=emb_rel_k, emb_rel_v=emb_rel_v, drop=drop, out=out, stat=stat), shapes, q.device)
+    with _on(q.device):
+        _check(lib().gtts_enc_attention_train_forward(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(emb_rel_k), _ptr(emb_rel_v), _ptr(drop),
+                                                      _ptr(out), _ptr(stat), B, C, L, int(n_heads), window, _stream()),
+               "gtts_enc_attention_train_forward")
+    return out, stat
+
+
+def enc_attention_train_backward(q, k, v, mask, emb_rel_k, emb_rel_v, drop, stat, dout, n_heads=2, window=0, grads=None):
+    """(dq, dk, dv, dek, dev) of enc_attention_train_forward from its inputs, `drop` and `stat` (dek = dev = None without a window).
+    grads: optional dict of preallocated outputs by those names."""
+    if not q.is_cuda:
+        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % q.device)
+    window = int(window or 0)
+    B, C, L, H, shapes = _att_train_shapes(q, n_heads, window)
+    g = dict(grads or {})
+    for n in ("dq", "dk", "dv") + (("dek", "dev") if window else ()):
+        if g.get(n) is None:
+            g[n] = torch.empty(shapes[n], dtype=torch.float32, device=q.device)
+    if not window:
+        g["dek"] = g["dev"] = None
+    _enc_op_tensors(dict(q=q, k=k, v=v, mask=mask, emb_rel_k=emb_rel_k, emb_rel_v=emb_rel_v, drop=drop, stat=stat, dout=dout, **g),
+                    shapes, q.device)
+    need = int(lib().gtts_enc_attention_train_scratch_bytes(B, C, L, int(n_heads), window))
+    scratch = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=q.device)
+    with _on(q.device):
+        _check(lib().gtts_enc_attention_train_backward(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(emb_rel_k), _ptr(emb_rel_v), _ptr(drop),
+                                                       _ptr(stat), _ptr(dout), _ptr(g["dq"]), _ptr(g["dk"]), _ptr(g["dv"]), _ptr(g["dek"]),
+                                                       _ptr(g["dev"]), _ptr(scratch), B, C, L, int(n_heads), window, _stream()),
+               "gtts_enc_attention_train_backward")
+    return g["dq"], g["dk"], g["dv"], g["dek"], g["dev"]
+
+
+def enc_layernorm_backward(dout, a, gamma, beta, bres=None, a_mask=None, out_mask=None, eps=1e-4, relu_in=False, relu_out=False,
+                           grads=None):
+    """(da, dbres, dgamma, dbeta) of enc_layernorm (dbres None without bres).  grads: optional dict of preallocated outputs."""
+    if not a.is_cuda:
+        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % a.device)
+    B, C, L = a.shape
+    shapes = dict(dout=(B, C, L), a=(B, C, L), bres=(B, C, L), gamma=(C,), beta=(C,), a_mask=(B, L), out_mask=(B, L), da=(B, C, L),
+                  dbres=(B, C, L), dgamma=(C,), dbeta=(C,))
+    g = dict(grads or {})
+    for n in ("da", "dgamma", "dbeta") + (("dbres",) if bres is not None else ()):
+        if g.get(n) is None:
+            g[n] = torch.empty(shapes[n], dtype=torch.float32, device=a.device)
+    if bres is None:
+        g["dbres"] = None
+    _enc_op_tensors(dict(dout=dout, a=a, bres=bres, gamma=gamma, beta=beta, a_mask=a_mask, out_mask=out_mask, **g), shapes, a.device)
+    need = int(lib().gtts_enc_layernorm_backward_scratch_floats(B, C, L))
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=a.device)
+    with _on(a.device):
+        _check(lib().gtts_enc_layernorm_backward(_ptr(dout), _ptr(a), _ptr(bres), _ptr(gamma), _ptr(beta), _ptr(a_mask), _ptr(out_mask),
+                                                 _ptr(g["da"]), _ptr(g["dbres"]), _ptr(g["dgamma"]), _ptr(g["dbeta"]), _ptr(scratch), B, C, L,
+                                                 float(eps), int(bool(relu_in)), int(bool(relu_out)), _stream()),
+               "gtts_enc_layernorm_backward")
+    return g["da"], g["dbres"], g["dgamma"], g["dbeta"]
 
 
 class PostNetPlan(_Native):

@@ -13,6 +13,9 @@ csrc/train*.hip behind torch.autograd.Function wrappers:
   RezeroResidual, MaskedResidualAdd, the plain residual add, FinalConv (64 -> 1 with both masks), ScoreLoss
   ResampleConv         Downsample / Upsample forward and all their gradients on the HIP kernels (Downsample's data gradient is an
                        Upsample call, Upsample's gradients are 3x3 stride-1 operations over the four stride-2 phases of dy)
+  EncAttentionCore     the transformer encoder's windowed relative-position attention between its convolutions, and EncLayerNorm, its
+                       LayerNorm with the fused residual (text_encoder.py, shared by TextEncoder and DiffVC's MelEncoder), on
+                       csrc/enc_train.hip; the encoder's Conv1d layers and embedding stay torch autograd
 The [B, dim] time / speaker MLPs stay stock torch ops.  On CPU tensors (tests) everything is stock torch.
 """
 import math
@@ -352,6 +355,77 @@ def op_counts():
 def _count(hip):
     if not FORCE_TORCH:
         _COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
+
+
+# The same pair for the transformer encoder's two kernel ops (EncAttentionCore, EncLayerNorm: text_encoder.py counts one per call
+# made with autograd on -- `hip` when the kernels of csrc/enc_train.hip ran, `fallback` when the module's torch composition did).
+# A pair of its own: op_counts() keeps counting the decoder / PostNet ops only.
+_ENC_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
+
+
+def reset_enc_op_counts():
+    _ENC_COUNTS["hip_ops"] = 0
+    _ENC_COUNTS["torch_fallback_ops"] = 0
+
+
+def enc_op_counts():
+    return _ENC_COUNTS["hip_ops"], _ENC_COUNTS["torch_fallback_ops"]
+
+
+def enc_count(hip):
+    if not FORCE_TORCH:
+        _ENC_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
+
+
+def enc_hip(t):
+    """An fp32 HIP tensor while the kernels are not switched off: what the encoder's training kernels take."""
+    return not FORCE_TORCH and t.is_cuda and t.dtype == torch.float32
+
+
+class EncAttentionCore(torch.autograd.Function):
+    """MultiHeadAttention.attention between its convolutions (text_encoder.py:145-175), self-attention with relative embeddings shared
+    by the heads, forward (dropout multiplier `drop` [b, h, t, t] or None) and backward on csrc/enc_train.hip.  Saved: the inputs and
+    `stat` [b, h, t, 2] (row maximum, reciprocal row sum) -- the backward recomputes the probabilities from them."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cols, ek, ev, drop, n_heads, window):
+        be = backend()
+        ek2 = None if ek is None else ek.detach().reshape(ek.shape[-2], ek.shape[-1]).contiguous()
+        ev2 = None if ev is None else ev.detach().reshape(ev.shape[-2], ev.shape[-1]).contiguous()
+        out, stat = be.enc_attention_train_forward(q, k, v, cols, ek2, ev2, drop, n_heads=n_heads, window=window)
+        ctx.save_for_backward(q, k, v, cols, ek2, ev2, drop, stat)
+        ctx.n_heads, ctx.window = n_heads, window
+        ctx.rel_shape = None if ek is None else tuple(ek.shape)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, cols, ek, ev, drop, stat = ctx.saved_tensors
+        dq, dk, dv, dek, dev = backend().enc_attention_train_backward(q, k, v, cols, ek, ev, drop, stat, dout.contiguous(),
+                                                                      n_heads=ctx.n_heads, window=ctx.window)
+        if dek is not None:
+            dek, dev = dek.reshape(ctx.rel_shape), dev.reshape(ctx.rel_shape)
+        return dq, dk, dv, None, dek, dev, None, None, None
+
+
+class EncLayerNorm(torch.autograd.Function):
+    """LayerNorm over channels of a [+ bres] (text_encoder.py:12-27): forward on the inference kernel (gtts_enc_layernorm), backward on
+    csrc/enc_train.hip, which recomputes mean and rstd from the saved inputs."""
+
+    @staticmethod
+    def forward(ctx, a, gamma, beta, bres, eps):
+        ctx.save_for_backward(a, gamma, beta, bres)
+        ctx.eps = eps
+        return backend().enc_layernorm(a, gamma.detach(), beta.detach(), bres=bres, eps=eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        a, gamma, beta, bres = ctx.saved_tensors
+        da, dbres, dgamma, dbeta = backend().enc_layernorm_backward(dout.contiguous(), a, gamma.detach(), beta.detach(), bres=bres,
+                                                                    eps=ctx.eps)
+        return da, dgamma, dbeta, dbres, None
 
 
 def _block_conv_kind(conv):

@@ -1,7 +1,10 @@
 """Text encoder + duration predictor with the reference's parameter layout (Grad-TTS/model/text_encoder.py).
 
 Inference (eval mode, torch.no_grad, HIP tensors) runs the kernels of csrc/enc.hip through gtts_enc_forward (SURVEY.md
-section 8f rank 4); training composes the torch modules below over the same parameters.  Written from the behaviour of
+section 8f rank 4).  Training composes the torch modules below over the same parameters, with two exceptions on fp32 HIP tensors
+under autograd: the attention core (MultiHeadAttention.attention) and LayerNorm run the kernels of csrc/enc_train.hip behind
+_train_ops.EncAttentionCore / EncLayerNorm -- no [b, h, t, t] tensor is built or kept; the Conv1d layers and the embedding stay
+torch autograd.  Written from the behaviour of
 the reference modules; parameter names / shapes are identical so `load_state_dict(strict=True)` of reference checkpoints
 works:
 
@@ -17,6 +20,7 @@ import math
 import torch
 import torch.nn.functional as F
 
+from . import _train_ops as _T
 from .base import BaseModule
 from .utils import sequence_mask
 
@@ -31,7 +35,16 @@ class LayerNorm(BaseModule):
         self.gamma = torch.nn.Parameter(torch.ones(channels))
         self.beta = torch.nn.Parameter(torch.zeros(channels))
 
-    def forward(self, x):
+    def forward(self, x, bres=None):
+        """LN(x + bres) (bres: an optional residual of x's shape, added in the kernel on the training path)."""
+        if torch.is_grad_enabled():
+            if _T.enc_hip(x) and x.dim() == 3 and (bres is None or (_T.enc_hip(bres) and bres.shape == x.shape)):
+                _T.enc_count(True)
+                return _T.EncLayerNorm.apply(x.contiguous(), self.gamma, self.beta, None if bres is None else bres.contiguous(),
+                                             self.eps)
+            _T.enc_count(False)
+        if bres is not None:
+            x = x + bres
         mu = x.mean(1, keepdim=True)
         var = ((x - mu) ** 2).mean(1, keepdim=True)
         y = (x - mu) * torch.rsqrt(var + self.eps)
@@ -86,7 +99,10 @@ class DurationPredictor(BaseModule):
 
 class MultiHeadAttention(BaseModule):
     """Self-attention with learned relative-position keys/values inside a +-window band
-    (text_encoder.py:96-215; heads share the relative embeddings)."""
+    (text_encoder.py:96-215; heads share the relative embeddings).
+
+    `self.attn` holds the attention probabilities of the last call, as in the reference -- except on the training kernel path (see
+    `attention`), where they are never materialised and `self.attn` is None."""
 
     def __init__(self, channels, out_channels, n_heads, window_size=None, heads_share=True, p_dropout=0.0,
                  proximal_bias=False, proximal_init=False):
@@ -121,10 +137,41 @@ class MultiHeadAttention(BaseModule):
         rel = pos[None, :] - pos[:, None] + w
         return rel.clamp(0, 2 * w), (rel >= 0) & (rel <= 2 * w)
 
-    def attention(self, query, key, value, mask=None):
+    def _train_kernel_ok(self, query, key, value, mask, seq_mask, self_attention):
+        """The training kernels (csrc/enc_train.hip) serve: autograd on, fp32 contiguous HIP tensors, self-attention whose mask is
+        the outer product of the [b, 1, t] sequence mask `seq_mask` (or no mask at all), relative embeddings shared by the heads
+        (or none), no proximal bias, and a length the kernels hold."""
+        if not (torch.is_grad_enabled() and self_attention and self.heads_share and not self.proximal_bias):
+            return False
+        if not all(_T.enc_hip(t) and t.is_contiguous() for t in (query, key, value)) or query.shape != key.shape:
+            return False
+        if mask is not None and (seq_mask is None or not _T.enc_hip(seq_mask) or seq_mask.numel() != key.shape[0] * key.shape[2]):
+            return False
+        if not _T.backend().enc_attention_train_ok(self.channels, self.n_heads, self.window_size or 0, key.shape[2]):
+            _warn_too_long("MultiHeadAttention (training kernels)", key.shape[2])
+            return False
+        return True
+
+    def attention(self, query, key, value, mask=None, seq_mask=None, self_attention=False):
+        """(out, p_attn).  With self_attention=True (MultiHeadAttention.forward says so when x is c) and the conditions of
+        `_train_kernel_ok`, the core runs on the HIP training kernels and p_attn is None: the probabilities exist only inside the
+        kernels.  Dropout there is `self.drop` of a [b, h, t, t] tensor of ones -- the same call on the same shape at the same point
+        as the composition below, so one seed draws the same masks on either path.  Everything else runs the composition."""
         b, d, t_s = key.shape
         t_t = query.shape[2]
         h, dk = self.n_heads, self.k_channels
+        if torch.is_grad_enabled():
+            if self._train_kernel_ok(query, key, value, mask, seq_mask, self_attention):
+                _T.enc_count(True)
+                cols = (torch.ones(b, t_s, dtype=torch.float32, device=key.device) if mask is None
+                        else seq_mask.reshape(b, t_s).contiguous())
+                drop = None
+                if self.training and self.drop.p > 0:
+                    drop = self.drop(torch.ones(b, h, t_s, t_s, dtype=torch.float32, device=key.device))
+                win = self.window_size or 0
+                ek, ev = (self.emb_rel_k, self.emb_rel_v) if win else (None, None)
+                return _T.EncAttentionCore.apply(query, key, value, cols, ek, ev, drop, h, win), None
+            _T.enc_count(False)
         q = query.view(b, h, dk, t_t).transpose(2, 3)
         k = key.view(b, h, dk, t_s).transpose(2, 3)
         v = value.view(b, h, dk, t_s).transpose(2, 3)
@@ -156,8 +203,11 @@ class MultiHeadAttention(BaseModule):
         out = out.transpose(2, 3).contiguous().view(b, d, t_t)
         return out, p_attn
 
-    def forward(self, x, c, attn_mask=None):
-        y, self.attn = self.attention(self.conv_q(x), self.conv_k(c), self.conv_v(c), mask=attn_mask)
+    def forward(self, x, c, attn_mask=None, seq_mask=None):
+        """seq_mask: the [b, 1, t] sequence mask whose outer product attn_mask is (Encoder passes it); without it a masked call
+        runs the torch composition."""
+        y, self.attn = self.attention(self.conv_q(x), self.conv_k(c), self.conv_v(c), mask=attn_mask, seq_mask=seq_mask,
+                                      self_attention=x is c)
         return self.conv_o(y)
 
 
@@ -202,8 +252,8 @@ class Encoder(BaseModule):
         pair_mask = x_mask.unsqueeze(2) * x_mask.unsqueeze(-1)
         for attn, n1, ffn, n2 in zip(self.attn_layers, self.norm_layers_1, self.ffn_layers, self.norm_layers_2):
             x = x * x_mask
-            x = n1(x + self.drop(attn(x, x, pair_mask)))
-            x = n2(x + self.drop(ffn(x, x_mask)))
+            x = n1(x, self.drop(attn(x, x, pair_mask, seq_mask=x_mask)))       # LN(x + y): the add rides in the LayerNorm kernel
+            x = n2(x, self.drop(ffn(x, x_mask)))
         return x * x_mask
 
 

@@ -1,0 +1,246 @@
+"""GPU tests (-m gpu) of the drop-in encoder modules under autograd: MultiHeadAttention.attention and LayerNorm on the kernels of
+csrc/enc_train.hip (model/_train_ops.py: EncAttentionCore, EncLayerNorm), everything else torch autograd.
+
+Small modules -- Encoder(24, 48, n_heads=2, n_layers=2, kernel_size=3, window_size=4) and a TextEncoder / MelEncoder of that width --
+at B = 3 with ragged lengths (17, 9, 1).
+  (a) without dropout: every parameter gradient and the input gradient against the same module in float64 on the CPU, <= 1e-4 of the
+      tensor's largest element per tensor; enc_op_counts() shows the expected kernel ops and no fallback; op_counts() does not move
+  (b) train() with p_dropout = 0.1: under one seed the kernel path and FORCE_TORCH draw the same masks -- outputs and gradients agree
+      within the same bound
+  (c) proximal_bias, cross-attention, CPU tensors and a length past gtts_enc_attention_train_ok run the composition, correctly
+  (d) no_grad + eval() still reaches gtts_enc_forward: bit-equal to _hip_forward"""
+import copy
+import importlib
+import warnings
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+BOUND = 1e-4
+LENS = (17, 9, 1)
+
+
+@pytest.fixture(scope="module")
+def M():
+    assert torch.cuda.is_available()
+    ns = type("M", (), {})()
+    ns.S = importlib.import_module("speech-backbones_amd")
+    ns.TE = importlib.import_module("speech-backbones_amd.model.text_encoder")
+    ns.ME = importlib.import_module("speech-backbones_amd.diffvc.model.encoder")
+    ns.TO = importlib.import_module("speech-backbones_amd.model._train_ops")
+    ns.dev = torch.device("cuda:0")
+    return ns
+
+
+def rel(got, ref):
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    n = float(ref.abs().max())
+    if n == 0.0:
+        return 0.0 if bool((got == 0).all()) else float("inf")
+    return float((got - ref).abs().max() / n)
+
+
+def seq_mask(L, dtype=torch.float32):
+    return (torch.arange(L).unsqueeze(0) < torch.tensor(LENS).unsqueeze(1)).to(dtype).unsqueeze(1)
+
+
+def _randomise(mod, seed):
+    """Every parameter non-trivial (the reference zero-initialises prenet.proj, which would hide the prenet's gradients)."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for n, p in mod.named_parameters():
+            if n.endswith("gamma"):
+                p.copy_(1.0 + 0.2 * (torch.rand(p.shape, generator=g) - 0.5))
+            elif n.endswith("beta") or n.endswith("proj.weight") and "prenet" in n:
+                p.copy_(0.2 * (torch.rand(p.shape, generator=g) - 0.5))
+    return mod
+
+
+def _grads(mod, run, inputs):
+    """Outputs and gradients of sum(out * fixed weights): (outs, {name: grad}) -- parameters by name, inputs as 'input<k>'."""
+    mod.zero_grad(set_to_none=True)
+    leaves = [x.clone().requires_grad_(True) if x.is_floating_point() else x for x in inputs]
+    outs = run(mod, *leaves)
+    outs = outs if isinstance(outs, tuple) else (outs,)
+    loss = 0.0
+    for k, o in enumerate(outs):
+        w = torch.randn(o.shape, generator=torch.Generator().manual_seed(900 + k)).to(o.dtype).to(o.device)
+        loss = loss + (o * w).sum()
+    loss.backward()
+    g = {n: p.grad for n, p in mod.named_parameters() if p.grad is not None}
+    for k, x in enumerate(leaves):
+        if x.is_floating_point() and x.grad is not None:
+            g["input%d" % k] = x.grad
+    return outs, g
+
+
+def _compare(tag, got, ref):
+    (o1, g1), (o2, g2) = got, ref
+    assert set(g1) == set(g2), (tag, sorted(set(g1) ^ set(g2)))
+    rows = [("out%d" % k, rel(a, b)) for k, (a, b) in enumerate(zip(o1, o2))]
+    for n in sorted(g1):
+        if n.endswith("conv_k.bias"):
+            # A key bias adds q_i . b to every score of row i and the softmax does not see a shift of a row: this gradient vanishes
+            # identically (float64 leaves 1e-17 of rounding residue, which is no scale to measure against).  It is the sum of dk over
+            # the positions as conv_q.bias's gradient is the sum of dq, so it is held to 1e-4 of THAT tensor's largest element.
+            scale = float(g2[n[:-len("conv_k.bias")] + "conv_q.bias"].detach().double().abs().max())
+            assert float(g2[n].detach().double().abs().max()) <= 1e-5 * scale, (tag, n, "the reference does not vanish")
+            rows.append((n, float((g1[n].detach().double().cpu() - g2[n].detach().double().cpu()).abs().max()) / scale))
+        else:
+            rows.append((n, rel(g1[n], g2[n])))
+    worst = max(rows, key=lambda r: r[1])
+    print("%-28s %d tensors, worst %s %.2e" % (tag, len(rows), worst[0], worst[1]))
+    bad = [r for r in rows if not r[1] <= BOUND]
+    assert not bad, (tag, bad)
+
+
+def _cases(M):
+    """name -> (fp32 module on the CPU, run(module, *inputs), CPU inputs, expected kernel ops with autograd on)."""
+    g = torch.Generator().manual_seed(3)
+    L = max(LENS)
+    enc = M.TE.Encoder(24, 48, n_heads=2, n_layers=2, kernel_size=3, window_size=4)
+    text = M.TE.TextEncoder(30, 8, 24, 48, 16, 2, 2, 3, 0.0, window_size=4)
+    mel = M.ME.MelEncoder(8, 24, 48, 2, 2, 3, 0.0, window_size=4)
+    ids = torch.randint(0, 30, (3, L), generator=g)
+    return {
+        "Encoder": (enc, lambda m, x, mk: m(x, mk), (torch.randn(3, 24, L, generator=g), seq_mask(L)), 2 + 4),
+        "TextEncoder": (text, lambda m, i, n: m(i, n)[:2], (ids, torch.tensor(LENS)), 3 + 2 + 4 + 2),
+        "MelEncoder": (mel, lambda m, x, mk: m(x, mk), (torch.randn(3, 8, L, generator=g), seq_mask(L)), 3 + 2 + 4),
+    }
+
+
+def _to(inputs, dev=None, dtype=None):
+    out = []
+    for x in inputs:
+        x = x.to(dev) if dev is not None else x
+        out.append(x.to(dtype) if dtype is not None and x.is_floating_point() else x)
+    return out
+
+
+@pytest.mark.parametrize("name", ["Encoder", "TextEncoder", "MelEncoder"])
+def test_gradients_match_the_module_in_float64(M, name):
+    torch.manual_seed(11)
+    mod, run, inputs, n_ops = _cases(M)[name]
+    _randomise(mod, 5)
+    mod.eval()                                     # (the prenet's dropout is 0.5 whatever p_dropout says; autograd stays on)
+    ref = _grads(copy.deepcopy(mod).double(), run, _to(inputs, dtype=torch.float64))
+    gpu = mod.to(M.dev)
+    M.TO.reset_op_counts()
+    M.TO.reset_enc_op_counts()
+    got = _grads(gpu, run, _to(inputs, M.dev))
+    assert M.TO.enc_op_counts() == (n_ops, 0), M.TO.enc_op_counts()
+    assert M.TO.op_counts() == (0, 0)
+    for att in gpu.encoder.attn_layers if name != "Encoder" else gpu.attn_layers:
+        assert att.attn is None                    # the probabilities are never materialised on the kernel path
+    _compare(name, got, ref)
+
+
+@pytest.mark.parametrize("name", ["Encoder", "MelEncoder"])
+def test_dropout_draws_the_same_masks_on_both_paths(M, name):
+    torch.manual_seed(12)
+    L = max(LENS)
+    g = torch.Generator().manual_seed(4)
+    if name == "Encoder":
+        mod = M.TE.Encoder(24, 48, n_heads=2, n_layers=2, kernel_size=3, p_dropout=0.1, window_size=4)
+        inputs = (torch.randn(3, 24, L, generator=g), seq_mask(L))
+    else:
+        mod = M.ME.MelEncoder(8, 24, 48, 2, 2, 3, 0.1, window_size=4)
+        inputs = (torch.randn(3, 8, L, generator=g), seq_mask(L))
+    run = lambda m, x, mk: m(x, mk)
+    mod = _randomise(mod, 6).to(M.dev).train()
+    inputs = _to(inputs, M.dev)
+    M.TO.reset_enc_op_counts()
+    torch.manual_seed(1234)
+    got = _grads(mod, run, inputs)
+    got = (got[0], {n: v.clone() for n, v in got[1].items()})
+    assert M.TO.enc_op_counts()[0] > 0 and M.TO.enc_op_counts()[1] == 0
+    M.TO.FORCE_TORCH = True
+    try:
+        torch.manual_seed(1234)
+        ref = _grads(mod, run, inputs)
+    finally:
+        M.TO.FORCE_TORCH = False
+    _compare(name + " dropout", got, ref)
+    # ... and the masks matter: another seed gives another result by far more than the bound
+    torch.manual_seed(99)
+    other = _grads(mod, run, inputs)
+    assert rel(other[0][0], got[0][0]) > 100 * BOUND
+
+
+def _att_run(M, att, x, c, mask, seq):
+    att.zero_grad(set_to_none=True)
+    xs, cs = x.clone().requires_grad_(True), (None if c is None else c.clone().requires_grad_(True))
+    y = att(xs, xs if cs is None else cs, attn_mask=mask, seq_mask=seq)
+    w = torch.randn(y.shape, generator=torch.Generator().manual_seed(7)).to(y.dtype).to(y.device)
+    (y * w).sum().backward()
+    g = {n: p.grad for n, p in att.named_parameters() if p.grad is not None}
+    g["x"] = xs.grad
+    if cs is not None:
+        g["c"] = cs.grad
+    return (y,), g
+
+
+@pytest.mark.parametrize("case", ["proximal_bias", "cross_attention", "cpu_tensor", "too_long"])
+def test_cases_that_must_run_the_composition(M, case):
+    torch.manual_seed(13)
+    g = torch.Generator().manual_seed(8)
+    L = 2497 if case == "too_long" else max(LENS)
+    B = 1 if case == "too_long" else 3
+    kw = dict(window_size=4)
+    if case == "proximal_bias":
+        kw["proximal_bias"] = True
+    if case == "cross_attention":
+        kw = dict(window_size=None)
+    att = M.TE.MultiHeadAttention(24, 24, 2, **kw)
+    x = torch.randn(B, 24, L, generator=g)
+    c = torch.randn(B, 24, 9, generator=g) if case == "cross_attention" else None
+    if case == "too_long":
+        assert M.S.enc_attention_train_ok(24, 2, 4, 2496) == 1 and M.S.enc_attention_train_ok(24, 2, 4, 2497) == 0
+        seq = (torch.arange(L) < 2000).float().view(1, 1, L)
+    else:
+        seq = seq_mask(L)
+    mask = None if case == "cross_attention" else seq.unsqueeze(2) * seq.unsqueeze(-1)
+    seq_arg = None if case == "cross_attention" else seq
+    d64 = lambda t: None if t is None else t.double()
+    ref = _att_run(M, copy.deepcopy(att).double(), x.double(), d64(c), d64(mask), d64(seq_arg))
+    dev = torch.device("cpu") if case == "cpu_tensor" else M.dev
+    mv = lambda t: None if t is None else t.to(dev)
+    att = att.to(dev)
+    M.TE._WARNED_TOO_LONG.discard("MultiHeadAttention (training kernels)")
+    M.TO.reset_enc_op_counts()
+    with warnings.catch_warnings(record=True) as rec:
+        warnings.simplefilter("always")
+        got = _att_run(M, att, mv(x), mv(c), mv(mask), mv(seq_arg))
+        again = _att_run(M, att, mv(x), mv(c), mv(mask), mv(seq_arg))
+    assert M.TO.enc_op_counts() == (0, 2)
+    assert att.attn is not None and tuple(att.attn.shape) == (B, 2, L, 9 if case == "cross_attention" else L)
+    said = [w for w in rec if issubclass(w.category, RuntimeWarning) and "too long" in str(w.message)]
+    assert len(said) == (1 if case == "too_long" else 0), [str(w.message) for w in rec]
+    _compare(case, got, ref)
+    assert torch.equal(again[0][0], got[0][0])
+
+
+def test_inference_still_runs_gtts_enc_forward(M):
+    torch.manual_seed(14)
+    g = torch.Generator().manual_seed(9)
+    L = max(LENS)
+    text = _randomise(M.TE.TextEncoder(30, 8, 24, 48, 16, 2, 2, 3, 0.1, window_size=4), 7).to(M.dev).eval()
+    ids, lens = torch.randint(0, 30, (3, L), generator=g).to(M.dev), torch.tensor(LENS).to(M.dev)
+    M.TO.reset_enc_op_counts()
+    with torch.no_grad():
+        mu, logw, mask = text(ids, lens)
+        mu2, logw2, mask2 = text._hip_forward(ids, lens)
+    assert torch.equal(mu, mu2) and torch.equal(logw, logw2) and torch.equal(mask, mask2)
+    mel = _randomise(M.ME.MelEncoder(8, 24, 48, 2, 2, 3, 0.1, window_size=4), 8).to(M.dev).eval()
+    x, mk = torch.randn(3, 8, L, generator=g).to(M.dev), seq_mask(L).to(M.dev)
+    with torch.no_grad():
+        y = mel(x, mk)
+        y2 = mel._hip_enc.forward(mel._hip_blob, x, mk)
+    assert mel._hip_enc is not None and torch.equal(y, y2)
+    assert M.TO.enc_op_counts() == (0, 0)                     # nothing of the training path ran
+    # the same modules with autograd on take the training kernels and agree with the inference kernels
+    with torch.enable_grad():
+        y3 = mel(x, mk)
+    assert M.TO.enc_op_counts() == (3 + 2 + 4, 0)
+    assert rel(y3, y) <= BOUND
