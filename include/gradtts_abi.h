@@ -734,6 +734,47 @@ int gtts_conv1d_forward(const gtts_conv1d *op, const void *packed, const float *
  * 2 ConvTranspose1d two 8-byte stores, 3 generic pointer path)}, from the launcher's own selection. */
 int gtts_conv1d_instance(const gtts_conv1d *op, int B, int Lin, int has_res, int accmode, int has_out_mask, int info[5]);
 
+/* ---- ABI 7 (additive): the encoder-decoder gradient path of GradTTS.compute_loss (Grad-TTS/model/tts.py:101-181, train.py) -----------
+ * In train.py the prior mean mu_y comes from the encoder, so the decoder's first layer needs a data gradient, the noising needs a
+ * backward, and the alignment glue between MAS and the decoder runs under autograd.  All fp32 VALU kernels, no atomics, every sum in a
+ * fixed order: two calls on the same inputs give the same bits.  Arguments are checked on the host before anything is launched. */
+/* First-layer data gradient, the counterpart of gtts_conv_wgrad_small:
+ *   dx[b,p,h,w] = mask[b,w] * sum_co sum_taps dy[b,co,h-kh+r,w-kw+r] * w[co,p,kh,kw]   (r = ksize / 2; taps outside the plane are zero)
+ * dy [B,cout,H,W], w [cout][cin][k][k] (the module's layout, nothing packed), mask [B,W] -> dx [B,cin,H,W].  GTTS_E_CONFIG unless cin is
+ * 2 or 3, ksize 3 or 1 and cout a multiple of 64; GTTS_E_SHAPE for B, H, W < 1 or a W too wide for the LDS tile (ksize 3: W > 2289). */
+int gtts_conv_dgrad_small(const float *dy, const float *w, const float *mask, float *dx, int B, int cin, int cout, int H, int W,
+                          int ksize, gtts_stream_t stream);
+/* Gradient of gtts_diffusion_noising w.r.t. x0 and mu (z and z_masked carry none): dx0 = d mask dxt, dmu = (1 - d) mask dxt, with
+ * d = e^{-cum/2} evaluated exactly as the forward kernel does.  dxt, dx0, dmu [B,F,T]; dx0 or dmu may be NULL, not both. */
+int gtts_diffusion_noising_backward(const float *dxt, const float *mask, const float *t, float beta_min, float beta_max, float *dx0,
+                                    float *dmu, int B, int F, int T, gtts_stream_t stream);
+/* path [B,t_x,T]: the 0/1 alignment of monotonic_align.maximum_path (at most one 1 per column, a token's frames one contiguous run).
+ * idx [B,T] int32: the token of each frame, -1 for an empty column; dur [B,t_x] fp32: frames per token (exact integers, what
+ * path.sum(-1) gives); first [B,t_x] int32: the first frame of each token's run, -1 for a token without frames.  T <= 40960. */
+int gtts_align_index(const float *path, int *idx, float *dur, int *first, int B, int t_x, int T, gtts_stream_t stream);
+/* Duration loss (tts.py:141-143, utils.py:42-44) without its normaliser: partials[b] = sum_i (logw - log(1e-8 + dur) x_mask)[b,i]^2,
+ * grad (nullable) [B,t_x] = 2 (logw - log(1e-8 + dur) x_mask); loss = sum(partials) / sum(x_lengths).  logw, dur, x_mask [B,t_x]. */
+int gtts_duration_loss(const float *logw, const float *dur, const float *x_mask, float *partials, float *grad, int B, int t_x,
+                       gtts_stream_t stream);
+/* The training crop and the aligned prior mean in one gather (tts.py:146-172): output frame c of sample b is input frame start[b] + c
+ * while c < kept[b] and empty from there on (no crop: S = T, start = 0, kept = y_lengths).
+ *   y_c[b,f,c] = y[b,f,start+c],  mu_y[b,f,c] = mu_x[b,f,idx[b,start+c]] (0 where idx is -1); both 0 for c >= kept[b]
+ *   partials[gtts_align_gather_partials(B,F,S)]: fixed-order sums of 0.5 ((y_c - mu_y)^2 + log 2 pi) over the live elements
+ *   (prior loss = sum(partials) / (sum(kept) F), tts.py:178-180).
+ * mu_x [B,F,t_x], y [B,F,T], idx [B,T], start / kept [B] int32 ON THE DEVICE (a kept[b] above S counts as S; start[b] + c is clamped
+ * into [0, T - 1]); y_c, mu_y [B,F,S].  GTTS_E_SHAPE: B, F, t_x, T or S < 1, S > T (a window longer than the frame axis: every kept[b]
+ * would lie below S, a batch the dense composition's own mask, sequence_mask(kept), cannot take either). */
+size_t gtts_align_gather_partials(int B, int F, int S);
+int gtts_align_gather_forward(const float *mu_x, const float *y, const int *idx, const int *start, const int *kept, float *y_c, float *mu_y,
+                              float *partials, int B, int F, int t_x, int T, int S, gtts_stream_t stream);
+/* Its gradient w.r.t. mu_x, a segment sum over each token's run (nothing is scattered):
+ *   dmu_x[b,f,i] = sum over the live output frames c of token i, ascending c, of (g_mu_y[b,f,c] + scale[0] (mu_y - y_c)[b,f,c])
+ * scale: ONE float on the device, (gradient of the prior loss) / (sum(kept) F); g_mu_y or scale may be NULL (not both; mu_y and y_c are
+ * read only with scale).  Tokens without a live frame get 0.  dur, first as written by gtts_align_index; dmu_x [B,F,t_x]. */
+int gtts_align_gather_backward(const float *g_mu_y, const float *mu_y, const float *y_c, const float *scale, const float *dur,
+                               const int *first, const int *start, const int *kept, float *dmu_x, int B, int F, int t_x, int S,
+                               gtts_stream_t stream);
+
 /* ---- debugging / tests: named intermediates of the last estimator call (keep_intermediates plans) ----- */
 int gtts_plan_num_tensors(const gtts_plan *plan);
 /* offset is in bytes into the workspace for the given (B,T); dims = {B,C,H,W}. */

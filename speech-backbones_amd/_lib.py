@@ -145,6 +145,13 @@ def lib():
         L.gtts_conv_wgrad_small_scratch_floats.argtypes = [i, i, i, i]
         L.gtts_conv_wgrad_small_scratch_floats.restype = sz
         L.gtts_conv_wgrad_small.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
+        L.gtts_conv_dgrad_small.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp]
+        L.gtts_diffusion_noising_backward.argtypes = [vp, vp, vp, f, f, vp, vp, i, i, i, vp]
+        L.gtts_align_index.argtypes = [vp, vp, vp, vp, i, i, i, vp]
+        L.gtts_duration_loss.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
+        L.gtts_align_gather_partials.argtypes, L.gtts_align_gather_partials.restype = [i, i, i], sz
+        L.gtts_align_gather_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp]
+        L.gtts_align_gather_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
         L.gtts_zero_insert2.argtypes = [vp, vp, i, i, i, i, vp]
         L.gtts_space_to_depth2.argtypes = [vp, vp, i, i, i, i, vp]
         L.gtts_final_conv_forward.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp]
@@ -1405,14 +1412,19 @@ def _tiles(c):
     return c == 64 or (c > 64 and c % 128 == 0)
 
 
+def _dgrad_small_ok(need_dgrad, shape):
+    """gtts_conv_dgrad_small stages whole rows with their halo in LDS: at most 2289 columns."""
+    return not need_dgrad or shape is None or int(shape[2]) <= 2289
+
+
 def conv3x3_supported(cin, cout, need_dgrad=True, shape=None):
     """Channel counts (and, with shape = (B, H, W), tensor sizes) the training conv kernels take (forward / data gradient /
-    weight gradient).  The first layer (the stacked 2- or 3-plane input, no data gradient wanted) has its own weight-gradient
-    kernel."""
+    weight gradient).  The first layer (the stacked 2- or 3-plane input) has its own weight-gradient and data-gradient kernels
+    (gtts_conv_wgrad_small, gtts_conv_dgrad_small)."""
     if shape is not None and not conv_size_ok(shape[0], cin, cout, shape[1], shape[2]):
         return False
-    if cin in (2, 3) and not need_dgrad:
-        return _tiles(cout)
+    if cin in (2, 3):
+        return _tiles(cout) and _dgrad_small_ok(need_dgrad, shape)
     return cin % 32 == 0 and cout % 32 == 0 and _tiles(cin) and _tiles(cout)
 
 
@@ -1685,8 +1697,8 @@ def conv1x1_supported(cin, cout, need_dgrad=True, shape=None):
     data gradient, cin) a whole number of the kernel's output tiles; the weight gradient whole 64 x 64 tiles."""
     if shape is not None and not conv_size_ok(shape[0], cin, cout, shape[1], shape[2]):
         return False
-    if cin in (2, 3) and not need_dgrad:          # first layer: own weight-gradient kernel
-        return _tiles(cout)
+    if cin in (2, 3):                             # first layer: own weight-gradient and data-gradient kernels
+        return _tiles(cout) and _dgrad_small_ok(need_dgrad, shape)
     return _tiles(cout) and cin % 64 == 0 and (_tiles(cin) or not need_dgrad)
 
 
@@ -1940,6 +1952,122 @@ def score_loss(eps, z_masked, t, beta_min, beta_max, inv_denom, want_grad=True):
         _check(lib().gtts_score_loss(_ptr(eps), _ptr(z_masked), _ptr(t), float(beta_min), float(beta_max), float(inv_denom),
                                      _ptr(part), _ptr(g), B, F, T, _stream()), "gtts_score_loss")
     return part.sum() * inv_denom, g
+
+
+def _out(out, name, shape, dtype, device):
+    """A preallocated output of the caller's (`out` dict, tests place them between guard margins) or a fresh one."""
+    t = None if out is None else out.get(name)
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise RuntimeError("output %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
+    return t
+
+
+def _i32c(t, name, device):
+    if not torch.is_tensor(t):
+        t = torch.tensor(t, dtype=torch.int32)
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def conv_dgrad_small(dy, weight, mask_cols=None, out=None):
+    """The first layer's data gradient (cin 2 or 3, its own kernel): dx [B,cin,H,W] of Conv2d_kxk(x * mask) for k = 3 (padding 1) or 1,
+    dy [B,cout,H,W], weight [cout,cin,k,k] (not packed), mask_cols [B,W] or None."""
+    if not dy.is_cuda:
+        raise RuntimeError("conv_dgrad_small needs HIP tensors (got %s); there is no CPU fallback" % dy.device)
+    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
+    B, cout, H, W = dy.shape
+    cin, ksize = int(weight.shape[1]), int(weight.shape[2])
+    if weight.shape[0] != cout or weight.shape[3] != ksize:
+        raise RuntimeError("weight %s does not match dy %s" % (tuple(weight.shape), tuple(dy.shape)))
+    mask_cols = _const(dy.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
+    dx = _out(out, "dx", (B, cin, H, W), torch.float32, dy.device)
+    with _on(dy.device):
+        _check(lib().gtts_conv_dgrad_small(_ptr(dy), _ptr(weight), _ptr(mask_cols), _ptr(dx), B, cin, cout, H, W, ksize, _stream()),
+               "gtts_conv_dgrad_small")
+    return dx
+
+
+def diffusion_noising_backward(dxt, mask, t, beta_min, beta_max, want_dx0=True, want_dmu=True, out=None):
+    """(dx0, dmu) of diffusion_noising (an output not wanted is None)."""
+    if not dxt.is_cuda:
+        raise RuntimeError("diffusion_noising_backward needs HIP tensors (got %s); there is no CPU fallback" % dxt.device)
+    dxt, mask, t = _f32c(dxt, "dxt"), _f32c(mask, "mask"), _f32c(t, "t")
+    B, F, T = dxt.shape
+    dx0 = _out(out, "dx0", (B, F, T), torch.float32, dxt.device) if want_dx0 else None
+    dmu = _out(out, "dmu", (B, F, T), torch.float32, dxt.device) if want_dmu else None
+    with _on(dxt.device):
+        _check(lib().gtts_diffusion_noising_backward(_ptr(dxt), _ptr(mask), _ptr(t), float(beta_min), float(beta_max), _ptr(dx0), _ptr(dmu),
+                                                     B, F, T, _stream()), "gtts_diffusion_noising_backward")
+    return dx0, dmu
+
+
+def align_index(path, out=None):
+    """The alignment path [B,t_x,T] of monotonic_align.maximum_path as indices: (idx [B,T] int32 token of each frame or -1,
+    dur [B,t_x] fp32 frames per token, first [B,t_x] int32 first frame of each token's run or -1)."""
+    if not path.is_cuda:
+        raise RuntimeError("align_index needs HIP tensors (got %s); there is no CPU fallback" % path.device)
+    path = _f32c(path, "path")
+    B, tx, T = path.shape
+    idx = _out(out, "idx", (B, T), torch.int32, path.device)
+    dur = _out(out, "dur", (B, tx), torch.float32, path.device)
+    first = _out(out, "first", (B, tx), torch.int32, path.device)
+    with _on(path.device):
+        _check(lib().gtts_align_index(_ptr(path), _ptr(idx), _ptr(dur), _ptr(first), B, tx, T, _stream()), "gtts_align_index")
+    return idx, dur, first
+
+
+def duration_loss(logw, dur, x_mask, want_grad=True, out=None):
+    """(sum((logw - log(1e-8 + dur) * x_mask)^2) as a 0-d tensor, its gradient w.r.t. logw or None): utils.py:42-44 without the
+    normaliser, which the caller keeps as a device scalar.  logw, dur, x_mask: B * t_x elements each."""
+    if not logw.is_cuda:
+        raise RuntimeError("duration_loss needs HIP tensors (got %s); there is no CPU fallback" % logw.device)
+    lw, d, m = _f32c(logw, "logw"), _f32c(dur, "dur"), _f32c(x_mask, "x_mask")
+    B, tx = int(d.shape[0]), int(d.shape[-1])
+    if lw.numel() != B * tx or m.numel() != B * tx:
+        raise RuntimeError("logw, dur and x_mask must hold [B, t_x] = [%d, %d] elements each" % (B, tx))
+    part = _out(out, "partials", (B,), torch.float32, lw.device)
+    g = _out(out, "grad", tuple(lw.shape), torch.float32, lw.device) if want_grad else None
+    with _on(lw.device):
+        _check(lib().gtts_duration_loss(_ptr(lw), _ptr(d), _ptr(m), _ptr(part), _ptr(g), B, tx, _stream()), "gtts_duration_loss")
+    return part.sum(), g
+
+
+def align_gather(mu_x, y, idx, start, kept, S, out=None):
+    """Training crop + aligned prior mean (tts.py:146-172) in one gather: (y_c [B,F,S], mu_y [B,F,S], sum over the live elements of
+    0.5 ((y_c - mu_y)^2 + log 2 pi) as a 0-d tensor).  start, kept: [B] integer tensors (or lists); S: output frames."""
+    if not mu_x.is_cuda:
+        raise RuntimeError("align_gather needs HIP tensors (got %s); there is no CPU fallback" % mu_x.device)
+    mx, yy = _f32c(mu_x, "mu_x"), _f32c(y, "y")
+    B, F, tx = mx.shape
+    T, S = int(yy.shape[2]), int(S)
+    if tuple(yy.shape[:2]) != (B, F) or tuple(idx.shape) != (B, T) or idx.dtype != torch.int32:
+        raise RuntimeError("mu_x [B,F,t_x], y [B,F,T] and idx [B,T] int32 disagree: %s, %s, %s" % (tuple(mx.shape), tuple(yy.shape), tuple(idx.shape)))
+    st, kp = _i32c(start, "start", mx.device), _i32c(kept, "kept", mx.device)
+    y_c = _out(out, "y_c", (B, F, S), torch.float32, mx.device)
+    mu_y = _out(out, "mu_y", (B, F, S), torch.float32, mx.device)
+    part = _out(out, "partials", (int(lib().gtts_align_gather_partials(B, F, S)),), torch.float32, mx.device)
+    with _on(mx.device):
+        _check(lib().gtts_align_gather_forward(_ptr(mx), _ptr(yy), _ptr(idx.contiguous()), _ptr(st), _ptr(kp), _ptr(y_c), _ptr(mu_y), _ptr(part),
+                                               B, F, tx, T, S, _stream()), "gtts_align_gather_forward")
+    return y_c, mu_y, part.sum()
+
+
+def align_gather_backward(g_mu_y, mu_y, y_c, scale, dur, first, start, kept, out=None):
+    """dmu_x [B,F,t_x] of align_gather: per token the sum, over its live output frames, of g_mu_y + scale * (mu_y - y_c).  g_mu_y
+    [B,F,S] or None; scale: a one-element device tensor, (gradient of the prior loss) / (sum(kept) F), or None (then mu_y, y_c unused)."""
+    if not dur.is_cuda:
+        raise RuntimeError("align_gather_backward needs HIP tensors (got %s); there is no CPU fallback" % dur.device)
+    g, my, yc, sc = _f32c(g_mu_y, "g_mu_y"), _f32c(mu_y, "mu_y"), _f32c(y_c, "y_c"), _f32c(scale, "scale")
+    ref = g if g is not None else my
+    B, F, S = ref.shape
+    tx = int(dur.shape[1])
+    st, kp = _i32c(start, "start", dur.device), _i32c(kept, "kept", dur.device)
+    dmu_x = _out(out, "dmu_x", (B, F, tx), torch.float32, dur.device)
+    with _on(dur.device):
+        _check(lib().gtts_align_gather_backward(_ptr(g), _ptr(my), _ptr(yc), _ptr(sc), _ptr(_f32c(dur, "dur")), _ptr(first.contiguous()), _ptr(st),
+                                                _ptr(kp), _ptr(dmu_x), B, F, tx, S, _stream()), "gtts_align_gather_backward")
+    return dmu_x
 
 
 def log_prior(mu_x, y):

@@ -2,6 +2,7 @@
 // per optimiser step at [16, C, 80, 172] (Grad-TTS/train.py:105-119; Grad-TTS/model/diffusion.py:244-252,281-294).
 //
 //   gtts_diffusion_noising   forward_diffusion (diffusion.py:244-252): xt = (x0 e^{-c/2} + mu (1 - e^{-c/2}) + z sqrt(1 - e^{-c})) mask
+//   gtts_diffusion_noising_backward   its gradient w.r.t. x0 and mu (GradTTS.compute_loss: mu comes from the encoder)
 //   gtts_score_loss          loss_t (diffusion.py:281-288): sum((eps sqrt(1 - e^{-c}) + z)^2) / (sum(mask) F) and d loss / d eps
 //   gtts_conv3x3_masked      y = Conv2d_3x3(x * mask) + bias      (Block.forward, diffusion.py:56-57) on the inference MFMA kernel;
 //                            the data gradient Conv2d_3x3(dy, W^T flipped) [* mask] is the same call with weights packed transposed
@@ -43,6 +44,23 @@ __global__ void noising_kernel(const float *__restrict__ x0, const float *__rest
     zm[i] = zz * m;
 }
 
+// gradient of the kernel above w.r.t. x0 and mu (z carries none): dx0 = d mask dxt, dmu = (1 - d) mask dxt with d = e^{-cum/2}
+// evaluated by the forward kernel's own expressions (either output nullable)
+__global__ void noising_backward_kernel(const float *__restrict__ dxt, const float *__restrict__ mask, const float *__restrict__ t,
+                                        float bmin, float bmax, float *__restrict__ dx0, float *__restrict__ dmu, int F, int T,
+                                        size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / ((size_t)F * T);
+    const int col = (int)(i % T);
+    const float tv = t[b];
+    const float cum = bmin * tv + 0.5f * (bmax - bmin) * (tv * tv);
+    const float decay = (float)exp(-0.5 * (double)cum);
+    const float g = dxt[i] * mask[b * T + col];
+    if (dx0) dx0[i] = g * decay;
+    if (dmu) dmu[i] = g * (1.0f - decay);
+}
+
 // r = eps * sqrt(1 - e^{-cum}) + z;  partial[blk] = sum r^2 (fixed order inside a workgroup);  geps = 2 r s / denom
 __global__ void score_loss_kernel(const float *__restrict__ eps, const float *__restrict__ z, const float *__restrict__ t,
                                   float bmin, float bmax, float inv_denom, float *__restrict__ partial,
@@ -77,6 +95,18 @@ extern "C" int gtts_diffusion_noising(const float *x0, const float *mu, const fl
     const size_t total = (size_t)B * F * T;
     hipLaunchKernelGGL(noising_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x0, mu, z, mask, t,
                        beta_min, beta_max, xt, z_masked, F, T, total);
+    GTTS_HIPCHK(hipGetLastError());
+    return GTTS_OK;
+}
+
+extern "C" int gtts_diffusion_noising_backward(const float *dxt, const float *mask, const float *t, float beta_min, float beta_max,
+                                               float *dx0, float *dmu, int B, int F, int T, gtts_stream_t stream) {
+    if (!dxt || !mask || !t || (!dx0 && !dmu)) return fail(GTTS_E_NULL, "gtts_diffusion_noising_backward: null argument");
+    if (B <= 0 || F <= 0 || T <= 0) return fail(GTTS_E_SHAPE, "gtts_diffusion_noising_backward: bad shape");
+    const size_t total = (size_t)B * F * T;
+    if (total >= ((size_t)1 << 39)) return fail(GTTS_E_SHAPE, "gtts_diffusion_noising_backward: bad shape");
+    hipLaunchKernelGGL(noising_backward_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dxt, mask, t,
+                       beta_min, beta_max, dx0, dmu, F, T, total);
     GTTS_HIPCHK(hipGetLastError());
     return GTTS_OK;
 }

@@ -131,6 +131,71 @@ __global__ void wgrad_small_finish_kernel(const float *__restrict__ part, float 
     else if (db) db[co] = (float)t;
 }
 
+// First-layer data gradient, the counterpart of the kernel above (wanted when the prior mean or the speaker plane carries a gradient:
+// GradTTS.compute_loss, every multi-speaker step):  dx[b,ci,h,w] = mask[b,w] sum_co sum_taps dy[b,co,h-ky+R,w-kx+R] w[co,ci,ky,kx].
+// Two or three output planes from cout input planes: one pass over dy.  grid (ceil(HW / DS_TP), B): a workgroup owns DS_TP consecutive
+// pixels of one sample's flattened plane (two per thread, 256 apart) and walks the output channels DS_CC at a time -- the dy chunk
+// with a halo of R (W + 1) pixels on both sides (zero outside the plane, which is what a tap above the first or below the last row
+// reads) and the chunk's weights are staged in LDS; a tap left of column 0 or right of column W - 1 is skipped by the column test.
+// Sums run over co ascending and the taps in a fixed order: no atomics, the same bits every call.
+constexpr int DS_TP = 512, DS_CC = 8;
+static inline size_t dgrad_small_lds_floats(int cin, int W, int ksize) {
+    return (size_t)DS_CC * (DS_TP + 2 * (ksize / 2) * (W + 1)) + (size_t)DS_CC * cin * ksize * ksize;
+}
+template <int CIN, int K>
+__global__ __launch_bounds__(256) void dgrad_small_kernel(const float *__restrict__ dy, const float *__restrict__ w, const float *__restrict__ mask,
+                                                          float *__restrict__ dx, int cout, int H, int W) {
+    constexpr int NT = CIN * K * K, R = K / 2;
+    extern __shared__ float s_dgs[];              // [DS_CC][span] dy with halo, then [DS_CC][NT] weights
+    const int halo = R * (W + 1), span = DS_TP + 2 * halo, HW = H * W;
+    float *s_dy = s_dgs, *s_w = s_dgs + (size_t)DS_CC * span;
+    const int bi = blockIdx.y, p0 = blockIdx.x * DS_TP, tid = threadIdx.x;
+    const float *pd = dy + (size_t)bi * cout * HW;
+    int pp[2], col[2];
+    float acc[2][CIN];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        pp[k] = p0 + k * 256 + tid;
+        col[k] = pp[k] % W;
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) acc[k][ci] = 0.f;
+    }
+    for (int co0 = 0; co0 < cout; co0 += DS_CC) {
+        __syncthreads();                          // (the previous chunk has been consumed)
+        for (int e = tid; e < DS_CC * span; e += 256) {
+            const int c = e / span, q = p0 - halo + (e - c * span);
+            s_dy[e] = (q >= 0 && q < HW) ? pd[(size_t)(co0 + c) * HW + q] : 0.f;
+        }
+        for (int e = tid; e < DS_CC * NT; e += 256) s_w[e] = w[(size_t)co0 * NT + e];
+        __syncthreads();
+#pragma unroll 2
+        for (int c = 0; c < DS_CC; ++c) {
+            float wr[NT];
+#pragma unroll
+            for (int i = 0; i < NT; ++i) wr[i] = s_w[c * NT + i];
+            const float *row = s_dy + (size_t)c * span + halo + tid;
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+                for (int ky = 0; ky < K; ++ky)
+#pragma unroll
+                    for (int kx = 0; kx < K; ++kx) {
+                        const int xc = col[k] - kx + R;
+                        const float g = (xc >= 0 && xc < W) ? row[k * 256 + (R - ky) * W + (R - kx)] : 0.f;
+#pragma unroll
+                        for (int ci = 0; ci < CIN; ++ci) acc[k][ci] = fmaf(g, wr[(ci * K + ky) * K + kx], acc[k][ci]);
+                    }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (pp[k] < HW) {
+            const float m = mask[(size_t)bi * W + col[k]];
+#pragma unroll
+            for (int ci = 0; ci < CIN; ++ci) dx[((size_t)bi * CIN + ci) * HW + pp[k]] = acc[k][ci] * m;
+        }
+}
+
 // final_conv: out[b,p] = (sum_c w[c] x[b,c,p] m + bias) m,  m = mask[b, p % W]   (diffusion.py:175-176); grid (ceil(HW/256), B)
 __global__ __launch_bounds__(256) void final_conv_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w, const float *__restrict__ bias,
                                                              const float *__restrict__ mask, float *__restrict__ out, int C, int HW, int W) {
@@ -234,6 +299,39 @@ extern "C" int gtts_conv_wgrad_small(const float *x, const float *mask, const fl
     const int nt = cin * ksize * ksize;
     hipLaunchKernelGGL(wgrad_small_finish_kernel, dim3((cout * (nt + 1) + 255) / 256), dim3(256), 0, st, scratch, dw, db, B * WS_SPLIT, cout, nt);
     GTTS_HIPCHK(hipGetLastError());
+    return GTTS_OK;
+}
+
+template <int CIN, int K>
+static hipError_t launch_dgrad_small(const float *dy, const float *w, const float *mask, float *dx, int B, int cout, int H, int W, hipStream_t st) {
+    const size_t smem = dgrad_small_lds_floats(CIN, W, K) * sizeof(float);
+    if (smem > 48 * 1024) {
+        const hipError_t e = raise_dyn_lds<&dgrad_small_kernel<CIN, K>>(smem);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((dgrad_small_kernel<CIN, K>), dim3((H * W + DS_TP - 1) / DS_TP, B), dim3(256), smem, st, dy, w, mask, dx, cout, H, W);
+    return hipGetLastError();
+}
+
+// dx [B,cin,H,W] of y = Conv2d_kxk(x * mask) + bias for the first layer: cin 2 or 3, k 3 (padding 1) or 1, cout a multiple of 64;
+// dy [B,cout,H,W], w [cout][cin][k][k] (the module's own layout: nothing is packed), mask [B,W]
+extern "C" int gtts_conv_dgrad_small(const float *dy, const float *w, const float *mask, float *dx, int B, int cin, int cout, int H, int W,
+                                     int ksize, gtts_stream_t stream) {
+    if (!dy || !w || !mask || !dx) return fail(GTTS_E_NULL, "gtts_conv_dgrad_small: null argument");
+    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long)H * W >= (1l << 28) || (long)B * std::max(cout, 1) * H * W >= (1l << 31))
+        return fail(GTTS_E_SHAPE, "gtts_conv_dgrad_small: bad shape B=%d H=%d W=%d", B, H, W);
+    if ((cin != 2 && cin != 3) || (ksize != 1 && ksize != 3) || cout <= 0 || cout % 64)
+        return fail(GTTS_E_CONFIG, "gtts_conv_dgrad_small: cin must be 2 or 3, the kernel 1x1 or 3x3 and cout a multiple of 64 (got cin %d, k %d, cout %d)",
+                    cin, ksize, cout);
+    if (dgrad_small_lds_floats(3, W, ksize) * sizeof(float) > 160 * 1024)          // (one limit for both plane counts: W <= 2289)
+        return fail(GTTS_E_SHAPE, "gtts_conv_dgrad_small: W=%d is too wide for the kernel's LDS tile", W);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e;
+    if (cin == 2 && ksize == 3) e = launch_dgrad_small<2, 3>(dy, w, mask, dx, B, cout, H, W, st);
+    else if (cin == 3 && ksize == 3) e = launch_dgrad_small<3, 3>(dy, w, mask, dx, B, cout, H, W, st);
+    else if (cin == 2) e = launch_dgrad_small<2, 1>(dy, w, mask, dx, B, cout, H, W, st);
+    else e = launch_dgrad_small<3, 1>(dy, w, mask, dx, B, cout, H, W, st);
+    GTTS_HIPCHK(e);
     return GTTS_OK;
 }
 

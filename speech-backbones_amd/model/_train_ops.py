@@ -13,6 +13,11 @@ csrc/train*.hip behind torch.autograd.Function wrappers:
   RezeroResidual, MaskedResidualAdd, the plain residual add, FinalConv (64 -> 1 with both masks), ScoreLoss
   ResampleConv         Downsample / Upsample forward and all their gradients on the HIP kernels (Downsample's data gradient is an
                        Upsample call, Upsample's gradients are 3x3 stride-1 operations over the four stride-2 phases of dy)
+  Noising, DurationLoss, AlignGather   what couples encoder and decoder in GradTTS.compute_loss (the train.py step): the noising with its
+                       gradient w.r.t. the prior mean, and the alignment glue between MAS and the decoder -- frames per token and the
+                       duration loss, the training crop, mu_y = attn^T . mu_x and the prior loss -- as index / gather / segment-sum
+                       kernels of csrc/glue_train.hip; the first layer's data gradient (the stacked (mu, xt[, spk]) planes carry a
+                       gradient then) is gtts_conv_dgrad_small, taken by MaskedConv3x3 / MaskedConv1x1 for 2 or 3 input planes
   EncAttentionCore     the transformer encoder's windowed relative-position attention between its convolutions, and EncLayerNorm, its
                        LayerNorm with the fused residual (text_encoder.py, shared by TextEncoder and DiffVC's MelEncoder), on
                        csrc/enc_train.hip; the encoder's Conv1d layers and embedding stay torch autograd
@@ -45,7 +50,9 @@ class MaskedConv3x3(torch.autograd.Function):
         need1 = x1 is not None and ctx.needs_input_grad[4]
         if ctx.needs_input_grad[0] or need1:
             c0 = x.shape[1]
-            if x1 is None:
+            if x1 is None and c0 in (2, 3):                         # first layer (stacked planes): its own kernel, one pass over dy
+                dx = be.conv_dgrad_small(dy, weight, cols)
+            elif x1 is None:
                 dx = be.conv3x3_dgrad(dy, weight, cols)             # (the mask rides in the convolution's epilogue)
             else:                                                   # mask and split in one pass each (contiguous results)
                 full = be.conv3x3_dgrad(dy, weight)
@@ -102,7 +109,7 @@ class MaskedConv1x1(torch.autograd.Function):
         dy = dy.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = be.conv1x1_dgrad(dy, weight, cols)
+            dx = be.conv_dgrad_small(dy, weight, cols) if x.shape[1] in (2, 3) else be.conv1x1_dgrad(dy, weight, cols)
         if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
             dw, db = be.conv1x1_wgrad(x, cols, dy, want_bias=ctx.has_bias)
         return dx, None, (dw if ctx.needs_input_grad[2] else None), (db if ctx.has_bias and ctx.needs_input_grad[3] else None)
@@ -335,6 +342,70 @@ class ScoreLoss(torch.autograd.Function):
         return g * dloss, None, None, None, None, None
 
 
+class Noising(torch.autograd.Function):
+    """Diffusion.forward_diffusion given the N(0,1) draw z, under autograd (GradTTS.compute_loss: mu comes from the encoder): the forward
+    is gtts_diffusion_noising -- the bits of the decoder-only path --, the backward gtts_diffusion_noising_backward.  z and the second
+    output (z * mask) carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x0, mu, z, mask, t, beta_min, beta_max):
+        xt, zm = backend().diffusion_noising(x0, mu, z, mask, t, beta_min, beta_max)
+        ctx.save_for_backward(mask, t)
+        ctx.betas = (beta_min, beta_max)
+        ctx.mark_non_differentiable(zm)
+        return xt, zm
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dxt, _dzm):
+        mask, t = ctx.saved_tensors
+        dx0, dmu = backend().diffusion_noising_backward(dxt.contiguous(), mask, t, ctx.betas[0], ctx.betas[1],
+                                                        want_dx0=ctx.needs_input_grad[0], want_dmu=ctx.needs_input_grad[1])
+        return dx0, dmu, None, None, None, None, None
+
+
+class DurationLoss(torch.autograd.Function):
+    """sum((logw - log(1e-8 + dur) * x_mask)^2) * inv_denom (tts.py:141-143, utils.py:42-44) with the gradient w.r.t. logw produced in
+    the same pass; dur: frames per token (align_index), inv_denom: 1 / sum(x_lengths) as a device scalar."""
+
+    @staticmethod
+    def forward(ctx, logw, dur, x_mask, inv_denom):
+        total, g = backend().duration_loss(logw, dur, x_mask, want_grad=True)
+        ctx.save_for_backward(g, inv_denom)
+        return total * inv_denom
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss):
+        g, inv_denom = ctx.saved_tensors
+        return g * (dloss * inv_denom), None, None, None
+
+
+class AlignGather(torch.autograd.Function):
+    """The training crop of y and of the alignment, mu_y = attn^T . mu_x and the prior loss (tts.py:146-181) as one gather:
+    (y_c, mu_y, prior_loss) from mu_x, y and the index form of the path (align_index).  Output frame c of sample b is input frame
+    start[b] + c while c < kept[b]; inv_denom: 1 / (sum(kept) * n_feats) as a device scalar.  The backward is a segment sum over each
+    token's run of frames: the gradient arriving through mu_y (the decoder) plus the prior loss's own."""
+
+    @staticmethod
+    def forward(ctx, mu_x, y, idx, dur, first, start, kept, S, inv_denom):
+        y_c, mu_y, total = backend().align_gather(mu_x, y, idx, start, kept, S)
+        ctx.save_for_backward(mu_y, y_c, dur, first, start, kept, inv_denom)
+        ctx.mark_non_differentiable(y_c)
+        ctx.set_materialize_grads(False)
+        return y_c, mu_y, total * inv_denom
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, _dy_c, g_mu_y, g_prior):
+        mu_y, y_c, dur, first, start, kept, inv_denom = ctx.saved_tensors
+        if g_mu_y is None and g_prior is None:
+            return (None,) * 9
+        scale = None if g_prior is None else (g_prior * inv_denom).reshape(1)
+        dmu_x = backend().align_gather_backward(None if g_mu_y is None else g_mu_y.contiguous(), mu_y, y_c, scale, dur, first, start, kept)
+        return (dmu_x,) + (None,) * 8
+
+
 FORCE_TORCH = False      # measurement switch (bench.py train_step): route every op to stock PyTorch-ROCm kernels
 
 # How many tensor-sized ops of the training path ran on the gtts:: kernels and how many fell back to stock torch ops because a gate
@@ -375,6 +446,26 @@ def enc_op_counts():
 def enc_count(hip):
     if not FORCE_TORCH:
         _ENC_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
+
+
+# And for the alignment glue of GradTTS.compute_loss (model/tts.py): one count per op -- the path's index form, the duration loss, the
+# crop / prior-mean gather with the prior loss -- `hip` when the kernels of csrc/glue_train.hip ran, `fallback` when HIP tensors took
+# the dense torch composition.
+_GLUE_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
+
+
+def reset_glue_op_counts():
+    _GLUE_COUNTS["hip_ops"] = 0
+    _GLUE_COUNTS["torch_fallback_ops"] = 0
+
+
+def glue_op_counts():
+    return _GLUE_COUNTS["hip_ops"], _GLUE_COUNTS["torch_fallback_ops"]
+
+
+def glue_count(hip, n=1):
+    if not FORCE_TORCH:
+        _GLUE_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += n
 
 
 def enc_hip(t):

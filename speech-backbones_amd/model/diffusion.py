@@ -333,6 +333,9 @@ class Diffusion(BaseModule):
         z = torch.randn(x0.shape, dtype=x0.dtype, device=x0.device, requires_grad=False)
         if x0.is_cuda and not x0.requires_grad and not mu.requires_grad and not _train_ops.FORCE_TORCH:
             return backend().diffusion_noising(x0, mu, z, mask, t, self.beta_min, self.beta_max)
+        if x0.is_cuda and x0.dtype == torch.float32 and mu.dtype == torch.float32 and not _train_ops.FORCE_TORCH:
+            # the encoder is attached (GradTTS.compute_loss): the same kernel under autograd, with a backward kernel of its own
+            return _train_ops.Noising.apply(x0, mu, z, mask, t, self.beta_min, self.beta_max)
         time = t[:, None, None]
         cum = get_noise(time, self.beta_min, self.beta_max, cumulative=True)
         decay = torch.exp(-0.5 * cum)

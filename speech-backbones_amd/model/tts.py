@@ -6,7 +6,7 @@ import random
 
 import torch
 
-from . import monotonic_align
+from . import _train_ops, monotonic_align
 from ._backend import backend
 from .base import BaseModule
 from .diffusion import Diffusion
@@ -100,6 +100,12 @@ class GradTTS(BaseModule):
         with torch.no_grad():
             attn = monotonic_align.maximum_path(self._mas_scores(mu_x, y), pair_mask.squeeze(1)).detach()
 
+        hip = _train_ops.enc_hip(mu_x) and _train_ops.enc_hip(y) and _train_ops.enc_hip(logw)
+        if hip:
+            return self._losses_hip(attn, mu_x, logw, x_mask, x_lengths, y, y_lengths, spk, out_size)
+        if mu_x.is_cuda:
+            _train_ops.glue_count(False, 3)
+
         # duration predictor target = log of the frames MAS gave each token (tts.py:141-143)
         frames_per_token = attn.sum(-1).unsqueeze(1)
         dur_loss = duration_loss(logw, torch.log(1e-8 + frames_per_token) * x_mask, x_lengths)
@@ -123,4 +129,29 @@ class GradTTS(BaseModule):
         diff_loss, _ = self.decoder.compute_loss(y, y_mask, mu_y, spk)
         nll = 0.5 * ((y - mu_y) ** 2 + math.log(2 * math.pi)) * y_mask
         prior_loss = nll.sum() / (y_mask.sum() * self.n_feats)
+        return dur_loss, prior_loss, diff_loss
+
+    def _losses_hip(self, attn, mu_x, logw, x_mask, x_lengths, y, y_lengths, spk, out_size):
+        """Everything of compute_loss after MAS on the kernels of csrc/glue_train.hip (fp32 HIP tensors): the 0/1 path is read once, into
+        its index form; the crop, mu_y = attn^T . mu_x and both encoder losses are a gather forward and a segment sum backward.  Same
+        window draws from Python's `random`, no host synchronisation beyond the crop's own `.tolist()`; normalisers stay device
+        scalars."""
+        be = backend()
+        frames = y.shape[-1]
+        idx, dur, first = be.align_index(attn)
+        dur_loss = _train_ops.DurationLoss.apply(logw, dur, x_mask, 1.0 / torch.sum(x_lengths))
+        if out_size is not None:
+            slack = (y_lengths - out_size).clamp(min=0).tolist()
+            start = torch.tensor([random.randrange(int(n)) if int(n) > 0 else 0 for n in slack], dtype=torch.int32).to(y.device)
+            kept = torch.clamp(y_lengths, max=out_size).to(torch.int32)
+            S = int(out_size)
+        else:
+            start = torch.zeros(y.shape[0], dtype=torch.int32, device=y.device)
+            kept = torch.clamp(y_lengths, max=frames).to(torch.int32)
+            S = frames
+        y_mask = sequence_mask(kept, S).unsqueeze(1).to(x_mask)
+        inv_denom = 1.0 / (torch.sum(kept) * self.n_feats)
+        y_c, mu_y, prior_loss = _train_ops.AlignGather.apply(mu_x, y, idx, dur, first, start, kept, S, inv_denom)
+        _train_ops.glue_count(True, 3)
+        diff_loss, _ = self.decoder.compute_loss(y_c, y_mask, mu_y, spk)
         return dur_loss, prior_loss, diff_loss
