@@ -537,6 +537,16 @@ int gtts_mel_pack(const gtts_mel *mel, void *packed, gtts_stream_t stream);
 int gtts_mel_filterbank(const gtts_mel *mel, float *host_out);
 int gtts_mel_forward(const gtts_mel *mel, const void *packed, const float *wav, const int *lengths, float *out, int B, int L,
                      gtts_stream_t stream);
+/* ---- ABI 7 (additive): the input gradient of gtts_mel_forward (csrc/mel_train.hip) -- what the HiFi-GAN mel loss sends to the generator.
+ * dmel [B,num_mels,T] -> dwav [B,L] for the same wav, lengths and blob as the forward; nothing else is kept from the forward, the frame
+ * spectra are formed again.  The clip passes the gradient where W mag >= 1e-5 (torch's clamp), frames at or beyond a row's own count and
+ * samples at or beyond lengths[b] get 0.  Two launches (windowed frame gradients [B][T][n_fft] into the workspace of
+ * gtts_mel_backward_workspace_bytes(B, L) bytes, then a gather per sample in a fixed order), no floating-point atomics: two calls
+ * return the same bits, and a row's gradient depends on that row alone.  Refused before any launch: null pointers (GTTS_E_NULL), B
+ * outside [1, 65535] and every L gtts_mel_frames refuses (GTTS_E_SHAPE), a short workspace (GTTS_E_WORKSPACE). */
+size_t gtts_mel_backward_workspace_bytes(const gtts_mel *mel, int B, int L);      /* 0 for a null handle, B <= 0 or a refused L */
+int gtts_mel_backward(const gtts_mel *mel, const void *packed, const float *wav, const int *lengths, const float *dmel, float *dwav,
+                      void *workspace, size_t workspace_bytes, int B, int L, gtts_stream_t stream);
 
 /* ---- ABI 6 (additive): DiffVC speaker encoder, the 256-d embedding `c` of DiffVC.forward (DiffVC/speaker_encoder/encoder/model.py:43-63,
  * inference.py:150-151) on csrc/spk.hip ---------------------------------------------------------------------------------------------

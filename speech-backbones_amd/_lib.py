@@ -242,6 +242,8 @@ def lib():
         L.gtts_mel_pack.argtypes = [vp, vp, vp]
         L.gtts_mel_filterbank.argtypes = [vp, vp]
         L.gtts_mel_forward.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
+        L.gtts_mel_backward_workspace_bytes.argtypes, L.gtts_mel_backward_workspace_bytes.restype = [vp, i, i], sz
+        L.gtts_mel_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_fgl_create.argtypes = [ctypes.POINTER(FglCfg), ctypes.POINTER(vp)]
         L.gtts_fgl_destroy.argtypes, L.gtts_fgl_destroy.restype = [vp], None
         L.gtts_fgl_samples.argtypes = [vp, i]
@@ -1063,6 +1065,32 @@ class MelPlan(_Native):
         with _on(y.device):
             self._call("forward", self._h, _ptr(blob), _ptr(y), _ptr(lengths), _ptr(out), B, L, _stream())
         return out
+
+    def backward_workspace_bytes(self, B, L):
+        """Bytes of the windowed frame gradients [B, frames(L), n_fft] the backward writes between its two launches."""
+        self.frames(L)
+        return int(self._fn("backward_workspace_bytes")(self._h, int(B), int(L)))
+
+    def backward(self, blob, y, dmel, lengths=None):
+        """The input gradient of forward (csrc/mel_train.hip): y [B, L], dmel [B, num_mels, frames(L)] -> dwav [B, L] fp32; the same
+        lengths as the forward's (gradient 0 at and beyond a row's length).  No floating-point atomics: two calls give the same bits."""
+        if y.dim() != 2:
+            raise RuntimeError("y must be [B, L] (got %s)" % (tuple(y.shape),))
+        B, L = y.shape
+        if dmel.device != y.device or tuple(dmel.shape) != (B, self.num_mels, self.frames(L)):
+            raise RuntimeError("dmel must be [%d, %d, %d] on y's device (got %s on %s)" %
+                               (B, self.num_mels, self.frames(L), tuple(dmel.shape), dmel.device))
+        y, dmel = _f32c(y, "y"), _f32c(dmel, "dmel")
+        if lengths is not None:
+            if not torch.is_tensor(lengths) or lengths.device != y.device or lengths.numel() != B:
+                raise RuntimeError("lengths must be a [B] integer tensor on y's HIP device")
+            lengths = lengths.to(torch.int32).contiguous()
+        ws = torch.empty(self.backward_workspace_bytes(B, L), dtype=torch.uint8, device=y.device)
+        dwav = torch.empty((B, L), dtype=torch.float32, device=y.device)
+        with _on(y.device):
+            self._call("backward", self._h, _ptr(blob), _ptr(y), _ptr(lengths), _ptr(dmel), _ptr(dwav), _ptr(ws), ws.numel(), B, L,
+                       _stream())
+        return dwav
 
 
 class FglPlan(_Native):

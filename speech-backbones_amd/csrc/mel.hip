@@ -24,30 +24,13 @@
 #include "../../include/gradtts_abi.h"
 #include "common.h"
 #include "kernels.h"
+#include "mel.h"
 #include "spectral.h"
 
 namespace gtts {
 
 constexpr int MEL_TF = 16;         // frames per workgroup
 constexpr int MEL_WAVES = 4;       // waves per workgroup; each transforms MEL_TF / MEL_WAVES frames
-
-struct MelArgs {
-    const float *wav;              // [B][L]
-    const int *lengths;            // [B] or nullptr
-    float *out;                    // [B][num_mels][T]
-    const float *win;              // [n_fft]           window, zero-padded to n_fft
-    const float2 *twm;             // [n_fft/2]         e^{-2 pi i k / (n_fft/2)}
-    const float2 *twn;             // [n_fft/2 + 1]     e^{-2 pi i k / n_fft}
-    const int4 *rows;              // [num_mels]        {first bin, chunks of 4 weights, offset into wts, 0}
-    const float *wts;              // [nw]              the rows' weights, each row zero-padded to whole chunks
-    int B, L, T, hop, pad, num_mels, kmax, kstride, nw;
-};
-
-// frames of a row of `len` samples (0 when the row cannot be reflected or holds no whole frame)
-__host__ __device__ inline int mel_frames_of(int len, int n_fft, int hop, int pad) {
-    if (len <= pad || len + 2 * pad < n_fft) return 0;
-    return (len + 2 * pad - n_fft) / hop + 1;
-}
 
 template <int LOGN>
 __global__ __launch_bounds__(64 * MEL_WAVES) void mel_kernel(MelArgs a) {
@@ -123,11 +106,7 @@ __global__ __launch_bounds__(64 * MEL_WAVES) void mel_kernel(MelArgs a) {
         float *mg = mag + f * a.kstride;
         for (int k = lane; k < a.kmax + 3; k += 64) {
             float v = 0.f;
-            if (k < a.kmax) {
-                const RealSplit sp = real_split(x[fft_at(k & (M - 1))], x[fft_at((M - k) & (M - 1))], twn[k]);
-                const float re = sp.e.x + sp.wo.x, im = sp.e.y + sp.wo.y;        // X[k] = E + W^k O
-                v = sqrtf(re * re + im * im + 1e-9f);
-            }
+            if (k < a.kmax) v = mel_magnitude(mel_bin(x[fft_at(k & (M - 1))], x[fft_at((M - k) & (M - 1))], twn[k]));        // X[k] = E + W^k O
             mg[k] = v;
         }
         wave_lds_sync();                  // the next frame overwrites this wave's buffers
@@ -138,15 +117,7 @@ __global__ __launch_bounds__(64 * MEL_WAVES) void mel_kernel(MelArgs a) {
         const int f = idx & (MEL_TF - 1), i = idx / MEL_TF, t = t0 + f;
         const int4 rw = rows[i];
         const float *mg = mag + f * a.kstride + rw.x;
-        const float4 *w4 = reinterpret_cast<const float4 *>(wts + rw.z);
-        float acc = 0.f;
-        for (int c = 0; c < rw.y; ++c) {
-            const float4 w = w4[c];
-            acc = fmaf(w.x, mg[4 * c], acc);
-            acc = fmaf(w.y, mg[4 * c + 1], acc);
-            acc = fmaf(w.z, mg[4 * c + 2], acc);
-            acc = fmaf(w.w, mg[4 * c + 3], acc);
-        }
+        const float acc = mel_project(mg, reinterpret_cast<const float4 *>(wts + rw.z), rw.y);
         // the log in float64, rounded once: the AMDGPU expansion of logf (v_log_f32 times ln 2) is two float32 ulps off at -11.5, where
         // the clipped cells of silence sit
         if (t < a.T) out[(size_t)i * a.T + t] = t < Tb ? (float)log((double)fmaxf(acc, 1e-5f)) : 0.f;
@@ -156,15 +127,6 @@ __global__ __launch_bounds__(64 * MEL_WAVES) void mel_kernel(MelArgs a) {
 }  // namespace gtts
 
 using namespace gtts;
-
-// host-side metadata: the configuration and the float64-computed tables, laid out as the device blob
-struct gtts_mel {
-    gtts_mel_cfg cfg;
-    int logn, pad, kmax, kstride, nw;
-    std::vector<float> fb;                  // [num_mels][n_fft/2 + 1]
-    std::vector<unsigned char> image;       // the packed blob
-    size_t off_win, off_twm, off_twn, off_rows, off_wts, smem;
-};
 
 namespace {
 
@@ -210,7 +172,24 @@ extern "C" int gtts_mel_create(const gtts_mel_cfg *cfg, gtts_mel **out) {
     m->off_twn = m->off_twm + align256((size_t)M * 8);
     m->off_rows = m->off_twn + align256((size_t)nb * 8);
     m->off_wts = m->off_rows + align256(rows.size() * 4);
-    m->image.assign(m->off_wts + align256(wts.size() * 4), 0);
+    // the backward's transposed table: the rows that touch bin k are a contiguous row range, as every row's support is a bin range
+    std::vector<int> cols(4 * (size_t)m->kmax, 0);
+    std::vector<float> wtt;
+    for (int k = 0; k < m->kmax; ++k) {
+        int i0 = c.num_mels, i1 = 0;
+        for (int i = 0; i < c.num_mels; ++i)
+            if (m->fb[(size_t)i * nb + k] != 0.f) { i0 = i < i0 ? i : i0; i1 = i + 1; }
+        if (i1 == 0) i0 = 0;
+        cols[4 * k] = i0; cols[4 * k + 1] = i1 - i0; cols[4 * k + 2] = (int)wtt.size();
+        for (int i = i0; i < i1; ++i) wtt.push_back(m->fb[(size_t)i * nb + k]);
+    }
+    if (wtt.empty()) wtt.push_back(0.f);
+    m->off_cols = m->off_wts + align256(wts.size() * 4);
+    m->off_wtt = m->off_cols + align256(cols.size() * 4);
+    m->image.assign(m->off_wtt + align256(wtt.size() * 4), 0);
+    memcpy(m->image.data() + m->off_cols, cols.data(), cols.size() * 4);
+    memcpy(m->image.data() + m->off_wtt, wtt.data(), wtt.size() * 4);
+    m->smem_bwd = mel_backward_lds(M, m->kstride, c.num_mels, m->nw);
     float *win = reinterpret_cast<float *>(m->image.data() + m->off_win);
     float *twm = reinterpret_cast<float *>(m->image.data() + m->off_twm), *twn = reinterpret_cast<float *>(m->image.data() + m->off_twn);
     const int left = (N - c.win_size) / 2;

@@ -2,7 +2,8 @@
 `mel_spectrogram` with the reference's signature and return value, `MAX_WAV_VALUE` and the dynamic-range helpers.
 
 `mel_spectrogram(y, ...)` on a HIP tensor with center=False is ONE launch of the kernel in csrc/mel.hip (plan and packed tables are
-cached per configuration and device).  On a CPU tensor (DataLoader workers), or with center=True, the same seven steps run as torch ops
+cached per configuration and device).  When y requires grad (the HiFi-GAN mel loss on the generated waveform) the same launch sits in
+an autograd Function whose backward is csrc/mel_train.hip: the values are the same bits, and y gets its gradient.  On a CPU tensor (DataLoader workers), or with center=True, the same seven steps run as torch ops
 written here: reflect pad, frame, periodic Hann window, one-sided DFT, sqrt(re^2 + im^2 + 1e-9), mel projection, log(max(., 1e-5)).
 The filterbank is librosa's default (slaney scale and normalisation), computed by the library in float64 -- librosa is not needed.
 
@@ -74,6 +75,31 @@ def _blob(cfg, device):
     return _blobs[key]
 
 
+class _KernelMel(torch.autograd.Function):
+    """The kernel path under autograd: forward is the gtts_mel_forward launch (the values of the no-grad path bit for bit), backward
+    the two launches of csrc/mel_train.hip, which form the frame spectra again from y -- nothing else is saved."""
+
+    @staticmethod
+    def forward(ctx, y, cfg, lens):
+        ctx.cfg, ctx.lens = cfg, lens
+        ctx.save_for_backward(y)
+        return _plan(cfg).forward(_blob(cfg, y.device), y, lens)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dmel):
+        y, = ctx.saved_tensors
+        return _plan(ctx.cfg).backward(_blob(ctx.cfg, y.device), y, dmel, ctx.lens), None, None
+
+
+def _kernel(y, cfg, lens=None):
+    """The kernel on a HIP tensor; differentiable exactly when y requires grad in grad mode (float32 / contiguous conversion first, so a
+    strided or float64 y gets its gradient through torch's own conversion)."""
+    if torch.is_grad_enabled() and y.requires_grad:
+        return _KernelMel.apply(y.to(torch.float32).contiguous(), cfg, lens)
+    return _plan(cfg).forward(_blob(cfg, y.device), y, lens)
+
+
 def _torch_recipe(y, cfg, center):
     """The seven steps in torch ops, on y's device and in y's floating dtype."""
     n_fft, _, _, hop, win, _, _ = cfg
@@ -110,7 +136,7 @@ def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin,
         if torch.max(y) > 1.:
             print('max value is ', torch.max(y))
     if y_lengths is None:
-        return _plan(cfg).forward(_blob(cfg, y.device), y) if on_hip else _torch_recipe(y, cfg, center)
+        return _kernel(y, cfg) if on_hip else _torch_recipe(y, cfg, center)
 
     p, B, L = (cfg[0] - cfg[3]) // 2, y.shape[0], y.shape[1]
     on_host = not (torch.is_tensor(y_lengths) and y_lengths.is_cuda)
@@ -122,7 +148,7 @@ def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin,
     span = 2 * p - (0 if center else cfg[0])          # center=True frames the row padded by n_fft / 2 more on both sides
     mel_lengths = torch.div(lens + span, cfg[3], rounding_mode='floor') + 1
     if on_hip:
-        mel = _plan(cfg).forward(_blob(cfg, y.device), y, lens.to(device=y.device, dtype=torch.int32))
+        mel = _kernel(y, cfg, lens.to(device=y.device, dtype=torch.int32))
         return mel, mel_lengths.to(y.device)
     mel = y.new_zeros((B, cfg[1], (L + span) // cfg[3] + 1))
     for b, n in enumerate(lens.tolist()):
