@@ -744,6 +744,30 @@ int gtts_conv1d_forward(const gtts_conv1d *op, const void *packed, const float *
  * 2 ConvTranspose1d two 8-byte stores, 3 generic pointer path)}, from the launcher's own selection. */
 int gtts_conv1d_instance(const gtts_conv1d *op, int B, int Lin, int has_res, int accmode, int has_out_mask, int info[5]);
 
+/* ---- ABI 7 (additive): gradients of one Conv1d layer (csrc/conv1d_train.hip) -- what the encoders' Conv1d layers need under autograd.
+ * Mode 0 handles only (a ConvTranspose1d handle is refused with GTTS_E_CONFIG); the handle's dilation is honoured.  For the layer
+ *   y[b,co,q] = (sum_ci sum_t W[co][ci][t] x[b,ci,q+off(t)] im[b,q+off(t)] + bias[co]) om[b,q],   off(t) = (t - (K-1)/2) dilation
+ * Data gradient: gtts_conv1d_forward on dy with a handle op_t created as (0, cout, cin, K, dilation, 1) -- the channels swapped --
+ *   whose packed weight gtts_conv1d_pack_dgrad writes from the FORWARD module's weight [cout][cin][K]: the ordinary packed layout of
+ *   op_t for W'[ci][co][t] = W[co][ci][K-1-t], in one launch; in_mask = the forward's output mask, out_mask = the forward's input mask,
+ *   a zero bias.
+ * Weight / bias gradient (dw [cout][cin][K], db [cout] or NULL: both overwritten, not accumulated; both masks may be NULL):
+ *   dw[co][ci][t] = sum_b sum_q dy[b,co,q] om[b,q] * x[b,ci,q+off(t)] im[b,q+off(t)]      terms with q + off(t) outside [0, L) are zero
+ *   db[co]        = sum_b sum_q dy[b,co,q] om[b,q]                                        (a plain fp32 sum)
+ *   Split-bf16 MFMAs with fp32 accumulation, any cin, cout >= 1.  The sum over (b, q) is cut into slices of whole 64-position chunks
+ *   whose partial tiles go to `workspace` (gtts_conv1d_wgrad_workspace_bytes(op, B, L) bytes; 0 for a refused call); a second launch adds
+ *   the slices in ascending order.  No atomics: two calls give the same bits.
+ * Refused on the host before anything is launched: null pointers GTTS_E_NULL; B or L < 1 and the sample limits of gtts_conv1d_forward
+ * GTTS_E_SHAPE; a short workspace GTTS_E_WORKSPACE.  Nothing is allocated or synchronised. */
+int gtts_conv1d_pack_dgrad(const gtts_conv1d *op_t, const float *weight, void *packed, gtts_stream_t stream);
+size_t gtts_conv1d_wgrad_workspace_bytes(const gtts_conv1d *op, int B, int L);
+int gtts_conv1d_wgrad(const gtts_conv1d *op, const float *x, const float *in_mask, const float *dy, const float *out_mask, float *dw,
+                      float *db, void *workspace, size_t workspace_bytes, int B, int L, gtts_stream_t stream);
+/* host only: the weight gradient's tiling at this shape, from the launcher's own arithmetic -- info = {output tile rows (co), output tile
+ * columns (ci), positions per chunk, slices, chunks per slice, empty slices (slices past the last chunk: they write zeros)}; one
+ * workgroup per (co tile, ci tile, tap, slice); workspace = slices * (cout * cin * K + cout) * 4 bytes. */
+int gtts_conv1d_wgrad_info(const gtts_conv1d *op, int B, int L, int info[6]);
+
 /* ---- ABI 7 (additive): the encoder-decoder gradient path of GradTTS.compute_loss (Grad-TTS/model/tts.py:101-181, train.py) -----------
  * In train.py the prior mean mu_y comes from the encoder, so the decoder's first layer needs a data gradient, the noising needs a
  * backward, and the alignment glue between MAS and the decoder runs under autograd.  All fp32 VALU kernels, no atomics, every sum in a

@@ -190,6 +190,10 @@ def lib():
         L.gtts_conv1d_pack.argtypes = [vp, vp, vp, vp]
         L.gtts_conv1d_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, f, f, vp, vp, i, i, vp]
         L.gtts_conv1d_instance.argtypes = [vp, i, i, i, i, i, ctypes.POINTER(i * 5)]
+        L.gtts_conv1d_pack_dgrad.argtypes = [vp, vp, vp, vp]
+        L.gtts_conv1d_wgrad_workspace_bytes.argtypes, L.gtts_conv1d_wgrad_workspace_bytes.restype = [vp, i, i], sz
+        L.gtts_conv1d_wgrad.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, i, i, vp]
+        L.gtts_conv1d_wgrad_info.argtypes = [vp, i, i, ctypes.POINTER(i * 6)]
         L.gtts_voc_hop.argtypes = [vp]
         L.gtts_voc_forward.argtypes = [vp, vp, vp, vp, vp, sz, i, i, vp]
         L.gtts_plan_num_tensors.argtypes = [vp]
@@ -788,6 +792,73 @@ class Conv1dOp(_Native):
             self._call("pack", self._h, _ptr(w), _ptr(blob), _stream())
             torch.cuda.current_stream().synchronize()
         return blob
+
+    def _pack_source(self, weight, blob, shape):
+        """What the unsynchronised packs take: the weight as it is (contiguous fp32 on a HIP device, no temporary copy that could die
+        before the launch runs) and a blob of packed_bytes() on its device (made here when None)."""
+        if tuple(weight.shape) != shape:
+            raise RuntimeError("weight has shape %s, expected %s" % (tuple(weight.shape), shape))
+        if not weight.is_cuda or weight.dtype != torch.float32 or not weight.is_contiguous():
+            raise RuntimeError("weight must be a contiguous fp32 tensor on a HIP device")
+        if blob is None:
+            blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=weight.device)
+        elif blob.device != weight.device or blob.dtype != torch.uint8 or blob.numel() < self.packed_bytes() or not blob.is_contiguous():
+            raise RuntimeError("blob must hold packed_bytes() = %d bytes on %s" % (self.packed_bytes(), weight.device))
+        return blob
+
+    def pack_into(self, weight, blob=None):
+        """pack() on the current stream WITHOUT a synchronise (the training path): weight [cout, cin, K] as it is, into `blob`."""
+        if self.mode != 0:
+            raise RuntimeError("pack_into serves Conv1d (mode 0) handles")
+        blob = self._pack_source(weight, blob, (self.cout, self.cin, self.K))
+        with _on(weight.device):
+            self._call("pack", self._h, _ptr(weight), _ptr(blob), _stream())
+        return blob
+
+    def pack_dgrad(self, weight, blob=None):
+        """On the TRANSPOSED handle Conv1dOp(0, cout, cin, K, dilation): packs the forward module's weight [cout, cin, K] = [self.cin,
+        self.cout, K] as W'[ci][co][t] = W[co][ci][K-1-t], one launch, no synchronise.  forward() of this handle on dy is then the data
+        gradient (in_mask = the forward's output mask, out_mask = its input mask, a zero bias)."""
+        blob = self._pack_source(weight, blob, (self.cin, self.cout, self.K))
+        with _on(weight.device):
+            self._call("pack_dgrad", self._h, _ptr(weight), _ptr(blob), _stream())
+        return blob
+
+    def wgrad_info(self, B, L):
+        """(tile rows, tile columns, positions per chunk, slices, chunks per slice, empty slices) of wgrad() at this shape: a host call."""
+        info = (ctypes.c_int * 6)()
+        self._call("wgrad_info", self._h, int(B), int(L), ctypes.byref(info))
+        return tuple(info)
+
+    def wgrad_workspace_bytes(self, B, L):
+        n = int(self._fn("wgrad_workspace_bytes")(self._h, int(B), int(L)))
+        if n == 0:
+            raise RuntimeError("gtts_conv1d_wgrad_workspace_bytes refused: %s" % lib().gtts_last_error().decode())
+        return n
+
+    def wgrad(self, x, dy, in_mask=None, out_mask=None, want_bias=True, dw=None, db=None, workspace=None):
+        """(dw [cout, cin, K], db [cout] or None) of the layer y = (conv(x * in_mask) + bias) * out_mask for x [B, cin, L], dy [B, cout, L],
+        masks [B, L] or None.  Contiguous fp32 tensors on x's HIP device, passed as they are; dw / db / workspace are made when None."""
+        if not x.is_cuda:
+            raise RuntimeError("x must live on a HIP device (got %s); there is no CPU fallback" % x.device)
+        B, cin, L = x.shape
+        if cin != self.cin:
+            raise RuntimeError("expected %d input channels, got %d" % (self.cin, cin))
+        if dw is None:
+            dw = torch.empty((self.cout, self.cin, self.K), dtype=torch.float32, device=x.device)
+        if db is None and want_bias:
+            db = torch.empty((self.cout,), dtype=torch.float32, device=x.device)
+        _enc_op_tensors({"x": x, "dy": dy, "in_mask": in_mask, "out_mask": out_mask, "dw": dw, "db": db},
+                        {"x": (B, cin, L), "dy": (B, self.cout, L), "in_mask": (B, L), "out_mask": (B, L), "dw": (self.cout, self.cin, self.K),
+                         "db": (self.cout,)}, x.device)
+        if workspace is None:
+            workspace = torch.empty(self.wgrad_workspace_bytes(B, L), dtype=torch.uint8, device=x.device)
+        elif workspace.device != x.device or not workspace.is_contiguous():
+            raise RuntimeError("workspace must be a contiguous tensor on %s" % x.device)
+        with _on(x.device):
+            self._call("wgrad", self._h, _ptr(x), _ptr(in_mask), _ptr(dy), _ptr(out_mask), _ptr(dw), _ptr(db), _ptr(workspace),
+                       workspace.numel() * workspace.element_size(), B, L, _stream())
+        return dw, db
 
     def forward(self, blob, bias, x, out=None, res=None, accsrc=None, accmode=0, div=1.0, slope=1.0, in_mask=None, out_mask=None):
         """x [B, cin, Lin] -> [B, cout, Lin * S] (written into `out` when given).  Every tensor must be contiguous fp32 on x's HIP

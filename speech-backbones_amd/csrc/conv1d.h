@@ -425,6 +425,9 @@ static inline hipError_t launch_c1(const C1Args &a, const C1Inst &r, hipStream_t
 //   mode 0: Conv1d weight [cout][cin][K]            rows m = co,        padded tap t < K: weight[co][ci][t]
 //   mode 1: ConvTranspose1d weight [cin][cout][Kt]  rows m = co*S + r,  tap t -> input offset d = t - 1:
 //           a = r + pad; j = a / S - d; k = a % S + S * j; weight[ci][co][k] if 0 <= j < Kt / S else 0
+//   mode 2: the data gradient's weight of a Conv1d (conv1d_train.hip): `w` is the FORWARD module's [cin][cout][K] as seen from the
+//           transposed layer being packed (its cin = the module's cout), rows m = the module's input channel, taps reversed:
+//           weight[ci][row][K - 1 - t]
 static __global__ void pack_conv1d_kernel(const float *__restrict__ w, __bf16 *__restrict__ dst, int mode, int cin, int cout, int K,
                                    int S, int pad, int MT, int nst, int tps, int nchunk, int ncot, size_t total) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -444,6 +447,8 @@ static __global__ void pack_conv1d_kernel(const float *__restrict__ w, __bf16 *_
     if (ci < cin && row < cout * S) {
         if (mode == 0) {
             if (tap < K) v = w[((size_t)row * cin + ci) * K + tap];
+        } else if (mode == 2) {
+            if (tap < K) v = w[((size_t)ci * cout + row) * K + (K - 1 - tap)];
         } else {
             const int co = row / S, r = row % S;
             const int d = tap - 1;
@@ -465,7 +470,7 @@ static __global__ void pack_conv1d_kernel(const float *__restrict__ w, __bf16 *_
 // pack one layer's weights (device pointers) into its blob slot
 static inline hipError_t launch_pack_conv1d(const float *w, unsigned char *dst, int mode, int cin, int cout, int K, int S, int pad,
                                             hipStream_t st) {
-    const int real = mode == 0 ? K : 3;
+    const int real = mode == 1 ? 3 : K;
     const C1Geom g = c1_geom(cout * S, real);
     const int nst = (real + g.tps - 1) / g.tps;
     const int nchunk = (cin + 15) / 16, ncot = (cout * S + g.MT - 1) / g.MT;

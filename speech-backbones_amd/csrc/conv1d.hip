@@ -5,22 +5,10 @@
 #include "../../include/gradtts_abi.h"
 #include "common.h"
 #include "conv1d.h"
+#include "conv1d_op.h"
 #include "kernels.h"
 
 using namespace gtts;
-
-struct gtts_conv1d {
-    int mode, cin, cout, K, dil, S;
-};
-
-// geometry, size checks and instance of one call; pointers are carried, never read
-static int conv1d_op_plan(const gtts_conv1d *op, C1Args &a, C1Inst *inst) {
-    a.cin = op->cin; a.cout = op->cout; a.S = op->S;
-    const int r = conv1d_plan(a, op->mode, op->K, op->dil, inst);
-    if (r == C1_OK) return GTTS_OK;
-    return fail(r == C1_E_SIZE ? GTTS_E_SHAPE : GTTS_E_CONFIG, "conv1d (cin %d, cout %d, k %d, dilation %d, stride %d, Lin %d): %s", op->cin,
-                op->cout, op->K, op->dil, op->S, a.Lin, c1_refusal_text(r));
-}
 
 extern "C" int gtts_conv1d_create(int mode, int cin, int cout, int K, int dilation, int S, gtts_conv1d **out) {
     if (!out) return fail(GTTS_E_NULL, "gtts_conv1d_create: null argument");

@@ -6,6 +6,7 @@ glow-tts code); inference on HIP tensors runs the kernels of csrc/enc.hip (gtts_
 """
 import torch
 
+from ...model import _train_ops as _T
 from ...model.text_encoder import ConvReluNorm, Encoder, _warn_too_long
 from .base import BaseModule
 
@@ -44,7 +45,7 @@ class MelEncoder(BaseModule):
                 return self._hip_enc.forward(self._hip_blob, x, x_mask)
             # beyond the attention kernels' length limit (gtts_enc_attention_path): the torch composition below, said once
             _warn_too_long("MelEncoder", x.shape[-1])
-        x = self.init_proj(x * x_mask)
+        x = _T.enc_conv1d(self.init_proj, x, in_mask=x_mask)
         x = self.prenet(x, x_mask)
         x = self.encoder(x, x_mask)
-        return self.term_proj(x * x_mask)
+        return _T.enc_conv1d(self.term_proj, x, in_mask=x_mask)

@@ -20,7 +20,11 @@ csrc/train*.hip behind torch.autograd.Function wrappers:
                        gradient then) is gtts_conv_dgrad_small, taken by MaskedConv3x3 / MaskedConv1x1 for 2 or 3 input planes
   EncAttentionCore     the transformer encoder's windowed relative-position attention between its convolutions, and EncLayerNorm, its
                        LayerNorm with the fused residual (text_encoder.py, shared by TextEncoder and DiffVC's MelEncoder), on
-                       csrc/enc_train.hip; the encoder's Conv1d layers and embedding stay torch autograd
+                       csrc/enc_train.hip
+  EncConv1d            the encoders' Conv1d layers (prenet, attention projections, FFN, proj_m, duration predictor, MelEncoder's
+                       init_proj / term_proj) with their masks: data gradient on the inference kernel of csrc/conv1d.h, weight / bias
+                       gradient on csrc/conv1d_train.hip, forward on that kernel too or (as wired: ENC_CONV_KERNEL_FORWARD) torch's
+                       fp32 conv1d; ReLU, dropout, residual adds and the embedding stay torch autograd
 The [B, dim] time / speaker MLPs stay stock torch ops.  On CPU tensors (tests) everything is stock torch.
 """
 import math
@@ -517,6 +521,147 @@ class EncLayerNorm(torch.autograd.Function):
         da, dbres, dgamma, dbeta = backend().enc_layernorm_backward(dout.contiguous(), a, gamma.detach(), beta.detach(), bres=bres,
                                                                     eps=ctx.eps)
         return da, dgamma, dbeta, dbres, None
+
+
+# And for the encoders' Conv1d layers (enc_conv1d below: prenet, attention projections, FFN, proj_m, duration predictor, MelEncoder's
+# init_proj / term_proj): one count per convolution called with autograd on -- `hip` when EncConv1d ran, `fallback` when the module call did.
+_ENC_CONV_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
+
+
+def reset_enc_conv_op_counts():
+    _ENC_CONV_COUNTS["hip_ops"] = 0
+    _ENC_CONV_COUNTS["torch_fallback_ops"] = 0
+
+
+def enc_conv_op_counts():
+    return _ENC_CONV_COUNTS["hip_ops"], _ENC_CONV_COUNTS["torch_fallback_ops"]
+
+
+def enc_conv_count(hip):
+    if not FORCE_TORCH:
+        _ENC_CONV_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
+
+
+_ENC_CONV_HANDLES = {}     # (cin, cout, K, dilation) -> (forward handle, transposed handle), or None where the kernel refuses the geometry
+
+
+def _enc_conv_handles(cin, cout, K, dilation):
+    """Host metadata only, made once per geometry: the layer's handle and the channel-swapped one its data gradient runs on."""
+    key = (int(cin), int(cout), int(K), int(dilation))
+    if key not in _ENC_CONV_HANDLES:
+        be = backend()
+        try:
+            _ENC_CONV_HANDLES[key] = (be.Conv1dOp(0, cin, cout, K, dilation), be.Conv1dOp(0, cout, cin, K, dilation))
+        except RuntimeError:       # more taps or a wider halo than the kernel holds (gtts_conv1d_create): the module call serves it
+            _ENC_CONV_HANDLES[key] = None
+    return _ENC_CONV_HANDLES[key]
+
+
+# Which forward enc_conv1d gives EncConv1d.  The encoders' gradients are far more sensitive to the forward's rounding than to the
+# backward's: on the GradTTS fixture of tests/test_gpu_tts_train_path.py a forward error of the split-bf16 grade (1.5e-6 of each
+# convolution's largest output, emulated on the CPU) moves ~100 parameter gradients by 1e-3 ... 1.7e-3 -- and, where it flips the sign of
+# one ReLU input, a whole row of an FFN weight gradient by 0.17 -- against that test's 5e-4, while the same error on every gradient the
+# convolutions return moves none by more than 2.8e-5 (DESIGN section 4.6.5).  So the wiring keeps the module's own fp32 convolution in the
+# forward and takes the kernels for the backward; EncConv1d(..., kernel_forward=True) is the all-kernel form, with the inference bits.
+ENC_CONV_KERNEL_FORWARD = False
+
+
+# Layer geometries (cin, cout, K) whose kernel path measured SLOWER than torch.nn.Conv1d autograd at both training shapes -- B = 16,
+# L = 190 (train.py) and B = 128, L = 128 (train_enc.py); tools/enc_conv_train_prof.py, profiles/enc_conv_train.json, the numbers in
+# DESIGN section 4.6.5 -- are left on the module call by enc_conv1d and counted as fallbacks.  Of the reference's nine layer kinds only
+# DurationPredictor.conv_2 (256 -> 256, k = 3: faster at the train.py shape) is not among them; the kernels are a first version and are
+# not tuned in this change.  Geometries nobody measured (other widths) take the kernels.
+ENC_CONV_LEFT_ON_TORCH = frozenset({(192, 192, 5), (192, 192, 1), (192, 768, 3), (768, 192, 3), (192, 80, 1), (80, 192, 1), (192, 256, 3),
+                                    (256, 1, 1)})
+
+
+class EncConv1d(torch.autograd.Function):
+    """y = (Conv1d(x * in_mask) + bias) * out_mask for a stride-1 'same'-padded Conv1d (masks [B, L] or None).  Backward: the data
+    gradient on the inference kernel (csrc/conv1d.h) with the weight packed transposed and tap-reversed, the weight / bias gradient on
+    csrc/conv1d_train.hip.  Forward: with kernel_forward the inference kernel (gtts_conv1d_forward: the bits of that layer in
+    gtts_enc_forward), else torch's conv1d on x * in_mask -- the bits of the module call.  The packed copies are made here, on the
+    stream, and live for this forward + backward; nothing synchronises and no random number is drawn."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, in_mask, out_mask, dilation=1, kernel_forward=True):
+        be = backend()
+        cout, cin, K = weight.shape
+        ctx.save_for_backward(x, weight, in_mask, out_mask)
+        ctx.dilation, ctx.has_bias = dilation, bias is not None
+        if not kernel_forward:
+            y = F.conv1d(x if in_mask is None else x * in_mask.unsqueeze(1), weight, bias, padding=dilation * (K - 1) // 2, dilation=dilation)
+            return y if out_mask is None else y * out_mask.unsqueeze(1)
+        fwd, _ = _enc_conv_handles(cin, cout, K, dilation)
+        b = be._const(x.device, "zeros", cout) if bias is None else bias.detach().contiguous()
+        return fwd.forward(fwd.pack_into(weight.detach().contiguous()), b, x, in_mask=in_mask, out_mask=out_mask)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        be = backend()
+        x, weight, in_mask, out_mask = ctx.saved_tensors
+        cout, cin, K = weight.shape
+        fwd, tr = _enc_conv_handles(cin, cout, K, ctx.dilation)
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:       # (false for MelEncoder.init_proj on a mel, the duration predictor's detached input)
+            blob = tr.pack_dgrad(weight.detach().contiguous())
+            dx = tr.forward(blob, be._const(x.device, "zeros", cin), dy, in_mask=out_mask, out_mask=in_mask)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_db:      # (one kernel produces both)
+            dw, db = fwd.wgrad(x, dy, in_mask, out_mask, want_bias=want_db)
+        return dx, (dw if ctx.needs_input_grad[1] else None), db, None, None, None, None
+
+
+def _enc_conv_mask(m, B, L):
+    """The [B, L] view of a sequence mask the kernels can take ([B, 1, L] or [B, L] fp32 on the device, no gradient), else None."""
+    if not enc_hip(m) or m.requires_grad or m.numel() != B * L or m.shape[0] != B or m.shape[-1] != L:
+        return None
+    return m.reshape(B, L).contiguous()
+
+
+def enc_conv1d(conv, x, in_mask=None, out_mask=None):
+    """conv(x * in_mask) * out_mask for a Conv1d of the encoders (either mask may be None).  With autograd on, fp32 HIP tensors and a
+    stride-1, ungrouped, zero-padded torch.nn.Conv1d with odd K and padding = dilation (K - 1) / 2 it runs EncConv1d, the masks riding in
+    the kernels (forward: ENC_CONV_KERNEL_FORWARD); everything else -- CPU tensors, FORCE_TORCH, no_grad, any other geometry, a layer
+    kind that measured slower than torch (ENC_CONV_LEFT_ON_TORCH) -- is the module call as written."""
+    if torch.is_grad_enabled():
+        args = _enc_conv_args(conv, x, in_mask, out_mask)
+        enc_conv_count(args is not None)
+        if args is not None:
+            return EncConv1d.apply(*args)
+    if in_mask is not None:
+        x = x * in_mask
+    y = conv(x)
+    return y if out_mask is None else y * out_mask
+
+
+def _enc_conv_args(conv, x, in_mask, out_mask):
+    """EncConv1d's arguments when the kernels serve this call, else None."""
+    if not (enc_hip(x) and x.dim() == 3 and type(conv) is torch.nn.Conv1d and enc_hip(conv.weight)):
+        return None
+    K, dil = conv.kernel_size[0], conv.dilation[0]
+    if not (conv.stride == (1,) and conv.groups == 1 and conv.padding_mode == "zeros" and K % 2 == 1 and
+            conv.padding == (dil * (K - 1) // 2,) and x.shape[1] == conv.in_channels and x.shape[0] >= 1 and x.shape[2] >= 1):
+        return None
+    if conv._forward_hooks or conv._forward_pre_hooks or (conv.bias is not None and not enc_hip(conv.bias)):
+        return None
+    B, cin, L = x.shape
+    if (cin, conv.out_channels, K) in ENC_CONV_LEFT_ON_TORCH:
+        return None
+    # (a sample beyond the kernels' 32-bit byte offsets takes the module call up front instead of failing inside backward())
+    if max((cin + 15) // 16 * 16, conv.out_channels) * L * 4 >= 2 ** 31 or _enc_conv_handles(cin, conv.out_channels, K, dil) is None:
+        return None
+    im = om = None
+    if in_mask is not None:
+        im = _enc_conv_mask(in_mask, B, L)
+        if im is None:
+            return None
+    if out_mask is not None:
+        om = _enc_conv_mask(out_mask, B, L)
+        if om is None:
+            return None
+    return x.contiguous(), conv.weight, conv.bias, im, om, dil, ENC_CONV_KERNEL_FORWARD
 
 
 def _block_conv_kind(conv):

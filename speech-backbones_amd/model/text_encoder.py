@@ -3,8 +3,10 @@
 Inference (eval mode, torch.no_grad, HIP tensors) runs the kernels of csrc/enc.hip through gtts_enc_forward (SURVEY.md
 section 8f rank 4).  Training composes the torch modules below over the same parameters, with two exceptions on fp32 HIP tensors
 under autograd: the attention core (MultiHeadAttention.attention) and LayerNorm run the kernels of csrc/enc_train.hip behind
-_train_ops.EncAttentionCore / EncLayerNorm -- no [b, h, t, t] tensor is built or kept; the Conv1d layers and the embedding stay
-torch autograd.  Written from the behaviour of
+_train_ops.EncAttentionCore / EncLayerNorm -- no [b, h, t, t] tensor is built or kept -- and every Conv1d layer goes through
+_train_ops.enc_conv1d (EncConv1d: torch's fp32 conv1d forward, the inference convolution kernel for the data gradient,
+csrc/conv1d_train.hip for the weight gradient, the sequence masks riding in the kernels); ReLU, dropout, residual adds and the embedding stay torch autograd.
+Written from the behaviour of
 the reference modules; parameter names / shapes are identical so `load_state_dict(strict=True)` of reference checkpoints
 works:
 
@@ -74,8 +76,8 @@ class ConvReluNorm(BaseModule):
     def forward(self, x, x_mask):
         y = x
         for conv, norm in zip(self.conv_layers, self.norm_layers):
-            y = self.relu_drop(norm(conv(y * x_mask)))
-        return (x + self.proj(y)) * x_mask
+            y = self.relu_drop(norm(_T.enc_conv1d(conv, y, in_mask=x_mask)))
+        return (x + _T.enc_conv1d(self.proj, y)) * x_mask
 
 
 class DurationPredictor(BaseModule):
@@ -92,9 +94,9 @@ class DurationPredictor(BaseModule):
         self.proj = torch.nn.Conv1d(filter_channels, 1, 1)
 
     def forward(self, x, x_mask):
-        x = self.drop(self.norm_1(torch.relu(self.conv_1(x * x_mask))))
-        x = self.drop(self.norm_2(torch.relu(self.conv_2(x * x_mask))))
-        return self.proj(x * x_mask) * x_mask
+        x = self.drop(self.norm_1(torch.relu(_T.enc_conv1d(self.conv_1, x, in_mask=x_mask))))
+        x = self.drop(self.norm_2(torch.relu(_T.enc_conv1d(self.conv_2, x, in_mask=x_mask))))
+        return _T.enc_conv1d(self.proj, x, in_mask=x_mask, out_mask=x_mask)
 
 
 class MultiHeadAttention(BaseModule):
@@ -206,9 +208,9 @@ class MultiHeadAttention(BaseModule):
     def forward(self, x, c, attn_mask=None, seq_mask=None):
         """seq_mask: the [b, 1, t] sequence mask whose outer product attn_mask is (Encoder passes it); without it a masked call
         runs the torch composition."""
-        y, self.attn = self.attention(self.conv_q(x), self.conv_k(c), self.conv_v(c), mask=attn_mask, seq_mask=seq_mask,
-                                      self_attention=x is c)
-        return self.conv_o(y)
+        y, self.attn = self.attention(_T.enc_conv1d(self.conv_q, x), _T.enc_conv1d(self.conv_k, c), _T.enc_conv1d(self.conv_v, c),
+                                      mask=attn_mask, seq_mask=seq_mask, self_attention=x is c)
+        return _T.enc_conv1d(self.conv_o, y)
 
 
 class FFN(BaseModule):
@@ -223,8 +225,8 @@ class FFN(BaseModule):
         self.drop = torch.nn.Dropout(p_dropout)
 
     def forward(self, x, x_mask):
-        y = self.drop(torch.relu(self.conv_1(x * x_mask)))
-        return self.conv_2(y * x_mask) * x_mask
+        y = self.drop(torch.relu(_T.enc_conv1d(self.conv_1, x, in_mask=x_mask)))
+        return _T.enc_conv1d(self.conv_2, y, in_mask=x_mask, out_mask=x_mask)
 
 
 class Encoder(BaseModule):
@@ -329,6 +331,6 @@ class TextEncoder(BaseModule):
         if self.n_spks > 1:
             h = torch.cat([h, spk.unsqueeze(-1).repeat(1, 1, h.shape[-1])], dim=1)
         h = self.encoder(h, x_mask)
-        mu = self.proj_m(h) * x_mask
+        mu = _T.enc_conv1d(self.proj_m, h, out_mask=x_mask)
         logw = self.proj_w(h.detach(), x_mask)
         return mu, logw, x_mask

@@ -1,0 +1,260 @@
+"""GPU tests (-m gpu) of the drop-in encoder modules under autograd with their Conv1d layers on the kernels (model/_train_ops.py:
+enc_conv1d -> EncConv1d; csrc/conv1d.h data gradient, csrc/conv1d_train.hip weight / bias gradient; the forward as wired is the module's
+own fp32 convolution, ENC_CONV_KERNEL_FORWARD puts the inference kernel there too -- (a) runs both).
+
+Encoder(24, 48, n_heads=2, n_layers=2, kernel_size=3, window_size=4) and a TextEncoder / MelEncoder of that width at B = 3 with ragged
+lengths (17, 9, 1), and one 1-layer Encoder(192, 768) at B = 2, L = 40:
+  (a) without dropout: every parameter gradient and the input gradient against the same module in float64 on the CPU, <= 1e-4 of the
+      tensor's largest element per tensor; enc_conv_op_counts() == (the module tree's Conv1d count, 0); the other counters are not moved
+      by the convolutions
+  (b) FORCE_TORCH leaves the counter at (0, 0) and, in train() with p_dropout = 0.1 under one seed, agrees within the same bound
+  (c) an even kernel, stride 2, groups 2, a padding other than dilation (K - 1) / 2, a CPU tensor and a mask that requires a gradient
+      are counted as fallbacks and are correct
+  (d) no_grad + eval() leaves the counter at (0, 0)
+  (e) one small GradTTS.compute_loss + backward step: every encoder convolution on the kernels, none fell back
+The layer kinds that measured slower than torch are left on the module call as shipped (_train_ops.ENC_CONV_LEFT_ON_TORCH, all of them
+at the reference's widths 192 / 768 / 80); (a) and (e) empty that set where they check the kernels at those widths, and (e) also
+checks the counts as shipped."""
+import copy
+import importlib
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+BOUND = 1e-4
+LENS = (17, 9, 1)
+
+
+@pytest.fixture(scope="module")
+def M():
+    assert torch.cuda.is_available()
+    ns = type("M", (), {})()
+    ns.TE = importlib.import_module("speech-backbones_amd.model.text_encoder")
+    ns.ME = importlib.import_module("speech-backbones_amd.diffvc.model.encoder")
+    ns.TO = importlib.import_module("speech-backbones_amd.model._train_ops")
+    ns.dev = torch.device("cuda:0")
+    return ns
+
+
+def rel(got, ref):
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    n = float(ref.abs().max())
+    if n == 0.0:
+        return 0.0 if bool((got == 0).all()) else float("inf")
+    return float((got - ref).abs().max() / n)
+
+
+def seq_mask(lens, L):
+    return (torch.arange(L).unsqueeze(0) < torch.tensor(lens).unsqueeze(1)).float().unsqueeze(1)
+
+
+def _randomise(mod, seed):
+    """Every parameter non-trivial (the reference zero-initialises prenet.proj, which would hide the prenet's gradients)."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for n, p in mod.named_parameters():
+            if n.endswith("gamma"):
+                p.copy_(1.0 + 0.2 * (torch.rand(p.shape, generator=g) - 0.5))
+            elif n.endswith("beta") or n.endswith("proj.weight") and "prenet" in n:
+                p.copy_(0.2 * (torch.rand(p.shape, generator=g) - 0.5))
+    return mod
+
+
+def _grads(mod, run, inputs):
+    """Outputs and gradients of sum(out * fixed weights): (outs, {name: grad}) -- parameters by name, inputs as 'input<k>'.  The
+    [B, 1, L] sequence mask is no leaf here: a mask that requires a gradient takes the module call (test_geometries_that_must_fall_back)."""
+    mod.zero_grad(set_to_none=True)
+    leaves = [x.clone().requires_grad_(True) if x.is_floating_point() and x.dim() == 3 and x.shape[1] > 1 else x for x in inputs]
+    outs = run(mod, *leaves)
+    outs = outs if isinstance(outs, tuple) else (outs,)
+    loss = 0.0
+    for k, o in enumerate(outs):
+        w = torch.randn(o.shape, generator=torch.Generator().manual_seed(900 + k)).to(o.dtype).to(o.device)
+        loss = loss + (o * w).sum()
+    loss.backward()
+    g = {n: p.grad for n, p in mod.named_parameters() if p.grad is not None}
+    for k, x in enumerate(leaves):
+        if x.is_floating_point() and x.grad is not None:
+            g["input%d" % k] = x.grad
+    return outs, g
+
+
+def _compare(tag, got, ref):
+    (o1, g1), (o2, g2) = got, ref
+    assert set(g1) == set(g2), (tag, sorted(set(g1) ^ set(g2)))
+    rows = [("out%d" % k, rel(a, b)) for k, (a, b) in enumerate(zip(o1, o2))]
+    for n in sorted(g1):
+        if n.endswith("conv_k.bias"):
+            # this gradient vanishes identically (a key bias shifts every score of a row alike): it is the sum of dk over the positions
+            # as conv_q.bias's is the sum of dq, so it is held to 1e-4 of THAT tensor's largest element
+            scale = float(g2[n[:-len("conv_k.bias")] + "conv_q.bias"].detach().double().abs().max())
+            assert float(g2[n].detach().double().abs().max()) <= 1e-5 * scale, (tag, n, "the reference does not vanish")
+            rows.append((n, float((g1[n].detach().double().cpu() - g2[n].detach().double().cpu()).abs().max()) / scale))
+        else:
+            rows.append((n, rel(g1[n], g2[n])))
+    worst = max(rows, key=lambda r: r[1])
+    print("%-28s %d tensors, worst %s %.2e" % (tag, len(rows), worst[0], worst[1]))
+    bad = [r for r in rows if not r[1] <= BOUND]
+    assert not bad, (tag, bad)
+
+
+def _cases(M):
+    """name -> (fp32 module on the CPU, run(module, *inputs), CPU inputs)."""
+    g = torch.Generator().manual_seed(3)
+    L = max(LENS)
+    enc = M.TE.Encoder(24, 48, n_heads=2, n_layers=2, kernel_size=3, window_size=4)
+    text = M.TE.TextEncoder(30, 8, 24, 48, 16, 2, 2, 3, 0.0, window_size=4)
+    mel = M.ME.MelEncoder(8, 24, 48, 2, 2, 3, 0.0, window_size=4)
+    wide = M.TE.Encoder(192, 768, n_heads=2, n_layers=1, kernel_size=3, window_size=4)
+    ids = torch.randint(0, 30, (3, L), generator=g)
+    return {
+        "Encoder": (enc, lambda m, x, mk: m(x, mk), (torch.randn(3, 24, L, generator=g), seq_mask(LENS, L))),
+        "TextEncoder": (text, lambda m, i, n: m(i, n)[:2], (ids, torch.tensor(LENS))),
+        "MelEncoder": (mel, lambda m, x, mk: m(x, mk), (torch.randn(3, 8, L, generator=g), seq_mask(LENS, L))),
+        "Encoder-192-768": (wide, lambda m, x, mk: m(x, mk), (torch.randn(2, 192, 40, generator=g), seq_mask((40, 23), 40))),
+    }
+
+
+def _to(inputs, dev=None, dtype=None):
+    out = []
+    for x in inputs:
+        x = x.to(dev) if dev is not None else x
+        out.append(x.to(dtype) if dtype is not None and x.is_floating_point() else x)
+    return out
+
+
+def n_convs(mod):
+    """Conv1d calls of one forward: every Conv1d of these module trees is called exactly once."""
+    return sum(1 for m in mod.modules() if isinstance(m, torch.nn.Conv1d))
+
+
+@pytest.mark.parametrize("kernel_forward", [False, True], ids=["torch-forward", "kernel-forward"])
+@pytest.mark.parametrize("name", ["Encoder", "TextEncoder", "MelEncoder", "Encoder-192-768"])
+def test_gradients_match_the_module_in_float64(M, name, kernel_forward, monkeypatch):
+    """As wired (the module's fp32 convolution forward, the kernels backward) and with the inference kernel in the forward as well."""
+    monkeypatch.setattr(M.TO, "ENC_CONV_KERNEL_FORWARD", kernel_forward)
+    monkeypatch.setattr(M.TO, "ENC_CONV_LEFT_ON_TORCH", frozenset())       # (the 192 / 768 layer: its kinds are left on torch as shipped)
+    torch.manual_seed(21)
+    mod, run, inputs = _cases(M)[name]
+    _randomise(mod, 5)
+    mod.eval()                                     # (the prenet's dropout is 0.5 whatever p_dropout says; autograd stays on)
+    ref = _grads(copy.deepcopy(mod).double(), run, _to(inputs, dtype=torch.float64))
+    gpu = mod.to(M.dev)
+    expect = {"Encoder": 2 * 6, "TextEncoder": 4 + 2 * 6 + 1 + 3, "MelEncoder": 1 + 4 + 2 * 6 + 1, "Encoder-192-768": 6}[name]
+    assert n_convs(gpu) == expect
+    M.TO.reset_op_counts(), M.TO.reset_enc_op_counts(), M.TO.reset_enc_conv_op_counts()
+    got = _grads(gpu, run, _to(inputs, M.dev))
+    assert M.TO.enc_conv_op_counts() == (expect, 0), M.TO.enc_conv_op_counts()
+    assert M.TO.op_counts() == (0, 0) and M.TO.enc_op_counts()[1] == 0 and M.TO.enc_op_counts()[0] > 0
+    _compare(name + (" kernel forward" if kernel_forward else ""), got, ref)
+
+
+@pytest.mark.parametrize("name", ["Encoder", "MelEncoder"])
+def test_force_torch_counts_nothing_and_agrees_under_one_dropout_seed(M, name):
+    torch.manual_seed(22)
+    L = max(LENS)
+    g = torch.Generator().manual_seed(4)
+    if name == "Encoder":
+        mod = M.TE.Encoder(24, 48, n_heads=2, n_layers=2, kernel_size=3, p_dropout=0.1, window_size=4)
+        inputs = (torch.randn(3, 24, L, generator=g), seq_mask(LENS, L))
+    else:
+        mod = M.ME.MelEncoder(8, 24, 48, 2, 2, 3, 0.1, window_size=4)
+        inputs = (torch.randn(3, 8, L, generator=g), seq_mask(LENS, L))
+    run = lambda m, x, mk: m(x, mk)
+    mod = _randomise(mod, 6).to(M.dev).train()
+    inputs = _to(inputs, M.dev)
+    M.TO.reset_enc_conv_op_counts()
+    torch.manual_seed(1234)
+    got = _grads(mod, run, inputs)
+    got = (got[0], {n: v.clone() for n, v in got[1].items()})
+    assert M.TO.enc_conv_op_counts() == (n_convs(mod), 0)
+    M.TO.reset_enc_conv_op_counts()
+    M.TO.FORCE_TORCH = True
+    try:
+        torch.manual_seed(1234)
+        ref = _grads(mod, run, inputs)
+    finally:
+        M.TO.FORCE_TORCH = False
+    assert M.TO.enc_conv_op_counts() == (0, 0)
+    _compare(name + " dropout", got, ref)
+    # ... and the masks matter: another seed gives another result by far more than the bound
+    torch.manual_seed(99)
+    other = _grads(mod, run, inputs)
+    assert rel(other[0][0], got[0][0]) > 100 * BOUND
+
+
+@pytest.mark.parametrize("case", ["even_kernel", "stride_2", "groups_2", "cpu_tensor", "padding_not_same", "mask_requires_grad"])
+def test_geometries_that_must_fall_back(M, case):
+    torch.manual_seed(23)
+    g = torch.Generator().manual_seed(8)
+    kw = {"even_kernel": dict(kernel_size=4, padding=2), "stride_2": dict(kernel_size=3, padding=1, stride=2),
+          "groups_2": dict(kernel_size=3, padding=1, groups=2), "cpu_tensor": dict(kernel_size=3, padding=1),
+          "padding_not_same": dict(kernel_size=3, padding=0), "mask_requires_grad": dict(kernel_size=3, padding=1)}[case]
+    conv = torch.nn.Conv1d(24, 48, **kw)
+    L = max(LENS)
+    x, mk = torch.randn(3, 24, L, generator=g), seq_mask(LENS, L)
+
+    def run(conv, x, mk):
+        conv.zero_grad(set_to_none=True)
+        xs, ms = x.clone().requires_grad_(True), mk.clone().requires_grad_(case == "mask_requires_grad")
+        y = M.TO.enc_conv1d(conv, xs, in_mask=ms)
+        w = torch.randn(y.shape, generator=torch.Generator().manual_seed(7)).to(y.dtype).to(y.device)
+        (y * w).sum().backward()
+        g = {"weight": conv.weight.grad, "bias": conv.bias.grad, "x": xs.grad}
+        if ms.grad is not None:
+            g["mask"] = ms.grad
+        return (y,), g
+    ref = run(copy.deepcopy(conv).double(), x.double(), mk.double())
+    dev = torch.device("cpu") if case == "cpu_tensor" else M.dev
+    conv = conv.to(dev)
+    M.TO.reset_enc_conv_op_counts()
+    got = run(conv, x.to(dev), mk.to(dev))
+    assert M.TO.enc_conv_op_counts() == (0, 1)
+    _compare(case, got, ref)
+    if case == "cpu_tensor":               # the same layer on the device takes the kernels
+        M.TO.reset_enc_conv_op_counts()
+        _compare(case + " on the device", run(conv.to(M.dev), x.to(M.dev), mk.to(M.dev)), ref)
+        assert M.TO.enc_conv_op_counts() == (1, 0)
+
+
+def test_no_grad_eval_counts_nothing(M):
+    torch.manual_seed(24)
+    g = torch.Generator().manual_seed(9)
+    L = max(LENS)
+    mel = _randomise(M.ME.MelEncoder(8, 24, 48, 2, 2, 3, 0.1, window_size=4), 8).to(M.dev).eval()
+    enc = M.TE.Encoder(24, 48, n_heads=2, n_layers=2, kernel_size=3, window_size=4).to(M.dev).eval()
+    x, mk = torch.randn(3, 8, L, generator=g).to(M.dev), seq_mask(LENS, L).to(M.dev)
+    M.TO.reset_enc_conv_op_counts()
+    with torch.no_grad():
+        y = mel(x, mk)                                           # gtts_enc_forward
+        z = enc(torch.randn(3, 24, L, generator=g).to(M.dev), mk)        # the bare Encoder has no inference plan: the module calls
+    assert M.TO.enc_conv_op_counts() == (0, 0)
+    with torch.enable_grad():
+        y2 = mel(x, mk)
+    assert M.TO.enc_conv_op_counts() == (n_convs(mel), 0)
+    assert rel(y2, y) <= BOUND and bool(torch.isfinite(z).all())
+
+
+def test_gradtts_step_has_no_convolution_fallback(M, monkeypatch):
+    """GradTTS.compute_loss + backward (the train.py step of tests/test_gpu_tts_train_path.py, single speaker, out_size = 48) with no
+    layer kind left on torch: all 24 attention projections, 12 FFN convolutions, the prenet's four, proj_m and the duration predictor's
+    three on the kernels.  As shipped, the kinds that measured slower than torch take the module call and are counted as fallbacks."""
+    import test_gpu_tts_train_path as TP
+    cpu0, inp = TP.setup(1)
+    gpu = copy.deepcopy(cpu0).to(M.dev)
+    M.TO.reset_enc_conv_op_counts()
+    TP.step(gpu, inp, M.dev, 48)
+    shipped = M.TO.enc_conv_op_counts()
+    left = sum(1 for m in gpu.encoder.modules() if isinstance(m, torch.nn.Conv1d)
+               and (m.in_channels, m.out_channels, m.kernel_size[0]) in M.TO.ENC_CONV_LEFT_ON_TORCH)
+    assert shipped == (n_convs(gpu.encoder) - left, left) and shipped[0] >= 1, shipped
+    monkeypatch.setattr(M.TO, "ENC_CONV_LEFT_ON_TORCH", frozenset())
+    gpu = copy.deepcopy(cpu0).to(M.dev)
+    M.TO.reset_enc_conv_op_counts()
+    losses = TP.step(gpu, inp, M.dev, 48)
+    assert all(l == l for l in losses)
+    n = n_convs(gpu.encoder)
+    assert n == 4 + 6 * 6 + 1 + 3
+    assert M.TO.enc_conv_op_counts() == (n, 0), M.TO.enc_conv_op_counts()
+    assert all(p.grad is not None and bool(torch.isfinite(p.grad).all()) for p in gpu.encoder.parameters() if p.requires_grad)

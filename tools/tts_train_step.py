@@ -71,7 +71,7 @@ def main():
                                                            int(y_lengths.max())),
            "device": torch.cuda.get_device_name(dev), "reps": args.reps, "warmup": args.warmup}
     counters = {"decoder": ("reset_op_counts", "op_counts"), "encoder": ("reset_enc_op_counts", "enc_op_counts"),
-                "glue": ("reset_glue_op_counts", "glue_op_counts")}
+                "glue": ("reset_glue_op_counts", "glue_op_counts"), "encoder_conv": ("reset_enc_conv_op_counts", "enc_conv_op_counts")}
     for reset, _ in counters.values():
         getattr(TO, reset, lambda: None)()
     random.seed(0)
