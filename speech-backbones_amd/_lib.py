@@ -1913,30 +1913,30 @@ def conv_resample(x, mask_cols, weight, bias, up, dgrad_of_down=False):
     return y
 
 
-def attn_train_forward(qkv):
+def attn_train_forward(qkv, out=None):
     """LinearAttention core (diffusion.py:90-100) on to_qkv's output qkv [B,384,H,W]: (out [B,128,H,W], ctx [B,4,32,32],
-    stat [B,4,32,2] = softmax row maxima and reciprocal sums)."""
+    stat [B,4,32,2] = softmax row maxima and reciprocal sums).  `out`: optional dict of preallocated out / ctx / stat."""
     qkv = _f32c(qkv, "qkv")
     B, C3, H, W = qkv.shape
     if C3 != 384:
         raise ValueError("attn_train_forward: to_qkv output must have 3 x 4 heads x 32 = 384 channels, got %d" % C3)
     N = H * W
-    out = torch.empty((B, 128, H, W), dtype=torch.float32, device=qkv.device)
-    ctx = torch.empty((B, 4, 32, 32), dtype=torch.float32, device=qkv.device)
-    stat = torch.empty((B, 4, 32, 2), dtype=torch.float32, device=qkv.device)
+    res = _out(out, "out", (B, 128, H, W), torch.float32, qkv.device)
+    ctx = _out(out, "ctx", (B, 4, 32, 32), torch.float32, qkv.device)
+    stat = _out(out, "stat", (B, 4, 32, 2), torch.float32, qkv.device)
     with _on(qkv.device):
         scratch = torch.empty(int(lib().gtts_attn_train_scratch_floats(B, N)), dtype=torch.float32, device=qkv.device)
-        _check(lib().gtts_attn_train_forward(_ptr(qkv), _ptr(out), _ptr(ctx), _ptr(stat), _ptr(scratch), B, N, _stream()),
+        _check(lib().gtts_attn_train_forward(_ptr(qkv), _ptr(res), _ptr(ctx), _ptr(stat), _ptr(scratch), B, N, _stream()),
                "gtts_attn_train_forward")
-    return out, ctx, stat
+    return res, ctx, stat
 
 
-def attn_train_backward(qkv, dout, ctx, stat):
-    """d qkv of attn_train_forward given d out."""
+def attn_train_backward(qkv, dout, ctx, stat, out=None):
+    """d qkv of attn_train_forward given d out.  `out`: optional dict with a preallocated dqkv."""
     qkv, dout = _f32c(qkv, "qkv"), _f32c(dout, "dout")
     B, C3, H, W = qkv.shape
     N = H * W
-    dqkv = torch.empty_like(qkv)
+    dqkv = _out(out, "dqkv", tuple(qkv.shape), torch.float32, qkv.device)
     dctx = torch.empty((B, 4, 32, 32), dtype=torch.float32, device=qkv.device)
     rdot = torch.empty((B, 4, 32), dtype=torch.float32, device=qkv.device)
     with _on(qkv.device):
@@ -1946,20 +1946,21 @@ def attn_train_backward(qkv, dout, ctx, stat):
     return dqkv
 
 
-def rezero_forward(f, g, x):
-    """f * g + x (Rezero + Residual, diffusion.py:40-46,103-108); g a 1-element device tensor."""
+def rezero_forward(f, g, x, out=None):
+    """f * g + x (Rezero + Residual, diffusion.py:40-46,103-108); g a 1-element device tensor.  `out`: optional dict with a
+    preallocated y."""
     f, x, g = _f32c(f, "f"), _f32c(x, "x"), _f32c(g, "g")
-    y = torch.empty_like(f)
+    y = _out(out, "y", tuple(f.shape), torch.float32, f.device)
     with _on(f.device):
         _check(lib().gtts_rezero_forward(_ptr(f), _ptr(x), _ptr(g), _ptr(y), f.numel(), _stream()), "gtts_rezero_forward")
     return y
 
 
-def rezero_backward(dy, f, g):
-    """(d f = dy * g, d g = sum(dy * f)) of rezero_forward."""
+def rezero_backward(dy, f, g, out=None):
+    """(d f = dy * g, d g = sum(dy * f)) of rezero_forward.  `out`: optional dict of preallocated df / dg."""
     dy, f, g = _f32c(dy, "dy"), _f32c(f, "f"), _f32c(g, "g")
-    df = torch.empty_like(f)
-    dg = torch.empty_like(g)
+    df = _out(out, "df", tuple(f.shape), torch.float32, f.device)
+    dg = _out(out, "dg", tuple(g.shape), torch.float32, f.device)
     with _on(f.device):
         scratch = torch.empty(int(lib().gtts_rezero_scratch_bytes(f.numel())), dtype=torch.uint8, device=f.device)
         _check(lib().gtts_rezero_backward(_ptr(dy), _ptr(f), _ptr(g), _ptr(df), _ptr(dg), _ptr(scratch), f.numel(), _stream()),
@@ -1967,27 +1968,28 @@ def rezero_backward(dy, f, g):
     return df, dg
 
 
-def gn_mish_forward(y, gamma, beta, mask_cols, groups, eps, tb=None):
+def gn_mish_forward(y, gamma, beta, mask_cols, groups, eps, tb=None, out=None):
     """(Mish(GroupNorm(y)) * mask [+ tb[:, :, None, None]], stats: (mean, rstd) pairs followed by reduction scratch) -- Block.forward
-    after the convolution (diffusion.py:53-58) and, with tb [B,C], ResnetBlock's time term (diffusion.py:75-76)."""
+    after the convolution (diffusion.py:53-58) and, with tb [B,C], ResnetBlock's time term (diffusion.py:75-76).  `out`: optional dict of
+    preallocated out / stats."""
     y, gamma, beta, mask_cols, tb = _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta"), _f32c(mask_cols, "mask"), _f32c(tb, "tb")
     B, C, H, W = y.shape
-    out = torch.empty_like(y)
-    stats = torch.empty(int(lib().gtts_gn_mish_stats_floats(B, int(groups))), dtype=torch.float32, device=y.device)
+    res = _out(out, "out", (B, C, H, W), torch.float32, y.device)
+    stats = _out(out, "stats", (int(lib().gtts_gn_mish_stats_floats(B, int(groups))),), torch.float32, y.device)
     with _on(y.device):
-        _check(lib().gtts_gn_mish_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(mask_cols), _ptr(tb), _ptr(out), _ptr(stats), B, C,
+        _check(lib().gtts_gn_mish_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(mask_cols), _ptr(tb), _ptr(res), _ptr(stats), B, C,
                                           H, W, int(groups), float(eps), _stream()), "gtts_gn_mish_forward")
-    return out, stats
+    return res, stats
 
 
-def gn_mish_backward(dout, y, gamma, beta, mask_cols, stats, groups, want_dtb=False):
-    """(dy, dgamma, dbeta[, dtb [B,C]]) of gn_mish_forward."""
+def gn_mish_backward(dout, y, gamma, beta, mask_cols, stats, groups, want_dtb=False, out=None):
+    """(dy, dgamma, dbeta[, dtb [B,C]]) of gn_mish_forward.  `out`: optional dict of preallocated dy / dgamma / dbeta / dtb."""
     dout, y = _f32c(dout, "dout"), _f32c(y, "y")
     B, C, H, W = y.shape
-    dy = torch.empty_like(y)
-    dg = torch.empty((C,), dtype=torch.float32, device=y.device)
-    db = torch.empty((C,), dtype=torch.float32, device=y.device)
-    dtb = torch.empty((B, C), dtype=torch.float32, device=y.device) if want_dtb else None
+    dy = _out(out, "dy", (B, C, H, W), torch.float32, y.device)
+    dg = _out(out, "dgamma", (C,), torch.float32, y.device)
+    db = _out(out, "dbeta", (C,), torch.float32, y.device)
+    dtb = _out(out, "dtb", (B, C), torch.float32, y.device) if want_dtb else None
     scratch = torch.empty(int(lib().gtts_gn_mish_scratch_bytes(B, C)), dtype=torch.uint8, device=y.device)
     with _on(y.device):
         _check(lib().gtts_gn_mish_backward(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")),
@@ -1996,27 +1998,28 @@ def gn_mish_backward(dout, y, gamma, beta, mask_cols, stats, groups, want_dtb=Fa
     return (dy, dg, db, dtb) if want_dtb else (dy, dg, db)
 
 
-def in_glu_forward(y, gamma, beta, eps=1e-5):
-    """(IN(y[:, :C]) * sigmoid(IN(y[:, C:])), stats) -- InstanceNorm2d(affine) + GLU(dim=1) of DiffVC's RefBlock (modules.py:128-157)."""
+def in_glu_forward(y, gamma, beta, eps=1e-5, out=None):
+    """(IN(y[:, :C]) * sigmoid(IN(y[:, C:])), stats) -- InstanceNorm2d(affine) + GLU(dim=1) of DiffVC's RefBlock (modules.py:128-157).
+    `out`: optional dict of preallocated out / stats."""
     y, gamma, beta = _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
     B, C2, H, W = y.shape
     C = C2 // 2
-    out = torch.empty((B, C, H, W), dtype=torch.float32, device=y.device)
-    stats = torch.empty(int(lib().gtts_in_glu_stats_floats(B, C)), dtype=torch.float32, device=y.device)
+    res = _out(out, "out", (B, C, H, W), torch.float32, y.device)
+    stats = _out(out, "stats", (int(lib().gtts_in_glu_stats_floats(B, C)),), torch.float32, y.device)
     with _on(y.device):
-        _check(lib().gtts_in_glu_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(out), _ptr(stats), B, C, H, W, float(eps), _stream()),
+        _check(lib().gtts_in_glu_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(res), _ptr(stats), B, C, H, W, float(eps), _stream()),
                "gtts_in_glu_forward")
-    return out, stats
+    return res, stats
 
 
-def in_glu_backward(dout, y, gamma, beta, stats):
-    """(dy, dgamma, dbeta) of in_glu_forward."""
+def in_glu_backward(dout, y, gamma, beta, stats, out=None):
+    """(dy, dgamma, dbeta) of in_glu_forward.  `out`: optional dict of preallocated dy / dgamma / dbeta."""
     dout, y = _f32c(dout, "dout"), _f32c(y, "y")
     B, C2, H, W = y.shape
     C = C2 // 2
-    dy = torch.empty_like(y)
-    dg = torch.empty((C2,), dtype=torch.float32, device=y.device)
-    db = torch.empty((C2,), dtype=torch.float32, device=y.device)
+    dy = _out(out, "dy", (B, C2, H, W), torch.float32, y.device)
+    dg = _out(out, "dgamma", (C2,), torch.float32, y.device)
+    db = _out(out, "dbeta", (C2,), torch.float32, y.device)
     scratch = torch.empty(int(lib().gtts_in_glu_scratch_floats(B, C)), dtype=torch.float32, device=y.device)
     with _on(y.device):
         _check(lib().gtts_in_glu_backward(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")), _ptr(stats),
@@ -2024,29 +2027,30 @@ def in_glu_backward(dout, y, gamma, beta, stats):
     return dy, dg, db
 
 
-def diffusion_noising(x0, mu, z, mask, t, beta_min, beta_max):
-    """Diffusion.forward_diffusion given the N(0,1) draw z: (xt, z * mask)   (diffusion.py:244-252)."""
+def diffusion_noising(x0, mu, z, mask, t, beta_min, beta_max, out=None):
+    """Diffusion.forward_diffusion given the N(0,1) draw z: (xt, z * mask)   (diffusion.py:244-252).  `out`: optional dict of
+    preallocated xt / zm."""
     x0, mu, z, mask, t = (_f32c(v, n) for v, n in ((x0, "x0"), (mu, "mu"), (z, "z"), (mask, "mask"), (t, "t")))
     B, F, T = x0.shape
-    xt, zm = torch.empty_like(x0), torch.empty_like(x0)
+    xt, zm = _out(out, "xt", (B, F, T), torch.float32, x0.device), _out(out, "zm", (B, F, T), torch.float32, x0.device)
     with _on(x0.device):
         _check(lib().gtts_diffusion_noising(_ptr(x0), _ptr(mu), _ptr(z), _ptr(mask), _ptr(t), float(beta_min), float(beta_max),
                                             _ptr(xt), _ptr(zm), B, F, T, _stream()), "gtts_diffusion_noising")
     return xt, zm
 
 
-def score_loss(eps, z_masked, t, beta_min, beta_max, inv_denom, want_grad=True):
+def score_loss(eps, z_masked, t, beta_min, beta_max, inv_denom, want_grad=True, out=None):
     """Diffusion.loss_t's reduction: (sum((eps s + z)^2) * inv_denom as a 0-d tensor, d loss / d eps or None).
     inv_denom: a Python float, or a 0-d device tensor (then nothing here synchronises with the host: the kernel runs with a
-    unit normaliser and loss and gradient are scaled by tensor ops)."""
+    unit normaliser and loss and gradient are scaled by tensor ops).  `out`: optional dict of preallocated partials / grad."""
     if torch.is_tensor(inv_denom):
-        loss, g = score_loss(eps, z_masked, t, beta_min, beta_max, 1.0, want_grad)
+        loss, g = score_loss(eps, z_masked, t, beta_min, beta_max, 1.0, want_grad, out)
         return loss * inv_denom, (g * inv_denom if g is not None else None)
     eps, z_masked, t = _f32c(eps, "eps"), _f32c(z_masked, "z"), _f32c(t, "t")
     B, F, T = eps.shape
     n = int(lib().gtts_score_loss_partials(B, F, T))
-    part = torch.empty(n, dtype=torch.float32, device=eps.device)
-    g = torch.empty_like(eps) if want_grad else None
+    part = _out(out, "partials", (n,), torch.float32, eps.device)
+    g = _out(out, "grad", (B, F, T), torch.float32, eps.device) if want_grad else None
     with _on(eps.device):
         _check(lib().gtts_score_loss(_ptr(eps), _ptr(z_masked), _ptr(t), float(beta_min), float(beta_max), float(inv_denom),
                                      _ptr(part), _ptr(g), B, F, T, _stream()), "gtts_score_loss")

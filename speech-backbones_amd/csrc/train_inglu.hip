@@ -8,9 +8,10 @@
 // padded batch.  One workgroup owns one (sample, channel pair): it reads the two planes (value half a = channel c, gate half
 // g = channel C + c) twice -- statistics, then apply; the second read is an L2 hit at RefBlock's plane sizes (80 x T_ref) -- and
 // nothing but y, d out and the four statistics travels between forward and backward: the normalised values, the sigmoid and the
-// products are recomputed (three transcendentals per output element against 12 B of traffic).  Reductions: per-thread fp32
-// partial sums over strided elements, combined across the workgroup in fp64 in a fixed order (deterministic); the parameter
-// gradients are reduced over the batch by a second, tiny kernel in sample order.
+// products are recomputed (three transcendentals per output element against 12 B of traffic).  Reductions: per-thread partial
+// sums over strided elements -- fp64 for the statistics, whose var = E[x^2] - mean^2 cancels on a plane with a large mean
+// (train_norm.hip), fp32 for the gradient sums -- combined across the workgroup in fp64 in a fixed order (deterministic); the
+// parameter gradients are reduced over the batch by a second, tiny kernel in sample order.
 #include <hip/hip_runtime.h>
 
 #include "../../include/gradtts_abi.h"
@@ -46,13 +47,12 @@ __global__ __launch_bounds__(256) void in_glu_fwd_kernel(const float *__restrict
     __shared__ double s_red[4 * 256];
     const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const float *ya = y + ((size_t)b * 2 * C + c) * HW, *yg = y + ((size_t)b * 2 * C + C + c) * HW;
-    float s1a = 0.f, s2a = 0.f, s1g = 0.f, s2g = 0.f;
+    double r[4] = {0.0, 0.0, 0.0, 0.0};
     for (int i = tid; i < HW; i += 256) {
-        const float va = ya[i], vg = yg[i];
-        s1a += va; s2a = fmaf(va, va, s2a);
-        s1g += vg; s2g = fmaf(vg, vg, s2g);
+        const double va = (double)ya[i], vg = (double)yg[i];
+        r[0] += va; r[1] = fma(va, va, r[1]);
+        r[2] += vg; r[3] = fma(vg, vg, r[3]);
     }
-    double r[4] = {(double)s1a, (double)s2a, (double)s1g, (double)s2g};
     block_sum4(r, s_red);
     const double inv = 1.0 / (double)HW;
     const double ma = r[0] * inv, mg = r[2] * inv;
