@@ -423,6 +423,15 @@ size_t gtts_conv_resample_packed_bytes(int cin, int cout, int up);
 int gtts_conv_resample_pack(const float *w, void *packed, int cin, int cout, int up, gtts_stream_t stream);
 int gtts_conv_resample(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B, int cin, int cout,
                        int H, int W, int up, gtts_stream_t stream);
+/* Which kernel instance a forward / data-gradient convolution of the training path runs (additive): the name a demangler prints
+ * ("gtts::conv_mfma_kernel<0, 1, 4, 2, 1, 1, 0, 2, 1, float, 2, 0>"), taken from the dispatch that launches it -- the entry point's
+ * shape checks, its launch arguments without pointers, and the launcher describing instead of launching.  Host only: no device call.
+ * kind 0: gtts_conv3x3_masked, 1: gtts_conv1x1_masked, 2: gtts_conv7x7_masked, 3: gtts_conv_resample (`up` is read for kind 3 only).
+ * B, cin, cout, H, W: those of the call asked about (a data gradient is the call with the forward's cin and cout swapped; Downsample's
+ * is an up = 1 call on the halved plane).  c0 in (0, cin): two sources (kind 0 only); 0 or cin: one.  buf [n] receives the name.
+ *   GTTS_E_NULL: buf NULL or n = 0; GTTS_E_CONFIG: unknown kind, two sources for a kind other than 0, no instance takes the call;
+ *   GTTS_E_SHAPE: what the entry point refuses; GTTS_E_WORKSPACE: n too small. */
+int gtts_conv_train_kernel_name(int kind, int B, int cin, int c0, int cout, int H, int W, int up, char *buf, size_t n);
 /* ABI 4: every weight pack of a training step in ONE launch.  item.kind: 0 Block 3x3 (gtts_conv3x3_pack), 1 1x1 (gtts_conv1x1_pack),
  * 2 Downsample, 3 Upsample (gtts_conv_resample_pack), 4 Downsample's data gradient (its forward weight [cout][cin][3][3] packed as the
  * zero-padded 4x4 transposed convolution; cin / cout those of the GRADIENT convolution); transposed as in the single-pack calls

@@ -141,6 +141,7 @@ def lib():
         L.gtts_conv_resample_packed_bytes.restype = sz
         L.gtts_conv_resample_pack.argtypes = [vp, vp, i, i, i, vp]
         L.gtts_conv_resample.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
+        L.gtts_conv_train_kernel_name.argtypes = [i, i, i, i, i, i, i, i, ctypes.c_char_p, sz]
         L.gtts_add_masked.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp]
         L.gtts_conv_wgrad_small_scratch_floats.argtypes = [i, i, i, i]
         L.gtts_conv_wgrad_small_scratch_floats.restype = sz
@@ -1652,12 +1653,33 @@ _CONV_KINDS = {kind: (ksize, two, om, "gtts_conv%s_masked" % kind, "gtts_conv%s_
                for kind, ksize, two, om in (("3x3", 3, True, True), ("7x7", 7, False, True), ("1x1", 1, False, False))}
 
 
-def _conv_run(kind, x, mask_cols, weight, bias, transposed, x1=None, out_mask=None):
+_TRAIN_NAME_KINDS = {"3x3": (0, 0), "1x1": (1, 0), "7x7": (2, 0), "dn": (3, 0), "up": (3, 1)}
+
+
+def conv_train_kernel_name(kind, B, cin, cout, H, W, c0=0):
+    """The kernel instance a forward / data-gradient convolution of the training path runs at this shape, as a demangler prints it
+    (gtts_conv_train_kernel_name: the launching dispatch describing itself; works without a GPU).  kind: "3x3", "1x1", "7x7", "dn"
+    (Downsample) or "up" (Upsample; Downsample's data gradient is an "up" call on the halved plane); B, cin, cout, H, W of the call
+    asked about (a data gradient: the forward's cin and cout swapped); c0 in (0, cin): the 3x3 call reads two sources."""
+    k, up = _TRAIN_NAME_KINDS[kind]
+    buf = ctypes.create_string_buffer(256)
+    _check(lib().gtts_conv_train_kernel_name(k, int(B), int(cin), int(c0), int(cout), int(H), int(W), up, buf, len(buf)),
+           "gtts_conv_train_kernel_name")
+    return buf.value.decode()
+
+
+def _given(t, name, shape, device, dtype=torch.float32):
+    """The caller's preallocated tensor `t` for the result `name` (tests place it between guard margins), or a fresh one: ValueError
+    unless it is contiguous, of that shape and dtype, and on that device."""
+    return _out(None if t is None else {name: t}, name, shape, dtype, device, exc=ValueError)
+
+
+def _conv_run(kind, x, mask_cols, weight, bias, transposed, x1=None, out_mask=None, out=None):
     _, two, om, name, _, _ = _CONV_KINDS[kind]
     B, c0, H, W = x.shape
     cin = c0 + (int(x1.shape[1]) if x1 is not None else 0)
     cout = weight.shape[1] if transposed else weight.shape[0]
-    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    y = _given(out, "out", (B, cout, H, W), x.device)
     src = (_ptr(x), _ptr(x1), c0, _ptr(mask_cols)) if two else (_ptr(x), _ptr(mask_cols))
     with _on(x.device):
         packed = _packed_weight(weight, cin, cout, transposed, kind)
@@ -1666,66 +1688,77 @@ def _conv_run(kind, x, mask_cols, weight, bias, transposed, x1=None, out_mask=No
     return y
 
 
-def _conv_dgrad(kind, dy, weight, mask_cols):
+def _conv_dgrad(kind, dy, weight, mask_cols, out=None):
     dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
     B, cout, H, W = dy.shape
     return _conv_run(kind, dy, _const(dy.device, "ones", B, W), weight, _const(dy.device, "zeros", int(weight.shape[1])), True,
-                     out_mask=_f32c(mask_cols, "mask"))
+                     out_mask=_f32c(mask_cols, "mask"), out=out)
 
 
-def _tiled_wgrad(kind, x, mask_cols, dy, x1=None, want_bias=True):
-    """(dW [cout,cin,k,k], db [cout] or None) by the kind's LDS-tiled deterministic reduction (train_wgrad.hip, train_wgrad7.hip)."""
+def _scratch(out, nbytes, device):
+    """The workspace of a weight-gradient call: `out["workspace"]` (fp32, exactly the bytes the call asks for) or a fresh one."""
+    if out is None or out.get("workspace") is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _out(out, "workspace", (nbytes // 4,), torch.float32, device, exc=ValueError)
+
+
+def _tiled_wgrad(kind, x, mask_cols, dy, x1=None, want_bias=True, out=None):
+    """(dW [cout,cin,k,k], db [cout] or None) by the kind's LDS-tiled deterministic reduction (train_wgrad.hip, train_wgrad7.hip).
+    `out`: optional dict of preallocated dw / db / workspace (fp32, gtts_conv<kind>_wgrad_workspace_bytes / 4 floats)."""
     ksize, two, _, _, name, ws_name = _CONV_KINDS[kind]
     B, c0, H, W = x.shape
     cin = c0 + (int(x1.shape[1]) if x1 is not None else 0)
     cout = int(dy.shape[1])
-    dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=x.device)
-    db = torch.empty((cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    dw = _out(out, "dw", (cout, cin, ksize, ksize), torch.float32, x.device, exc=ValueError)
+    db = _out(out, "db", (cout,), torch.float32, x.device, exc=ValueError) if want_bias else None
     src = (_ptr(x), _ptr(x1), c0) if two else (_ptr(x),)
     with _on(x.device):
         L = lib()
         nws = int(getattr(L, ws_name)(B, cin, cout, H, W))
-        ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+        ws = _scratch(out, nws, x.device)
         _check(getattr(L, name)(*src, _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws, B, cin, cout, H, W, _stream()), name)
     return dw, db
 
 
-def _wgrad_small(x, mask_cols, dy, ksize, want_bias=True):
-    """The first layer's weight gradient (cin 2 or 3: its own kernel)."""
+def _wgrad_small(x, mask_cols, dy, ksize, want_bias=True, out=None):
+    """The first layer's weight gradient (cin 2 or 3: its own kernel).  `out`: optional dict of preallocated dw / db / workspace
+    (gtts_conv_wgrad_small_scratch_floats floats)."""
     B, cin, H, W = x.shape
     cout = int(dy.shape[1])
-    dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=x.device)
-    db = torch.empty((cout,), dtype=torch.float32, device=x.device) if want_bias else None
+    dw = _out(out, "dw", (cout, cin, ksize, ksize), torch.float32, x.device, exc=ValueError)
+    db = _out(out, "db", (cout,), torch.float32, x.device, exc=ValueError) if want_bias else None
     with _on(x.device):
-        scratch = torch.empty(int(lib().gtts_conv_wgrad_small_scratch_floats(B, cin, cout, ksize)), dtype=torch.float32, device=x.device)
+        scratch = _out(out, "workspace", (int(lib().gtts_conv_wgrad_small_scratch_floats(B, cin, cout, ksize)),), torch.float32, x.device,
+                       exc=ValueError)
         _check(lib().gtts_conv_wgrad_small(_ptr(x), _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(scratch), B, cin, cout, H, W, ksize,
                                            _stream()), "gtts_conv_wgrad_small")
     return dw, db
 
 
-def conv3x3_masked(x, mask_cols, weight, bias, x1=None):
+def conv3x3_masked(x, mask_cols, weight, bias, x1=None, out=None):
     """Conv2d_3x3(cat(x, x1) * mask) + bias (Block.forward, diffusion.py:56-57; the concatenation of the up path, :166, is read in
-    place): x [B,c0,H,W], x1 [B,c1,H,W] or None, mask_cols [B,W], weight [cout,c0+c1,3,3]."""
+    place): x [B,c0,H,W], x1 [B,c1,H,W] or None, mask_cols [B,W], weight [cout,c0+c1,3,3].  `out`: optional preallocated result."""
     x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
-    return _conv_run("3x3", x, mask_cols, weight, bias, False, _f32c(x1, "x1"))
+    return _conv_run("3x3", x, mask_cols, weight, bias, False, _f32c(x1, "x1"), out=out)
 
 
-def conv3x3_dgrad(dy, weight, mask_cols=None):
+def conv3x3_dgrad(dy, weight, mask_cols=None, out=None):
     """Gradient of conv3x3_masked w.r.t. (x * mask): a 3x3 convolution of dy with the transposed, flipped weights; with
-    mask_cols [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue)."""
-    return _conv_dgrad("3x3", dy, weight, mask_cols)
+    mask_cols [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue).  `out`: optional preallocated result."""
+    return _conv_dgrad("3x3", dy, weight, mask_cols, out=out)
 
 
-def conv3x3_wgrad(x, mask_cols, dy, x1=None):
-    """(dW [cout,cin,3,3], db [cout]) of conv3x3_masked (x1: second source of a concatenated input, c0 a multiple of 64)."""
+def conv3x3_wgrad(x, mask_cols, dy, x1=None, out=None):
+    """(dW [cout,cin,3,3], db [cout]) of conv3x3_masked (x1: second source of a concatenated input, c0 a multiple of 64).  `out`:
+    optional dict of preallocated dw / db / workspace."""
     x, mask_cols, dy, x1 = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy"), _f32c(x1, "x1")
     cin, cout = int(x.shape[1]) + (int(x1.shape[1]) if x1 is not None else 0), int(dy.shape[1])
     if cin in (2, 3) and x1 is None:
-        return _wgrad_small(x, mask_cols, dy, 3)
+        return _wgrad_small(x, mask_cols, dy, 3, out=out)
     if cin % 64 or cout % 64:
         raise ValueError("conv3x3_wgrad: cin and cout must be multiples of 64, or cin 2 or 3 from one source (got cin %d, cout %d)"
                          % (cin, cout))
-    return _tiled_wgrad("3x3", x, mask_cols, dy, x1)
+    return _tiled_wgrad("3x3", x, mask_cols, dy, x1, out=out)
 
 
 def conv7x7_supported(cin, cout, need_dgrad=True, shape=None):
@@ -1736,56 +1769,61 @@ def conv7x7_supported(cin, cout, need_dgrad=True, shape=None):
     return int(cin) > 0 and int(cout) > 0 and int(cin) % 64 == 0 and int(cout) % 64 == 0
 
 
-def conv7x7_masked(x, mask_cols, weight, bias):
+def conv7x7_masked(x, mask_cols, weight, bias, out=None):
     """Conv2d_7x7(x * mask, padding 3) + bias (PostNet Block, DiffVC/model/postnet.py:21-23): x [B,cin,H,W], mask_cols [B,W],
-    weight [cout,cin,7,7]."""
+    weight [cout,cin,7,7].  `out`: optional preallocated result."""
     x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
-    return _conv_run("7x7", x, mask_cols, weight, bias, False)
+    return _conv_run("7x7", x, mask_cols, weight, bias, False, out=out)
 
 
-def conv7x7_dgrad(dy, weight, mask_cols=None):
+def conv7x7_dgrad(dy, weight, mask_cols=None, out=None):
     """Gradient of conv7x7_masked w.r.t. (x * mask): a 7x7 convolution of dy with the transposed, flipped weights; with mask_cols
-    [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue)."""
-    return _conv_dgrad("7x7", dy, weight, mask_cols)
+    [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue).  `out`: optional preallocated result."""
+    return _conv_dgrad("7x7", dy, weight, mask_cols, out=out)
 
 
-def conv7x7_wgrad(x, mask_cols, dy):
-    """(dW [cout,cin,7,7], db [cout]) of conv7x7_masked (train_wgrad7.hip: deterministic split-bf16 MFMA reduction)."""
-    return _tiled_wgrad("7x7", _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy"))
+def conv7x7_wgrad(x, mask_cols, dy, out=None):
+    """(dW [cout,cin,7,7], db [cout]) of conv7x7_masked (train_wgrad7.hip: deterministic split-bf16 MFMA reduction).  `out`: optional
+    dict of preallocated dw / db / workspace."""
+    return _tiled_wgrad("7x7", _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy"), out=out)
 
 
-def postnet_expand(x, mask, w, bias=None):
-    """out [B,C,F,T] = w[c] * x[b,f,t] * mask[b,t] + bias[c] (PostNet init_conv; final_conv's data gradient with bias None)."""
+def postnet_expand(x, mask, w, bias=None, out=None):
+    """out [B,C,F,T] = w[c] * x[b,f,t] * mask[b,t] + bias[c] (PostNet init_conv; final_conv's data gradient with bias None).  `out`:
+    optional preallocated result."""
     x, mask, w = _f32c(x, "x"), _f32c(mask, "mask"), _f32c(w, "weight")
     B, F, T = x.shape
     C = int(w.numel())
     bias = _const(x.device, "zeros", C) if bias is None else _f32c(bias, "bias")
-    out = torch.empty((B, C, F, T), dtype=torch.float32, device=x.device)
+    out = _given(out, "out", (B, C, F, T), x.device)
     with _on(x.device):
         _check(lib().gtts_postnet_expand(_ptr(x), _ptr(mask), _ptr(w), _ptr(bias), _ptr(out), B, C, F, T, _stream()), "gtts_postnet_expand")
     return out
 
 
-def postnet_collapse(x, mask, w, bias=None):
-    """out [B,F,T] = sum_c w[c] * x[b,c,f,t] * mask[b,t] + bias (PostNet final_conv; init_conv's data gradient with bias None)."""
+def postnet_collapse(x, mask, w, bias=None, out=None):
+    """out [B,F,T] = sum_c w[c] * x[b,c,f,t] * mask[b,t] + bias (PostNet final_conv; init_conv's data gradient with bias None).  `out`:
+    optional preallocated result."""
     x, mask, w = _f32c(x, "x"), _f32c(mask, "mask"), _f32c(w, "weight")
     B, C, F, T = x.shape
     bias = _const(x.device, "zeros", 1) if bias is None else _f32c(bias, "bias")
-    out = torch.empty((B, F, T), dtype=torch.float32, device=x.device)
+    out = _given(out, "out", (B, F, T), x.device)
     with _on(x.device):
         _check(lib().gtts_postnet_collapse(_ptr(x), _ptr(mask), _ptr(w), _ptr(bias), _ptr(out), B, C, F, T, _stream()), "gtts_postnet_collapse")
     return out
 
 
-def postnet_chan_dot(a, v, mask, want_dot=True, want_sum=True):
+def postnet_chan_dot(a, v, mask, want_dot=True, want_sum=True, out=None):
     """(dot [C], sum [C]) over a [B,C,F,T]: dot[c] = sum a[b,c] * v[b] * mask[b,t] (v [B,F,T], v / mask None: 1), sum[c] = sum a[b,c]
-    (fixed-order reduction; an output not wanted is None)."""
+    (fixed-order reduction; an output not wanted is None).  `out`: optional dict of preallocated dot / sum / workspace
+    (gtts_postnet_chan_dot_scratch_floats floats)."""
     a, v, mask = _f32c(a, "a"), _f32c(v, "v"), _f32c(mask, "mask")
     B, C, F, T = a.shape
-    dot = torch.empty((C,), dtype=torch.float32, device=a.device) if want_dot else None
-    sm = torch.empty((C,), dtype=torch.float32, device=a.device) if want_sum else None
+    dot = _out(out, "dot", (C,), torch.float32, a.device, exc=ValueError) if want_dot else None
+    sm = _out(out, "sum", (C,), torch.float32, a.device, exc=ValueError) if want_sum else None
     with _on(a.device):
-        scratch = torch.empty(int(lib().gtts_postnet_chan_dot_scratch_floats(B, C, F, T)), dtype=torch.float32, device=a.device)
+        scratch = _out(out, "workspace", (int(lib().gtts_postnet_chan_dot_scratch_floats(B, C, F, T)),), torch.float32, a.device,
+                       exc=ValueError)
         _check(lib().gtts_postnet_chan_dot(_ptr(a), _ptr(v), _ptr(mask), _ptr(dot), _ptr(sm), _ptr(scratch), B, C, F, T, _stream()),
                "gtts_postnet_chan_dot")
     return dot, sm
@@ -1801,87 +1839,92 @@ def conv1x1_supported(cin, cout, need_dgrad=True, shape=None):
     return _tiles(cout) and cin % 64 == 0 and (_tiles(cin) or not need_dgrad)
 
 
-def conv1x1_masked(x, mask_cols, weight, bias):
+def conv1x1_masked(x, mask_cols, weight, bias, out=None):
     """Conv2d_1x1(x * mask) + bias (res_conv / to_qkv / to_out, diffusion.py:70,87-88): x [B,cin,H,W], mask_cols [B,W] or None,
-    weight [cout,cin,1,1], bias [cout] or None."""
+    weight [cout,cin,1,1], bias [cout] or None.  `out`: optional preallocated result."""
     x, weight = _f32c(x, "x"), _f32c(weight, "weight")
     B, W = int(x.shape[0]), int(x.shape[3])
     mask_cols = _const(x.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
     bias = _const(x.device, "zeros", int(weight.shape[0])) if bias is None else _f32c(bias, "bias")
-    return _conv_run("1x1", x, mask_cols, weight, bias, False)
+    return _conv_run("1x1", x, mask_cols, weight, bias, False, out=out)
 
 
-def conv1x1_dgrad(dy, weight, mask_cols=None):
-    """Gradient of conv1x1_masked w.r.t. x: the 1x1 convolution of dy * mask (columns do not mix) with the transposed weight."""
+def conv1x1_dgrad(dy, weight, mask_cols=None, out=None):
+    """Gradient of conv1x1_masked w.r.t. x: the 1x1 convolution of dy * mask (columns do not mix) with the transposed weight.  `out`:
+    optional preallocated result."""
     dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
     B, W = int(dy.shape[0]), int(dy.shape[3])
     mask_cols = _const(dy.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
-    return _conv_run("1x1", dy, mask_cols, weight, _const(dy.device, "zeros", int(weight.shape[1])), True)
+    return _conv_run("1x1", dy, mask_cols, weight, _const(dy.device, "zeros", int(weight.shape[1])), True, out=out)
 
 
-def conv1x1_wgrad(x, mask_cols, dy, want_bias=True):
-    """(dW [cout,cin,1,1], db [cout] or None) of conv1x1_masked."""
+def conv1x1_wgrad(x, mask_cols, dy, want_bias=True, out=None):
+    """(dW [cout,cin,1,1], db [cout] or None) of conv1x1_masked.  `out`: optional dict of preallocated dw / db / workspace."""
     x, mask_cols, dy = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy")
     if x.shape[1] in (2, 3):
-        return _wgrad_small(x, _const(x.device, "ones", int(x.shape[0]), int(x.shape[3])) if mask_cols is None else mask_cols, dy, 1, want_bias)
-    return _tiled_wgrad("1x1", x, mask_cols, dy, want_bias=want_bias)
+        return _wgrad_small(x, _const(x.device, "ones", int(x.shape[0]), int(x.shape[3])) if mask_cols is None else mask_cols, dy, 1, want_bias,
+                            out=out)
+    return _tiled_wgrad("1x1", x, mask_cols, dy, want_bias=want_bias, out=out)
 
 
-def add_masked(a, b, mask_cols, channels=None):
+def add_masked(a, b, mask_cols, channels=None, out=None):
     """a + b * mask (a None: b * mask; mask_cols None: a + b) over [B,C,H,W] with mask_cols [B,W].  channels = (c_begin, c_end):
-    b is that channel range of a wider contiguous tensor (read in place; the result is contiguous)."""
+    b is that channel range of a wider contiguous tensor (read in place; the result is contiguous).  `out`: optional preallocated result."""
     a, b, mask_cols = _f32c(a, "a"), _f32c(b, "b"), _f32c(mask_cols, "mask")
     B, Cb, H, W = b.shape
     c0, c1 = (0, Cb) if channels is None else channels
-    out = torch.empty((B, c1 - c0, H, W), dtype=torch.float32, device=b.device)
+    out = _given(out, "out", (B, c1 - c0, H, W), b.device)
     with _on(b.device):
         _check(lib().gtts_add_masked(_ptr(a), ctypes.c_void_p(b.data_ptr() + 4 * c0 * H * W), _ptr(mask_cols), _ptr(out), B, c1 - c0, H, W,
                                      0 if channels is None else Cb, _stream()), "gtts_add_masked")
     return out
 
 
-def zero_insert2(x):
-    """[B,C,h,w] -> [B,C,2h,2w] with x at the even positions and zeros elsewhere."""
+def zero_insert2(x, out=None):
+    """[B,C,h,w] -> [B,C,2h,2w] with x at the even positions and zeros elsewhere.  `out`: optional preallocated result."""
     x = _f32c(x, "x")
     B, C, h, w = x.shape
-    out = torch.empty((B, C, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+    out = _given(out, "out", (B, C, 2 * h, 2 * w), x.device)
     with _on(x.device):
         _check(lib().gtts_zero_insert2(_ptr(x), _ptr(out), B, C, h, w, _stream()), "gtts_zero_insert2")
     return out
 
 
-def space_to_depth2(x):
-    """[B,C,2h,2w] -> [B,4C,h,w]: channel block (pr * 2 + pc) holds rows 2y + 1 - pr and columns 2x + 1 - pc."""
+def space_to_depth2(x, out=None):
+    """[B,C,2h,2w] -> [B,4C,h,w]: channel block (pr * 2 + pc) holds rows 2y + 1 - pr and columns 2x + 1 - pc.  `out`: optional
+    preallocated result."""
     x = _f32c(x, "x")
     B, C, H2, W2 = x.shape
     if H2 % 2 or W2 % 2:
         raise ValueError("space_to_depth2: even height and width expected, got %d x %d" % (H2, W2))
-    out = torch.empty((B, 4 * C, H2 // 2, W2 // 2), dtype=torch.float32, device=x.device)
+    out = _given(out, "out", (B, 4 * C, H2 // 2, W2 // 2), x.device)
     with _on(x.device):
         _check(lib().gtts_space_to_depth2(_ptr(x), _ptr(out), B, C, H2 // 2, W2 // 2, _stream()), "gtts_space_to_depth2")
     return out
 
 
-def final_conv_forward(x, weight, bias, mask_cols):
-    """(Conv2d_1x1(x * mask) + bias) * mask for the 64 -> 1 final convolution (diffusion.py:175-176): [B,1,H,W]."""
+def final_conv_forward(x, weight, bias, mask_cols, out=None):
+    """(Conv2d_1x1(x * mask) + bias) * mask for the 64 -> 1 final convolution (diffusion.py:175-176): [B,1,H,W].  `out`: optional
+    preallocated result."""
     x, weight, bias, mask_cols = _f32c(x, "x"), _f32c(weight, "weight"), _f32c(bias, "bias"), _f32c(mask_cols, "mask")
     B, C, H, W = x.shape
-    out = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
+    out = _given(out, "out", (B, 1, H, W), x.device)
     with _on(x.device):
         _check(lib().gtts_final_conv_forward(_ptr(x), _ptr(weight), _ptr(bias), _ptr(mask_cols), _ptr(out), B, C, H, W, _stream()),
                "gtts_final_conv_forward")
     return out
 
 
-def final_conv_backward(x, weight, mask_cols, dout):
-    """(dx, dweight [1,C,1,1], dbias [1]) of final_conv_forward."""
+def final_conv_backward(x, weight, mask_cols, dout, out=None):
+    """(dx, dweight [1,C,1,1], dbias [1]) of final_conv_forward.  `out`: optional dict of preallocated dx / dw / db / workspace
+    (gtts_final_conv_scratch_floats floats)."""
     x, weight, mask_cols, dout = _f32c(x, "x"), _f32c(weight, "weight"), _f32c(mask_cols, "mask"), _f32c(dout, "dout")
     B, C, H, W = x.shape
-    dx = torch.empty_like(x)
-    dw = torch.empty((1, C, 1, 1), dtype=torch.float32, device=x.device)
-    db = torch.empty((1,), dtype=torch.float32, device=x.device)
+    dx = _out(out, "dx", (B, C, H, W), torch.float32, x.device, exc=ValueError)
+    dw = _out(out, "dw", (1, C, 1, 1), torch.float32, x.device, exc=ValueError)
+    db = _out(out, "db", (1,), torch.float32, x.device, exc=ValueError)
     with _on(x.device):
-        scratch = torch.empty(int(lib().gtts_final_conv_scratch_floats(B, C, H, W)), dtype=torch.float32, device=x.device)
+        scratch = _out(out, "workspace", (int(lib().gtts_final_conv_scratch_floats(B, C, H, W)),), torch.float32, x.device, exc=ValueError)
         _check(lib().gtts_final_conv_backward(_ptr(x), _ptr(weight), _ptr(mask_cols), _ptr(dout), _ptr(dx), _ptr(dw), _ptr(db),
                                               _ptr(scratch), B, C, H, W, _stream()), "gtts_final_conv_backward")
     return dx, dw, db
@@ -1894,10 +1937,11 @@ def resample_supported(cin, cout, H, W, up, B=1):
     return _tiles(cin) and _tiles(cout) and (up or (H % 2 == 0 and W % 2 == 0))
 
 
-def conv_resample(x, mask_cols, weight, bias, up, dgrad_of_down=False):
+def conv_resample(x, mask_cols, weight, bias, up, dgrad_of_down=False, out=None):
     """Downsample (up False: Conv2d 3x3 stride 2 pad 1, weight [cout,cin,3,3]) or Upsample (up True: ConvTranspose2d 4x4 stride 2
     pad 1, weight [cin,cout,4,4]) of x * mask (diffusion.py:19-34).  dgrad_of_down: x is the gradient of a Downsample output and
-    weight that Downsample's forward weight; the result is its data gradient (an Upsample with the zero-padded kernel)."""
+    weight that Downsample's forward weight; the result is its data gradient (an Upsample with the zero-padded kernel).  `out`: optional
+    preallocated result."""
     x, mask_cols, weight = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight")
     B, cin, H, W = x.shape
     if dgrad_of_down:
@@ -1905,7 +1949,7 @@ def conv_resample(x, mask_cols, weight, bias, up, dgrad_of_down=False):
     else:
         cout, kind = (int(weight.shape[1]), "up") if up else (int(weight.shape[0]), "dn")
     bias = _const(x.device, "zeros", cout) if bias is None else _f32c(bias, "bias")
-    y = torch.empty((B, cout, 2 * H, 2 * W) if up else (B, cout, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    y = _given(out, "out", (B, cout, 2 * H, 2 * W) if up else (B, cout, H // 2, W // 2), x.device)
     with _on(x.device):
         packed = _packed_weight(weight, cin, cout, False, kind)
         _check(lib().gtts_conv_resample(_ptr(x), _ptr(mask_cols), _ptr(packed), _ptr(bias), _ptr(y), B, cin, cout, H, W, 1 if up else 0,
@@ -2057,13 +2101,13 @@ def score_loss(eps, z_masked, t, beta_min, beta_max, inv_denom, want_grad=True, 
     return part.sum() * inv_denom, g
 
 
-def _out(out, name, shape, dtype, device):
+def _out(out, name, shape, dtype, device, exc=RuntimeError):
     """A preallocated output of the caller's (`out` dict, tests place them between guard margins) or a fresh one."""
     t = None if out is None else out.get(name)
     if t is None:
         return torch.empty(shape, dtype=dtype, device=device)
     if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
-        raise RuntimeError("output %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
+        raise exc("output %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
     return t
 
 

@@ -8,6 +8,7 @@
 //                            the data gradient Conv2d_3x3(dy, W^T flipped) [* mask] is the same call with weights packed transposed
 //   gtts_conv7x7_masked, gtts_conv1x1_masked, gtts_conv_resample     the same launch setup (conv_train_launch) on the 7x7, 1x1 and
 //                            Downsample / Upsample inference kernels, and gtts_*_pack / gtts_pack_batch, which pack their weights
+//   gtts_conv_train_kernel_name   which kernel instance such a call runs, from the same checks, arguments and dispatch (host only)
 // The weight gradients are fixed-order MFMA reductions over pixels in train_wgrad.hip and train_wgrad7.hip; GroupNorm + Mish, the
 // attention core and the elementwise ops of the step are train_norm.hip, train_attn.hip and train_elem.hip.  Every tensor-sized op
 // of the step, forward and backward, is a kernel of this library: model/_train_ops.py wraps the entry points in
@@ -16,6 +17,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 #include "../../include/gradtts_abi.h"
 #include "common.h"
@@ -128,12 +130,12 @@ extern "C" int gtts_score_loss(const float *eps, const float *z_masked, const fl
 // mask prologue (mask [B][Win] on the input columns) and the plain epilogue, one weight and bias for the whole batch.  x1 (nullable):
 // the input is the channel concatenation of x [B,c0,..] and x1 [B,cin-c0,..], read in place; omask (nullable): [B][Wout] column mask
 // multiplied into the output.  `fn`: the entry point, for the error text.  The callers have validated every argument.
-static int conv_train_launch(int mode, const char *fn, const float *x, const float *x1, int c0, const float *mask, const float *omask,
-                             const void *packed, const float *bias, float *y, int B, int cin, int cout, int Hin, int Win, int Hout,
-                             int Wout, gtts_stream_t stream) {
+// conv_train_args is that setup alone (two: the input has a second source); gtts_conv_train_kernel_name calls it without pointers.
+static ConvArgs conv_train_args(const float *x, const float *x1, bool two, int c0, const float *mask, const float *omask, const void *packed,
+                                const float *bias, float *y, int B, int cin, int cout, int Hin, int Win, int Hout, int Wout) {
     ConvArgs a;
     memset(&a, 0, sizeof(a));
-    a.src0 = x; a.src1 = x1 ? x1 : x; a.c0 = x1 ? c0 : cin; a.c1 = x1 ? cin - c0 : 0; a.cin = cin;
+    a.src0 = x; a.src1 = two ? x1 : x; a.c0 = two ? c0 : cin; a.c1 = two ? cin - c0 : 0; a.cin = cin;
     a.B = B; a.Hin = Hin; a.Win = Win; a.Hout = Hout; a.Wout = Wout;
     a.mask = mask; a.T = Win; a.lvl_in = a.lvl_out = 0;
     a.pro = PRO_MASK; a.epi = EPI_PLAIN;
@@ -141,6 +143,13 @@ static int conv_train_launch(int mode, const char *fn, const float *x, const flo
     a.bias = bias; a.bias_bstride = 0;
     a.cout = cout; a.out = y; a.groups = 8; a.nsplit = 2;
     a.omask = omask;
+    return a;
+}
+
+static int conv_train_launch(int mode, const char *fn, const float *x, const float *x1, int c0, const float *mask, const float *omask,
+                             const void *packed, const float *bias, float *y, int B, int cin, int cout, int Hin, int Win, int Hout,
+                             int Wout, gtts_stream_t stream) {
+    const ConvArgs a = conv_train_args(x, x1, x1 != nullptr, c0, mask, omask, packed, bias, y, B, cin, cout, Hin, Win, Hout, Wout);
     const hipError_t e = launch_conv(mode, a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(GTTS_E_HIP, "%s (cin %d, cout %d): %s", fn, cin, cout, hipGetErrorString(e));
     return GTTS_OK;
@@ -169,6 +178,14 @@ extern "C" int gtts_conv3x3_pack(const float *w, void *packed, int cin, int cout
     return train_pack(transposed ? CONV_C3 + 16 : CONV_C3, "gtts_conv3x3_pack", w, packed, cin, cout, stream);
 }
 
+// (the shape checks of an entry point are a function of their own: gtts_conv_train_kernel_name refuses what the entry point refuses)
+static int conv3x3_check(const char *fn, bool two, int c0, int B, int cin, int cout, int H, int W) {
+    if (two && (c0 <= 0 || c0 >= cin || c0 % 16)) return fail(GTTS_E_SHAPE, "%s: c0 must be a multiple of 16 inside (0, cin) (got %d of %d)", fn, c0, cin);
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "%s: bad shape", fn);
+    if (cout % (cout > 64 ? 128 : 64) != 0) return fail(GTTS_E_SHAPE, "%s: cout must be 64 or a multiple of 128 (got %d)", fn, cout);
+    return GTTS_OK;
+}
+
 // y = Conv2d_3x3(x * mask, packed W) + bias; x [B,cin,H,W], mask [B,W] (columns), y [B,cout,H,W].  cout % 64 == 0 (128 above 64).
 // x1 (nullable) / c0: the input is the channel concatenation of x [B,c0,H,W] and x1 [B,cin-c0,H,W] (c0 a multiple of 16), read
 // in place (torch.cat of the up path, diffusion.py:166)
@@ -177,9 +194,8 @@ extern "C" int gtts_conv3x3_pack(const float *w, void *packed, int cin, int cout
 extern "C" int gtts_conv3x3_masked(const float *x, const float *x1, int c0, const float *mask, const float *omask, const void *packed,
                                    const float *bias, float *y, int B, int cin, int cout, int H, int W, gtts_stream_t stream) {
     if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv3x3_masked: null argument");
-    if (x1 && (c0 <= 0 || c0 >= cin || c0 % 16)) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: c0 must be a multiple of 16 inside (0, cin) (got %d of %d)", c0, cin);
-    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: bad shape");
-    if (cout % (cout > 64 ? 128 : 64) != 0) return fail(GTTS_E_SHAPE, "gtts_conv3x3_masked: cout must be 64 or a multiple of 128 (got %d)", cout);
+    const int rc = conv3x3_check("gtts_conv3x3_masked", x1 != nullptr, c0, B, cin, cout, H, W);
+    if (rc != GTTS_OK) return rc;
     return conv_train_launch(CONV_C3, "gtts_conv3x3_masked", x, x1, c0, mask, omask, packed, bias, y, B, cin, cout, H, W, H, W, stream);
 }
 
@@ -218,12 +234,18 @@ extern "C" int gtts_conv1x1_pack(const float *w, void *packed, int cin, int cout
     return train_pack(transposed ? CONV_P1 + 16 : CONV_P1, "gtts_conv1x1_pack", w, packed, cin, cout, stream);
 }
 
+static int conv1x1_check(const char *fn, int B, int cin, int cout, int H, int W) {
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "%s: bad shape", fn);
+    if (cout % (cout > 64 ? 128 : 64) != 0) return fail(GTTS_E_SHAPE, "%s: cout must be 64 or a multiple of 128 (got %d)", fn, cout);
+    return GTTS_OK;
+}
+
 // y = Conv2d_1x1(x * mask, packed W) + bias; x [B,cin,H,W], mask [B,W] (columns), bias [cout], y [B,cout,H,W]
 extern "C" int gtts_conv1x1_masked(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B,
                                    int cin, int cout, int H, int W, gtts_stream_t stream) {
     if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv1x1_masked: null argument");
-    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv1x1_masked: bad shape");
-    if (cout % (cout > 64 ? 128 : 64) != 0) return fail(GTTS_E_SHAPE, "gtts_conv1x1_masked: cout must be 64 or a multiple of 128 (got %d)", cout);
+    const int rc = conv1x1_check("gtts_conv1x1_masked", B, cin, cout, H, W);
+    if (rc != GTTS_OK) return rc;
     return conv_train_launch(CONV_P1, "gtts_conv1x1_masked", x, nullptr, 0, mask, nullptr, packed, bias, y, B, cin, cout, H, W, H, W, stream);
 }
 
@@ -238,16 +260,53 @@ extern "C" int gtts_conv_resample_pack(const float *w, void *packed, int cin, in
     return train_pack(up ? CONV_UP : CONV_DN, "gtts_conv_resample_pack", w, packed, cin, cout, stream);
 }
 
+static int resample_check(const char *fn, int B, int cin, int cout, int H, int W, int up) {
+    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "%s: bad shape", fn);
+    if (!up && ((H | W) & 1)) return fail(GTTS_E_SHAPE, "%s: Downsample needs even H and W (got %d x %d)", fn, H, W);
+    if (cin % 16 != 0 || cout % (cout > 64 ? 128 : 64) != 0)
+        return fail(GTTS_E_SHAPE, "%s: cin must be a multiple of 16 and cout 64 or a multiple of 128 (got %d, %d)", fn, cin, cout);
+    return GTTS_OK;
+}
+
 // y = conv(x * mask) + bias; x [B,cin,H,W], mask [B,W] (columns of the INPUT).  H and W even for up = 0.
 extern "C" int gtts_conv_resample(const float *x, const float *mask, const void *packed, const float *bias, float *y, int B, int cin,
                                   int cout, int H, int W, int up, gtts_stream_t stream) {
     if (!x || !mask || !packed || !bias || !y) return fail(GTTS_E_NULL, "gtts_conv_resample: null argument");
-    if (B <= 0 || cin <= 0 || cout <= 0 || H <= 0 || W <= 0) return fail(GTTS_E_SHAPE, "gtts_conv_resample: bad shape");
-    if (!up && ((H | W) & 1)) return fail(GTTS_E_SHAPE, "gtts_conv_resample: Downsample needs even H and W (got %d x %d)", H, W);
-    if (cin % 16 != 0 || cout % (cout > 64 ? 128 : 64) != 0)
-        return fail(GTTS_E_SHAPE, "gtts_conv_resample: cin must be a multiple of 16 and cout 64 or a multiple of 128 (got %d, %d)", cin, cout);
+    const int rc = resample_check("gtts_conv_resample", B, cin, cout, H, W, up);
+    if (rc != GTTS_OK) return rc;
     return conv_train_launch(up ? CONV_UP : CONV_DN, up ? "gtts_conv_resample (up)" : "gtts_conv_resample (down)", x, nullptr, 0, mask, nullptr,
                              packed, bias, y, B, cin, cout, H, W, up ? 2 * H : H / 2, up ? 2 * W : W / 2, stream);
+}
+
+// ---- which kernel instance a forward / data-gradient convolution of the training path runs (additive; host only, no device call):
+// the shape checks of the entry point, conv_train_args without pointers, and launch_conv describing instead of launching (common.h).
+// kind 0: gtts_conv3x3_masked, 1: gtts_conv1x1_masked, 2: gtts_conv7x7_masked, 3: gtts_conv_resample (`up` read for kind 3 only).
+// cin / cout / H / W are those of the call asked about (a data gradient is a call with the forward's cin and cout swapped, Downsample's
+// an up = 1 call on the halved plane); c0 in (0, cin): two sources (kind 0 only), 0 or cin: one.  buf receives the name, NUL-terminated.
+extern "C" int gtts_conv_train_kernel_name(int kind, int B, int cin, int c0, int cout, int H, int W, int up, char *buf, size_t n) {
+    const char *fn = "gtts_conv_train_kernel_name";
+    if (!buf || n == 0) return fail(GTTS_E_NULL, "%s: null argument", fn);
+    buf[0] = 0;
+    if (kind < 0 || kind > 3) return fail(GTTS_E_CONFIG, "%s: unknown kind %d", fn, kind);
+    const bool two = c0 != 0 && c0 != cin;
+    if (two && kind != 0) return fail(GTTS_E_CONFIG, "%s: only the 3x3 convolution takes two sources", fn);
+    int rc, mode, Ho = H, Wo = W;
+    switch (kind) {
+        case 0: rc = conv3x3_check(fn, two, c0, B, cin, cout, H, W); mode = CONV_C3; break;
+        case 1: rc = conv1x1_check(fn, B, cin, cout, H, W); mode = CONV_P1; break;
+        case 2: rc = conv7x7_check(fn, B, cin, cout, H, W); mode = CONV_C7; break;
+        default:
+            rc = resample_check(fn, B, cin, cout, H, W, up); mode = up ? CONV_UP : CONV_DN;
+            if (rc == GTTS_OK) { Ho = up ? 2 * H : H / 2; Wo = up ? 2 * W : W / 2; }
+            break;
+    }
+    if (rc != GTTS_OK) return rc;
+    std::string name;
+    const ConvArgs a = conv_train_args(nullptr, nullptr, two, c0, nullptr, nullptr, nullptr, nullptr, nullptr, B, cin, cout, H, W, Ho, Wo);
+    if (launch_conv(mode, a, nullptr, &name) != hipSuccess) return fail(GTTS_E_CONFIG, "%s: no kernel instance takes cin %d, cout %d at %d x %d", fn, cin, cout, H, W);
+    if (name.size() + 1 > n) return fail(GTTS_E_WORKSPACE, "%s: the name needs %zu bytes", fn, name.size() + 1);
+    memcpy(buf, name.c_str(), name.size() + 1);
+    return GTTS_OK;
 }
 
 // ---- all weight packs of a training step in one launch (ABI 4) ----------------------------------------------------------

@@ -112,6 +112,33 @@ def test_conv_resample_validates(L):
         assert f(x, m, p, b, y, 2, 64, 64, H, W, 0, None) == E_SHAPE, (H, W)
 
 
+def test_conv_train_kernel_name_validates(L):
+    """Host only: the entry point's own shape checks, then the launching dispatch describing itself -- no pointer but the buffer."""
+    f = L.gtts_conv_train_kernel_name
+    buf = ctypes.create_string_buffer(256)
+    assert f(0, 2, 64, 0, 64, 80, 44, 0, None, 256) == E_NULL and f(0, 2, 64, 0, 64, 80, 44, 0, buf, 0) == E_NULL
+    for kind in (-1, 4):
+        assert f(kind, 2, 64, 0, 64, 80, 44, 0, buf, 256) == E_CONFIG, kind
+    for kind in (1, 2, 3):                                                  # two sources: the 3x3 convolution only
+        assert f(kind, 2, 128, 64, 64, 80, 44, 0, buf, 256) == E_CONFIG, kind
+    for c0 in (-16, 144, 24):                                               # c0 a multiple of 16 inside (0, cin)
+        assert f(0, 2, 128, c0, 64, 80, 44, 0, buf, 256) == E_SHAPE, c0
+    for kind in (0, 1, 2, 3):                                               # what the entry points refuse
+        for B, cin, cout, H, W in ((0, 64, 64, 80, 44), (2, 0, 64, 80, 44), (2, 64, -64, 80, 44), (2, 64, 64, 0, 44), (2, 64, 64, 80, 0)):
+            assert f(kind, B, cin, 0, cout, H, W, 0, buf, 256) == E_SHAPE, (kind, B, cin, cout, H, W)
+    for kind in (0, 1, 3):
+        for cout in (32, 96, 192):
+            assert f(kind, 2, 64, 0, cout, 80, 44, 1, buf, 256) == E_SHAPE, (kind, cout)
+    assert f(2, 2, 96, 0, 64, 80, 44, 0, buf, 256) == E_CONFIG and f(2, 2, 64, 0, 32, 80, 44, 0, buf, 256) == E_CONFIG     # 7x7: whole 64-channel tiles
+    assert f(2, 4096, 64, 0, 64, 80, 172, 0, buf, 256) == E_SHAPE                                                        # ... below 2^29 elements
+    assert f(3, 2, 24, 0, 64, 80, 44, 0, buf, 256) == E_SHAPE and f(3, 2, 64, 0, 64, 79, 44, 0, buf, 256) == E_SHAPE     # Downsample: cin % 16, even H
+    assert f(3, 2, 64, 0, 64, 79, 43, 1, buf, 256) == OK and buf.value == b"gtts::conv_up4_kernel"                        # (Upsample takes odd sizes)
+    assert f(0, 2, 64, 0, 64, 80, 44, 0, buf, 8) == E_WORKSPACE and buf.value == b""                                      # the name does not fit
+    assert f(0, 2, 64, 0, 64, 80, 44, 0, buf, 256) == OK and buf.value.startswith(b"gtts::conv_mfma_kernel<0, ")
+    assert f(0, 2, 128, 64, 64, 80, 44, 0, buf, 256) == OK and f(0, 2, 64, 64, 64, 80, 44, 0, buf, 256) == OK             # c0 = cin: one source
+    assert f(1, 2, 3, 0, 64, 80, 44, 0, buf, 256) == OK and buf.value.endswith(b"2, 0, float, 2, 0>")                     # ragged channels: FULLC = 0
+
+
 def test_attention_core_validates(L):
     qkv, out, ctx, stat, scr, dout, dqkv, dctx, rdot = _fake(9)
     f, g = L.gtts_attn_train_forward, L.gtts_attn_train_backward
