@@ -12,6 +12,8 @@ import collections
 import torch
 import torch.nn.functional as F
 
+from case_util import relerr, seq_mask  # noqa: F401
+
 REL = 1e-4          # split-bf16 contractions, fp32 accumulate (tests/test_gpu_hifigan.py)
 
 # epilogue ids of Conv1dOp.instance (csrc/conv1d.h, C1Epilogue)
@@ -112,7 +114,7 @@ def _mask(lens, B, L):
     if lens is None:
         return None
     assert len(lens) == B and max(lens) <= L
-    return (torch.arange(L).unsqueeze(0) < torch.tensor(lens).unsqueeze(1)).float()
+    return seq_mask(lens, L)
 
 
 def make_inputs(c):
@@ -166,11 +168,6 @@ def reference(c, d, dtype=torch.float64, w=None, toff_shift=0, drop_res=False):
     if d["out_mask"] is not None:
         v = v * t(d["out_mask"]).unsqueeze(1)
     return v
-
-
-def relerr(got, ref):
-    """max |got - ref| / max |ref| over all elements, nothing masked out."""
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
 
 
 def bf16_round(w):

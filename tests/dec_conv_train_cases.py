@@ -48,6 +48,8 @@ import functools
 import torch
 import torch.nn.functional as F
 
+from case_util import relerr, seq_mask  # noqa: F401
+
 PER_ELEM = 2.0 ** -14
 EMUL_FACTOR = 4.0
 REL_CAP = 1e-4
@@ -208,7 +210,7 @@ def contraction(c):
 
 
 def _mask(c):
-    return (torch.arange(c.W).unsqueeze(0) < torch.tensor(c.lens).unsqueeze(1)).float()
+    return seq_mask(c.lens, c.W)
 
 
 def _draw(kind, g, shape, role):
@@ -525,11 +527,6 @@ def emulate(c, d, mistake=None):
 
 
 # =========================================================================================================================== errors
-def relerr(got, ref):
-    """max |got - ref| / max |ref| over all elements, nothing masked out."""
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
-
-
 def worst_ratio(got, ref, M):
     """max over elements of |got - ref| / M (an element with M = 0 must be exact: inf otherwise)."""
     err, M = (got.double() - ref.double()).abs(), M.double()

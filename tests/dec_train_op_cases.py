@@ -39,6 +39,8 @@ import collections
 import torch
 import torch.nn.functional as F
 
+from case_util import relerr_zero_exact as relerr, seq_mask as _seq_mask  # noqa: F401
+
 GRAD_ABS = 2e-6
 GRAD_REL = 1e-4                 # the project's per-op gradient bound
 FWD_REL = 1e-5                  # the project's bound for fp32 forward ops
@@ -55,15 +57,6 @@ def bound(e32, name):
     return min(4.0 * e32 + GRAD_ABS, cap(name))
 
 
-def relerr(got, ref, scale=None):
-    """max |got - ref| / scale, scale = max |ref| unless given; an all-zero reference without a scale asks for exact zeros."""
-    got, ref = torch.as_tensor(got).double(), torch.as_tensor(ref).double()
-    n = float(ref.abs().max()) if scale is None else float(scale)
-    if n == 0.0:
-        return 0.0 if bool((got == 0).all()) else float("inf")
-    return float((got - ref).abs().max() / n)
-
-
 def ratioerr(got, ref):
     """max |got / ref - 1|, element-wise."""
     got, ref = torch.as_tensor(got).double(), torch.as_tensor(ref).double()
@@ -73,10 +66,6 @@ def ratioerr(got, ref):
 def _lens(B, W):
     """Ragged columns: one full utterance, then one of length 1, then one cut mid-row; repeated."""
     return [(W, 1, max(1, W // 2 + 1))[b % 3] for b in range(B)]
-
-
-def _seq_mask(lens, n):
-    return (torch.arange(n).unsqueeze(0) < torch.as_tensor(lens).unsqueeze(1)).float()
 
 
 KINDS = ("plain", "offset30", "offset40", "offset300", "short", "saturated")

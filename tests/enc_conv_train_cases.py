@@ -18,6 +18,8 @@ import collections
 import torch
 import torch.nn.functional as F
 
+from case_util import relerr, seq_mask  # noqa: F401
+
 REL = 1e-4          # split-bf16 contractions, fp32 accumulate: e = max |got - ref| / max |ref| per tensor (tests/conv1d_cases.py)
 CHUNK = 64          # positions per chunk of the weight-gradient kernel (checked against wgrad_info by the CPU test)
 TILE = 64           # its output tile, rows (co) and columns (ci)
@@ -75,7 +77,7 @@ def _mask(lens, B, L):
     if lens is None:
         return None
     assert len(lens) == B and max(lens) <= L
-    return (torch.arange(L).unsqueeze(0) < torch.tensor(lens).unsqueeze(1)).float()
+    return seq_mask(lens, L)
 
 
 def make_inputs(c):
@@ -147,8 +149,3 @@ def formulas(c, d, mistake=None, dtype=torch.float64):
         dw[:, :, k] = torch.einsum("boq,biq->oi", dym[..., :n], xs[..., :n])
     db = dym[..., :n].sum((0, 2)) if c.bias else None
     return dict(dx=dx, dw=dw, db=db)
-
-
-def relerr(got, ref):
-    """max |got - ref| / max |ref| over all elements, nothing masked out."""
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())

@@ -30,6 +30,7 @@ import math
 
 import torch
 
+from case_util import relerr, seq_mask as _mask  # noqa: F401
 from oracle import encoder_oracle as E
 
 ELEMENTWISE_ABS = 2e-6          # the project's fp32 elementwise rule: e <= 4 e_ref32 + 2e-6 (test_gpu_spk.py, test_gpu_op_parity.py)
@@ -42,17 +43,8 @@ def bound(e32):
     return min(4.0 * e32 + ELEMENTWISE_ABS, REDUCTION_REL)
 
 
-def relerr(got, ref):
-    """max |got - ref| / max |ref| over all elements, nothing masked out (NaN if anything is not finite)."""
-    return float((got.double() - ref.double()).abs().max() / ref.double().abs().max())
-
-
 def exceeds(e, b):
     return not (e <= b)          # a NaN exceeds every bound
-
-
-def _mask(lens, L):
-    return (torch.arange(L).unsqueeze(0) < torch.tensor(lens).unsqueeze(1)).float()
 
 
 # =============================================================================================================== attention

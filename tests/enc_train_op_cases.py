@@ -22,6 +22,7 @@ import math
 import torch
 
 import enc_op_cases as K
+from case_util import relerr_zero_exact as relerr, seq_mask  # noqa: F401
 from oracle import encoder_oracle as E
 
 GRAD_ABS = 2e-6
@@ -35,15 +36,6 @@ SATURATED_FINITE_ONLY = ("dq", "dk", "dek")
 
 def bound(e32):
     return min(4.0 * e32 + GRAD_ABS, GRAD_REL)
-
-
-def relerr(got, ref):
-    """max |got - ref| / max |ref|; an all-zero reference asks for exact zeros."""
-    got, ref = got.double(), ref.double()
-    n = float(ref.abs().max())
-    if n == 0.0:
-        return 0.0 if bool((got == 0).all()) else float("inf")
-    return float((got - ref).abs().max() / n)
 
 
 def held(c, name):
@@ -69,7 +61,7 @@ def att_train_inputs(c):
     g = torch.Generator().manual_seed(5999)
     B, H, dk, L, w = c.B, c.heads, c.dk, c.L, c.window
     C = H * dk
-    mask = (torch.arange(L).unsqueeze(0) < torch.tensor(c.lens).unsqueeze(1)).float()
+    mask = seq_mask(c.lens, L)
     sd = E.make_state("mel", n_feats=4, C=C, filt=C, n_heads=H, n_layers=1, window=w, seed=399)
     p = "encoder.attn_layers.0."
     x = torch.randn(B, C, L, generator=g) * mask.unsqueeze(1)

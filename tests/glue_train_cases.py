@@ -24,6 +24,8 @@ import types
 import torch
 import torch.nn.functional as F
 
+from case_util import relerr_zero_exact as relerr, seq_mask as _seq_mask  # noqa: F401
+
 GRAD_ABS = 2e-6
 GRAD_REL = 1e-4
 LOG_2PI = math.log(2 * math.pi)
@@ -34,22 +36,9 @@ def bound(e32):
     return min(4.0 * e32 + GRAD_ABS, GRAD_REL)
 
 
-def relerr(got, ref):
-    """max |got - ref| / max |ref|; an all-zero reference asks for exact zeros."""
-    got, ref = torch.as_tensor(got).double(), torch.as_tensor(ref).double()
-    n = float(ref.abs().max())
-    if n == 0.0:
-        return 0.0 if bool((got == 0).all()) else float("inf")
-    return float((got - ref).abs().max() / n)
-
-
 def _lens(B, W):
     """Ragged columns: one full sample, one cut mid-row, one of length 1."""
     return [W, max(1, W // 2 + 1), 1][:B]
-
-
-def _seq_mask(lens, n):
-    return (torch.arange(n).unsqueeze(0) < torch.as_tensor(lens).unsqueeze(1)).float()
 
 
 # ======================================================================================================== A: first-layer data gradient

@@ -13,6 +13,8 @@ Edge shapes (level widths T, T/2, T/4; convolution tiles are 32 columns wide):
 DiffVC dim 128 and 256 take (1, 4) and (2, 36) only (the float64 references grow with dim^2)."""
 import collections
 
+import torch
+
 PREC_NAME = {0: "bf16x3", 1: "bf16", 2: "bf16_store", 3: "f16f8"}
 EDGE_SHAPES = collections.OrderedDict([((1, 4), [3]), ((2, 36), [36, 19]), ((3, 132), [132, 67, 1]), ((16, 4), [4, 3, 2, 1] * 4)])
 EXTRA_LENGTHS = {(5, 100): [100, 77, 51, 26, 1], (1, 92): [91], (1, 8): [7], (1, 256): [255]}
@@ -125,3 +127,44 @@ NOT_CHECKED_HERE = {
 def claims(case, label, kernel):
     """The check kinds that claim one op of Plan.ops (exactly one, or the catalogue test fails)."""
     return [kind for kind, rule in CLAIMS.items() if rule(case, label, kernel)]
+
+
+# What tests/test_gpu_parity_full.py, test_gpu_attention.py and test_gpu_op_parity.py share: the U-Net's op names, two bounds, the
+# float64 attention and the reader of a plan's named intermediates.
+REL = 1e-4          # bf16x3 contractions, fp32 accumulate (measured ~2e-5 per call)
+FMT_FACTOR = 4.0    # bf16 / bf16_store: e_kernel <= FMT_FACTOR * e_fmt
+RESNETS = ["downs.0.0", "downs.0.1", "downs.1.0", "downs.1.1", "downs.2.0", "downs.2.1", "mid_block1", "mid_block2",
+           "ups.0.0", "ups.0.1", "ups.1.0", "ups.1.1"]
+ATTNS = {"downs.0.2": "downs.0.1", "downs.1.2": "downs.1.1", "downs.2.2": "downs.2.1", "mid_attn": "mid_block1",
+         "ups.0.2": "ups.0.1", "ups.1.2": "ups.1.1"}
+
+
+def attention_f64(sd, a, X, bf16_operands=False, dtype=torch.float64):
+    """(ctx [B,4,32,32], branch = g * LinearAttention(X) [B,C,H,W], max |k|) in float64.  bf16_operands: X and the two weights are
+    rounded to bf16 first (the error the bf16 formats force); softmax and every sum stay float64.  dtype=torch.float32: the same
+    chain in plain fp32, for the float32 reference's own context error."""
+    p = a + ".fn.fn."
+    B, C, H, W = X.shape
+    rnd = (lambda v: v.float().to(torch.bfloat16).to(dtype)) if bf16_operands else (lambda v: v.to(dtype))
+    x = rnd(X).reshape(B, C, H * W)
+    wqkv = rnd(sd[p + "to_qkv.weight"]).reshape(384, C)
+    wout = rnd(sd[p + "to_out.weight"]).reshape(C, 128)
+    qkv = torch.einsum("oc,bcn->bon", wqkv, x).view(B, 3, 4, 32, H * W)
+    q, k, v = qkv[:, 0], qkv[:, 1], qkv[:, 2]
+    ctx = torch.einsum("bhdn,bhen->bhde", torch.softmax(k, -1), v)
+    out = torch.einsum("bhde,bhdn->bhen", ctx, q).reshape(B, 128, H * W)
+    y = torch.einsum("oc,bcn->bon", wout, out) + sd[p + "to_out.bias"].to(dtype)[None, :, None]
+    return ctx, (y * sd[a + ".fn.g"].to(dtype)).view(B, C, H, W), float(k.abs().max())
+
+
+def _reader(ws, infos, store_bf16=False):
+    """name -> CPU fp32 copy of one named intermediate of the workspace.  With bf16 activation storage the activation tensors of
+    plan.hip (kind TK_ACT: "x0", "<op>.raw", "<op>.out") are 2-byte; the per-sample ones ("<attn>.ctx", "<attn>.bfold") stay fp32.
+    Plan.tensors has no view of 2-byte tensors, so the offsets are read as Plan.vc_tensors reads them."""
+    def get(name):
+        off, dims = infos[name]
+        n = dims[0] * dims[1] * dims[2] * dims[3]
+        if store_bf16 and (name == "x0" or name.endswith((".raw", ".out"))):
+            return ws[off: off + 2 * n].view(torch.bfloat16).view(*dims).float().cpu()
+        return ws[off: off + 4 * n].view(torch.float32).view(*dims).cpu()
+    return get

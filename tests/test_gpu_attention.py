@@ -27,53 +27,22 @@ Shapes (attn_geom of csrc/kernels.h; head-per-wave kernel at C = 64: 64-pixel ti
   T 1640 [1639]     per-head C 256 / C 128 at HW 8200: 33 tiles, tps 2, last slice one tile of 8 px (level-2 attentions only)
 Each row of the printed table (-s) is one (case, attention); figures: profiles/attention_parity.txt.
 """
-import importlib
 
 import pytest
 import torch
 
 from oracle import diffvc_oracle as V
 from oracle import gradtts_oracle as O
-from test_gpu_parity_full import ATTNS
+from gpu_guards import S, dev  # noqa: F401
+from op_parity_cases import ATTNS, FMT_FACTOR, _reader, attention_f64
 
 pytestmark = pytest.mark.gpu
 BOUND = 2e-4            # bf16x3 / f16f8: local branch bound of test_linear_attention_with_unit_rezero_gain, also for the context
-FMT_FACTOR = 4.0        # bf16 / bf16_store: e_kernel <= FMT_FACTOR * e_fmt
 BIG = 1e30              # the branch is checked where its float64 reference stays below this
 T_REF = 24
 
 LENGTHS = {(1, 4): [3], (2, 36): [36, 19], (2, 100): [100, 57], (1, 412): [411], (1, 1640): [1639], (3, 72): [72, 41, 1]}
 LEVEL2 = ("downs.2.2", "mid_attn", "ups.0.2")
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-# ------------------------------------------------------------------------------------------------ float64 reference
-def attention_f64(sd, a, X, bf16_operands=False, dtype=torch.float64):
-    """(ctx [B,4,32,32], branch = g * LinearAttention(X) [B,C,H,W], max |k|) in float64.  bf16_operands: X and the two weights are
-    rounded to bf16 first (the error the bf16 formats force); softmax and every sum stay float64.  dtype=torch.float32: the same
-    chain in plain fp32, for the float32 reference's own context error."""
-    p = a + ".fn.fn."
-    B, C, H, W = X.shape
-    rnd = (lambda v: v.float().to(torch.bfloat16).to(dtype)) if bf16_operands else (lambda v: v.to(dtype))
-    x = rnd(X).reshape(B, C, H * W)
-    wqkv = rnd(sd[p + "to_qkv.weight"]).reshape(384, C)
-    wout = rnd(sd[p + "to_out.weight"]).reshape(C, 128)
-    qkv = torch.einsum("oc,bcn->bon", wqkv, x).view(B, 3, 4, 32, H * W)
-    q, k, v = qkv[:, 0], qkv[:, 1], qkv[:, 2]
-    ctx = torch.einsum("bhdn,bhen->bhde", torch.softmax(k, -1), v)
-    out = torch.einsum("bhde,bhdn->bhen", ctx, q).reshape(B, 128, H * W)
-    y = torch.einsum("oc,bcn->bon", wout, out) + sd[p + "to_out.bias"].to(dtype)[None, :, None]
-    return ctx, (y * sd[a + ".fn.g"].to(dtype)).view(B, C, H, W), float(k.abs().max())
 
 
 def attn_geom(HW, C):
@@ -153,19 +122,6 @@ def _plan(S, dev, arch, dim, prec, conv_ws, n_spks=1):
 
 def _mask(B, T):
     return O.sequence_mask(torch.tensor(LENGTHS[(B, T)]), T).unsqueeze(1).float()
-
-
-def _reader(ws, infos, store_bf16=False):
-    """name -> CPU fp32 copy of one named intermediate of the workspace.  With bf16 activation storage the activation tensors of
-    plan.hip (kind TK_ACT: "x0", "<op>.raw", "<op>.out") are 2-byte; the per-sample ones ("<attn>.ctx", "<attn>.bfold") stay fp32.
-    Plan.tensors has no view of 2-byte tensors, so the offsets are read as Plan.vc_tensors reads them."""
-    def get(name):
-        off, dims = infos[name]
-        n = dims[0] * dims[1] * dims[2] * dims[3]
-        if store_bf16 and (name == "x0" or name.endswith((".raw", ".out"))):
-            return ws[off: off + 2 * n].view(torch.bfloat16).view(*dims).float().cpu()
-        return ws[off: off + 4 * n].view(torch.float32).view(*dims).cpu()
-    return get
 
 
 def _run_gradtts(S, dev, B, T, prec="bf16x3", conv_ws=False, n_spks=1, scale=1.0):

@@ -9,55 +9,27 @@ CPU.  The catalogue is tests/conv1d_cases.py; tests/test_conv1d_cases_cpu.py pro
               farther than any read the staging can issue, pad channels included) hold NaN, `out` inside one filled with a sentinel:
               the result must be finite, every element of `out` written, the margins untouched
 Run with -s for the table; the recorded figures are in profiles/conv1d_parity.txt."""
-import importlib
-
 import pytest
 import torch
 
 import conv1d_cases as C
+from gpu_guards import SENTINEL, Outputs, S, dev, guarded_inputs, table_row  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -12345.675
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def guarded(t, margin, fill, dev):
-    """(view, whole): a contiguous device copy of t in the middle of a larger allocation filled with `fill`."""
-    whole = torch.full((t.numel() + 2 * margin,), fill, dtype=torch.float32, device=dev)
-    view = whole[margin:margin + t.numel()].view(t.shape)
-    view.copy_(t)
-    return view, whole
 
 
 def run_case(S, dev, c, d, op=None):
     """The layer on the GPU between guards; returns the CPU result after checking the margins of `out`."""
     op = op or S.Conv1dOp(**C.op_kwargs(c))
     margin = 16 * c.Lin * c.S + 64
-    nan = float("nan")
-    t = {k: (None if d[k] is None else guarded(d[k], margin, nan, dev)[0]) for k in ("x", "bias", "res", "accsrc", "in_mask", "out_mask")}
-    out, whole = guarded(torch.full((c.B, c.cout, c.Lin * c.S), SENTINEL), margin, SENTINEL, dev)
+    t = guarded_inputs(d, ("x", "bias", "res", "accsrc", "in_mask", "out_mask"), margin, dev)
+    o = Outputs(dev, margin)
+    out = o.result("out", (c.B, c.cout, c.Lin * c.S))
     blob = op.pack(d["w"], dev)
     got = op.forward(blob, t["bias"], t["x"], out=out, res=t["res"], accsrc=t["accsrc"], accmode=c.accmode, div=c.div, slope=c.slope,
                      in_mask=t["in_mask"], out_mask=t["out_mask"])
     assert got.data_ptr() == out.data_ptr()
-    torch.cuda.synchronize()
-    whole = whole.cpu()
-    n = out.numel()
-    assert bool((whole[:margin] == SENTINEL).all()) and bool((whole[margin + n:] == SENTINEL).all()), "%s wrote outside its output" % c.id
-    return whole[margin:margin + n].view(out.shape).clone()
-
-
-_HEADER = []
+    return o.collect(c.id, values=False)["out"]          # written / finite: asserted by the caller, after its table row
 
 
 @pytest.mark.parametrize("cid", [c.id for c in C.CASES])
@@ -72,10 +44,8 @@ def test_layer_matches_float64(S, dev, cid):
     got = run_case(S, dev, c, d, op)
     finite = bool(torch.isfinite(got).all())
     e = C.relerr(got, ref) if finite else float("nan")
-    if not _HEADER:
-        _HEADER.append(1)
-        print("\n%-28s %-22s %-8s %9s %9s %9s" % ("case", "instance MT,TPS,AI,KCH", "epilogue", "max|ref|", "e", "e32"))
-    print("%-28s %-22s %-8s %9.3f %9.2e %9.2e" % (c.id, "%d,%d,%d,%d" % inst[:4], C.EPI_NAME[inst[4]], float(ref.abs().max()), e, e32))
+    table_row(__name__, "\n%-28s %-22s %-8s %9s %9s %9s" % ("case", "instance MT,TPS,AI,KCH", "epilogue", "max|ref|", "e", "e32"),
+              "%-28s %-22s %-8s %9.3f %9.2e %9.2e" % (c.id, "%d,%d,%d,%d" % inst[:4], C.EPI_NAME[inst[4]], float(ref.abs().max()), e, e32))
     assert finite, "%s: non-finite output (a read outside the input reached the result)" % c.id
     assert not bool((got == SENTINEL).any()), "%s: an output element was never written" % c.id
     assert e <= C.REL, (c.id, e)

@@ -11,64 +11,21 @@ these bounds tell sixteen restated geometry mistakes and two arithmetic ones fro
   repeats   every call is made twice and gives the same bits
   instance  the kernel instance each forward / data-gradient call ran, from the dispatch that launched it (conv_train_kernel_name)
 Run with -s for the table; the recorded figures are in profiles/dec_conv_train_parity.txt."""
-import importlib
-
 import pytest
 import torch
 
 import dec_conv_train_cases as C
-from test_gpu_enc_conv_train_ops import SENTINEL, guarded, intact
+from gpu_guards import NAN, TO, L, Outputs, dev, guarded, guarded_inputs, table_row, twice  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 MARGIN = 4096          # floats: above three rows of the widest case, a multiple of the 16-byte loads
-NAN = float("nan")
 CONV_IDS = [c.id for c in C.CASES if c.op in C.CONV_OPS]
 GLUE_IDS = [c.id for c in C.CASES if c.op in C.GLUE_OPS]
 
 
-@pytest.fixture(scope="module")
-def L():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")._lib
-
-
-@pytest.fixture(scope="module")
-def TO():
-    return importlib.import_module("speech-backbones_amd.model._train_ops")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-class Guards:
-    """Sentinel-filled, guarded result tensors and workspaces by name."""
-
-    def __init__(self, dev):
-        self.dev, self.results, self.spaces = dev, {}, {}
-
-    def result(self, name, *shape):
-        self.results[name] = guarded(torch.full(shape, SENTINEL), MARGIN, SENTINEL, self.dev)
-        return self.results[name][0]
-
-    def space(self, name, floats):
-        self.spaces[name] = guarded(torch.full((floats,), SENTINEL), MARGIN, SENTINEL, self.dev)
-        return self.spaces[name][0]
-
-    def collect(self, cid):
-        """CPU copies of the results: margins intact, every element written and finite; workspaces: margins intact."""
-        torch.cuda.synchronize()
-        got = {n: intact(v, w, MARGIN, "%s %s" % (cid, n)) for n, (v, w) in self.results.items()}
-        for n, (v, w) in self.spaces.items():
-            w = w.cpu()
-            assert bool((w[:MARGIN] == SENTINEL).all()) and bool((w[MARGIN + v.numel():] == SENTINEL).all()), "%s: written outside %s" % (cid, n)
-        return got
-
-
 def device_inputs(c, d, dev):
     """The case's inputs on the device, each inside NaN margins; a two-source input as its two tensors."""
-    t = {k: (None if v is None else guarded(v, MARGIN, NAN, dev)[0]) for k, v in d.items()}
+    t = guarded_inputs(d, d, MARGIN, dev)
     if c.c0 and c.op == "c3":
         t["x"], t["x1"] = guarded(d["x"][:, :c.c0].contiguous(), MARGIN, NAN, dev)[0], guarded(d["x"][:, c.c0:].contiguous(), MARGIN, NAN, dev)[0]
     return t
@@ -76,76 +33,65 @@ def device_inputs(c, d, dev):
 
 def run_wrappers(L, c, t, dev):
     """{y, dx, dw, db} (those the op has) through the wrappers the autograd Functions call, every result and workspace between guards."""
-    g = Guards(dev)
+    g = Outputs(dev, MARGIN)
+    res = lambda name, *shape: g.result(name, shape)
     B, ci, co, H, W, k = c.B, c.cin, c.cout, c.H, c.W, c.k
     lib = L.lib()
     x, dy, w, bias, mask = t["x"], t["dy"], t["w"], t["bias"], t["mask"]
-    wg = lambda floats: dict(dw=g.result("dw", *C.w_shape(c)), db=g.result("db", co) if C.has_bias(c) else None, workspace=g.space("ws", floats))
+    wg = lambda floats: dict(dw=res("dw", *C.w_shape(c)), db=res("db", co) if C.has_bias(c) else None, workspace=g.space("ws", floats))
     if c.op in ("c3", "c1", "c7"):
         kind = C.REGIME_KIND[c.op]
         fwd, dgrad, wgrad = [getattr(L, "conv%s_%s" % (kind, f)) for f in ("masked", "dgrad", "wgrad")]
         extra = dict(x1=t.get("x1")) if c.op == "c3" else {}
-        fwd(x, mask, w, bias, out=g.result("y", B, co, H, W), **extra)
-        dgrad(dy, w, mask, out=g.result("dx", B, ci, H, W))
+        fwd(x, mask, w, bias, out=res("y", B, co, H, W), **extra)
+        dgrad(dy, w, mask, out=res("dx", B, ci, H, W))
         nws = int(getattr(lib, "gtts_conv%s_wgrad_workspace_bytes" % kind)(B, ci, co, H, W)) // 4
         if c.op == "c1":
             wgrad(x, mask, dy, want_bias=C.has_bias(c), out=wg(nws))
         else:
             wgrad(x, mask, dy, out=wg(nws), **extra)
     elif c.op == "dn":
-        L.conv_resample(x, mask, w, bias, False, out=g.result("y", B, co, H // 2, W // 2))
-        gi = L.conv_resample(dy, L._const(dev, "ones", B, W // 2), w, None, True, dgrad_of_down=True, out=g.result("gi", B, ci, H, W))
-        L.add_masked(None, gi, mask, out=g.result("dx", B, ci, H, W))
-        z = L.zero_insert2(dy, out=g.result("z", B, co, H, W))
+        L.conv_resample(x, mask, w, bias, False, out=res("y", B, co, H // 2, W // 2))
+        gi = L.conv_resample(dy, L._const(dev, "ones", B, W // 2), w, None, True, dgrad_of_down=True, out=res("gi", B, ci, H, W))
+        L.add_masked(None, gi, mask, out=res("dx", B, ci, H, W))
+        z = L.zero_insert2(dy, out=res("z", B, co, H, W))
         L.conv3x3_wgrad(x, mask, z, out=wg(int(lib.gtts_conv3x3_wgrad_workspace_bytes(B, ci, co, H, W)) // 4))
     elif c.op == "up":
-        L.conv_resample(x, mask, w, bias, True, out=g.result("y", B, co, 2 * H, 2 * W))
+        L.conv_resample(x, mask, w, bias, True, out=res("y", B, co, 2 * H, 2 * W))
     elif c.op == "first":
-        (L.conv3x3_masked if k == 3 else L.conv1x1_masked)(x, mask, w, bias, out=g.result("y", B, co, H, W))
-        L.conv_dgrad_small(dy, w, mask, out=dict(dx=g.result("dx", B, ci, H, W)))
+        (L.conv3x3_masked if k == 3 else L.conv1x1_masked)(x, mask, w, bias, out=res("y", B, co, H, W))
+        L.conv_dgrad_small(dy, w, mask, out=dict(dx=res("dx", B, ci, H, W)))
         (L.conv3x3_wgrad if k == 3 else L.conv1x1_wgrad)(x, mask, dy, out=wg(int(lib.gtts_conv_wgrad_small_scratch_floats(B, ci, co, k))))
     elif c.op == "final":
-        L.final_conv_forward(x, w, bias, mask, out=g.result("y", B, 1, H, W))
-        L.final_conv_backward(x, w, mask, dy, out=dict(dx=g.result("dx", B, ci, H, W), dw=g.result("dw", 1, ci, 1, 1), db=g.result("db", 1),
+        L.final_conv_forward(x, w, bias, mask, out=res("y", B, 1, H, W))
+        L.final_conv_backward(x, w, mask, dy, out=dict(dx=res("dx", B, ci, H, W), dw=res("dw", 1, ci, 1, 1), db=res("db", 1),
                                                          workspace=g.space("ws", int(lib.gtts_final_conv_scratch_floats(B, ci, H, W)))))
     elif c.op == "pexp":
-        L.postnet_expand(x, mask, w, bias, out=g.result("y", B, co, H, W))
-        L.postnet_collapse(dy, mask, w, out=g.result("dx", B, H, W))
-        L.postnet_chan_dot(dy, x, mask, out=dict(dot=g.result("dw", co), sum=g.result("db", co),
+        L.postnet_expand(x, mask, w, bias, out=res("y", B, co, H, W))
+        L.postnet_collapse(dy, mask, w, out=res("dx", B, H, W))
+        L.postnet_chan_dot(dy, x, mask, out=dict(dot=res("dw", co), sum=res("db", co),
                                                  workspace=g.space("ws", int(lib.gtts_postnet_chan_dot_scratch_floats(B, co, H, W)))))
     elif c.op == "pcol":
-        L.postnet_collapse(x, mask, w, bias, out=g.result("y", B, H, W))
-        L.postnet_expand(dy, mask, w, out=g.result("dx", B, ci, H, W))
+        L.postnet_collapse(x, mask, w, bias, out=res("y", B, H, W))
+        L.postnet_expand(dy, mask, w, out=res("dx", B, ci, H, W))
         L.postnet_chan_dot(x, dy, mask, want_sum=False,
-                           out=dict(dot=g.result("dw", ci), workspace=g.space("ws", int(lib.gtts_postnet_chan_dot_scratch_floats(B, ci, H, W)))))
+                           out=dict(dot=res("dw", ci), workspace=g.space("ws", int(lib.gtts_postnet_chan_dot_scratch_floats(B, ci, H, W)))))
         L.postnet_chan_dot(dy.unsqueeze(1), None, None, want_dot=False,
-                           out=dict(sum=g.result("db", 1), workspace=g.space("ws1", int(lib.gtts_postnet_chan_dot_scratch_floats(B, 1, H, W)))))
+                           out=dict(sum=res("db", 1), workspace=g.space("ws1", int(lib.gtts_postnet_chan_dot_scratch_floats(B, 1, H, W)))))
     else:
         raise KeyError(c.op)
     return g.collect(c.id)
 
 
-def twice(run):
-    a, b = run(), run()
-    for n in a:
-        assert torch.equal(a[n].view(torch.int32), b[n].view(torch.int32)), "%s differs between two calls on the same inputs" % n
-    return a
-
-
-_HEADER = []
-
-
 def check(c, got, ref, M, base, names, instances):
     """One table row per tensor, then the catalogue's bound of each."""
-    if not _HEADER:
-        _HEADER.append(1)
-        print("\n%-46s %-3s %-66s %10s %9s %9s %9s" % ("case", "", "kernel instance", "max|ref|", "e", "e_base", "|err|/M"))
     bad = []
     for n in names:
         assert float(ref[n].abs().max()) > 0.0 and got[n].shape == ref[n].shape, (c.id, n, got[n].shape)
         e = C.relerr(got[n], ref[n])
         ratio = "%9.2e" % C.worst_ratio(got[n], ref[n], M[n]) if C.split_bf16(c, n) else "        -"
-        print("%-46s %-3s %-66s %10.3e %9.2e %9.2e %s" % (c.id, n, instances.get(n, "-"), float(ref[n].abs().max()), e, base[n], ratio))
+        table_row(__name__, "\n%-46s %-3s %-66s %10s %9s %9s %9s" % ("case", "", "kernel instance", "max|ref|", "e", "e_base", "|err|/M"),
+                  "%-46s %-3s %-66s %10.3e %9.2e %9.2e %s" % (c.id, n, instances.get(n, "-"), float(ref[n].abs().max()), e, base[n], ratio))
         if not C.passes(c, n, got[n], ref[n], M[n], base[n]):
             bad.append((n, e, base[n], ratio))
     assert not bad, (c.id, bad)
@@ -177,8 +123,8 @@ def test_glue_ops_have_the_bits_of_the_torch_expression(L, dev, cid):
     t = device_inputs(c, d, dev)
 
     def run():
-        g = Guards(dev)
-        out = g.result("out", *ref.shape)
+        g = Outputs(dev, MARGIN)
+        out = g.result("out", ref.shape)
         if c.op == "zi":
             L.zero_insert2(t["b"], out=out)
         elif c.op == "s2d":

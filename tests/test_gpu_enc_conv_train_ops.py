@@ -9,81 +9,30 @@ tests/enc_conv_train_cases.py; tests/test_enc_conv_train_cases_cpu.py proves whi
   bits     two backward calls agree bit for bit; pack_dgrad equals the ordinary pack of the flipped, transposed weight; EncConv1d's
            forward equals Conv1dOp.forward
 Run with -s for the table; the recorded figures are in profiles/enc_conv_train_parity.txt."""
-import importlib
-
 import pytest
 import torch
 
 import enc_conv_train_cases as C
+from gpu_guards import NAN, TO, Outputs, S, dev, guarded, guarded_inputs, table_row  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -12345.675
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def TO():
-    return importlib.import_module("speech-backbones_amd.model._train_ops")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def guarded(t, margin, fill, dev):
-    """(view, whole): a contiguous device copy of t in the middle of a larger allocation filled with `fill`."""
-    whole = torch.full((t.numel() + 2 * margin,), fill, dtype=torch.float32, device=dev)
-    view = whole[margin:margin + t.numel()].view(t.shape)
-    view.copy_(t)
-    return view, whole
-
-
-def intact(view, whole, margin, what):
-    """The CPU copy of a guarded output after checking that its margins still hold the sentinel and every element was written."""
-    whole = whole.cpu()
-    n = view.numel()
-    assert bool((whole[:margin] == SENTINEL).all()) and bool((whole[margin + n:] == SENTINEL).all()), "%s: written outside" % what
-    got = whole[margin:margin + n].view(view.shape).clone()
-    assert not bool((got == SENTINEL).any()), "%s: an element was never written" % what
-    assert bool(torch.isfinite(got).all()), "%s: non-finite (a read outside an input reached the result)" % what
-    return got
 
 
 def backward_through_binding(S, dev, c, d):
     """dx (None when the case asks for none), dw, db (None without a bias) on the GPU between guards."""
     fwd, tr = S.Conv1dOp(0, c.cin, c.cout, c.K, c.dil), S.Conv1dOp(0, c.cout, c.cin, c.K, c.dil)
     margin = 16 * c.L * (c.K * c.dil + 1) + 64
-    nan = float("nan")
-    t = {k: (None if d[k] is None else guarded(d[k], margin, nan, dev)[0]) for k in ("x", "dy", "in_mask", "out_mask", "w")}
-    zero = guarded(torch.zeros(c.cin), margin, nan, dev)[0]
-    sent = lambda *shape: guarded(torch.full(shape, SENTINEL), margin, SENTINEL, dev)
-    dx = None
+    t = guarded_inputs(d, ("x", "dy", "in_mask", "out_mask", "w"), margin, dev)
+    zero = guarded(torch.zeros(c.cin), margin, NAN, dev)[0]
+    o = Outputs(dev, margin)
     if c.x_grad:
-        dxv, dxw = sent(c.B, c.cin, c.L)
-        tr.forward(tr.pack_dgrad(t["w"]), zero, t["dy"], out=dxv, in_mask=t["out_mask"], out_mask=t["in_mask"])
-    dwv, dww = sent(c.cout, c.cin, c.K)
-    dbv, dbw = sent(c.cout) if c.bias else (None, None)
+        tr.forward(tr.pack_dgrad(t["w"]), zero, t["dy"], out=o.result("dx", (c.B, c.cin, c.L)), in_mask=t["out_mask"], out_mask=t["in_mask"])
     nws = fwd.wgrad_workspace_bytes(c.B, c.L)
     assert nws % 4 == 0
-    wsv, wsw = sent(nws // 4)
-    fwd.wgrad(t["x"], t["dy"], t["in_mask"], t["out_mask"], want_bias=c.bias, dw=dwv, db=dbv, workspace=wsv)
-    torch.cuda.synchronize()
-    if c.x_grad:
-        dx = intact(dxv, dxw, margin, c.id + " dx")
-    dw = intact(dwv, dww, margin, c.id + " dw")
-    db = intact(dbv, dbw, margin, c.id + " db") if c.bias else None
-    wsw = wsw.cpu()
-    assert bool((wsw[:margin] == SENTINEL).all()) and bool((wsw[margin + nws // 4:] == SENTINEL).all()), c.id + ": written outside the workspace"
-    return dx, dw, db
-
-
-_HEADER = []
+    fwd.wgrad(t["x"], t["dy"], t["in_mask"], t["out_mask"], want_bias=c.bias, dw=o.result("dw", (c.cout, c.cin, c.K)),
+              db=o.result("db", (c.cout,)) if c.bias else None, workspace=o.space("workspace", nws // 4))
+    got = o.collect(c.id)
+    return got.get("dx"), got["dw"], got.get("db")
 
 
 @pytest.mark.parametrize("cid", [c.id for c in C.CASES])
@@ -98,15 +47,13 @@ def test_gradients_match_float64(S, dev, cid):
         rows.append(("dx", dx, ref["dx"], ref32["dx"]))
     if c.bias:
         rows.append(("db", db, ref["db"], ref32["db"]))
-    if not _HEADER:
-        _HEADER.append(1)
-        print("\n%-20s %-22s %-4s %9s %9s %9s" % ("case", "slices,per,empty", "", "max|ref|", "e", "e_ref32"))
     info = S.Conv1dOp(0, c.cin, c.cout, c.K, c.dil).wgrad_info(c.B, c.L)
     bad = []
     for name, got, r64, r32 in rows:
         assert float(r64.abs().max()) > 0.0
         e, e32 = C.relerr(got, r64), C.relerr(r32, r64)
-        print("%-20s %-22s %-4s %9.3f %9.2e %9.2e" % (c.id, "%d,%d,%d" % info[3:], name, float(r64.abs().max()), e, e32))
+        table_row(__name__, "\n%-20s %-22s %-4s %9s %9s %9s" % ("case", "slices,per,empty", "", "max|ref|", "e", "e_ref32"),
+                  "%-20s %-22s %-4s %9.3f %9.2e %9.2e" % (c.id, "%d,%d,%d" % info[3:], name, float(r64.abs().max()), e, e32))
         if not e <= C.REL or (name == "db" and not e <= C.db_bound(e32)):
             bad.append((name, e, e32))
     assert not bad, (c.id, bad)

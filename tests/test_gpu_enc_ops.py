@@ -15,7 +15,6 @@ below tells restated kernel mistakes from the kernels.
             workspace's A / x / H2 slots bit for bit: the entry points are the kernels the encoder runs, not twins
 Run with -s for the table; the recorded figures are in profiles/enc_op_parity.txt."""
 import functools
-import importlib
 import math
 
 import pytest
@@ -23,48 +22,26 @@ import torch
 import torch.nn.functional as F
 
 import enc_op_cases as K
+from gpu_guards import SENTINEL, Outputs, S, dev, guarded_inputs, table_row  # noqa: F401
 from oracle import encoder_oracle as E
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -12345.675
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def guarded(t, margin, fill, dev):
-    """(view, whole): a contiguous device copy of t in the middle of a larger allocation filled with `fill`."""
-    whole = torch.full((t.numel() + 2 * margin,), fill, dtype=torch.float32, device=dev)
-    view = whole[margin:margin + t.numel()].view(t.shape)
-    view.copy_(t)
-    return view, whole
 
 
 def _run(dev, shape, margin, call):
-    """`call(out)` between guards; the CPU result after checking the sentinel margins of `out`."""
-    out, whole = guarded(torch.full(shape, SENTINEL), margin, SENTINEL, dev)
+    """`call(out)` between guards; the CPU result after checking the sentinel margins of `out` (written / finite: asserted by the
+    tests, after their table row)."""
+    o = Outputs(dev, margin)
+    out = o.result("out", shape)
     got = call(out)
     assert got.data_ptr() == out.data_ptr()
-    torch.cuda.synchronize()
-    whole = whole.cpu()
-    n = out.numel()
-    assert bool((whole[:margin] == SENTINEL).all()) and bool((whole[margin + n:] == SENTINEL).all()), "a write outside the output"
-    return whole[margin:margin + n].view(shape).clone()
+    return o.collect(values=False)["out"]
 
 
 def run_att(S, dev, c, d, path):
     B, C, L = d["q"].shape
     margin = 4 * L + 256                 # farther than any clamped lane could reach: a whole row of keys and a 64-key block
-    nan = float("nan")
-    t = {k: (None if d[k] is None else guarded(d[k], margin, nan, dev)[0]) for k in ("q", "k", "v", "mask", "ek", "ev")}
+    t = guarded_inputs(d, ("q", "k", "v", "mask", "ek", "ev"), margin, dev)
     return _run(dev, (B, C, L), margin, lambda out: S.enc_attention(t["q"], t["k"], t["v"], t["mask"], t["ek"], t["ev"], n_heads=c.heads,
                                                                     window=c.window, path=path, out=out))
 
@@ -72,8 +49,7 @@ def run_att(S, dev, c, d, path):
 def run_ln(S, dev, c, d):
     B, C, L = d["a"].shape
     margin = 16 * L + 256                # a 16-position tile of every one of 16 channel lanes
-    nan = float("nan")
-    t = {k: (None if d[k] is None else guarded(d[k], margin, nan, dev)[0]) for k in ("a", "bres", "gamma", "beta", "a_mask", "out_mask")}
+    t = guarded_inputs(d, ("a", "bres", "gamma", "beta", "a_mask", "out_mask"), margin, dev)
     return _run(dev, (B, C, L), margin, lambda out: S.enc_layernorm(t["a"], t["gamma"], t["beta"], bres=t["bres"], a_mask=t["a_mask"],
                                                                     out_mask=t["out_mask"], eps=K.EPS, relu_in=c.relu_in,
                                                                     relu_out=c.relu_out, out=out))
@@ -108,14 +84,9 @@ def att_got(S, dev, cid, path):
     return _GOT[cid, path]
 
 
-_HEADER = set()
-
-
 def _row(kind, kernel, cid, shape, regime, maxref, e, e32, b):
-    if kind not in _HEADER:
-        _HEADER.add(kind)
-        print("\n%-24s %-40s %-16s %-10s %9s %9s %9s %9s" % ("kernel", "case", "B,C,L", "regime", "max|ref|", "e", "e_ref32", "bound"))
-    print("%-24s %-40s %-16s %-10s %9.3f %9.2e %9.2e %9.2e" % (kernel, cid, "%d,%d,%d" % shape, regime, maxref, e, e32, b))
+    table_row((__name__, kind), "\n%-24s %-40s %-16s %-10s %9s %9s %9s %9s" % ("kernel", "case", "B,C,L", "regime", "max|ref|", "e", "e_ref32", "bound"),
+              "%-24s %-40s %-16s %-10s %9.3f %9.2e %9.2e %9.2e" % (kernel, cid, "%d,%d,%d" % shape, regime, maxref, e, e32, b))
 
 
 ATT_RUNS = [(c.id, p) for c in K.ATT_CASES for p in c.paths]

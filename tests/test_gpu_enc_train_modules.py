@@ -16,6 +16,8 @@ import warnings
 import pytest
 import torch
 
+from case_util import relerr_zero_exact, seq_mask as _seq_mask
+
 pytestmark = pytest.mark.gpu
 BOUND = 1e-4
 LENS = (17, 9, 1)
@@ -34,15 +36,11 @@ def M():
 
 
 def rel(got, ref):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    n = float(ref.abs().max())
-    if n == 0.0:
-        return 0.0 if bool((got == 0).all()) else float("inf")
-    return float((got - ref).abs().max() / n)
+    return relerr_zero_exact(got.detach().cpu(), ref.detach().cpu())
 
 
 def seq_mask(L, dtype=torch.float32):
-    return (torch.arange(L).unsqueeze(0) < torch.tensor(LENS).unsqueeze(1)).to(dtype).unsqueeze(1)
+    return _seq_mask(LENS, L).to(dtype).unsqueeze(1)
 
 
 def _randomise(mod, seed):

@@ -11,84 +11,41 @@ restated backward mistakes from the kernels.
   repeats   a second backward on the same inputs is torch.equal to the first, tensor by tensor
 Run with -s for the table."""
 import functools
-import importlib
 
 import pytest
 import torch
 
 import enc_op_cases as K
 import enc_train_op_cases as T
+from gpu_guards import NAN, SENTINEL, Outputs, S, dev, guarded_inputs, table_row, twice  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -12345.675
-NAN = float("nan")
 
 
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def guarded(t, margin, fill, dev):
-    """(view, whole): a contiguous device copy of t in the middle of a larger allocation filled with `fill`."""
-    whole = torch.full((t.numel() + 2 * margin,), fill, dtype=torch.float32, device=dev)
-    view = whole[margin:margin + t.numel()].view(t.shape)
-    view.copy_(t)
-    return view, whole
-
-
-class Outputs:
-    """Sentinel-filled, guarded output tensors by name; `collect` checks the margins and returns CPU copies."""
-
-    def __init__(self, shapes, margin, dev):
-        self.margin = margin
-        self.t = {n: guarded(torch.full(s, SENTINEL), margin, SENTINEL, dev) for n, s in shapes.items()}
-
-    def view(self, n):
-        return self.t[n][0] if n in self.t else None
-
-    def collect(self):
-        torch.cuda.synchronize()
-        got = {}
-        for n, (view, whole) in self.t.items():
-            w, m, k = whole.cpu(), self.margin, view.numel()
-            assert bool((w[:m] == SENTINEL).all()) and bool((w[m + k:] == SENTINEL).all()), "a write outside %s" % n
-            got[n] = w[m:m + k].view(view.shape).clone()
-        return got
-
-
-def run_att(S, dev, c, d, drop=None, twice=True):
-    """Forward + backward of one case through the ABI wrappers -> dict(out, stat, dq, dk, dv[, dek, dev]); with twice, the backward
-    runs again into fresh outputs and must give the same bits."""
+def run_att(S, dev, c, d, drop=None):
+    """Forward + backward of one case through the ABI wrappers -> dict(out, stat, dq, dk, dv[, dek, dev]); the backward runs again
+    into fresh outputs and must give the same bits.  Only the margins are checked here: written / finite are asserted by the tests,
+    after their table row."""
     B, C, L, H, w = c.B, c.heads * c.dk, c.L, c.heads, c.window
     margin = 4 * L + 256
-    inp = dict(d, dout=T.att_dout(c), drop=drop)
-    t = {n: (None if inp[n] is None else guarded(inp[n], margin, NAN, dev)[0]) for n in ("q", "k", "v", "mask", "ek", "ev", "dout", "drop")}
+    t = guarded_inputs(dict(d, dout=T.att_dout(c), drop=drop), ("q", "k", "v", "mask", "ek", "ev", "dout", "drop"), margin, dev)
     fshapes = dict(out=(B, C, L), stat=(B, H, L, 2))
     gshapes = dict(dq=(B, C, L), dk=(B, C, L), dv=(B, C, L))
     if w:
         gshapes.update(dek=(2 * w + 1, c.dk), dev=(2 * w + 1, c.dk))
-    fo = Outputs(fshapes, margin, dev)
+    fo = Outputs(dev, margin).with_results(fshapes)
     out, stat = S.enc_attention_train_forward(t["q"], t["k"], t["v"], t["mask"], t["ek"], t["ev"], t["drop"], n_heads=H, window=w,
                                               out=fo.view("out"), stat=fo.view("stat"))
     assert out.data_ptr() == fo.view("out").data_ptr()
-    got = fo.collect()
-    runs = []
-    for _ in range(2 if twice else 1):
-        go = Outputs(gshapes, margin, dev)
+    got = fo.collect(values=False)
+
+    def backward():
+        go = Outputs(dev, margin).with_results(gshapes)
         S.enc_attention_train_backward(t["q"], t["k"], t["v"], t["mask"], t["ek"], t["ev"], t["drop"], stat, t["dout"], n_heads=H, window=w,
-                                       grads={n: go.view(n) for n in gshapes})
-        runs.append(go.collect())
-    for n in gshapes:
-        if twice:
-            assert torch.equal(runs[0][n], runs[1][n]), "%s: %s differs between two backward calls on the same inputs" % (c.id, n)
-    got.update(runs[0])
+                                       grads=go.views())
+        return go.collect(values=False)
+
+    got.update(twice(backward, c.id))
     return got
 
 
@@ -101,14 +58,9 @@ def att_ref(cid, dropped):
     return c, d, drop, T.att_grads(c, d, drop=drop), T.att_grads(c, d, torch.float32, drop=drop)
 
 
-_HEADER = set()
-
-
 def _row(kind, cid, name, maxref, e, e32, b, note=""):
-    if kind not in _HEADER:
-        _HEADER.add(kind)
-        print("\n%-46s %-7s %10s %9s %9s %9s" % ("case", "tensor", "max|ref|", "e", "e_ref32", "bound"))
-    print("%-46s %-7s %10.3e %9.2e %9.2e %9.2e %s" % (cid, name, maxref, e, e32, b, note))
+    table_row((__name__, kind), "\n%-46s %-7s %10s %9s %9s %9s" % ("case", "tensor", "max|ref|", "e", "e_ref32", "bound"),
+              "%-46s %-7s %10.3e %9.2e %9.2e %9.2e %s" % (cid, name, maxref, e, e32, b, note))
 
 
 def _check_att(cid, dropped, S, dev):
@@ -178,20 +130,18 @@ def ln_ref(cid):
 def run_ln(S, dev, c, d):
     B, C, L = c.B, c.C, c.L
     margin = 16 * L + 256
-    inp = dict(d, dout=T.ln_dout(c))
-    t = {n: (None if inp[n] is None else guarded(inp[n], margin, NAN, dev)[0]) for n in ("dout", "a", "bres", "gamma", "beta", "a_mask", "out_mask")}
+    t = guarded_inputs(dict(d, dout=T.ln_dout(c)), ("dout", "a", "bres", "gamma", "beta", "a_mask", "out_mask"), margin, dev)
     shapes = dict(da=(B, C, L), dgamma=(C,), dbeta=(C,))
     if c.bres:
         shapes["dbres"] = (B, C, L)
-    runs = []
-    for _ in range(2):
-        go = Outputs(shapes, margin, dev)
+
+    def backward():
+        go = Outputs(dev, margin).with_results(shapes)
         S.enc_layernorm_backward(t["dout"], t["a"], t["gamma"], t["beta"], bres=t["bres"], a_mask=t["a_mask"], out_mask=t["out_mask"],
-                                 eps=K.EPS, relu_in=c.relu_in, relu_out=c.relu_out, grads={n: go.view(n) for n in shapes})
-        runs.append(go.collect())
-    for n in shapes:
-        assert torch.equal(runs[0][n], runs[1][n]), "%s: %s differs between two backward calls on the same inputs" % (c.id, n)
-    return runs[0]
+                                 eps=K.EPS, relu_in=c.relu_in, relu_out=c.relu_out, grads=go.views())
+        return go.collect(values=False)
+
+    return twice(backward, c.id)
 
 
 @pytest.mark.parametrize("cid", [c.id for c in K.LN_CASES])

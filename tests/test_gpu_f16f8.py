@@ -14,24 +14,11 @@ import torch
 
 from conftest import oracle_n50
 from oracle import gradtts_oracle as O
+from case_util import relerr_floor as relerr
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def relerr(a, b):
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 RAW = ["downs.0.0", "downs.0.1", "downs.1.0", "downs.1.1", "downs.2.0", "downs.2.1", "mid_block1", "mid_block2",

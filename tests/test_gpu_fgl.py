@@ -21,6 +21,7 @@ import torch
 
 import fgl_oracle as FO
 import mel_oracle as MO
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 CFG256 = (256, 40, 16000, 64)           # fewer butterflies than lanes
@@ -41,19 +42,8 @@ def c64_of(z):
 
 
 @pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
 def U():
     return importlib.import_module("speech-backbones_amd.diffvc.model.utils")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -18,7 +18,6 @@ f16f8: a range limit of the format (tests/test_gpu_range.py, contract (b)).  The
 utterance the input of the 3x3 convolution of mid_block2.block1 (mid_attn.out, 1.5e6) is the first beyond 65504 -- the first
 non-finite tap of the f16f8 plan is mid_block2.b1.raw, on both convolution kernels (walk: profiles/attention_parity.txt) -- and the up path then reaches 4.4e18.  That utterance is not finite there, utterances 0 and 1 are, and Plan.range_status() must report the limit:
 events > 0 and max |x| = inf (non-finite GroupNorm statistics).  Both tests assert this per precision."""
-import importlib
 
 import numpy as np
 import pytest
@@ -28,6 +27,7 @@ import torch.nn.functional as F
 from conftest import golden
 from oracle import diffvc_oracle as V
 from oracle import gradtts_oracle as O
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
@@ -35,17 +35,6 @@ B, T, LENGTHS = 3, 72, [72, 41, 1]
 
 precs = pytest.mark.parametrize("prec", ["bf16x3", "f16f8"])
 kernels = pytest.mark.parametrize("conv_ws", [False, True], ids=["conv_mfma", "conv_ws"])
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -17,74 +17,16 @@ import pytest
 import torch
 
 import glue_train_cases as G
+from gpu_guards import INT_GUARD, NAN, L, Outputs, dev, guarded, guarded_inputs, table_row, twice  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -12345.675
-ISENTINEL = -12345
-NAN = float("nan")
 MARGIN = 1024
 
 
-@pytest.fixture(scope="module")
-def L():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")._lib
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def guarded(t, dev):
-    """A contiguous device copy of t in the middle of a larger allocation whose margins hold NaN (int32: 2^30)."""
-    fill = NAN if t.dtype == torch.float32 else 1 << 30
-    whole = torch.full((t.numel() + 2 * MARGIN,), fill, dtype=t.dtype, device=dev)
-    view = whole[MARGIN:MARGIN + t.numel()].view(t.shape)
-    view.copy_(t)
-    return view
-
-
-class Outputs:
-    """Sentinel-filled, guarded output tensors by name; `collect` checks the margins, that every element was written, and returns CPU
-    copies."""
-
-    def __init__(self, shapes, dev):
-        self.t = {}
-        for n, (shape, dtype) in shapes.items():
-            fill = SENTINEL if dtype == torch.float32 else ISENTINEL
-            numel = 1
-            for s in shape:
-                numel *= s
-            whole = torch.full((numel + 2 * MARGIN,), fill, dtype=dtype, device=dev)
-            self.t[n] = (whole[MARGIN:MARGIN + numel].view(shape), whole, fill)
-
-    def views(self):
-        return {n: v[0] for n, v in self.t.items()}
-
-    def collect(self):
-        torch.cuda.synchronize()
-        got = {}
-        for n, (view, whole, fill) in self.t.items():
-            w, k = whole.cpu(), view.numel()
-            ref = torch.tensor(fill, dtype=w.dtype)
-            assert bool((w[:MARGIN] == ref).all()) and bool((w[MARGIN + k:] == ref).all()), "a write outside %s" % n
-            got[n] = w[MARGIN:MARGIN + k].view(view.shape).clone()
-            assert not bool((got[n] == ref).any()), "an element of %s was never written" % n
-            if got[n].dtype == torch.float32:
-                assert bool(torch.isfinite(got[n]).all()), "non-finite %s (a read outside an input)" % n
-        return got
-
-
-_HEADER = []
-
-
 def held(cid, name, got, ref, r32, fails):
-    if not _HEADER:
-        _HEADER.append(1)
-        print("\n%-34s %-10s %10s %9s %9s %9s" % ("case", "tensor", "max|ref|", "e", "e_ref32", "bound"))
     e32, e = G.relerr(r32, ref), G.relerr(got, ref)
-    print("%-34s %-10s %10.3e %9.2e %9.2e %9.2e" % (cid, name, float(torch.as_tensor(ref).abs().max()), e, e32, G.bound(e32)))
+    table_row(__name__, "\n%-34s %-10s %10s %9s %9s %9s" % ("case", "tensor", "max|ref|", "e", "e_ref32", "bound"),
+              "%-34s %-10s %10.3e %9.2e %9.2e %9.2e" % (cid, name, float(torch.as_tensor(ref).abs().max()), e, e32, G.bound(e32)))
     if not (e <= 4.0 * e32 + G.GRAD_ABS and e <= G.GRAD_REL):
         fails.append((name, e, e32))
 
@@ -103,37 +45,39 @@ def refs(fam, cid):
 @pytest.mark.parametrize("cid", [c.id for c in G.A_CASES])
 def test_first_layer_data_gradient_matches_float64(L, dev, cid):
     c, d, ref, r32, _ = refs("A", cid)
-    t = {n: guarded(d[n], dev) for n in ("dy", "w", "mask")}
-    runs = []
-    for _ in range(2):
-        o = Outputs(dict(dx=((c.B, c.cin, c.H, c.W), torch.float32)), dev)
+    t = guarded_inputs(d, ("dy", "w", "mask"), MARGIN, dev)
+
+    def run():
+        o = Outputs(dev, MARGIN).with_results(dict(dx=(c.B, c.cin, c.H, c.W)))
         dx = L.conv_dgrad_small(t["dy"], t["w"], t["mask"], out=o.views())
         assert dx.data_ptr() == o.views()["dx"].data_ptr()
-        runs.append(o.collect())
-    assert torch.equal(runs[0]["dx"], runs[1]["dx"]), "%s: dx differs between two calls on the same inputs" % cid
+        return o.collect()
+
+    got = twice(run, cid)
     fails = []
-    held(cid, "dx", runs[0]["dx"], ref["dx"], r32["dx"], fails)
+    held(cid, "dx", got["dx"], ref["dx"], r32["dx"], fails)
     assert not fails, (cid, fails)
-    assert float((runs[0]["dx"] * (1.0 - d["mask"])[:, None, None, :]).abs().max()) == 0.0      # a masked column receives no gradient
+    assert float((got["dx"] * (1.0 - d["mask"])[:, None, None, :]).abs().max()) == 0.0      # a masked column receives no gradient
 
 
 @pytest.mark.parametrize("mode", G.B_MODES)
 @pytest.mark.parametrize("cid", [c.id for c in G.B_CASES])
 def test_noising_backward_matches_float64(L, dev, cid, mode):
     c, d, ref, r32, _ = refs("B", cid)
-    t = {n: guarded(d[n], dev) for n in ("dxt", "mask", "t")}
+    t = guarded_inputs(d, ("dxt", "mask", "t"), MARGIN, dev)
     want = ("dx0", "dmu") if mode == "both" else (mode,)
-    runs = []
-    for _ in range(2):
-        o = Outputs({n: ((c.B, c.F, c.T), torch.float32) for n in want}, dev)
+
+    def run():
+        o = Outputs(dev, MARGIN).with_results({n: (c.B, c.F, c.T) for n in want})
         dx0, dmu = L.diffusion_noising_backward(t["dxt"], t["mask"], t["t"], G.BETA_MIN, G.BETA_MAX, want_dx0="dx0" in want,
                                                 want_dmu="dmu" in want, out=o.views())
         assert (dx0 is None) == ("dx0" not in want) and (dmu is None) == ("dmu" not in want)
-        runs.append(o.collect())
+        return o.collect()
+
+    got = twice(run, cid)
     fails = []
     for n in want:
-        assert torch.equal(runs[0][n], runs[1][n]), "%s: %s differs between two calls on the same inputs" % (cid, n)
-        held(cid + " " + mode, n, runs[0][n], ref[n], r32[n], fails)
+        held(cid + " " + mode, n, got[n], ref[n], r32[n], fails)
     assert not fails, (cid, mode, fails)
 
 
@@ -159,52 +103,54 @@ def test_alignment_glue_matches_float64(L, dev, cid):
     B, Fd, tx, T, S = c.B, c.F, c.tx, c.T, d["S"]
     kept = G.c_kept(c, d).to(torch.int32)
     f32, i32 = torch.float32, torch.int32
-    t = {n: guarded(d[n], dev) for n in ("path", "mu_x", "logw", "x_mask", "y", "g_mu_y")}
-    t["start"], t["kept"] = guarded(torch.tensor(d["starts"], dtype=i32), dev), guarded(kept, dev)
+    t = guarded_inputs(d, ("path", "mu_x", "logw", "x_mask", "y", "g_mu_y"), MARGIN, dev)
+    t.update(guarded_inputs(dict(start=torch.tensor(d["starts"], dtype=i32), kept=kept), ("start", "kept"), MARGIN, dev))
     fails = []
     # ---- the index form of the path: counts, compared exactly
-    o = Outputs(dict(idx=((B, T), i32), dur=((B, tx), f32), first=((B, tx), i32)), dev)
+    o = Outputs(dev, MARGIN).with_results(dict(idx=(B, T), dur=(B, tx), first=(B, tx)), dtypes=dict(idx=i32, first=i32))
     idx, dur, first = L.align_index(t["path"], out=o.views())
     got = o.collect()
     for n in ("idx", "dur", "first"):
         assert torch.equal(got[n], man[n]), (cid, n)
     # ---- duration loss and d / d logw
     inv_d = 1.0 / float(d["x_lengths"].sum())
-    runs = []
-    for _ in range(2):
-        o = Outputs(dict(partials=((B,), f32), grad=((B, 1, tx), f32)), dev)
+
+    def duration_loss():
+        o = Outputs(dev, MARGIN).with_results(dict(partials=(B,), grad=(B, 1, tx)))
         total, g = L.duration_loss(t["logw"], dur, t["x_mask"], out=o.views())
-        runs.append(dict(o.collect(), total=total.cpu()))
-    assert all(torch.equal(runs[0][n], runs[1][n]) for n in runs[0]), "%s: the duration loss differs between two calls" % cid
-    held(cid, "dur_loss", runs[0]["total"].double() * inv_d, ref["dur_loss"], r32["dur_loss"], fails)
-    held(cid, "dlogw", runs[0]["grad"].double() * (G.G_DUR * inv_d), ref["dlogw"], r32["dlogw"], fails)
+        return dict(o.collect(), total=total.cpu())
+
+    got = twice(duration_loss, cid + ", the duration loss")
+    held(cid, "dur_loss", got["total"].double() * inv_d, ref["dur_loss"], r32["dur_loss"], fails)
+    held(cid, "dlogw", got["grad"].double() * (G.G_DUR * inv_d), ref["dlogw"], r32["dlogw"], fails)
     # ---- crop + gather + prior loss: copies compared exactly
     inv_p = 1.0 / (float(kept.sum()) * Fd)
-    o = Outputs(dict(y_c=((B, Fd, S), f32), mu_y=((B, Fd, S), f32), partials=((int(L.lib().gtts_align_gather_partials(B, Fd, S)),), f32)), dev)
+    o = Outputs(dev, MARGIN).with_results(dict(y_c=(B, Fd, S), mu_y=(B, Fd, S), partials=(int(L.lib().gtts_align_gather_partials(B, Fd, S)),)))
     y_c, mu_y, total = L.align_gather(t["mu_x"], t["y"], idx, t["start"], t["kept"], S, out=o.views())
     got = dict(o.collect(), total=total.cpu())
     for n in ("y_c", "mu_y"):
         assert torch.equal(got[n], man[n].float()) and torch.equal(got[n], r32[n]), (cid, n)
     held(cid, "prior_loss", got["total"].double() * inv_p, ref["prior_loss"], r32["prior_loss"], fails)
     # (start and kept live on the device: a kept above S cannot be refused on the host -- it counts as S)
-    o2 = Outputs(dict(y_c=((B, Fd, S), f32), mu_y=((B, Fd, S), f32), partials=(tuple(got["partials"].shape), f32)), dev)
+    o2 = Outputs(dev, MARGIN).with_results(dict(y_c=(B, Fd, S), mu_y=(B, Fd, S), partials=tuple(got["partials"].shape)))
     over = torch.where(kept == S, kept + 5, kept)
-    L.align_gather(t["mu_x"], t["y"], idx, t["start"], guarded(over, dev), S, out=o2.views())
+    L.align_gather(t["mu_x"], t["y"], idx, t["start"], guarded(over, MARGIN, INT_GUARD, dev)[0], S, out=o2.views())
     got2 = o2.collect()
     assert all(torch.equal(got[n], got2[n]) for n in ("y_c", "mu_y", "partials")), "%s: kept > S must count as S" % cid
     # ---- the segment sum: gradient through mu_y plus the prior loss's own
-    scale = guarded(torch.tensor([G.G_PRIOR * inv_p], dtype=f32), dev)
-    runs = []
-    for _ in range(2):
-        o = Outputs(dict(dmu_x=((B, Fd, tx), f32)), dev)
+    scale = guarded(torch.tensor([G.G_PRIOR * inv_p], dtype=f32), MARGIN, NAN, dev)[0]
+
+    def backward():
+        o = Outputs(dev, MARGIN).with_results(dict(dmu_x=(B, Fd, tx)))
         L.align_gather_backward(t["g_mu_y"], mu_y, y_c, scale, dur, first, t["start"], t["kept"], out=o.views())
-        runs.append(o.collect())
-    assert torch.equal(runs[0]["dmu_x"], runs[1]["dmu_x"]), "%s: dmu_x differs between two backward calls on the same inputs" % cid
-    held(cid, "dmu_x", runs[0]["dmu_x"], ref["dmu_x"], r32["dmu_x"], fails)
+        return o.collect()
+
+    dmu_x = twice(backward, cid)["dmu_x"]
+    held(cid, "dmu_x", dmu_x, ref["dmu_x"], r32["dmu_x"], fails)
     assert not fails, (cid, fails)
     # tokens without a live frame (padding, outside the window) get exact zeros; either term alone is the other's complement
     dead = man["dmu_x"].abs().sum(1) == 0
-    assert float(runs[0]["dmu_x"].abs().sum(1)[dead].max() if bool(dead.any()) else 0.0) == 0.0
+    assert float(dmu_x.abs().sum(1)[dead].max() if bool(dead.any()) else 0.0) == 0.0
     only_g = L.align_gather_backward(t["g_mu_y"], None, None, None, dur, first, t["start"], t["kept"]).cpu().double()
     only_p = L.align_gather_backward(None, mu_y, y_c, scale, dur, first, t["start"], t["kept"]).cpu().double()
     assert G.relerr(only_g + only_p, ref["dmu_x"]) <= G.bound(G.relerr(r32["dmu_x"], ref["dmu_x"])), cid

@@ -10,25 +10,12 @@ import torch
 
 from conftest import golden
 from oracle import hifigan_oracle as H
+from case_util import relerr_floor as relerr
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
 CFGS = {"v1": H.V1, "small": H.SMALL, "rb2": H.SMALL_RB2}
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def relerr(a, b):
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 @pytest.mark.parametrize("tag", ["v1", "small", "rb2"])

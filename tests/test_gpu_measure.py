@@ -2,25 +2,14 @@
 the un-traced timeline records every launch of a sampler call on the stream it ran on, and the one-launch batched weight pack
 (gtts_pack_batch) is bit-identical to the per-weight packs it replaces."""
 import ctypes
-import importlib
 
 import pytest
 import torch
 
 from oracle import gradtts_oracle as O
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 def test_measured_ceilings_are_sane(S, dev):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import mel_oracle as MO
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 L37 = 256 * 37 + 100
@@ -21,19 +22,8 @@ CFGS = {"cfg1": MO.CFG1, "cfg2": MO.CFG2}
 
 
 @pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
 def MD():
     return importlib.import_module("speech-backbones_amd.hifi_gan.meldataset")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

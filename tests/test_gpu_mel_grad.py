@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 import mel_grad_cases as C
 import mel_oracle as MO
+from gpu_guards import S, dev  # noqa: F401
 from oracle import hifigan_oracle as H
 
 pytestmark = pytest.mark.gpu
@@ -24,19 +25,8 @@ PARITY = [(c, B) for c in C.CASES for B in ((3,) if c[2] else (1, 2, 3))]       
 
 
 @pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
 def MD():
     return importlib.import_module("speech-backbones_amd.hifi_gan.meldataset")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -19,7 +19,7 @@ Check kinds (op_parity_cases.CLAIMS) and their references:
   tail_identity  Mish(GN(b2.raw)) * mask + x * mask           res_tail   ... + res_conv(x * mask)
   downsample     conv2d(stride 2) of the masked attention output; where the level-0 attention output is folded into the Downsample's
                  weights (bf16x3 / f16f8) the op reads the attention's INPUT X, and the reference is that convolution of
-                 (X + g * LinearAttention(X)) * mask, the attention in float64 (attention_f64 of tests/test_gpu_attention.py)
+                 (X + g * LinearAttention(X)) * mask, the attention in float64 (attention_f64 of tests/op_parity_cases.py)
   upsample       conv_transpose2d(stride 2, padding 1) of the masked input
   ref_conv       DiffVC RefBlock convolutions: input (GLU(InstanceNorm(prev.raw)) [+ time bias]) * ref_mask, float64 statistics
   instnorm       ref.blockNN.sc / .sh against float64 instance statistics (all positions, like InstanceNorm2d)
@@ -32,10 +32,10 @@ Check kinds (op_parity_cases.CLAIMS) and their references:
                  not 0 at those frames, and the comparison covers them like every other element)
 
 Bounds (the project's existing ones):
-  bf16x3 / f16f8 contractions   e <= 1e-4 (REL of tests/test_gpu_parity_full.py); own error column: the same op in fp32 torch
+  bf16x3 / f16f8 contractions   e <= 1e-4 (REL of tests/op_parity_cases.py); own error column: the same op in fp32 torch
   scale / shift                 e <= 1e-5
   elementwise fp32              e <= 4 e_ref32 + 2e-6 (tests/test_gpu_spk.py), e_ref32 the same op in float32 torch on the CPU
-  bf16 / bf16_store             e <= 4 e_fmt (FMT_FACTOR of tests/test_gpu_attention.py): e_fmt is the float64 reference with the contraction's
+  bf16 / bf16_store             e <= 4 e_fmt (FMT_FACTOR of tests/op_parity_cases.py): e_fmt is the float64 reference with the contraction's
                                 input (after its prologue, where the kernel rounds it) and weights rounded to bf16, bf16_store: the output
                                 rounded too.  An elementwise op with a bf16 output: e_fmt is that output rounding.
   bf16, fp32 storage            in addition e_vs_fmt <= e_fmt: the kernel against the rounded-operand product itself must be nearer to it
@@ -50,7 +50,6 @@ Bounds (the project's existing ones):
                                 statistics from *.raw in float64.
 Each op prints one row with -s: label, kernel instance (Plan.ops), shape, e_kernel, the reference's own error, the bound; the rows of a
 whole case are printed before anything is asserted.  Figures: profiles/op_parity.txt."""
-import importlib
 import math
 
 import pytest
@@ -58,26 +57,15 @@ import torch
 import torch.nn.functional as F
 
 import op_parity_cases as C
+from op_parity_cases import FMT_FACTOR, REL, RESNETS, _reader, attention_f64
 from oracle import diffvc_oracle as V
 from oracle import gradtts_oracle as O
-from test_gpu_attention import FMT_FACTOR, _reader, attention_f64
-from test_gpu_parity_full import REL, RESNETS
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SCALE_SHIFT = 1e-5
 SEED = 99
 T_VALUE = 0.7           # DiffVC: the t at which xt_ref was diffused; the estimator call itself gets one t per utterance, like Grad-TTS
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 # ------------------------------------------------------------------------------------------------ float64 / float32 operations

@@ -14,28 +14,15 @@ import torch
 from conftest import golden
 from oracle import gradtts_oracle as O
 from oracle import mas as MAS
+from case_util import relerr_floor as relerr
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
 
 
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
 def _t(a):
     return torch.from_numpy(np.asarray(a))
-
-
-def relerr(a, b):
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 _plans = {}

@@ -20,26 +20,13 @@ from conftest import oracle_n50
 
 from oracle import diffvc_oracle as V
 from oracle import gradtts_oracle as O
+from case_util import relerr_floor as relerr
+from gpu_guards import S, dev  # noqa: F401
+from op_parity_cases import ATTNS, REL, RESNETS
 
 pytestmark = pytest.mark.gpu
-REL = 1e-4          # bf16x3 contractions, fp32 accumulate (measured ~2e-5 per call)
 REL_BF16 = 2.5e-2   # plain-bf16 contractions (config 3), single estimator call (measured ~8e-3)
 REL_BF16_STORE = 4e-2   # bf16 contractions AND bf16 activation storage (config 3 as written)
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def relerr(a, b):
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 # ------------------------------------------------------------------------------------------------ config 2, N = 50
@@ -70,12 +57,6 @@ def test_reverse_diffusion_n50_t1024_mel_scale_abs(S, dev):
 
 
 # ------------------------------------------------------------------------------------------------ per-op parity
-RESNETS = ["downs.0.0", "downs.0.1", "downs.1.0", "downs.1.1", "downs.2.0", "downs.2.1", "mid_block1", "mid_block2",
-           "ups.0.0", "ups.0.1", "ups.1.0", "ups.1.1"]
-ATTNS = {"downs.0.2": "downs.0.1", "downs.1.2": "downs.1.1", "downs.2.2": "downs.2.1", "mid_attn": "mid_block1",
-         "ups.0.2": "ups.0.1", "ups.1.2": "ups.1.1"}
-
-
 def _run_with_taps(S, dev, sd, B, T, n_spks=1, seed=1234, conv_ws=False):
     inp = O.make_inputs(B, T, seed=seed, spk_dim=64 if n_spks > 1 else None)
     t = torch.linspace(0.15, 0.9, B)

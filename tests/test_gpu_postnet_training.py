@@ -14,19 +14,9 @@ import torch.nn.functional as F
 
 from oracle import encoder_oracle as E
 from oracle import postnet_oracle as P
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 def _modules():

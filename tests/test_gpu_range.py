@@ -14,23 +14,10 @@ import pytest
 import torch
 
 from oracle import gradtts_oracle as O
+from case_util import relerr_floor as relerr
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def relerr(a, b):
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 def _big_weight_state(value=70.0, layer="downs.1.0.block2.block.0.weight"):

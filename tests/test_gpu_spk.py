@@ -5,27 +5,16 @@ Bounds.  Parity: max |hidden - ref| <= 1e-3 and max |embeds - ref| <= 1e-3, the 
 O(1) hidden state and the unit-norm embedding.  Precision: the kernels are fp32 throughout (fp32-input MFMA = an fmaf chain, expf,
 tanhf), so e_kernel <= 4 e_ref32 + 2e-6 is asserted as well, e_ref32 being the same recipe in float32 torch on the CPU; with -s every
 case prints both and their ratio.  Batch and slicing independence: bit for bit.  The sequence tile is 16: (17, 160) crosses it."""
-import importlib
 
 import numpy as np
 import pytest
 import torch
 
 import spk_oracle as SO
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(1, 1), (1, 2), (3, 7), (16, 160), (17, 160), (1, 1000)]
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

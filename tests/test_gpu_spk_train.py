@@ -18,24 +18,14 @@ import torch
 
 import ge2e_oracle as GO
 import spk_oracle as SO
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
 def G():
     return importlib.import_module("speech-backbones_amd.diffvc.speaker_encoder.encoder.ge2e")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

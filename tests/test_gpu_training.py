@@ -10,24 +10,11 @@ import torch
 import torch.nn.functional as F
 
 from oracle import gradtts_oracle as O
+from case_util import relerr_floor as relerr
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def relerr(a, b):
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 @pytest.mark.parametrize("B,cin,cout,H,W", [(2, 64, 64, 80, 64), (1, 128, 256, 20, 44), (3, 256, 128, 10, 17), (2, 512, 128, 20, 16),

@@ -24,20 +24,10 @@ import torch.nn.functional as F
 
 import wgrad_regimes as R
 from oracle import gradtts_oracle as O
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def S():
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

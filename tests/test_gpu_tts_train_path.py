@@ -16,6 +16,7 @@ import random
 
 import pytest
 import torch
+from case_util import relerr_floor as relerr
 
 pytestmark = pytest.mark.gpu
 B, TX, T = 3, 17, 64
@@ -26,10 +27,6 @@ X_LENGTHS, Y_LENGTHS = (17, 11, 14), (64, 48, 40)
 def dev():
     assert torch.cuda.is_available()
     return torch.device("cuda:0")
-
-
-def relerr(a, b):
-    return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
 @functools.lru_cache(maxsize=None)

@@ -12,6 +12,7 @@ import torch
 
 import spk_oracle as SO
 import wav_oracle as WO
+from gpu_guards import S, dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 L37 = 441 * 37 + 100
@@ -20,18 +21,6 @@ L_MEL_TILE = 160 * 32       # 33 frames: one past a tile of the mel kernel (16 f
 RESAMPLE_CASES = [(22050, 16000, L) for L in (1, 5, 441, 442, 1000, L37, L_RS_TILE)] + \
                  [(s, r, L) for (s, r) in WO.RATIOS[1:] for L in (5, 1000)]
 MEL_LENGTHS = (201, 400, 1600, 160 * 59 + 31, 16000, L_MEL_TILE)
-
-
-@pytest.fixture(scope="module")
-def S():
-    import importlib
-    assert torch.cuda.is_available()
-    return importlib.import_module("speech-backbones_amd")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
