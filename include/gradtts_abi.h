@@ -818,6 +818,49 @@ int gtts_align_gather_backward(const float *g_mu_y, const float *mu_y, const flo
                                const int *first, const int *start, const int *kept, float *dmu_x, int B, int F, int t_x, int S,
                                gtts_stream_t stream);
 
+/* ---- ABI 7 (additive): the condition path of the DiffVC decoder's training step (csrc/train_cond.hip, csrc/train_inglu.hip) -----------
+ * All fp32 VALU kernels, no atomics, every sum in a fixed order: two calls on the same inputs give the same bits.  The caller owns
+ * every buffer; arguments are checked on the host before anything is launched (GTTS_E_NULL, then GTTS_E_SHAPE: B, C, H, W < 1,
+ * B > 65535 or H W >= 2^31, then GTTS_E_CONFIG).
+ * Condition field: the convolution of the condition vector broadcast over the mel plane (DiffVC/model/diffusion.py:74-76) as the bias
+ * field it is.  U [B,taps,C], taps = 9 in (kh, kw) order (a 3x3 convolution with padding 1) or 1 (a 1x1); mask [B,W]:
+ *   out[b,c,h,w] = base[b,c,h,w] + sum_{kh,kw} [0 <= h+kh-1 < H][0 <= w+kw-1 < W] mask[b,w+kw-1] U[b,kh,kw,c]     (taps 1: mask[b,w] U[b,c])
+ * base (nullable: zeros) and out [B,C,H,W], two buffers.  GTTS_E_CONFIG for any other taps. */
+int gtts_cond_field_forward(const float *U, const float *mask, const float *base, float *out, int B, int C, int H, int W, int taps,
+                            gtts_stream_t stream);
+/* S[b,kh,kw,c] = sum_{h,w} dy[b,c,h,w] (the same gates): dy [B,C,H,W] is read once -> S [B,taps,C]. */
+int gtts_cond_field_backward(const float *dy, const float *mask, float *S, int B, int C, int H, int W, int taps, gtts_stream_t stream);
+/* RefBlock's masked mean (DiffVC/model/modules.py:165-166): p[b,c] = sum_{h,w} y[b,c,h,w] mask[b,w] / (sum_w mask[b,w] H), y [B,C,H,W],
+ * mask [B,W] -> p [B,C] (a row of mask without a live column divides by zero, as the composition does), and its gradient
+ * dy[b,c,h,w] = dp[b,c] mask[b,w] / (sum_w mask[b,w] H). */
+int gtts_masked_mean_forward(const float *y, const float *mask, float *p, int B, int C, int H, int W, gtts_stream_t stream);
+int gtts_masked_mean_backward(const float *dp, const float *mask, float *dy, int B, int C, int H, int W, gtts_stream_t stream);
+/* gtts_in_glu_forward / _backward with RefBlock's time-bias add (modules.py:159,162) behind the GLU: out = IN-GLU(y) + tb[b,c], tb [B,C];
+ * the backward call also writes dtb [B,C] = sum_{h,w} dout.  stats and scratch as for gtts_in_glu_*; dy, dgamma and dbeta have the bits
+ * gtts_in_glu_backward gives on the same dout. */
+int gtts_in_glu_tb_forward(const float *y, const float *gamma, const float *beta, const float *tb, float *out, float *stats, int B, int C,
+                           int H, int W, float eps, gtts_stream_t stream);
+int gtts_in_glu_tb_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *stats, float *dy,
+                            float *dgamma, float *dbeta, float *dtb, float *scratch, int B, int C, int H, int W, gtts_stream_t stream);
+
+/* RefBlock's narrow 3x3 convolutions (csrc/train_narrow.hip): cin 1 or 32, cout 64 or 128 (GTTS_E_CONFIG otherwise; the data gradient:
+ * cin 32), padding 1, the semantics of gtts_conv3x3_masked --
+ *   y[b,n,h,w] = omask[b,w] (bias[n] + sum_{k,kh,kw} w[n,k,kh,kw] x[b,k,h+kh-1,w+kw-1] mask[b,w+kw-1])      omask nullable (no output mask)
+ * on the fp32-input MFMA (fp32 products, fp32 accumulation in a fixed order: fp32-grade results, the same bits on every call).
+ * x [B,cin,H,W], w [cout][cin][3][3] (the module's layout, nothing packed by the caller), mask / omask [B,W], y / dy [B,cout,H,W].
+ * workspace: gtts_conv3x3_narrow_workspace_bytes(B, cin, cout, H, W, op) bytes, op 0 forward, 1 data gradient (both: the re-laid-out
+ * weights), 2 weight gradient (per-slice partial sums, added in slice order by a second kernel); 0 for what the entry points refuse.
+ * GTTS_E_SHAPE: B, H, W < 1, B > 65535, H W >= 2^29; GTTS_E_WORKSPACE: fewer bytes than that.
+ *   dgrad  dx = mask * (the convolution of dy omask with the transposed, flipped weights): the gradient of the forward call w.r.t. x
+ *   wgrad  dw [cout][cin][3][3] and db [cout] (nullable) of the forward call: sums over (dy omask) and (x mask) */
+size_t gtts_conv3x3_narrow_workspace_bytes(int B, int cin, int cout, int H, int W, int op);
+int gtts_conv3x3_narrow_forward(const float *x, const float *mask, const float *omask, const float *w, const float *bias, float *y,
+                                void *workspace, size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream);
+int gtts_conv3x3_narrow_dgrad(const float *dy, const float *omask, const float *mask, const float *w, float *dx, void *workspace,
+                              size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream);
+int gtts_conv3x3_narrow_wgrad(const float *x, const float *mask, const float *omask, const float *dy, float *dw, float *db, void *workspace,
+                              size_t workspace_bytes, int B, int cin, int cout, int H, int W, gtts_stream_t stream);
+
 /* ---- debugging / tests: named intermediates of the last estimator call (keep_intermediates plans) ----- */
 int gtts_plan_num_tensors(const gtts_plan *plan);
 /* offset is in bytes into the workspace for the given (B,T); dims = {B,C,H,W}. */

@@ -228,6 +228,16 @@ def lib():
         L.gtts_in_glu_scratch_floats.restype = sz
         L.gtts_in_glu_forward.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, vp]
         L.gtts_in_glu_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
+        L.gtts_in_glu_tb_forward.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, f, vp]
+        L.gtts_in_glu_tb_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp]
+        L.gtts_cond_field_forward.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp]
+        L.gtts_cond_field_backward.argtypes = [vp, vp, vp, i, i, i, i, i, vp]
+        L.gtts_masked_mean_forward.argtypes = [vp, vp, vp, i, i, i, i, vp]
+        L.gtts_masked_mean_backward.argtypes = [vp, vp, vp, i, i, i, i, vp]
+        L.gtts_conv3x3_narrow_workspace_bytes.argtypes, L.gtts_conv3x3_narrow_workspace_bytes.restype = [i, i, i, i, i, i], sz
+        L.gtts_conv3x3_narrow_forward.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
+        L.gtts_conv3x3_narrow_dgrad.argtypes = [vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
+        L.gtts_conv3x3_narrow_wgrad.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, i, i, i, i, i, vp]
         L.gtts_conv7x7_packed_bytes.argtypes = [i, i]
         L.gtts_conv7x7_packed_bytes.restype = sz
         L.gtts_conv7x7_pack.argtypes = [vp, vp, i, i, i, vp]
@@ -1525,7 +1535,15 @@ def conv3x3_supported(cin, cout, need_dgrad=True, shape=None):
         return False
     if cin in (2, 3):
         return _tiles(cout) and _dgrad_small_ok(need_dgrad, shape)
+    if conv3x3_narrow(cin, cout):
+        return cin == 32 or not need_dgrad
     return cin % 32 == 0 and cout % 32 == 0 and _tiles(cin) and _tiles(cout)
+
+
+def conv3x3_narrow(cin, cout):
+    """RefBlock's narrow layers (DiffVC/model/modules.py:128-157 at base 32): 1 or 32 input channels, which fit no 64-channel tile and
+    have kernels of their own (csrc/train_narrow.hip; cin 1: no data gradient -- its input is data)."""
+    return int(cin) in (1, 32) and int(cout) in (64, 128)
 
 
 _PACKED = {}       # (id(weight), transposed, kind) -> (weakref to the weight, its version, pack generation, packed blob)
@@ -1739,12 +1757,16 @@ def conv3x3_masked(x, mask_cols, weight, bias, x1=None, out=None):
     """Conv2d_3x3(cat(x, x1) * mask) + bias (Block.forward, diffusion.py:56-57; the concatenation of the up path, :166, is read in
     place): x [B,c0,H,W], x1 [B,c1,H,W] or None, mask_cols [B,W], weight [cout,c0+c1,3,3].  `out`: optional preallocated result."""
     x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
+    if x1 is None and conv3x3_narrow(weight.shape[1], weight.shape[0]):
+        return conv3x3_narrow_forward(x, mask_cols, weight, bias, out=None if out is None else {"out": out})
     return _conv_run("3x3", x, mask_cols, weight, bias, False, _f32c(x1, "x1"), out=out)
 
 
 def conv3x3_dgrad(dy, weight, mask_cols=None, out=None):
     """Gradient of conv3x3_masked w.r.t. (x * mask): a 3x3 convolution of dy with the transposed, flipped weights; with
     mask_cols [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue).  `out`: optional preallocated result."""
+    if conv3x3_narrow(weight.shape[1], weight.shape[0]):
+        return conv3x3_narrow_dgrad(dy, weight, mask_cols, out=None if out is None else {"dx": out})
     return _conv_dgrad("3x3", dy, weight, mask_cols, out=out)
 
 
@@ -1755,10 +1777,74 @@ def conv3x3_wgrad(x, mask_cols, dy, x1=None, out=None):
     cin, cout = int(x.shape[1]) + (int(x1.shape[1]) if x1 is not None else 0), int(dy.shape[1])
     if cin in (2, 3) and x1 is None:
         return _wgrad_small(x, mask_cols, dy, 3, out=out)
+    if x1 is None and conv3x3_narrow(cin, cout):
+        return conv3x3_narrow_wgrad(x, mask_cols, dy, out=out)
     if cin % 64 or cout % 64:
         raise ValueError("conv3x3_wgrad: cin and cout must be multiples of 64, or cin 2 or 3 from one source (got cin %d, cout %d)"
                          % (cin, cout))
     return _tiled_wgrad("3x3", x, mask_cols, dy, x1, out=out)
+
+
+def _narrow_ws(out, B, cin, cout, H, W, op, device):
+    nws = int(lib().gtts_conv3x3_narrow_workspace_bytes(B, cin, cout, H, W, op))
+    if nws == 0:
+        raise ValueError("the narrow 3x3 kernels take cin 1 or 32 (the data gradient: 32) and cout 64 or 128 (got cin %d, cout %d, B %d, "
+                         "%d x %d)" % (cin, cout, B, H, W))
+    return _scratch(out, nws, device), nws
+
+
+def conv3x3_narrow_forward(x, mask_cols, weight, bias, out_mask=None, out=None):
+    """Conv2d_3x3(x * mask) + bias [times out_mask] for RefBlock's narrow layers (cin 1 or 32, cout 64 or 128) on csrc/train_narrow.hip:
+    x [B,cin,H,W], mask_cols / out_mask [B,W], weight [cout,cin,3,3] as the module holds it.  `out`: optional dict of a preallocated
+    out / workspace (fp32, gtts_conv3x3_narrow_workspace_bytes / 4 floats)."""
+    _hip_only(x, "conv3x3_narrow_forward")
+    x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
+    B, cin, H, W = x.shape
+    cout = int(weight.shape[0])
+    if tuple(weight.shape) != (cout, cin, 3, 3) or tuple(mask_cols.shape) != (B, W) or tuple(bias.shape) != (cout,):
+        raise ValueError("conv3x3_narrow_forward: x %s, weight %s, bias %s and mask %s do not match" %
+                         (tuple(x.shape), tuple(weight.shape), tuple(bias.shape), tuple(mask_cols.shape)))
+    y = _out(out, "out", (B, cout, H, W), torch.float32, x.device, exc=ValueError)
+    with _on(x.device):
+        ws, nws = _narrow_ws(out, B, cin, cout, H, W, 0, x.device)
+        _check(lib().gtts_conv3x3_narrow_forward(_ptr(x), _ptr(mask_cols), _ptr(_f32c(out_mask, "out_mask")), _ptr(weight), _ptr(bias), _ptr(y),
+                                                 _ptr(ws), nws, B, cin, cout, H, W, _stream()), "gtts_conv3x3_narrow_forward")
+    return y
+
+
+def conv3x3_narrow_dgrad(dy, weight, mask_cols=None, out_mask=None, out=None):
+    """dx [B,cin,H,W] of conv3x3_narrow_forward (cin 32): mask_cols (None: ones) is the forward's input mask, out_mask its output mask.
+    `out`: optional dict of a preallocated dx / workspace."""
+    _hip_only(dy, "conv3x3_narrow_dgrad")
+    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
+    B, cout, H, W = dy.shape
+    cin = int(weight.shape[1])
+    if tuple(weight.shape) != (cout, cin, 3, 3):
+        raise ValueError("conv3x3_narrow_dgrad: weight %s does not match dy %s" % (tuple(weight.shape), tuple(dy.shape)))
+    mask_cols = _const(dy.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
+    dx = _out(out, "dx", (B, cin, H, W), torch.float32, dy.device, exc=ValueError)
+    with _on(dy.device):
+        ws, nws = _narrow_ws(out, B, cin, cout, H, W, 1, dy.device)
+        _check(lib().gtts_conv3x3_narrow_dgrad(_ptr(dy), _ptr(_f32c(out_mask, "out_mask")), _ptr(mask_cols), _ptr(weight), _ptr(dx), _ptr(ws),
+                                               nws, B, cin, cout, H, W, _stream()), "gtts_conv3x3_narrow_dgrad")
+    return dx
+
+
+def conv3x3_narrow_wgrad(x, mask_cols, dy, out_mask=None, want_bias=True, out=None):
+    """(dW [cout,cin,3,3], db [cout] or None) of conv3x3_narrow_forward.  `out`: optional dict of preallocated dw / db / workspace."""
+    _hip_only(x, "conv3x3_narrow_wgrad")
+    x, mask_cols, dy = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy")
+    B, cin, H, W = x.shape
+    cout = int(dy.shape[1])
+    if tuple(dy.shape) != (B, cout, H, W) or tuple(mask_cols.shape) != (B, W):
+        raise ValueError("conv3x3_narrow_wgrad: x %s, dy %s and mask %s do not match" % (tuple(x.shape), tuple(dy.shape), tuple(mask_cols.shape)))
+    dw = _out(out, "dw", (cout, cin, 3, 3), torch.float32, x.device, exc=ValueError)
+    db = _out(out, "db", (cout,), torch.float32, x.device, exc=ValueError) if want_bias else None
+    with _on(x.device):
+        ws, nws = _narrow_ws(out, B, cin, cout, H, W, 2, x.device)
+        _check(lib().gtts_conv3x3_narrow_wgrad(_ptr(x), _ptr(mask_cols), _ptr(_f32c(out_mask, "out_mask")), _ptr(dy), _ptr(dw), _ptr(db),
+                                               _ptr(ws), nws, B, cin, cout, H, W, _stream()), "gtts_conv3x3_narrow_wgrad")
+    return dw, db
 
 
 def conv7x7_supported(cin, cout, need_dgrad=True, shape=None):
@@ -2069,6 +2155,102 @@ def in_glu_backward(dout, y, gamma, beta, stats, out=None):
         _check(lib().gtts_in_glu_backward(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")), _ptr(stats),
                                           _ptr(dy), _ptr(dg), _ptr(db), _ptr(scratch), B, C, H, W, _stream()), "gtts_in_glu_backward")
     return dy, dg, db
+
+
+def in_glu_tb_forward(y, gamma, beta, tb, eps=1e-5, out=None):
+    """in_glu_forward + tb[:, :, None, None] (RefBlock's time-bias add, modules.py:159,162), tb [B,C].  `out`: as in_glu_forward."""
+    y, gamma, beta, tb = _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta"), _f32c(tb, "tb")
+    B, C2, H, W = y.shape
+    C = C2 // 2
+    if tuple(tb.shape) != (B, C):
+        raise ValueError("tb %s does not match y %s" % (tuple(tb.shape), tuple(y.shape)))
+    res = _out(out, "out", (B, C, H, W), torch.float32, y.device)
+    stats = _out(out, "stats", (int(lib().gtts_in_glu_stats_floats(B, C)),), torch.float32, y.device)
+    with _on(y.device):
+        _check(lib().gtts_in_glu_tb_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(tb), _ptr(res), _ptr(stats), B, C, H, W, float(eps),
+                                            _stream()), "gtts_in_glu_tb_forward")
+    return res, stats
+
+
+def in_glu_tb_backward(dout, y, gamma, beta, stats, out=None):
+    """(dy, dgamma, dbeta, dtb [B,C]) of in_glu_tb_forward.  `out`: optional dict of preallocated dy / dgamma / dbeta / dtb."""
+    dout, y = _f32c(dout, "dout"), _f32c(y, "y")
+    B, C2, H, W = y.shape
+    C = C2 // 2
+    dy = _out(out, "dy", (B, C2, H, W), torch.float32, y.device)
+    dg = _out(out, "dgamma", (C2,), torch.float32, y.device)
+    db = _out(out, "dbeta", (C2,), torch.float32, y.device)
+    dtb = _out(out, "dtb", (B, C), torch.float32, y.device)
+    scratch = torch.empty(int(lib().gtts_in_glu_scratch_floats(B, C)), dtype=torch.float32, device=y.device)
+    with _on(y.device):
+        _check(lib().gtts_in_glu_tb_backward(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")), _ptr(stats),
+                                             _ptr(dy), _ptr(dg), _ptr(db), _ptr(dtb), _ptr(scratch), B, C, H, W, _stream()),
+               "gtts_in_glu_tb_backward")
+    return dy, dg, db, dtb
+
+
+def _hip_only(t, what):
+    if not t.is_cuda:
+        raise RuntimeError("%s needs HIP tensors (got %s); there is no CPU fallback" % (what, t.device))
+
+
+def cond_field(U, mask_cols, H, base=None, out=None):
+    """base + the bias field of a condition vector convolved over the [H, W] plane (gtts_cond_field_forward): U [B,taps,C] with taps 9
+    ((kh, kw) order, 3x3 with padding 1) or 1 (1x1), mask_cols [B,W], base [B,C,H,W] or None -> [B,C,H,W].  `out`: optional dict of a
+    preallocated out."""
+    _hip_only(U, "cond_field")
+    U, mask_cols, base = _f32c(U, "U"), _f32c(mask_cols, "mask"), _f32c(base, "base")
+    B, taps, C = U.shape
+    W = int(mask_cols.shape[-1])
+    if tuple(mask_cols.shape) != (B, W) or (base is not None and tuple(base.shape) != (B, C, int(H), W)):
+        raise ValueError("cond_field: U %s, mask %s and base %s do not match" % (tuple(U.shape), tuple(mask_cols.shape),
+                                                                                 None if base is None else tuple(base.shape)))
+    res = _out(out, "out", (B, C, int(H), W), torch.float32, U.device, exc=ValueError)
+    with _on(U.device):
+        _check(lib().gtts_cond_field_forward(_ptr(U), _ptr(mask_cols), _ptr(base), _ptr(res), B, C, int(H), W, int(taps), _stream()),
+               "gtts_cond_field_forward")
+    return res
+
+
+def cond_field_backward(dy, mask_cols, taps, out=None):
+    """S [B,taps,C]: the gradient of cond_field w.r.t. U (the gradient w.r.t. base is dy itself).  `out`: optional dict of a preallocated S."""
+    _hip_only(dy, "cond_field_backward")
+    dy, mask_cols = _f32c(dy, "dy"), _f32c(mask_cols, "mask")
+    B, C, H, W = dy.shape
+    if tuple(mask_cols.shape) != (B, W):
+        raise ValueError("cond_field_backward: dy %s and mask %s do not match" % (tuple(dy.shape), tuple(mask_cols.shape)))
+    S = _out(out, "S", (B, int(taps), C), torch.float32, dy.device, exc=ValueError)
+    with _on(dy.device):
+        _check(lib().gtts_cond_field_backward(_ptr(dy), _ptr(mask_cols), _ptr(S), B, C, H, W, int(taps), _stream()), "gtts_cond_field_backward")
+    return S
+
+
+def masked_mean(y, mask_cols, out=None):
+    """p [B,C] = sum_{h,w} y mask / (sum_w mask H): RefBlock's masked mean over the plane (modules.py:165-166).  y [B,C,H,W], mask_cols
+    [B,W].  `out`: optional dict of a preallocated p."""
+    _hip_only(y, "masked_mean")
+    y, mask_cols = _f32c(y, "y"), _f32c(mask_cols, "mask")
+    B, C, H, W = y.shape
+    if tuple(mask_cols.shape) != (B, W):
+        raise ValueError("masked_mean: y %s and mask %s do not match" % (tuple(y.shape), tuple(mask_cols.shape)))
+    p = _out(out, "p", (B, C), torch.float32, y.device, exc=ValueError)
+    with _on(y.device):
+        _check(lib().gtts_masked_mean_forward(_ptr(y), _ptr(mask_cols), _ptr(p), B, C, H, W, _stream()), "gtts_masked_mean_forward")
+    return p
+
+
+def masked_mean_backward(dp, mask_cols, H, out=None):
+    """dy [B,C,H,W] of masked_mean: dp [B,C] broadcast over the live columns.  `out`: optional dict of a preallocated dy."""
+    _hip_only(dp, "masked_mean_backward")
+    dp, mask_cols = _f32c(dp, "dp"), _f32c(mask_cols, "mask")
+    B, C = dp.shape
+    W = int(mask_cols.shape[-1])
+    if tuple(mask_cols.shape) != (B, W):
+        raise ValueError("masked_mean_backward: dp %s and mask %s do not match" % (tuple(dp.shape), tuple(mask_cols.shape)))
+    dy = _out(out, "dy", (B, C, int(H), W), torch.float32, dp.device, exc=ValueError)
+    with _on(dp.device):
+        _check(lib().gtts_masked_mean_backward(_ptr(dp), _ptr(mask_cols), _ptr(dy), B, C, int(H), W, _stream()), "gtts_masked_mean_backward")
+    return dy
 
 
 def diffusion_noising(x0, mu, z, mask, t, beta_min, beta_max, out=None):

@@ -5,7 +5,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["plan.hip", "conv_mfma.hip", "conv_ws.hip", "conv_up.hip", "attn.hip", "misc.hip", "pack.hip", "mas.hip", "vc.hip", "glue.hip", "glue_train.hip", "voc.hip", "enc.hip", "enc_train.hip", "conv1d.hip", "conv1d_train.hip", "train.hip", "train_norm.hip", "train_wgrad.hip", "train_wgrad7.hip", "train_attn.hip", "train_elem.hip", "train_inglu.hip", "postnet.hip", "mel.hip", "mel_train.hip", "fgl.hip", "spk.hip", "spk_train.hip", "wav.hip", "ubench.hip"]
+SOURCES = ["plan.hip", "conv_mfma.hip", "conv_ws.hip", "conv_up.hip", "attn.hip", "misc.hip", "pack.hip", "mas.hip", "vc.hip", "glue.hip", "glue_train.hip", "voc.hip", "enc.hip", "enc_train.hip", "conv1d.hip", "conv1d_train.hip", "train.hip", "train_norm.hip", "train_wgrad.hip", "train_wgrad7.hip", "train_attn.hip", "train_elem.hip", "train_inglu.hip", "train_cond.hip", "train_narrow.hip", "postnet.hip", "mel.hip", "mel_train.hip", "fgl.hip", "spk.hip", "spk_train.hip", "wav.hip", "ubench.hip"]
 HEADERS = ["common.h", "kernels.h", "conv1d.h", "conv1d_op.h", "spk.h", "spectral.h", "mel.h", os.path.join("..", "..", "include", "gradtts_abi.h")]
 # The SLP vectoriser packs the GroupNorm / Mish / split arithmetic of the conv prologue into v_pk_*_f32.  Beside MFMAs a
 # packed f32 op costs more issue time than the two scalar ops it replaces (MI355X guide; measured here: -1.6 % per U-Net call).

@@ -40,10 +40,12 @@ __device__ __forceinline__ void block_sum4(double (&v)[4], double *s) {      // 
 // (full-precision exp and division: the kernels are bound by HBM, and RefBlock's output conditions the whole score network)
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// grid (C, B), 256 threads.  stats [B][C][4] = mean_a, rstd_a, mean_g, rstd_g.
+// grid (C, B), 256 threads.  stats [B][C][4] = mean_a, rstd_a, mean_g, rstd_g.  TB: + tb[b, c] behind the GLU (RefBlock's time-bias
+// adds, modules.py:159,162); the instance without it is the kernel as it was.
+template <bool TB>
 __global__ __launch_bounds__(256) void in_glu_fwd_kernel(const float *__restrict__ y, const float *__restrict__ gamma,
-                                                          const float *__restrict__ beta, float *__restrict__ out,
-                                                          float *__restrict__ stats, int C, int HW, float eps) {
+                                                          const float *__restrict__ beta, const float *__restrict__ tb,
+                                                          float *__restrict__ out, float *__restrict__ stats, int C, int HW, float eps) {
     __shared__ double s_red[4 * 256];
     const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const float *ya = y + ((size_t)b * 2 * C + c) * HW, *yg = y + ((size_t)b * 2 * C + C + c) * HW;
@@ -68,14 +70,20 @@ __global__ __launch_bounds__(256) void in_glu_fwd_kernel(const float *__restrict
     const float ga = gamma[c] * rstd_a, ba = fmaf(-mean_a, ga, beta[c]);
     const float gg = gamma[C + c] * rstd_g, bg = fmaf(-mean_g, gg, beta[C + c]);
     float *o = out + ((size_t)b * C + c) * HW;
-    for (int i = tid; i < HW; i += 256) o[i] = fmaf(ya[i], ga, ba) * sigmoid_f(fmaf(yg[i], gg, bg));
+    if constexpr (TB) {
+        const float t = tb[(size_t)b * C + c];
+        for (int i = tid; i < HW; i += 256) o[i] = fmaf(ya[i], ga, ba) * sigmoid_f(fmaf(yg[i], gg, bg)) + t;
+    } else {
+        for (int i = tid; i < HW; i += 256) o[i] = fmaf(ya[i], ga, ba) * sigmoid_f(fmaf(yg[i], gg, bg));
+    }
 }
 
-// grid (C, B), 256 threads.  pgrad [B][2C][2]: this sample's share of (dgamma, dbeta) of the two channels.
+// grid (C, B), 256 threads.  pgrad [B][2C][2]: this sample's share of (dgamma, dbeta) of the two channels.  TB: dtb[b, c] = sum d out.
+template <bool TB>
 __global__ __launch_bounds__(256) void in_glu_bwd_kernel(const float *__restrict__ dout, const float *__restrict__ y,
                                                           const float *__restrict__ gamma, const float *__restrict__ beta,
                                                           const float *__restrict__ stats, float *__restrict__ dy,
-                                                          float *__restrict__ pgrad, int C, int HW) {
+                                                          float *__restrict__ pgrad, float *__restrict__ dtb, int C, int HW) {
     __shared__ double s_red[4 * 256];
     const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const float *ya = y + ((size_t)b * 2 * C + c) * HW, *yg = y + ((size_t)b * 2 * C + C + c) * HW;
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(256) void in_glu_bwd_kernel(const float *__restrict
     const float mean_a = st[0], rstd_a = st[1], mean_g = st[2], rstd_g = st[3];
     const float gma = gamma[c], bta = beta[c], gmg = gamma[C + c], btg = beta[C + c];
     // d a = d out sigma(g), d g = d out a sigma(g) (1 - sigma(g)); per plane: S1 = sum d, S2 = sum d x_hat
-    float s1a = 0.f, s2a = 0.f, s1g = 0.f, s2g = 0.f;
+    float s1a = 0.f, s2a = 0.f, s1g = 0.f, s2g = 0.f, sd = 0.f;
     for (int i = tid; i < HW; i += 256) {
         const float xa = (ya[i] - mean_a) * rstd_a, xg = (yg[i] - mean_g) * rstd_g;
         const float a = fmaf(xa, gma, bta), sg = sigmoid_f(fmaf(xg, gmg, btg));
@@ -92,6 +100,12 @@ __global__ __launch_bounds__(256) void in_glu_bwd_kernel(const float *__restrict
         const float da = d * sg, dg = d * a * sg * (1.0f - sg);
         s1a += da; s2a = fmaf(da, xa, s2a);
         s1g += dg; s2g = fmaf(dg, xg, s2g);
+        if constexpr (TB) sd += d;
+    }
+    if constexpr (TB) {
+        double rt[4] = {(double)sd, 0.0, 0.0, 0.0};
+        block_sum4(rt, s_red);
+        if (tid == 0) dtb[(size_t)b * C + c] = (float)rt[0];
     }
     double r[4] = {(double)s1a, (double)s2a, (double)s1g, (double)s2g};
     block_sum4(r, s_red);
@@ -140,9 +154,19 @@ extern "C" int gtts_in_glu_forward(const float *y, const float *gamma, const flo
     if (!y || !gamma || !beta || !out || !stats) return fail(GTTS_E_NULL, "gtts_in_glu_forward: null argument");
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
         return fail(GTTS_E_SHAPE, "gtts_in_glu_forward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-    hipLaunchKernelGGL(in_glu_fwd_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, out, stats, C, H * W, eps);
+    hipLaunchKernelGGL(in_glu_fwd_kernel<false>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, nullptr, out, stats, C, H * W, eps);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_forward: %s", hipGetErrorString(e));
+}
+
+extern "C" int gtts_in_glu_tb_forward(const float *y, const float *gamma, const float *beta, const float *tb, float *out, float *stats, int B,
+                                      int C, int H, int W, float eps, gtts_stream_t stream) {
+    if (!y || !gamma || !beta || !tb || !out || !stats) return fail(GTTS_E_NULL, "gtts_in_glu_tb_forward: null argument");
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
+        return fail(GTTS_E_SHAPE, "gtts_in_glu_tb_forward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+    hipLaunchKernelGGL(in_glu_fwd_kernel<true>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, tb, out, stats, C, H * W, eps);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_tb_forward: %s", hipGetErrorString(e));
 }
 
 extern "C" int gtts_in_glu_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *stats, float *dy,
@@ -152,8 +176,23 @@ extern "C" int gtts_in_glu_backward(const float *dout, const float *y, const flo
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
         return fail(GTTS_E_SHAPE, "gtts_in_glu_backward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(in_glu_bwd_kernel, dim3(C, B), dim3(256), 0, st, dout, y, gamma, beta, stats, dy, scratch, C, H * W);
+    hipLaunchKernelGGL(in_glu_bwd_kernel<false>, dim3(C, B), dim3(256), 0, st, dout, y, gamma, beta, stats, dy, scratch, nullptr, C, H * W);
     hipLaunchKernelGGL(in_glu_param_kernel, dim3((2 * C + 127) / 128), dim3(128), 0, st, scratch, dgamma, dbeta, B, 2 * C);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_backward: %s", hipGetErrorString(e));
+}
+
+// (the forward's tb is not read again: d out / d tb = 1)
+extern "C" int gtts_in_glu_tb_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *stats, float *dy,
+                                       float *dgamma, float *dbeta, float *dtb, float *scratch, int B, int C, int H, int W,
+                                       gtts_stream_t stream) {
+    if (!dout || !y || !gamma || !beta || !stats || !dy || !dgamma || !dbeta || !dtb || !scratch)
+        return fail(GTTS_E_NULL, "gtts_in_glu_tb_backward: null argument");
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
+        return fail(GTTS_E_SHAPE, "gtts_in_glu_tb_backward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(in_glu_bwd_kernel<true>, dim3(C, B), dim3(256), 0, st, dout, y, gamma, beta, stats, dy, scratch, dtb, C, H * W);
+    hipLaunchKernelGGL(in_glu_param_kernel, dim3((2 * C + 127) / 128), dim3(128), 0, st, scratch, dgamma, dbeta, B, 2 * C);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_tb_backward: %s", hipGetErrorString(e));
 }

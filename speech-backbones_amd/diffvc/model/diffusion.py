@@ -114,8 +114,12 @@ class GradLogPEstimator(BaseModule):
         this is GradLogPEstimator.forward, diffusion.py:61-106).  The trunk -- every 3x3 / 1x1 / resampling convolution with its
         data and weight gradients, GroupNorm + Mish + time term, the LinearAttention core, the residual adds, the final conv -- runs
         on the gtts:: training kernels of the Grad-TTS network (model/_train_ops.py; channel counts 64 or multiples of 128, i.e. every
-        dim_base that is one); the condition path (time MLP, RefBlock's InstanceNorm + GLU stack on the one-channel reference mel,
-        cond_block) composes stock torch ops: ~5 % of the step's FLOPs.  CPU tensors take the same code on stock ops."""
+        dim_base that is one).  The condition path: RefBlock's wide convolutions on those kernels too, its InstanceNorm + GLU stack with
+        the two time-bias adds on csrc/train_inglu.hip and its tail pooled first (csrc/train_cond.hip); the condition vector's share of
+        the first ResnetBlock stays a convolution over the broadcast plane on the trunk's kernels (_first_resnet; the bias-field form,
+        _train_ops.CondField, is built and tested per op but not wired: DESIGN.md section 4.6.8).  What stays stock torch: the
+        Linear layers on [B, <= 1024] vectors (time MLP, cond_block, mlp1 / mlp2, the pooled final_conv) and the narrow RefBlock
+        convolutions of _train_ops.COND_LEFT_ON_TORCH.  CPU tensors take the same code on stock ops."""
         if not T.FORCE_TORCH and x.is_cuda:
             be = backend()
             be.new_pack_generation()

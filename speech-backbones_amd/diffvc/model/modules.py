@@ -46,31 +46,53 @@ class RefBlock(BaseModule):
         self.final_conv = torch.nn.Conv2d(4 * base, out_dim, 1)
 
     @staticmethod
-    def _block(blk, y, mask):
-        """conv3x3(y * mask) -> InstanceNorm -> GLU (DiffVC/model/modules.py:140-157).  Training on the GPU: the convolution (forward, data
-        and weight gradient) on the gtts:: training kernels where their tiles allow (64 or a multiple of 128 channels on both sides:
-        block22 / block31 / block32 = 90 % of RefBlock's FLOPs at out_dim 128; the three narrow layers stay on the framework's
-        convolution), InstanceNorm + GLU of all six blocks on csrc/train_inglu.hip."""
+    def _block(blk, y, mask, tb=None):
+        """conv3x3(y * mask) -> InstanceNorm -> GLU [+ tb[:, :, None, None]] (DiffVC/model/modules.py:140-162).  Training on the GPU: the
+        convolution (forward, data and weight gradient) on the gtts:: training kernels where their tiles allow (64 or a multiple of 128
+        channels on both sides: block22 / block31 / block32 = 90 % of RefBlock's FLOPs at out_dim 128; the narrow layer kinds listed in
+        _train_ops.COND_LEFT_ON_TORCH stay on the framework's convolution), InstanceNorm + GLU of all six blocks on csrc/train_inglu.hip,
+        with the time-bias add of block12 / block22 and its gradient inside those kernels."""
         from ...model import _train_ops as T
         from ...model._backend import backend
         conv, norm = blk[0], blk[1]
         if not (torch.is_grad_enabled() and T._hip(y) and y.dim() == 4 and not T.FORCE_TORCH):
-            return blk(y * mask)
-        if backend().conv3x3_supported(conv.in_channels, conv.out_channels, need_dgrad=True, shape=(y.shape[0], y.shape[2], y.shape[3])):
+            h = blk(y * mask)
+            return h if tb is None else h + tb[:, :, None, None]
+        be, kind = backend(), (conv.in_channels, conv.out_channels)
+        narrow = be.conv3x3_narrow(*kind)
+        if (kind not in T.COND_LEFT_ON_TORCH and conv.kernel_size == (3, 3) and
+                be.conv3x3_supported(*kind, need_dgrad=y.requires_grad or not narrow, shape=(y.shape[0], y.shape[2], y.shape[3]))):
             T._count(True)
+            if narrow:
+                T.cond_count(True)
             h = T.MaskedConv3x3.apply(y.contiguous(), mask, conv.weight, conv.bias, None)
         else:
+            T.cond_count(False)
             h = conv(y * mask)
         if norm.affine and not norm.track_running_stats:
             T._count(True)
-            return T.InstNormGlu.apply(h.contiguous(), norm.weight, norm.bias, norm.eps)
-        return blk[2](norm(h))
+            if tb is None:
+                return T.InstNormGlu.apply(h.contiguous(), norm.weight, norm.bias, norm.eps)
+            T.cond_count(True)
+            return T.InstNormGluBias.apply(h.contiguous(), norm.weight, norm.bias, norm.eps, tb.contiguous())
+        h = blk[2](norm(h))
+        if tb is not None:
+            T.cond_count(False)
+            h = h + tb[:, :, None, None]
+        return h
 
     def forward(self, x, mask, time_emb):
-        y = self._block(self.block12, self._block(self.block11, x, mask), mask)
-        y = y + self.mlp1(time_emb)[:, :, None, None]
-        y = self._block(self.block22, self._block(self.block21, y, mask), mask)
-        y = y + self.mlp2(time_emb)[:, :, None, None]
+        """modules.py:152-166.  Training on the GPU: final_conv -> * mask -> masked mean is linear, so the plane is pooled first
+        (csrc/train_cond.hip) and the 1x1 weight is applied to the pooled [B, 4 base] vector; the bias passes through the mean
+        unchanged."""
+        from ...model import _train_ops as T
+        y = self._block(self.block12, self._block(self.block11, x, mask), mask, self.mlp1(time_emb))
+        y = self._block(self.block22, self._block(self.block21, y, mask), mask, self.mlp2(time_emb))
         y = self._block(self.block32, self._block(self.block31, y, mask), mask)
+        fc = self.final_conv
+        if torch.is_grad_enabled() and T._hip(y) and T._hip(mask) and fc.kernel_size == (1, 1):
+            T.cond_count(True)
+            p = T.MaskedMean.apply(y.contiguous(), mask)
+            return torch.nn.functional.linear(p, fc.weight.view(fc.out_channels, fc.in_channels), fc.bias)
         y = self.final_conv(y * mask)
         return (y * mask).sum((2, 3)) / (mask.sum((2, 3)) * x.shape[2])

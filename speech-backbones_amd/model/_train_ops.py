@@ -25,6 +25,10 @@ csrc/train*.hip behind torch.autograd.Function wrappers:
                        init_proj / term_proj) with their masks: data gradient on the inference kernel of csrc/conv1d.h, weight / bias
                        gradient on csrc/conv1d_train.hip, forward on that kernel too or (as wired: ENC_CONV_KERNEL_FORWARD) torch's
                        fp32 conv1d; ReLU, dropout, residual adds and the embedding stay torch autograd
+  MaskedMean, InstNormGluBias, CondField   the condition path of the DiffVC decoder (csrc/train_cond.hip, train_inglu.hip): RefBlock's
+                       tail pooled before its 1x1 weight, its time-bias adds inside InstanceNorm + GLU; RefBlock's narrow 3x3 layers
+                       (cin 1 / 32) go through MaskedConv3x3 to the fp32-MFMA kernels of csrc/train_narrow.hip; CondField, a condition
+                       vector's convolution over the plane as a bias field, is an op with its tests that the step does not use
 The [B, dim] time / speaker MLPs stay stock torch ops.  On CPU tensors (tests) everything is stock torch.
 """
 import math
@@ -187,6 +191,59 @@ class InstNormGlu(torch.autograd.Function):
         y, gamma, beta, stats = ctx.saved_tensors
         dy, dg, db = backend().in_glu_backward(dout.contiguous(), y, gamma, beta, stats)
         return dy, dg, db, None
+
+
+class InstNormGluBias(torch.autograd.Function):
+    """InstNormGlu + tb[:, :, None, None] (RefBlock's time-bias adds, DiffVC/model/modules.py:159,162): the add rides in the kernel's
+    store and its gradient, a sum over the plane, in the backward kernel's reduction."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, eps, tb):
+        out, stats = backend().in_glu_tb_forward(y, gamma, beta, tb, eps)
+        ctx.save_for_backward(y, gamma, beta, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, gamma, beta, stats = ctx.saved_tensors
+        dy, dg, db, dtb = backend().in_glu_tb_backward(dout.contiguous(), y, gamma, beta, stats)
+        return dy, dg, db, None, dtb
+
+
+class CondField(torch.autograd.Function):
+    """base + the convolution of a condition vector broadcast over the mel plane, as the bias field it is (csrc/train_cond.hip): U
+    [B, taps, C] = the weight's condition columns contracted with the vector (taps 9: 3x3 in (kh, kw) order, 1: 1x1), mask [B,1,1,W].
+    d U is the gated sum of dy over the plane, d base is dy."""
+
+    @staticmethod
+    def forward(ctx, U, mask, base):
+        cols = mask.reshape(mask.shape[0], mask.shape[-1])
+        ctx.save_for_backward(cols)
+        ctx.taps = U.shape[1]
+        return backend().cond_field(U, cols, base.shape[2], base)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (cols,) = ctx.saved_tensors
+        dy = dy.contiguous()
+        dU = backend().cond_field_backward(dy, cols, ctx.taps) if ctx.needs_input_grad[0] else None
+        return dU, None, (dy if ctx.needs_input_grad[2] else None)
+
+
+class MaskedMean(torch.autograd.Function):
+    """(y * mask).sum((2, 3)) / (mask.sum((2, 3)) * H) (RefBlock's pooling, DiffVC/model/modules.py:165-166): y [B,C,H,W] -> [B,C]."""
+
+    @staticmethod
+    def forward(ctx, y, mask):
+        cols = mask.reshape(mask.shape[0], mask.shape[-1])
+        ctx.save_for_backward(cols)
+        ctx.H = y.shape[2]
+        return backend().masked_mean(y, cols)
+
+    @staticmethod
+    def backward(ctx, dp):
+        (cols,) = ctx.saved_tensors
+        return backend().masked_mean_backward(dp.contiguous(), cols, ctx.H), None
 
 
 class MaskedResidualAdd(torch.autograd.Function):
@@ -470,6 +527,38 @@ def glue_op_counts():
 def glue_count(hip, n=1):
     if not FORCE_TORCH:
         _GLUE_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += n
+
+
+# And for the condition path of the DiffVC decoder (RefBlock's narrow convolutions, its two time-bias adds and its pooled tail; the two
+# condition fields where a caller uses them): one count per op -- `hip` when the kernels of csrc/train_cond.hip / train_inglu.hip ran,
+# `fallback` when HIP tensors took stock torch ops.  A GradLogPEstimator with use_ref_t counts 6 ops per step: 3 narrow convolutions,
+# 2 time-bias adds, 1 pool; the fallbacks are the narrow convolutions of COND_LEFT_ON_TORCH.
+_COND_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
+
+
+def reset_cond_op_counts():
+    _COND_COUNTS["hip_ops"] = 0
+    _COND_COUNTS["torch_fallback_ops"] = 0
+
+
+def cond_op_counts():
+    return _COND_COUNTS["hip_ops"], _COND_COUNTS["torch_fallback_ops"]
+
+
+def cond_count(hip):
+    if not FORCE_TORCH:
+        _COND_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
+
+
+# RefBlock's narrow 3x3 convolutions, as (cin, cout), that run on the framework's convolution under autograd; every other convolution
+# of the condition path runs on the gtts:: kernels.  RefBlock.final_conv and the condition columns of the first ResnetBlock are never
+# listed: the first is no convolution any more (MaskedMean), the second runs on the trunk's MFMA kernels.  tests/test_gpu_cond_train_modules.py records the step's
+# torch.nn.functional.conv2d calls against this set.
+# Left on torch by measurement (tools/vc_cond_train_step.py --layers on an MI355X, B = 16 x 80 x 128, forward + every gradient of one
+# layer, median of 9): the fp32-MFMA kernels of csrc/train_narrow.hip take 0.44 ms (1 -> 64), 1.00 ms (32 -> 64) and 1.72 ms (32 -> 128)
+# against 0.23, 0.36 and 0.58 ms of the framework's convolution.  The kernels stay, with their per-op tests (they are fp32-exact and
+# repeat bit for bit); a kind leaves this set when its kernel is the faster one.
+COND_LEFT_ON_TORCH = frozenset({(1, 64), (32, 64), (32, 128)})
 
 
 def enc_hip(t):
@@ -827,7 +916,7 @@ def _pack_specs(est):
                     specs.append((mod.weight, ci, co, False, "dn"))
                     specs.append((mod.weight, co, ci, False, "dn_T"))
             elif mod.kernel_size == (3, 3) and mod.stride == (1, 1) and ci >= 16:
-                if be.conv3x3_supported(ci, co, need_dgrad=True):
+                if be.conv3x3_supported(ci, co, need_dgrad=True) and not be.conv3x3_narrow(ci, co):      # (the narrow kernels pack nothing)
                     specs.append((mod.weight, ci, co, False, "3x3"))
                     specs.append((mod.weight, co, ci, True, "3x3"))
             elif mod.kernel_size == (1, 1) and ci >= 16:
