@@ -1665,6 +1665,40 @@ def _const(device, kind, *shape):
     return v
 
 
+def _out(out, name, shape, dtype, device, exc=RuntimeError):
+    """A preallocated output of the caller's (`out` dict, tests place them between guard margins) or a fresh one."""
+    t = None if out is None else out.get(name)
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise exc("output %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
+    return t
+
+
+def _given(t, name, shape, device, dtype=torch.float32):
+    """The caller's preallocated tensor `t` for the result `name` (tests place it between guard margins), or a fresh one: ValueError
+    unless it is contiguous, of that shape and dtype, and on that device."""
+    return _out(None if t is None else {name: t}, name, shape, dtype, device, exc=ValueError)
+
+
+def _scratch(out, nbytes, device):
+    """The workspace of a weight-gradient call: `out["workspace"]` (fp32, exactly the bytes the call asks for) or a fresh one."""
+    if out is None or out.get("workspace") is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return _out(out, "workspace", (nbytes // 4,), torch.float32, device, exc=ValueError)
+
+
+def _i32c(t, name, device):
+    if not torch.is_tensor(t):
+        t = torch.tensor(t, dtype=torch.int32)
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _hip_only(t, what):
+    if not t.is_cuda:
+        raise RuntimeError("%s needs HIP tensors (got %s); there is no CPU fallback" % (what, t.device))
+
+
 # kind -> (kernel size, the entry points take a second source x1 / c0, the forward entry point takes an output mask, the names of
 # the forward / data-gradient entry point, of the weight gradient and of its workspace size)
 _CONV_KINDS = {kind: (ksize, two, om, "gtts_conv%s_masked" % kind, "gtts_conv%s_wgrad" % kind, "gtts_conv%s_wgrad_workspace_bytes" % kind)
@@ -1686,12 +1720,6 @@ def conv_train_kernel_name(kind, B, cin, cout, H, W, c0=0):
     return buf.value.decode()
 
 
-def _given(t, name, shape, device, dtype=torch.float32):
-    """The caller's preallocated tensor `t` for the result `name` (tests place it between guard margins), or a fresh one: ValueError
-    unless it is contiguous, of that shape and dtype, and on that device."""
-    return _out(None if t is None else {name: t}, name, shape, dtype, device, exc=ValueError)
-
-
 def _conv_run(kind, x, mask_cols, weight, bias, transposed, x1=None, out_mask=None, out=None):
     _, two, om, name, _, _ = _CONV_KINDS[kind]
     B, c0, H, W = x.shape
@@ -1711,13 +1739,6 @@ def _conv_dgrad(kind, dy, weight, mask_cols, out=None):
     B, cout, H, W = dy.shape
     return _conv_run(kind, dy, _const(dy.device, "ones", B, W), weight, _const(dy.device, "zeros", int(weight.shape[1])), True,
                      out_mask=_f32c(mask_cols, "mask"), out=out)
-
-
-def _scratch(out, nbytes, device):
-    """The workspace of a weight-gradient call: `out["workspace"]` (fp32, exactly the bytes the call asks for) or a fresh one."""
-    if out is None or out.get("workspace") is None:
-        return torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return _out(out, "workspace", (nbytes // 4,), torch.float32, device, exc=ValueError)
 
 
 def _tiled_wgrad(kind, x, mask_cols, dy, x1=None, want_bias=True, out=None):
@@ -2128,70 +2149,44 @@ def gn_mish_backward(dout, y, gamma, beta, mask_cols, stats, groups, want_dtb=Fa
     return (dy, dg, db, dtb) if want_dtb else (dy, dg, db)
 
 
-def in_glu_forward(y, gamma, beta, eps=1e-5, out=None):
-    """(IN(y[:, :C]) * sigmoid(IN(y[:, C:])), stats) -- InstanceNorm2d(affine) + GLU(dim=1) of DiffVC's RefBlock (modules.py:128-157).
-    `out`: optional dict of preallocated out / stats."""
-    y, gamma, beta = _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
-    B, C2, H, W = y.shape
-    C = C2 // 2
-    res = _out(out, "out", (B, C, H, W), torch.float32, y.device)
-    stats = _out(out, "stats", (int(lib().gtts_in_glu_stats_floats(B, C)),), torch.float32, y.device)
-    with _on(y.device):
-        _check(lib().gtts_in_glu_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(res), _ptr(stats), B, C, H, W, float(eps), _stream()),
-               "gtts_in_glu_forward")
-    return res, stats
-
-
-def in_glu_backward(dout, y, gamma, beta, stats, out=None):
-    """(dy, dgamma, dbeta) of in_glu_forward.  `out`: optional dict of preallocated dy / dgamma / dbeta."""
-    dout, y = _f32c(dout, "dout"), _f32c(y, "y")
-    B, C2, H, W = y.shape
-    C = C2 // 2
-    dy = _out(out, "dy", (B, C2, H, W), torch.float32, y.device)
-    dg = _out(out, "dgamma", (C2,), torch.float32, y.device)
-    db = _out(out, "dbeta", (C2,), torch.float32, y.device)
-    scratch = torch.empty(int(lib().gtts_in_glu_scratch_floats(B, C)), dtype=torch.float32, device=y.device)
-    with _on(y.device):
-        _check(lib().gtts_in_glu_backward(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")), _ptr(stats),
-                                          _ptr(dy), _ptr(dg), _ptr(db), _ptr(scratch), B, C, H, W, _stream()), "gtts_in_glu_backward")
-    return dy, dg, db
-
-
-def in_glu_tb_forward(y, gamma, beta, tb, eps=1e-5, out=None):
-    """in_glu_forward + tb[:, :, None, None] (RefBlock's time-bias add, modules.py:159,162), tb [B,C].  `out`: as in_glu_forward."""
+def in_glu_forward(y, gamma, beta, eps=1e-5, tb=None, out=None):
+    """(IN(y[:, :C]) * sigmoid(IN(y[:, C:])) [+ tb[:, :, None, None]], stats) -- InstanceNorm2d(affine) + GLU(dim=1) of DiffVC's RefBlock
+    (modules.py:128-157) and, with tb [B,C], its time-bias add (modules.py:159,162).  `out`: optional dict of preallocated out / stats."""
     y, gamma, beta, tb = _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta"), _f32c(tb, "tb")
     B, C2, H, W = y.shape
     C = C2 // 2
-    if tuple(tb.shape) != (B, C):
+    if tb is not None and tuple(tb.shape) != (B, C):
         raise ValueError("tb %s does not match y %s" % (tuple(tb.shape), tuple(y.shape)))
     res = _out(out, "out", (B, C, H, W), torch.float32, y.device)
     stats = _out(out, "stats", (int(lib().gtts_in_glu_stats_floats(B, C)),), torch.float32, y.device)
     with _on(y.device):
-        _check(lib().gtts_in_glu_tb_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(tb), _ptr(res), _ptr(stats), B, C, H, W, float(eps),
-                                            _stream()), "gtts_in_glu_tb_forward")
+        if tb is None:
+            _check(lib().gtts_in_glu_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(res), _ptr(stats), B, C, H, W, float(eps), _stream()),
+                   "gtts_in_glu_forward")
+        else:
+            _check(lib().gtts_in_glu_tb_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(tb), _ptr(res), _ptr(stats), B, C, H, W, float(eps),
+                                                _stream()), "gtts_in_glu_tb_forward")
     return res, stats
 
 
-def in_glu_tb_backward(dout, y, gamma, beta, stats, out=None):
-    """(dy, dgamma, dbeta, dtb [B,C]) of in_glu_tb_forward.  `out`: optional dict of preallocated dy / dgamma / dbeta / dtb."""
-    dout, y = _f32c(dout, "dout"), _f32c(y, "y")
+def in_glu_backward(dout, y, gamma, beta, stats, want_dtb=False, out=None):
+    """(dy, dgamma, dbeta[, dtb [B,C]]) of in_glu_forward.  `out`: optional dict of preallocated dy / dgamma / dbeta / dtb."""
+    dout, y, gamma, beta = _f32c(dout, "dout"), _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
     B, C2, H, W = y.shape
     C = C2 // 2
     dy = _out(out, "dy", (B, C2, H, W), torch.float32, y.device)
     dg = _out(out, "dgamma", (C2,), torch.float32, y.device)
     db = _out(out, "dbeta", (C2,), torch.float32, y.device)
-    dtb = _out(out, "dtb", (B, C), torch.float32, y.device)
+    dtb = _out(out, "dtb", (B, C), torch.float32, y.device) if want_dtb else None
     scratch = torch.empty(int(lib().gtts_in_glu_scratch_floats(B, C)), dtype=torch.float32, device=y.device)
     with _on(y.device):
-        _check(lib().gtts_in_glu_tb_backward(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")), _ptr(stats),
-                                             _ptr(dy), _ptr(dg), _ptr(db), _ptr(dtb), _ptr(scratch), B, C, H, W, _stream()),
-               "gtts_in_glu_tb_backward")
-    return dy, dg, db, dtb
-
-
-def _hip_only(t, what):
-    if not t.is_cuda:
-        raise RuntimeError("%s needs HIP tensors (got %s); there is no CPU fallback" % (what, t.device))
+        if want_dtb:
+            _check(lib().gtts_in_glu_tb_backward(_ptr(dout), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(dy), _ptr(dg), _ptr(db),
+                                                 _ptr(dtb), _ptr(scratch), B, C, H, W, _stream()), "gtts_in_glu_tb_backward")
+        else:
+            _check(lib().gtts_in_glu_backward(_ptr(dout), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(dy), _ptr(dg), _ptr(db),
+                                              _ptr(scratch), B, C, H, W, _stream()), "gtts_in_glu_backward")
+    return (dy, dg, db, dtb) if want_dtb else (dy, dg, db)
 
 
 def cond_field(U, mask_cols, H, base=None, out=None):
@@ -2283,27 +2278,10 @@ def score_loss(eps, z_masked, t, beta_min, beta_max, inv_denom, want_grad=True, 
     return part.sum() * inv_denom, g
 
 
-def _out(out, name, shape, dtype, device, exc=RuntimeError):
-    """A preallocated output of the caller's (`out` dict, tests place them between guard margins) or a fresh one."""
-    t = None if out is None else out.get(name)
-    if t is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
-        raise exc("output %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
-    return t
-
-
-def _i32c(t, name, device):
-    if not torch.is_tensor(t):
-        t = torch.tensor(t, dtype=torch.int32)
-    return t.to(device=device, dtype=torch.int32).contiguous()
-
-
 def conv_dgrad_small(dy, weight, mask_cols=None, out=None):
     """The first layer's data gradient (cin 2 or 3, its own kernel): dx [B,cin,H,W] of Conv2d_kxk(x * mask) for k = 3 (padding 1) or 1,
     dy [B,cout,H,W], weight [cout,cin,k,k] (not packed), mask_cols [B,W] or None."""
-    if not dy.is_cuda:
-        raise RuntimeError("conv_dgrad_small needs HIP tensors (got %s); there is no CPU fallback" % dy.device)
+    _hip_only(dy, "conv_dgrad_small")
     dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
     B, cout, H, W = dy.shape
     cin, ksize = int(weight.shape[1]), int(weight.shape[2])
@@ -2319,8 +2297,7 @@ def conv_dgrad_small(dy, weight, mask_cols=None, out=None):
 
 def diffusion_noising_backward(dxt, mask, t, beta_min, beta_max, want_dx0=True, want_dmu=True, out=None):
     """(dx0, dmu) of diffusion_noising (an output not wanted is None)."""
-    if not dxt.is_cuda:
-        raise RuntimeError("diffusion_noising_backward needs HIP tensors (got %s); there is no CPU fallback" % dxt.device)
+    _hip_only(dxt, "diffusion_noising_backward")
     dxt, mask, t = _f32c(dxt, "dxt"), _f32c(mask, "mask"), _f32c(t, "t")
     B, F, T = dxt.shape
     dx0 = _out(out, "dx0", (B, F, T), torch.float32, dxt.device) if want_dx0 else None
@@ -2334,8 +2311,7 @@ def diffusion_noising_backward(dxt, mask, t, beta_min, beta_max, want_dx0=True, 
 def align_index(path, out=None):
     """The alignment path [B,t_x,T] of monotonic_align.maximum_path as indices: (idx [B,T] int32 token of each frame or -1,
     dur [B,t_x] fp32 frames per token, first [B,t_x] int32 first frame of each token's run or -1)."""
-    if not path.is_cuda:
-        raise RuntimeError("align_index needs HIP tensors (got %s); there is no CPU fallback" % path.device)
+    _hip_only(path, "align_index")
     path = _f32c(path, "path")
     B, tx, T = path.shape
     idx = _out(out, "idx", (B, T), torch.int32, path.device)
@@ -2349,8 +2325,7 @@ def align_index(path, out=None):
 def duration_loss(logw, dur, x_mask, want_grad=True, out=None):
     """(sum((logw - log(1e-8 + dur) * x_mask)^2) as a 0-d tensor, its gradient w.r.t. logw or None): utils.py:42-44 without the
     normaliser, which the caller keeps as a device scalar.  logw, dur, x_mask: B * t_x elements each."""
-    if not logw.is_cuda:
-        raise RuntimeError("duration_loss needs HIP tensors (got %s); there is no CPU fallback" % logw.device)
+    _hip_only(logw, "duration_loss")
     lw, d, m = _f32c(logw, "logw"), _f32c(dur, "dur"), _f32c(x_mask, "x_mask")
     B, tx = int(d.shape[0]), int(d.shape[-1])
     if lw.numel() != B * tx or m.numel() != B * tx:
@@ -2365,8 +2340,7 @@ def duration_loss(logw, dur, x_mask, want_grad=True, out=None):
 def align_gather(mu_x, y, idx, start, kept, S, out=None):
     """Training crop + aligned prior mean (tts.py:146-172) in one gather: (y_c [B,F,S], mu_y [B,F,S], sum over the live elements of
     0.5 ((y_c - mu_y)^2 + log 2 pi) as a 0-d tensor).  start, kept: [B] integer tensors (or lists); S: output frames."""
-    if not mu_x.is_cuda:
-        raise RuntimeError("align_gather needs HIP tensors (got %s); there is no CPU fallback" % mu_x.device)
+    _hip_only(mu_x, "align_gather")
     mx, yy = _f32c(mu_x, "mu_x"), _f32c(y, "y")
     B, F, tx = mx.shape
     T, S = int(yy.shape[2]), int(S)
@@ -2385,8 +2359,7 @@ def align_gather(mu_x, y, idx, start, kept, S, out=None):
 def align_gather_backward(g_mu_y, mu_y, y_c, scale, dur, first, start, kept, out=None):
     """dmu_x [B,F,t_x] of align_gather: per token the sum, over its live output frames, of g_mu_y + scale * (mu_y - y_c).  g_mu_y
     [B,F,S] or None; scale: a one-element device tensor, (gradient of the prior loss) / (sum(kept) F), or None (then mu_y, y_c unused)."""
-    if not dur.is_cuda:
-        raise RuntimeError("align_gather_backward needs HIP tensors (got %s); there is no CPU fallback" % dur.device)
+    _hip_only(dur, "align_gather_backward")
     g, my, yc, sc = _f32c(g_mu_y, "g_mu_y"), _f32c(mu_y, "mu_y"), _f32c(y_c, "y_c"), _f32c(scale, "scale")
     ref = g if g is not None else my
     B, F, S = ref.shape
@@ -2401,8 +2374,7 @@ def align_gather_backward(g_mu_y, mu_y, y_c, scale, dur, first, start, kept, out
 
 def log_prior(mu_x, y):
     """MAS score matrix of GradTTS.compute_loss (tts.py:130-139): [B,F,t_x], [B,F,T] -> [B,t_x,T], one launch."""
-    if not mu_x.is_cuda:
-        raise RuntimeError("log_prior needs HIP tensors; there is no CPU fallback")
+    _hip_only(mu_x, "log_prior")
     mx, yy = _f32c(mu_x.detach(), "mu_x"), _f32c(y.detach(), "y")
     B, F, tx = mx.shape
     if yy.shape[0] != B or yy.shape[1] != F:
@@ -2419,8 +2391,7 @@ def expand_alignment(duration, x_mask, y_lengths, mu_x, T, noise=None, temperatu
 
     duration, x_mask: [B, t_x]; y_lengths: [B] integer; mu_x: [B, F, t_x]; noise: [B, F, T] or None.
     Returns (attn [B, t_x, T], mu_y [B, F, T], z [B, F, T] or None), bit-identical to the reference's CPU path."""
-    if not mu_x.is_cuda:
-        raise RuntimeError("expand_alignment needs HIP tensors; there is no CPU fallback")
+    _hip_only(mu_x, "expand_alignment")
     d, m, mx = _f32c(duration, "duration"), _f32c(x_mask, "x_mask"), _f32c(mu_x, "mu_x")
     B, F, tx = mx.shape
     if d.shape != (B, tx) or m.shape != (B, tx):

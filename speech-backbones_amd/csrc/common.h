@@ -108,6 +108,23 @@ __device__ __forceinline__ void split_bf16(float x, __bf16 &h, __bf16 &l) {
     h = (__bf16)x;
     l = (__bf16)(x - (float)h);
 }
+// eight of them, as the two 16-byte LDS units the weight-gradient kernels stage (train_wgrad.hip, train_wgrad7.hip)
+__device__ __forceinline__ void split8(const float (&v)[8], u32x4 &hi, u32x4 &lo) {
+    bf16x8 vh, vl;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        __bf16 h, l;
+        split_bf16(v[i], h, l);
+        vh[i] = h;
+        vl[i] = l;
+    }
+    hi = __builtin_bit_cast(u32x4, vh);
+    lo = __builtin_bit_cast(u32x4, vl);
+}
+
+// full-precision exp and division (train_inglu.hip: bound by HBM, and RefBlock's output conditions the whole score network; spk.hip:
+// the LSTM gates)
+__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ---------------------------------------------------------------------------------------------------
 // GTTS_PREC_F16F8: the "f16 + fp8 cross terms" split of an fp32 contraction (conv_mfma.hip, NSPLIT == 3).
@@ -234,6 +251,27 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_f<0x141>(v));
     v = fmaxf(v, dpp_f<0x140>(v));
     return fmaxf(fmaxf(lane_f(v, 0), lane_f(v, 16)), fmaxf(lane_f(v, 32), lane_f(v, 48)));
+}
+
+// Fixed-order fp64 sum of N values across a 256-thread workgroup (train_norm.hip, train_inglu.hip, train_cond.hip): a halving tree
+// in LDS, s: N x 256 doubles, value k in slots [k * 256, (k + 1) * 256); the result is valid in every thread.
+// block_sum_d (vc.hip), spk_block_sum, spk_block_sum256 and wav_tile_sumsq reduce on other trees: merging them here would change bits.
+template <int N>
+__device__ __forceinline__ void block_sum_n(double (&v)[N], double *s) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < N; ++k) s[k * 256 + tid] = v[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) s[k * 256 + tid] += s[k * 256 + tid + o];
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = s[k * 256];
+    __syncthreads();
 }
 
 // ---------------------------------------------------------------------------------------------------

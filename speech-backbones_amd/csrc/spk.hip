@@ -99,8 +99,6 @@ __global__ __launch_bounds__(256) void spk_proj_kernel(SpkProjArgs a) {
 
 // ---- the recurrence of one layer.  SAVE (training forward, spk_train.hip): the activated gates overwrite G and c_t goes to a.C;
 // the arithmetic is the same, so both instances give the same bits.
-__device__ __forceinline__ float spk_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 template <bool SAVE>
 __global__ __launch_bounds__(64 * SPK_WAVES) void spk_rec_kernel(SpkRecArgs a) {
     __shared__ __attribute__((aligned(16))) float hs[2][SPK_TILE][SPK_HS];
@@ -155,8 +153,8 @@ __global__ __launch_bounds__(64 * SPK_WAVES) void spk_rec_kernel(SpkRecArgs a) {
             [[maybe_unused]] f32x4 act[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float gi = spk_sigmoid(acc[4 * u + 0][r]), gf = spk_sigmoid(acc[4 * u + 1][r]);
-                const float gg = tanhf(acc[4 * u + 2][r]), go = spk_sigmoid(acc[4 * u + 3][r]);
+                const float gi = sigmoid_f(acc[4 * u + 0][r]), gf = sigmoid_f(acc[4 * u + 1][r]);
+                const float gg = tanhf(acc[4 * u + 2][r]), go = sigmoid_f(acc[4 * u + 3][r]);
                 c[u][r] = fmaf(gf, c[u][r], gi * gg);
                 h[r] = go * tanhf(c[u][r]);
                 if constexpr (SAVE) { act[0][r] = gi; act[1][r] = gf; act[2][r] = gg; act[3][r] = go; }

@@ -20,25 +20,6 @@
 
 namespace gtts {
 
-// s: N x 256 doubles; the result is valid in every thread
-template <int N>
-__device__ __forceinline__ void block_sum_n(double (&v)[N], double *s) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k * 256 + tid] = v[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) s[k * 256 + tid] += s[k * 256 + tid + o];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = s[k * 256];
-    __syncthreads();
-}
-
 // grid (C, B), 256 threads.  U [B][TAPS][C], mask [B][W], base (nullable) and out [B][C][H][W].
 template <int TAPS>
 __global__ __launch_bounds__(256) void cond_field_fwd_kernel(const float *__restrict__ U, const float *__restrict__ mask,

@@ -20,26 +20,6 @@
 
 namespace gtts {
 
-__device__ __forceinline__ void block_sum4(double (&v)[4], double *s) {      // s: 4 x 256 doubles; result valid in every thread
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s[k * 256 + tid] = v[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s[k * 256 + tid] += s[k * 256 + tid + o];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = s[k * 256];
-    __syncthreads();
-}
-
-// (full-precision exp and division: the kernels are bound by HBM, and RefBlock's output conditions the whole score network)
-__device__ __forceinline__ float sigmoid_f(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // grid (C, B), 256 threads.  stats [B][C][4] = mean_a, rstd_a, mean_g, rstd_g.  TB: + tb[b, c] behind the GLU (RefBlock's time-bias
 // adds, modules.py:159,162); the instance without it is the kernel as it was.
 template <bool TB>
@@ -55,7 +35,7 @@ __global__ __launch_bounds__(256) void in_glu_fwd_kernel(const float *__restrict
         r[0] += va; r[1] = fma(va, va, r[1]);
         r[2] += vg; r[3] = fma(vg, vg, r[3]);
     }
-    block_sum4(r, s_red);
+    block_sum_n<4>(r, s_red);
     const double inv = 1.0 / (double)HW;
     const double ma = r[0] * inv, mg = r[2] * inv;
     double vva = fma(-ma, ma, r[1] * inv), vvg = fma(-mg, mg, r[3] * inv);
@@ -104,11 +84,11 @@ __global__ __launch_bounds__(256) void in_glu_bwd_kernel(const float *__restrict
     }
     if constexpr (TB) {
         double rt[4] = {(double)sd, 0.0, 0.0, 0.0};
-        block_sum4(rt, s_red);
+        block_sum_n<4>(rt, s_red);
         if (tid == 0) dtb[(size_t)b * C + c] = (float)rt[0];
     }
     double r[4] = {(double)s1a, (double)s2a, (double)s1g, (double)s2g};
-    block_sum4(r, s_red);
+    block_sum_n<4>(r, s_red);
     if (tid == 0) {
         float *pa = pgrad + ((size_t)b * 2 * C + c) * 2, *pg = pgrad + ((size_t)b * 2 * C + C + c) * 2;
         pa[0] = (float)r[1]; pa[1] = (float)r[0];          // dgamma share = sum d x_hat, dbeta share = sum d
@@ -149,50 +129,54 @@ using namespace gtts;
 extern "C" size_t gtts_in_glu_stats_floats(int B, int C) { return B > 0 && C > 0 ? (size_t)B * C * 4 : 0; }
 extern "C" size_t gtts_in_glu_scratch_floats(int B, int C) { return B > 0 && C > 0 ? (size_t)B * 2 * C * 2 : 0; }
 
+// One host body per direction: `tb` / `dtb` null selects the instance without the time term; the four entries below pass their own
+// names (the gtts_in_glu_tb_* ones having refused a null tb / dtb themselves, under the same code and text).
+static int in_glu_forward(const char *entry, const float *y, const float *gamma, const float *beta, const float *tb, float *out,
+                          float *stats, int B, int C, int H, int W, float eps, gtts_stream_t stream) {
+    if (!y || !gamma || !beta || !out || !stats) return fail(GTTS_E_NULL, "%s: null argument", entry);
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
+        return fail(GTTS_E_SHAPE, "%s: bad shape B=%d C=%d H=%d W=%d", entry, B, C, H, W);
+    hipLaunchKernelGGL(tb ? in_glu_fwd_kernel<true> : in_glu_fwd_kernel<false>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, y, gamma,
+                       beta, tb, out, stats, C, H * W, eps);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "%s: %s", entry, hipGetErrorString(e));
+}
+
+// (the forward's tb is not read again: d out / d tb = 1)
+static int in_glu_backward(const char *entry, const float *dout, const float *y, const float *gamma, const float *beta, const float *stats,
+                           float *dy, float *dgamma, float *dbeta, float *dtb, float *scratch, int B, int C, int H, int W,
+                           gtts_stream_t stream) {
+    if (!dout || !y || !gamma || !beta || !stats || !dy || !dgamma || !dbeta || !scratch)
+        return fail(GTTS_E_NULL, "%s: null argument", entry);
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
+        return fail(GTTS_E_SHAPE, "%s: bad shape B=%d C=%d H=%d W=%d", entry, B, C, H, W);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(dtb ? in_glu_bwd_kernel<true> : in_glu_bwd_kernel<false>, dim3(C, B), dim3(256), 0, st, dout, y, gamma, beta, stats,
+                       dy, scratch, dtb, C, H * W);
+    hipLaunchKernelGGL(in_glu_param_kernel, dim3((2 * C + 127) / 128), dim3(128), 0, st, scratch, dgamma, dbeta, B, 2 * C);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "%s: %s", entry, hipGetErrorString(e));
+}
+
 extern "C" int gtts_in_glu_forward(const float *y, const float *gamma, const float *beta, float *out, float *stats, int B, int C, int H,
                                    int W, float eps, gtts_stream_t stream) {
-    if (!y || !gamma || !beta || !out || !stats) return fail(GTTS_E_NULL, "gtts_in_glu_forward: null argument");
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
-        return fail(GTTS_E_SHAPE, "gtts_in_glu_forward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-    hipLaunchKernelGGL(in_glu_fwd_kernel<false>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, nullptr, out, stats, C, H * W, eps);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_forward: %s", hipGetErrorString(e));
+    return in_glu_forward("gtts_in_glu_forward", y, gamma, beta, nullptr, out, stats, B, C, H, W, eps, stream);
 }
 
 extern "C" int gtts_in_glu_tb_forward(const float *y, const float *gamma, const float *beta, const float *tb, float *out, float *stats, int B,
                                       int C, int H, int W, float eps, gtts_stream_t stream) {
-    if (!y || !gamma || !beta || !tb || !out || !stats) return fail(GTTS_E_NULL, "gtts_in_glu_tb_forward: null argument");
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
-        return fail(GTTS_E_SHAPE, "gtts_in_glu_tb_forward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-    hipLaunchKernelGGL(in_glu_fwd_kernel<true>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, tb, out, stats, C, H * W, eps);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_tb_forward: %s", hipGetErrorString(e));
+    if (!tb) return fail(GTTS_E_NULL, "gtts_in_glu_tb_forward: null argument");
+    return in_glu_forward("gtts_in_glu_tb_forward", y, gamma, beta, tb, out, stats, B, C, H, W, eps, stream);
 }
 
 extern "C" int gtts_in_glu_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *stats, float *dy,
                                     float *dgamma, float *dbeta, float *scratch, int B, int C, int H, int W, gtts_stream_t stream) {
-    if (!dout || !y || !gamma || !beta || !stats || !dy || !dgamma || !dbeta || !scratch)
-        return fail(GTTS_E_NULL, "gtts_in_glu_backward: null argument");
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
-        return fail(GTTS_E_SHAPE, "gtts_in_glu_backward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(in_glu_bwd_kernel<false>, dim3(C, B), dim3(256), 0, st, dout, y, gamma, beta, stats, dy, scratch, nullptr, C, H * W);
-    hipLaunchKernelGGL(in_glu_param_kernel, dim3((2 * C + 127) / 128), dim3(128), 0, st, scratch, dgamma, dbeta, B, 2 * C);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_backward: %s", hipGetErrorString(e));
+    return in_glu_backward("gtts_in_glu_backward", dout, y, gamma, beta, stats, dy, dgamma, dbeta, nullptr, scratch, B, C, H, W, stream);
 }
 
-// (the forward's tb is not read again: d out / d tb = 1)
 extern "C" int gtts_in_glu_tb_backward(const float *dout, const float *y, const float *gamma, const float *beta, const float *stats, float *dy,
                                        float *dgamma, float *dbeta, float *dtb, float *scratch, int B, int C, int H, int W,
                                        gtts_stream_t stream) {
-    if (!dout || !y || !gamma || !beta || !stats || !dy || !dgamma || !dbeta || !dtb || !scratch)
-        return fail(GTTS_E_NULL, "gtts_in_glu_tb_backward: null argument");
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || B > 65535 || (size_t)H * W >= ((size_t)1 << 31))
-        return fail(GTTS_E_SHAPE, "gtts_in_glu_tb_backward: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(in_glu_bwd_kernel<true>, dim3(C, B), dim3(256), 0, st, dout, y, gamma, beta, stats, dy, scratch, dtb, C, H * W);
-    hipLaunchKernelGGL(in_glu_param_kernel, dim3((2 * C + 127) / 128), dim3(128), 0, st, scratch, dgamma, dbeta, B, 2 * C);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GTTS_OK : fail(GTTS_E_HIP, "gtts_in_glu_tb_backward: %s", hipGetErrorString(e));
+    if (!dtb) return fail(GTTS_E_NULL, "gtts_in_glu_tb_backward: null argument");
+    return in_glu_backward("gtts_in_glu_tb_backward", dout, y, gamma, beta, stats, dy, dgamma, dbeta, dtb, scratch, B, C, H, W, stream);
 }

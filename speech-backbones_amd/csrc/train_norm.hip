@@ -19,29 +19,11 @@
 
 namespace gtts {
 
-// fixed-order workgroup sum of two doubles (256 threads); result valid in every thread
-__device__ __forceinline__ void block_sum2(double &a, double &b, double *s_a, double *s_b) {
-    const int tid = threadIdx.x;
-    s_a[tid] = a;
-    s_b[tid] = b;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-            s_a[tid] += s_a[tid + o];
-            s_b[tid] += s_b[tid + o];
-        }
-        __syncthreads();
-    }
-    a = s_a[0];
-    b = s_b[0];
-    __syncthreads();
-}
-
 // grid (B * groups, GN_SPLIT): partial (sum, sum of squares) of one slice of a (sample, group) region -- a contiguous run of
 // (C / groups) * HW floats -- as doubles; 128 regions alone would leave half of the chip idle
 constexpr int GN_SPLIT = 16;
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__ y, double *__restrict__ partial, size_t n) {
-    __shared__ double s_a[256], s_b[256];
+    __shared__ double s_red[2 * 256];
     const size_t per = (n + GN_SPLIT - 1) / GN_SPLIT, i0 = blockIdx.y * per, i1 = i0 + per < n ? i0 + per : n;
     const float *p = y + (size_t)blockIdx.x * n;
     double d1 = 0.0, d2 = 0.0;          // fp64 throughout: the square of an fp32 value is exact in fp64 (header)
@@ -50,10 +32,11 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__
         d1 += v;
         d2 = fma(v, v, d2);
     }
-    block_sum2(d1, d2, s_a, s_b);
+    double r[2] = {d1, d2};
+    block_sum_n<2>(r, s_red);
     if (threadIdx.x == 0) {
-        partial[2 * ((size_t)blockIdx.x * GN_SPLIT + blockIdx.y)] = d1;
-        partial[2 * ((size_t)blockIdx.x * GN_SPLIT + blockIdx.y) + 1] = d2;
+        partial[2 * ((size_t)blockIdx.x * GN_SPLIT + blockIdx.y)] = r[0];
+        partial[2 * ((size_t)blockIdx.x * GN_SPLIT + blockIdx.y) + 1] = r[1];
     }
 }
 // one thread per (sample, group): mean and 1 / sqrt(var + eps) from the GN_SPLIT partials (fixed order)
@@ -108,7 +91,7 @@ __global__ __launch_bounds__(256) void gn_mish_bwd_reduce_kernel(const float *__
                                                                   const float *__restrict__ mask, const float *__restrict__ stats,
                                                                   float *__restrict__ ws, float *__restrict__ dtb, int C, int HW, int W,
                                                                   int cpg) {
-    __shared__ double s_a[256], s_b[256];
+    __shared__ double s_red[2 * 256];
     const int bc = blockIdx.x, b = bc / C, c = bc - b * C, g = c / cpg;
     const float mean = stats[2 * (b * (C / cpg) + g)], rstd = stats[2 * (b * (C / cpg) + g) + 1];
     const float ga = gamma[c], be = beta[c];
@@ -133,15 +116,16 @@ __global__ __launch_bounds__(256) void gn_mish_bwd_reduce_kernel(const float *__
     d1 += (double)s1;
     d2 += (double)s2;
     d3 += (double)s3;
-    block_sum2(d1, d2, s_a, s_b);
+    double r[2] = {d1, d2};
+    block_sum_n<2>(r, s_red);
     if (threadIdx.x == 0) {
-        ws[2 * bc] = (float)d1;
-        ws[2 * bc + 1] = (float)d2;
+        ws[2 * bc] = (float)r[0];
+        ws[2 * bc + 1] = (float)r[1];
     }
     if (dtb) {          // gradient of the time bias: the plain sum of d out over the plane
-        double z = 0.0;
-        block_sum2(d3, z, s_a, s_b);
-        if (threadIdx.x == 0) dtb[bc] = (float)d3;
+        double rt[2] = {d3, 0.0};
+        block_sum_n<2>(rt, s_red);
+        if (threadIdx.x == 0) dtb[bc] = (float)rt[0];
     }
 }
 

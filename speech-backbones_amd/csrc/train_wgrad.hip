@@ -43,19 +43,6 @@ constexpr int X_ROW = 6;         // 16-byte slots per (ci, row): a left pad slot
                                  // neighbour dwords of EVERY block sit at fixed offsets from it (one address register per lane)
 constexpr int X_STRIDE = 25;     // 16-byte slots per ci: 4 rows x X_ROW + 1 pad (odd)
 
-__device__ __forceinline__ void split8(const float (&v)[8], u32x4 &hi, u32x4 &lo) {
-    bf16x8 vh, vl;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        __bf16 h, l;
-        split_bf16(v[i], h, l);
-        vh[i] = h;
-        vl[i] = l;
-    }
-    hi = __builtin_bit_cast(u32x4, vh);
-    lo = __builtin_bit_cast(u32x4, vl);
-}
-
 // Wave-specialised: waves 0-3 are CONSUMERS (one 32 co x 32 ci x 9 tap accumulator block each: fragment reads, the
 // alignbit shifts and MFMAs only), waves 4-7 are PRODUCERS (global loads, mask, hi / lo split, LDS writes, bias sums).  The LDS
 // tile is double-buffered and one barrier per chunk hands a buffer over: the producers stage chunk c + 1 (and have the loads

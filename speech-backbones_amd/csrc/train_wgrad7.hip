@@ -54,19 +54,6 @@ constexpr int W7_DY = 9;     // 16-byte slots per co: 8 blocks + 1 pad
 constexpr int W7_X = 11;     // 16-byte slots per ci: left edge, 8 blocks, right edge, 1 pad
 constexpr int W7_RESIDENT_WGS = 2 * 256;     // resident workgroups of conv7x7_wgrad_kernel on an MI355X: 2 per CU x 256 CUs
 
-__device__ __forceinline__ void w7_split8(const float (&v)[8], u32x4 &hi, u32x4 &lo) {
-    bf16x8 vh, vl;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        __bf16 h, l;
-        split_bf16(v[i], h, l);
-        vh[i] = h;
-        vl[i] = l;
-    }
-    hi = __builtin_bit_cast(u32x4, vh);
-    lo = __builtin_bit_cast(u32x4, vl);
-}
-
 __global__ __launch_bounds__(256, 2) void conv7x7_wgrad_kernel(const Wgrad7Args a) {
     __shared__ __attribute__((aligned(16))) u32x4 s_dy[2][64 * W7_DY];     // [hi | lo][co][slot]
     __shared__ __attribute__((aligned(16))) u32x4 s_x[2][64 * W7_X];       // [hi | lo][ci][slot]
@@ -154,10 +141,10 @@ __global__ __launch_bounds__(256, 2) void conv7x7_wgrad_kernel(const Wgrad7Args 
                 if (want_db) bsum[k] += vd[i];
             }
             u32x4 hi, lo;
-            w7_split8(vx, hi, lo);
+            split8(vx, hi, lo);
             s_x[0][c * W7_X + 1 + blk_t] = hi;
             s_x[1][c * W7_X + 1 + blk_t] = lo;
-            w7_split8(vd, hi, lo);
+            split8(vd, hi, lo);
             s_dy[0][c * W7_DY + blk_t] = hi;
             s_dy[1][c * W7_DY + blk_t] = lo;
         }

@@ -55,7 +55,7 @@ class RefBlock(BaseModule):
         from ...model import _train_ops as T
         from ...model._backend import backend
         conv, norm = blk[0], blk[1]
-        if not (torch.is_grad_enabled() and T._hip(y) and y.dim() == 4 and not T.FORCE_TORCH):
+        if not (torch.is_grad_enabled() and T._hip(y) and y.dim() == 4):
             h = blk(y * mask)
             return h if tb is None else h + tb[:, :, None, None]
         be, kind = backend(), (conv.in_channels, conv.out_channels)
@@ -71,10 +71,9 @@ class RefBlock(BaseModule):
             h = conv(y * mask)
         if norm.affine and not norm.track_running_stats:
             T._count(True)
-            if tb is None:
-                return T.InstNormGlu.apply(h.contiguous(), norm.weight, norm.bias, norm.eps)
-            T.cond_count(True)
-            return T.InstNormGluBias.apply(h.contiguous(), norm.weight, norm.bias, norm.eps, tb.contiguous())
+            if tb is not None:
+                T.cond_count(True)
+            return T.InstNormGlu.apply(h.contiguous(), norm.weight, norm.bias, norm.eps, None if tb is None else tb.contiguous())
         h = blk[2](norm(h))
         if tb is not None:
             T.cond_count(False)

@@ -25,7 +25,7 @@ csrc/train*.hip behind torch.autograd.Function wrappers:
                        init_proj / term_proj) with their masks: data gradient on the inference kernel of csrc/conv1d.h, weight / bias
                        gradient on csrc/conv1d_train.hip, forward on that kernel too or (as wired: ENC_CONV_KERNEL_FORWARD) torch's
                        fp32 conv1d; ReLU, dropout, residual adds and the embedding stay torch autograd
-  MaskedMean, InstNormGluBias, CondField   the condition path of the DiffVC decoder (csrc/train_cond.hip, train_inglu.hip): RefBlock's
+  MaskedMean, InstNormGlu (tb), CondField   the condition path of the DiffVC decoder (csrc/train_cond.hip, train_inglu.hip): RefBlock's
                        tail pooled before its 1x1 weight, its time-bias adds inside InstanceNorm + GLU; RefBlock's narrow 3x3 layers
                        (cin 1 / 32) go through MaskedConv3x3 to the fp32-MFMA kernels of csrc/train_narrow.hip; CondField, a condition
                        vector's convolution over the plane as a bias field, is an op with its tests that the step does not use
@@ -39,13 +39,83 @@ import torch.nn.functional as F
 from ._backend import backend
 
 
+FORCE_TORCH = False      # measurement switch (bench.py train_step): route every op to stock PyTorch-ROCm kernels
+
+
+def _hip(t):
+    """THE gate: an fp32 HIP tensor while the kernels are not switched off (FORCE_TORCH is read at call time: bench.py and the tools
+    assign it on this module) -- what every training kernel takes."""
+    return not FORCE_TORCH and t.is_cuda and t.dtype == torch.float32
+
+
+enc_hip = _hip           # (the encoder modules' name for it)
+
+
+def _cols(mask):
+    """A mask's [B,W] view ([B,1,1,W], or PostNet's [B,1,W]; no copy of a contiguous mask); None stays None."""
+    return None if mask is None else mask.reshape(mask.shape[0], mask.shape[-1])
+
+
+class _OpCounter:
+    """One (hip_ops, torch_fallback_ops) pair: how many ops of one part of the training path ran on the gtts:: kernels and how many
+    fell back to stock torch ops.  Nothing is counted while FORCE_TORCH is on."""
+    __slots__ = ("hip_ops", "torch_fallback_ops")
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.hip_ops = self.torch_fallback_ops = 0
+
+    def read(self):
+        return self.hip_ops, self.torch_fallback_ops
+
+    def count(self, hip, n=1):
+        if not FORCE_TORCH:
+            if hip:
+                self.hip_ops += n
+            else:
+                self.torch_fallback_ops += n
+
+
+# How many tensor-sized ops of the training path ran on the gtts:: kernels and how many fell back to stock torch ops because a gate
+# (shape, dtype, device, channel multiple) failed.  A fallback is correct but slow, and silent otherwise: callers / tests read
+# `op_counts()` after a step (tests/test_gpu_training.py asserts (n, 0) on the reference's shapes).
+_COUNTS = _OpCounter()
+reset_op_counts, op_counts, _count = _COUNTS.reset, _COUNTS.read, _COUNTS.count
+
+# The same pair for the transformer encoder's two kernel ops (EncAttentionCore, EncLayerNorm: text_encoder.py counts one per call
+# made with autograd on -- `hip` when the kernels of csrc/enc_train.hip ran, `fallback` when the module's torch composition did).
+# A pair of its own: op_counts() keeps counting the decoder / PostNet ops only.
+_ENC_COUNTS = _OpCounter()
+reset_enc_op_counts, enc_op_counts, enc_count = _ENC_COUNTS.reset, _ENC_COUNTS.read, _ENC_COUNTS.count
+
+# And for the alignment glue of GradTTS.compute_loss (model/tts.py): one count per op -- the path's index form, the duration loss, the
+# crop / prior-mean gather with the prior loss -- `hip` when the kernels of csrc/glue_train.hip ran, `fallback` when HIP tensors took
+# the dense torch composition.
+_GLUE_COUNTS = _OpCounter()
+reset_glue_op_counts, glue_op_counts, glue_count = _GLUE_COUNTS.reset, _GLUE_COUNTS.read, _GLUE_COUNTS.count
+
+# And for the condition path of the DiffVC decoder (RefBlock's narrow convolutions, its two time-bias adds and its pooled tail; the two
+# condition fields where a caller uses them): one count per op -- `hip` when the kernels of csrc/train_cond.hip / train_inglu.hip ran,
+# `fallback` when HIP tensors took stock torch ops.  A GradLogPEstimator with use_ref_t counts 6 ops per step: 3 narrow convolutions,
+# 2 time-bias adds, 1 pool; the fallbacks are the narrow convolutions of COND_LEFT_ON_TORCH.
+_COND_COUNTS = _OpCounter()
+reset_cond_op_counts, cond_op_counts, cond_count = _COND_COUNTS.reset, _COND_COUNTS.read, _COND_COUNTS.count
+
+# And for the encoders' Conv1d layers (enc_conv1d below: prenet, attention projections, FFN, proj_m, duration predictor, MelEncoder's
+# init_proj / term_proj): one count per convolution called with autograd on -- `hip` when EncConv1d ran, `fallback` when the module call did.
+_ENC_CONV_COUNTS = _OpCounter()
+reset_enc_conv_op_counts, enc_conv_op_counts, enc_conv_count = _ENC_CONV_COUNTS.reset, _ENC_CONV_COUNTS.read, _ENC_CONV_COUNTS.count
+
+
 class MaskedConv3x3(torch.autograd.Function):
     """y = Conv2d_3x3(cat(x, x1) * mask) + bias with all three gradients on the HIP kernels (x1 None: one source)."""
 
     @staticmethod
     def forward(ctx, x, mask, weight, bias, x1=None):
         be = backend()
-        cols = mask.reshape(mask.shape[0], mask.shape[-1])          # [B,1,1,W] -> [B,W]
+        cols = _cols(mask)
         ctx.save_for_backward(x, cols, weight, x1)
         return be.conv3x3_masked(x, cols, weight, bias, x1)
 
@@ -80,7 +150,7 @@ class MaskedConv7x7(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, weight, bias):
         be = backend()
-        cols = mask.reshape(mask.shape[0], mask.shape[-1])          # [B,1,1,W] -> [B,W]
+        cols = _cols(mask)
         ctx.save_for_backward(x, cols, weight)
         return be.conv7x7_masked(x, cols, weight, bias)
 
@@ -105,7 +175,7 @@ class MaskedConv1x1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mask, weight, bias):
         be = backend()
-        cols = None if mask is None else mask.reshape(mask.shape[0], mask.shape[-1])
+        cols = _cols(mask)
         ctx.save_for_backward(x, cols, weight)
         ctx.has_bias = bias is not None
         return be.conv1x1_masked(x, cols, weight, bias)
@@ -162,7 +232,7 @@ class GnMishMask(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, mask, gamma, beta, groups, eps, tb=None):
         be = backend()
-        cols = mask.reshape(mask.shape[0], mask.shape[-1])          # [B,1,1,W] -> [B,W]
+        cols = _cols(mask)
         out, stats = be.gn_mish_forward(y, gamma, beta, cols, groups, eps, tb)
         ctx.save_for_backward(y, cols, gamma, beta, stats)
         ctx.groups = groups
@@ -177,37 +247,22 @@ class GnMishMask(torch.autograd.Function):
 
 
 class InstNormGlu(torch.autograd.Function):
-    """InstanceNorm2d(affine) -> GLU(dim=1) on a convolution output [B, 2C, H, W] (DiffVC RefBlock, DiffVC/model/modules.py:128-157) with
-    forward and backward on csrc/train_inglu.hip."""
+    """InstanceNorm2d(affine) -> GLU(dim=1) on a convolution output [B, 2C, H, W] (DiffVC RefBlock, DiffVC/model/modules.py:128-157)
+    [+ tb[:, :, None, None]: RefBlock's time-bias adds, modules.py:159,162 -- the add rides in the kernel's store and its gradient, a sum
+    over the plane, in the backward kernel's reduction] with forward and backward on csrc/train_inglu.hip."""
 
     @staticmethod
-    def forward(ctx, y, gamma, beta, eps):
-        out, stats = backend().in_glu_forward(y, gamma, beta, eps)
+    def forward(ctx, y, gamma, beta, eps, tb=None):
+        out, stats = backend().in_glu_forward(y, gamma, beta, eps, tb)
         ctx.save_for_backward(y, gamma, beta, stats)
+        ctx.has_tb = tb is not None
         return out
 
     @staticmethod
     def backward(ctx, dout):
         y, gamma, beta, stats = ctx.saved_tensors
-        dy, dg, db = backend().in_glu_backward(dout.contiguous(), y, gamma, beta, stats)
-        return dy, dg, db, None
-
-
-class InstNormGluBias(torch.autograd.Function):
-    """InstNormGlu + tb[:, :, None, None] (RefBlock's time-bias adds, DiffVC/model/modules.py:159,162): the add rides in the kernel's
-    store and its gradient, a sum over the plane, in the backward kernel's reduction."""
-
-    @staticmethod
-    def forward(ctx, y, gamma, beta, eps, tb):
-        out, stats = backend().in_glu_tb_forward(y, gamma, beta, tb, eps)
-        ctx.save_for_backward(y, gamma, beta, stats)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        y, gamma, beta, stats = ctx.saved_tensors
-        dy, dg, db, dtb = backend().in_glu_tb_backward(dout.contiguous(), y, gamma, beta, stats)
-        return dy, dg, db, None, dtb
+        r = backend().in_glu_backward(dout.contiguous(), y, gamma, beta, stats, want_dtb=ctx.has_tb)
+        return r[0], r[1], r[2], None, (r[3] if ctx.has_tb else None)
 
 
 class CondField(torch.autograd.Function):
@@ -217,7 +272,7 @@ class CondField(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, U, mask, base):
-        cols = mask.reshape(mask.shape[0], mask.shape[-1])
+        cols = _cols(mask)
         ctx.save_for_backward(cols)
         ctx.taps = U.shape[1]
         return backend().cond_field(U, cols, base.shape[2], base)
@@ -235,7 +290,7 @@ class MaskedMean(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, mask):
-        cols = mask.reshape(mask.shape[0], mask.shape[-1])
+        cols = _cols(mask)
         ctx.save_for_backward(cols)
         ctx.H = y.shape[2]
         return backend().masked_mean(y, cols)
@@ -251,7 +306,7 @@ class MaskedResidualAdd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, v, mask):
-        cols = None if mask is None else mask.reshape(mask.shape[0], mask.shape[-1])
+        cols = _cols(mask)
         ctx.save_for_backward(cols)
         return backend().add_masked(h, v, cols)
 
@@ -268,7 +323,7 @@ class FinalConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, mask, weight, bias):
-        cols = mask.reshape(mask.shape[0], mask.shape[-1])
+        cols = _cols(mask)
         ctx.save_for_backward(x, cols, weight)
         return backend().final_conv_forward(x, weight, bias, cols)
 
@@ -325,7 +380,7 @@ class ResampleConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, mask, weight, bias, up):
-        cols = mask.reshape(mask.shape[0], mask.shape[-1])
+        cols = _cols(mask)
         ctx.save_for_backward(x, cols, weight)
         ctx.up = bool(up)
         ctx.bias_n = int(bias.shape[0])
@@ -467,89 +522,6 @@ class AlignGather(torch.autograd.Function):
         return (dmu_x,) + (None,) * 8
 
 
-FORCE_TORCH = False      # measurement switch (bench.py train_step): route every op to stock PyTorch-ROCm kernels
-
-# How many tensor-sized ops of the training path ran on the gtts:: kernels and how many fell back to stock torch ops because a gate
-# (shape, dtype, device, channel multiple) failed.  A fallback is correct but slow, and silent otherwise: callers / tests read
-# `op_counts()` after a step (tests/test_gpu_training.py asserts (n, 0) on the reference's shapes).
-_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
-
-
-def reset_op_counts():
-    _COUNTS["hip_ops"] = 0
-    _COUNTS["torch_fallback_ops"] = 0
-
-
-def op_counts():
-    return _COUNTS["hip_ops"], _COUNTS["torch_fallback_ops"]
-
-
-def _count(hip):
-    if not FORCE_TORCH:
-        _COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
-
-
-# The same pair for the transformer encoder's two kernel ops (EncAttentionCore, EncLayerNorm: text_encoder.py counts one per call
-# made with autograd on -- `hip` when the kernels of csrc/enc_train.hip ran, `fallback` when the module's torch composition did).
-# A pair of its own: op_counts() keeps counting the decoder / PostNet ops only.
-_ENC_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
-
-
-def reset_enc_op_counts():
-    _ENC_COUNTS["hip_ops"] = 0
-    _ENC_COUNTS["torch_fallback_ops"] = 0
-
-
-def enc_op_counts():
-    return _ENC_COUNTS["hip_ops"], _ENC_COUNTS["torch_fallback_ops"]
-
-
-def enc_count(hip):
-    if not FORCE_TORCH:
-        _ENC_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
-
-
-# And for the alignment glue of GradTTS.compute_loss (model/tts.py): one count per op -- the path's index form, the duration loss, the
-# crop / prior-mean gather with the prior loss -- `hip` when the kernels of csrc/glue_train.hip ran, `fallback` when HIP tensors took
-# the dense torch composition.
-_GLUE_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
-
-
-def reset_glue_op_counts():
-    _GLUE_COUNTS["hip_ops"] = 0
-    _GLUE_COUNTS["torch_fallback_ops"] = 0
-
-
-def glue_op_counts():
-    return _GLUE_COUNTS["hip_ops"], _GLUE_COUNTS["torch_fallback_ops"]
-
-
-def glue_count(hip, n=1):
-    if not FORCE_TORCH:
-        _GLUE_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += n
-
-
-# And for the condition path of the DiffVC decoder (RefBlock's narrow convolutions, its two time-bias adds and its pooled tail; the two
-# condition fields where a caller uses them): one count per op -- `hip` when the kernels of csrc/train_cond.hip / train_inglu.hip ran,
-# `fallback` when HIP tensors took stock torch ops.  A GradLogPEstimator with use_ref_t counts 6 ops per step: 3 narrow convolutions,
-# 2 time-bias adds, 1 pool; the fallbacks are the narrow convolutions of COND_LEFT_ON_TORCH.
-_COND_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
-
-
-def reset_cond_op_counts():
-    _COND_COUNTS["hip_ops"] = 0
-    _COND_COUNTS["torch_fallback_ops"] = 0
-
-
-def cond_op_counts():
-    return _COND_COUNTS["hip_ops"], _COND_COUNTS["torch_fallback_ops"]
-
-
-def cond_count(hip):
-    if not FORCE_TORCH:
-        _COND_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
-
-
 # RefBlock's narrow 3x3 convolutions, as (cin, cout), that run on the framework's convolution under autograd; every other convolution
 # of the condition path runs on the gtts:: kernels.  RefBlock.final_conv and the condition columns of the first ResnetBlock are never
 # listed: the first is no convolution any more (MaskedMean), the second runs on the trunk's MFMA kernels.  tests/test_gpu_cond_train_modules.py records the step's
@@ -559,11 +531,6 @@ def cond_count(hip):
 # against 0.23, 0.36 and 0.58 ms of the framework's convolution.  The kernels stay, with their per-op tests (they are fp32-exact and
 # repeat bit for bit); a kind leaves this set when its kernel is the faster one.
 COND_LEFT_ON_TORCH = frozenset({(1, 64), (32, 64), (32, 128)})
-
-
-def enc_hip(t):
-    """An fp32 HIP tensor while the kernels are not switched off: what the encoder's training kernels take."""
-    return not FORCE_TORCH and t.is_cuda and t.dtype == torch.float32
 
 
 class EncAttentionCore(torch.autograd.Function):
@@ -610,25 +577,6 @@ class EncLayerNorm(torch.autograd.Function):
         da, dbres, dgamma, dbeta = backend().enc_layernorm_backward(dout.contiguous(), a, gamma.detach(), beta.detach(), bres=bres,
                                                                     eps=ctx.eps)
         return da, dgamma, dbeta, dbres, None
-
-
-# And for the encoders' Conv1d layers (enc_conv1d below: prenet, attention projections, FFN, proj_m, duration predictor, MelEncoder's
-# init_proj / term_proj): one count per convolution called with autograd on -- `hip` when EncConv1d ran, `fallback` when the module call did.
-_ENC_CONV_COUNTS = {"hip_ops": 0, "torch_fallback_ops": 0}
-
-
-def reset_enc_conv_op_counts():
-    _ENC_CONV_COUNTS["hip_ops"] = 0
-    _ENC_CONV_COUNTS["torch_fallback_ops"] = 0
-
-
-def enc_conv_op_counts():
-    return _ENC_CONV_COUNTS["hip_ops"], _ENC_CONV_COUNTS["torch_fallback_ops"]
-
-
-def enc_conv_count(hip):
-    if not FORCE_TORCH:
-        _ENC_CONV_COUNTS["hip_ops" if hip else "torch_fallback_ops"] += 1
 
 
 _ENC_CONV_HANDLES = {}     # (cin, cout, K, dilation) -> (forward handle, transposed handle), or None where the kernel refuses the geometry
@@ -766,7 +714,7 @@ def _block_conv_kind(conv):
 def _hip_conv_ok(v, conv):
     # (shape: the kernels address one call's tensors with 32-bit byte offsets -- oversize batches / crops take the torch path
     # up front instead of failing inside loss.backward())
-    if FORCE_TORCH or not v.is_cuda or v.dtype != torch.float32:
+    if not _hip(v):
         return False
     shape = (v.shape[0], v.shape[2], v.shape[3])
     kind = _block_conv_kind(conv)
@@ -779,7 +727,7 @@ def _hip_conv_ok(v, conv):
 
 def _conv1x1(v, m, conv):
     """conv(v * m) for a 1x1 nn.Conv2d (m None: no mask)."""
-    if (not FORCE_TORCH and v.is_cuda and v.dtype == torch.float32 and conv.kernel_size == (1, 1) and
+    if (_hip(v) and conv.kernel_size == (1, 1) and
             backend().conv1x1_supported(conv.in_channels, conv.out_channels, need_dgrad=v.requires_grad,
                                         shape=(v.shape[0], v.shape[2], v.shape[3]))):
         _count(True)
@@ -790,10 +738,6 @@ def _conv1x1(v, m, conv):
 
 def _mish(v):
     return v * torch.tanh(F.softplus(v))
-
-
-def _hip(v):
-    return not FORCE_TORCH and v.is_cuda and v.dtype == torch.float32
 
 
 def _conv_gn_mish(blk, v, m, tb=None, v1=None):
@@ -868,8 +812,7 @@ def attention(res, v):
     att = rez.fn
     b, c, hh, ww = v.shape
     qkv = _conv1x1(v, None, att.to_qkv)
-    hip = (not FORCE_TORCH and v.is_cuda and v.dtype == torch.float32 and att.heads == 4 and qkv.shape[1] == 384 and
-           v.numel() % 4 == 0)
+    hip = _hip(v) and att.heads == 4 and qkv.shape[1] == 384 and v.numel() % 4 == 0
     if hip:
         out = LinearAttentionCore.apply(qkv.contiguous())
     else:
@@ -988,7 +931,7 @@ def postnet(pn, x, mask):
     m = mask.unsqueeze(1)                                           # [B,1,1,T]
     ic, fc = pn.init_conv, pn.final_conv
     hip_io = _hip(x) and mask.dtype == torch.float32 and ic.in_channels == 1 and fc.out_channels == 1
-    cols = mask.reshape(mask.shape[0], mask.shape[-1]).contiguous() if hip_io else None
+    cols = _cols(mask).contiguous() if hip_io else None
     if hip_io:
         _count(True)
         v = PostNetInitConv.apply(x.contiguous(), cols, ic.weight, ic.bias)

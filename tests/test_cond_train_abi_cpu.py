@@ -43,11 +43,17 @@ def test_new_symbols_are_exported_declared_and_bound(S):
     assert L.gtts_abi_version() == 7
     assert "#define GTTS_ABI_VERSION 7" in hdr and "ABI 7 (additive): the condition path" in hdr
     assert L.gtts_conv3x3_narrow_workspace_bytes.restype is ctypes.c_size_t
-    for n in ("cond_field", "cond_field_backward", "masked_mean", "masked_mean_backward", "in_glu_tb_forward", "in_glu_tb_backward",
+    for n in ("cond_field", "cond_field_backward", "masked_mean", "masked_mean_backward", "in_glu_forward", "in_glu_backward",
               "conv3x3_narrow", "conv3x3_narrow_forward", "conv3x3_narrow_dgrad", "conv3x3_narrow_wgrad"):
         assert callable(getattr(S._lib, n)), n
+    # one InstanceNorm + GLU wrapper pair serves both C entry pairs: the time term is an optional argument, as in gn_mish_forward / _backward
+    sig = __import__("inspect").signature
+    assert sig(S._lib.in_glu_forward).parameters["tb"].default is None
+    assert sig(S._lib.in_glu_backward).parameters["want_dtb"].default is False
+    assert not hasattr(S._lib, "in_glu_tb_forward") and not hasattr(S._lib, "in_glu_tb_backward")
     T = __import__("importlib").import_module("speech-backbones_amd.model._train_ops")
-    for n in ("CondField", "MaskedMean", "InstNormGluBias", "cond_op_counts", "reset_cond_op_counts", "COND_LEFT_ON_TORCH"):
+    assert sig(T.InstNormGlu.forward).parameters["tb"].default is None and not hasattr(T, "InstNormGluBias")
+    for n in ("CondField", "MaskedMean", "InstNormGlu", "cond_op_counts", "reset_cond_op_counts", "COND_LEFT_ON_TORCH"):
         assert hasattr(T, n), n
     sources = __import__("importlib").import_module("speech-backbones_amd.build").SOURCES
     assert "train_cond.hip" in sources and "train_narrow.hip" in sources
@@ -173,7 +179,7 @@ def test_the_new_ops_have_no_cpu_fallback_and_check_their_shapes(S):
     x, m = torch.zeros(1, 4, 2, 3), torch.ones(1, 3)
     for call in (lambda: L.cond_field(torch.zeros(1, 9, 4), m, 2, x), lambda: L.cond_field_backward(x, m, 9),
                  lambda: L.masked_mean(x, m), lambda: L.masked_mean_backward(torch.zeros(1, 4), m, 2),
-                 lambda: L.in_glu_tb_forward(x, torch.ones(4), torch.zeros(4), torch.zeros(1, 2)),
+                 lambda: L.in_glu_forward(x, torch.ones(4), torch.zeros(4), tb=torch.zeros(1, 2)),
                  lambda: L.conv3x3_narrow_forward(torch.zeros(1, 1, 2, 3), m, torch.zeros(64, 1, 3, 3), torch.zeros(64)),
                  lambda: L.conv3x3_narrow_dgrad(torch.zeros(1, 64, 2, 3), torch.zeros(64, 32, 3, 3), m),
                  lambda: L.conv3x3_narrow_wgrad(torch.zeros(1, 32, 2, 3), m, torch.zeros(1, 64, 2, 3))):

@@ -1,5 +1,6 @@
 """GPU parity tests (-m gpu) of the kernels of the DiffVC decoder's condition path under training, one op at a time through the ABI
-wrappers of _lib.py: gtts_cond_field_forward / _backward, gtts_masked_mean_forward / _backward, gtts_in_glu_tb_forward / _backward,
+wrappers of _lib.py: gtts_cond_field_forward / _backward, gtts_masked_mean_forward / _backward, gtts_in_glu_tb_forward / _backward
+(in_glu_forward with tb, in_glu_backward with want_dtb),
 gtts_conv3x3_narrow_forward / _dgrad / _wgrad.
 The catalogue is tests/cond_train_cases.py; tests/test_cond_train_cases_cpu.py proves its restatements and that the bound below tells
 restated mistakes from the kernels' contract.
@@ -102,12 +103,12 @@ def test_instance_norm_glu_with_time_bias_matches_float64(L, dev, cid):
 
     def forward():
         o = Outputs(dev, MARGIN).with_results(dict(out=(c.B, c.C, c.H, c.W), stats=(int(L.lib().gtts_in_glu_stats_floats(c.B, c.C)),)))
-        stats["s"] = L.in_glu_tb_forward(t["y"], t["gamma"], t["beta"], t["tb"], G.G_EPS, out=o.views())[1]
+        stats["s"] = L.in_glu_forward(t["y"], t["gamma"], t["beta"], G.G_EPS, tb=t["tb"], out=o.views())[1]
         return o.collect(cid)
 
     def backward():
         o = Outputs(dev, MARGIN).with_results(dict(dy=(c.B, 2 * c.C, c.H, c.W), dgamma=(2 * c.C,), dbeta=(2 * c.C,), dtb=(c.B, c.C)))
-        L.in_glu_tb_backward(t["dout"], t["y"], t["gamma"], t["beta"], stats["s"].clone(), out=o.views())
+        L.in_glu_backward(t["dout"], t["y"], t["gamma"], t["beta"], stats["s"].clone(), want_dtb=True, out=o.views())
         return o.collect(cid)
 
     got = twice(forward, cid)
