@@ -10,7 +10,9 @@
  *   - plain C: pointers + sizes, no torch types.  All tensors are fp32, contiguous, row-major, in the
  *     reference's own layouts ([B,80,T] mels, [B,1,T] masks flattened to [B,T], NCHW inside).
  *   - the CALLER owns every device buffer (inputs, outputs, packed weights, workspace); the library never
- *     allocates device memory and keeps no device pointer after a call returns.
+ *     allocates device memory and keeps no device pointer after a call returns.  Workspace, scratch, saved-state and
+ *     output buffers (a packed-weight blob before its pack call included) may hold ANY bytes on entry: no result depends on
+ *     what a call did not write itself (tests/test_gpu_fresh_memory.py).
  *   - every call enqueues on the given hipStream_t and returns without synchronising (two documented exceptions, both off the
  *     sampling path: gtts_pack_weights of a GTTS_PREC_F16F8 plan and gtts_workspace_status).  The sampler may fan sub-batches
  *     out onto side streams, but only onto streams the CALLER registered with gtts_plan_set_streams (they are forked

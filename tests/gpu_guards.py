@@ -5,7 +5,9 @@ function takes the device it works on, so tests/test_gpu_guards_cpu.py proves on
 
   inputs    fp32 between NaN margins, int32 between INT_GUARD: a kernel that reads outside a tensor computes a NaN or indexes far away
   outputs   filled with SENTINEL (int32: ISENTINEL), margins included: a surviving fill inside is an element never written, a disturbed
-            one outside a write out of bounds.  "Never written" compares bit patterns."""
+            one outside a write out of bounds.  "Never written" compares bit patterns.
+  scratch   a workspace and its margins hold WS_BITS in every word (a NaN as fp32 and as bf16 halves, -1 as int32): a kernel that reads
+            scratch it has not written, even under a factor 0, returns a NaN; the margins are compared as bits (NaN != NaN)."""
 import importlib
 
 import pytest
@@ -15,6 +17,7 @@ SENTINEL = -12345.675
 ISENTINEL = -12345
 NAN = float("nan")
 INT_GUARD = 1 << 30
+WS_BITS = -1                # 0xFFFFFFFF as int32: the fill of a workspace
 
 
 def guarded(t, margin, fill, dev):
@@ -37,14 +40,19 @@ class Outputs:
     def __init__(self, dev, margin):
         self.dev, self.margin, self.results, self.spaces = dev, margin, {}, {}
 
-    def _new(self, shape, dtype):
+    def _new(self, shape, dtype, bits=None):
+        """(view, whole, fill as int32 bits): filled with SENTINEL / ISENTINEL, or every word with `bits`."""
         assert dtype in (torch.float32, torch.int32), dtype
-        fill = SENTINEL if dtype == torch.float32 else ISENTINEL
         numel = 1
         for s in shape:
             numel *= s
-        whole = torch.full((numel + 2 * self.margin,), fill, dtype=dtype, device=self.dev)
-        return whole[self.margin:self.margin + numel].view(shape), whole, fill
+        if bits is None:
+            fill = SENTINEL if dtype == torch.float32 else ISENTINEL
+            whole = torch.full((numel + 2 * self.margin,), fill, dtype=dtype, device=self.dev)
+            bits = int(torch.tensor(fill, dtype=dtype).view(torch.int32))
+        else:
+            whole = torch.full((numel + 2 * self.margin,), bits, dtype=torch.int32, device=self.dev).view(dtype)
+        return whole[self.margin:self.margin + numel].view(shape), whole, bits
 
     def result(self, name, shape, dtype=torch.float32):
         self.results[name] = self._new(tuple(shape), dtype)
@@ -57,8 +65,8 @@ class Outputs:
         return self
 
     def space(self, name, floats):
-        """A workspace of `floats` fp32: only its margins are checked."""
-        self.spaces[name] = self._new((floats,), torch.float32)
+        """A workspace of `floats` fp32 over WS_BITS: only its margins are checked."""
+        self.spaces[name] = self._new((floats,), torch.float32, WS_BITS)
         return self.spaces[name][0]
 
     def views(self):
@@ -77,14 +85,14 @@ class Outputs:
         for store in (self.results, self.spaces):
             for n, (view, whole, fill) in store.items():
                 w, m, k = whole.cpu(), self.margin, view.numel()
-                ref = torch.tensor(fill, dtype=w.dtype)
-                assert bool((w[:m] == ref).all()) and bool((w[m + k:] == ref).all()), "%sa write outside %s" % (pre, n)
+                ref, wb = torch.tensor(fill, dtype=torch.int32), w.view(torch.int32)
+                assert bool((wb[:m] == ref).all()) and bool((wb[m + k:] == ref).all()), "%sa write outside %s" % (pre, n)
                 if store is self.spaces:
                     continue
                 got[n] = w[m:m + k].view(view.shape).clone()
                 if not values:
                     continue
-                assert not bool((got[n].view(torch.int32) == ref.view(torch.int32)).any()), "%san element of %s was never written" % (pre, n)
+                assert not bool((got[n].view(torch.int32) == ref).any()), "%san element of %s was never written" % (pre, n)
                 if w.dtype == torch.float32:
                     vals = got[n].reshape(-1)[:head[n]] if n in head else got[n]
                     assert bool(torch.isfinite(vals).all()), "%snon-finite %s (a read outside an input)" % (pre, n)

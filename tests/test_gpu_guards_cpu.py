@@ -98,9 +98,30 @@ def test_head_limits_the_finite_check_and_nothing_else():
 def test_a_workspace_is_checked_at_its_margins_only():
     o = outputs()
     ws = o.spaces["ws"][0]
-    assert bool((ws == torch.tensor(G.SENTINEL)).all())                          # never written: collect() accepts that
-    ws[2] = math.nan
+    assert bool((ws.view(I32) == G.WS_BITS).all())                               # never written: collect() accepts that
+    ws[2] = 7.0
     assert "ws" not in o.collect()
+
+
+def test_a_workspace_lies_over_nan_bits_and_its_margins_are_compared_as_bits():
+    """Every word of a workspace and of its margins is 0xFFFFFFFF: a NaN to a kernel that reads scratch before writing it, whatever factor
+    it multiplies it by.  A value comparison would call every margin word disturbed (NaN != NaN), or none if it skipped NaNs."""
+    o = outputs()
+    view, whole_ws, bits = o.spaces["ws"]
+    assert bits == G.WS_BITS == -1 and whole_ws.dtype == F32 and view.dtype == F32 and whole_ws.numel() == 5 + 2 * MARGIN
+    assert bool((whole_ws.view(I32) == -1).all()) and bool(torch.isnan(whole_ws).all())
+    assert bool(torch.isnan(view * 0.0).all())                                   # what a finite fill could not show
+    assert view.data_ptr() == whole_ws.data_ptr() + 4 * MARGIN
+    o.collect("intact")                                                          # NaN margins, untouched: no write outside
+    whole_ws.view(I32)[MARGIN - 1] = 0x7FC00000                                  # another NaN: the same to `==` on floats, other bits
+    with pytest.raises(AssertionError, match="^c: a write outside ws$"):
+        o.collect("c")
+    o = outputs()
+    o.spaces["ws"][1][-1] = G.SENTINEL                                           # the results' fill is a write into a workspace margin
+    with pytest.raises(AssertionError, match="^a write outside ws$"):
+        o.collect()
+    # results keep SENTINEL, value and bits
+    assert bool((whole(outputs(), "y")[:MARGIN] == torch.tensor(G.SENTINEL)).all()) and o.results["idx"][2] == G.ISENTINEL
 
 
 def test_twice_compares_bits_and_names_the_tensor():
