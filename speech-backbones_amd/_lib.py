@@ -334,7 +334,74 @@ def _ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _launch(device, name, *args):
+    """THE call of an entry point that takes a stream: with `device` current (as _on makes it), gtts_<...> `name` on tensors and None
+    as pointers, every other argument (ints, floats, ctypes values) as it is, and the current stream last; a failure raises through
+    _check under the same name."""
+    if device.type != "cuda":
+        raise RuntimeError("%s launches on a HIP device (got %s); there is no CPU fallback" % (name, device))
+    fn = getattr(_lib or lib(), name)
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    index, current = device.index, torch.cuda.current_device()
+    if index is None or index == current:                    # (the free path of _on, without its context)
+        rc = fn(*args, _raw_stream(current))
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*args, _raw_stream(index))
+    if rc:
+        _check(rc, name)
+
+
+def _raw_stream(index):
+    """The current stream of device `index` as the address the entry points take -- what _stream gives, without building the
+    torch.cuda.Stream object in between (a microsecond of host time per launch, which pays for the argument checks of a wrapper)."""
+    return _RAW_STREAM(index)
+
+
+# (torch keeps the raw getter under torch._C; a build without it takes the public road)
+_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda index: torch.cuda.current_stream(index).cuda_stream)
+
+
+class ArgumentError(ValueError, RuntimeError):
+    """An argument that a wrapper refuses before anything is launched: ONE type for every family.  The wrappers no longer tell a
+    ValueError family (decoder, PostNet, condition path) from a RuntimeError one (encoders, glue): this type is both, so every
+    `except` and every test written against either keeps catching what it caught; new code catches ArgumentError."""
+
+
+def _in(op, name, t, shape=None, dev=None, strict=False, optional=False, dtype=torch.float32):
+    """THE rule for a tensor the wrapper `op` passes to a kernel as the input `name`; returns the tensor the kernel reads.
+    None is accepted (and returned) where the argument is `optional`.  dev: the call's device; None for the call's first tensor, which
+    has to live on a HIP device (there is no CPU fallback).  Coercing (default): `dtype` and a contiguous layout are produced, by a copy
+    only where the tensor does not have them.  strict (the encoder ops, which take views into larger allocations as they are): both
+    are required, nothing is converted or copied.  shape: a tuple is the exact shape; an int the element count (where callers pass
+    different views of the same memory: a weight given flat or as [1,C,1,1]); None: not checked (the tensor the sizes are read from)."""
+    if t is None:
+        if optional:
+            return None
+        raise ArgumentError("%s: %s is required (got None)" % (op, name))
+    if (not t.is_cuda) if dev is None else (t.device != dev):
+        if t.is_cuda:
+            raise ArgumentError("%s: %s lives on %s, the call runs on %s" % (op, name, t.device, dev))
+        raise ArgumentError("%s: %s must live on a HIP device (got %s); the kernels need HIP tensors, there is no CPU fallback" %
+                            (op, name, t.device))
+    if strict:
+        if t.dtype != dtype or not t.is_contiguous():
+            raise ArgumentError("%s: %s must be a contiguous %s tensor on %s" % (op, name, dtype, t.device))
+    else:
+        if t.dtype != dtype:
+            t = t.to(dtype)
+        t = t.contiguous()
+    if shape is not None:
+        if shape.__class__ is int:
+            if t.numel() != shape:
+                raise ArgumentError("%s: %s has %d elements (shape %s), expected %d" % (op, name, t.numel(), tuple(t.shape), shape))
+        elif t.shape != shape:
+            raise ArgumentError("%s: %s has shape %s, expected %s" % (op, name, tuple(t.shape), tuple(shape)))
+    return t
+
+
 def _f32c(t, name):
+    """The handle methods' coercion (they keep their own checks and messages)."""
     if t is None:
         return None
     if not t.is_cuda:
@@ -366,6 +433,10 @@ class _Native:
 
     def _call(self, op, *args):
         _check(self._fn(op)(*args), _sym(self._family, op))
+
+    def _launch(self, device, op, *args):
+        """_launch of this family's entry point `op`, which takes the handle first."""
+        _launch(device, _sym(self._family, op), self._h, *args)
 
     def __reduce__(self):
         return (_rebuild, (type(self), self._kw))
@@ -409,9 +480,8 @@ class _Native:
     def _pack(self, params, device, *extra):
         keep, arr = params
         blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
-        with torch.cuda.device(blob.device):
-            self._call("pack", self._h, arr, len(keep), *extra, _ptr(blob), _stream())
-            torch.cuda.current_stream().synchronize()     # sources in `keep` may be temporaries
+        self._launch(blob.device, "pack", arr, len(keep), *extra, blob)
+        torch.cuda.current_stream(blob.device).synchronize()     # sources in `keep` may be temporaries
         return blob
 
     def pack(self, state, device):
@@ -516,8 +586,7 @@ class Plan(_Native):
         if ws is None:
             return 0, 0.0
         n, mx = ctypes.c_uint(0), ctypes.c_float(0.0)
-        with torch.cuda.device(ws.device):
-            _check(lib().gtts_workspace_status(_ptr(ws), ctypes.byref(n), ctypes.byref(mx), _stream()), "gtts_workspace_status")
+        _launch(ws.device, "gtts_workspace_status", ws, ctypes.byref(n), ctypes.byref(mx))
         return int(n.value), float(mx.value)
 
     # ---- weights
@@ -528,7 +597,7 @@ class Plan(_Native):
         half = self.cfg.dim // 2
         # exactly SinusoidalPosEmb's frequency table, computed on the host CPU like the reference (diffusion.py:121-122)
         freq = torch.exp(torch.arange(half).float() * -(math.log(10000) / (half - 1))).to(device)
-        return self._pack(params, device, _ptr(freq))
+        return self._pack(params, device, freq)
 
     # ---- GradLogPEstimator2d.forward
     def estimator_forward(self, blob, x, mask, mu, t, spk=None):
@@ -542,10 +611,7 @@ class Plan(_Native):
                                                                          tuple(mu.shape), tuple(t.shape)))
         out = torch.empty_like(x)
         ws = self.workspace(B, T, x.device)
-        with torch.cuda.device(x.device):
-            _check(lib().gtts_estimator_forward(self._h, _ptr(blob), _ptr(x), _ptr(mask), _ptr(mu), _ptr(t), _ptr(spk),
-                                                _ptr(out), _ptr(ws), ws.numel(), B, T, _stream()),
-                   "gtts_estimator_forward")
+        _launch(x.device, "gtts_estimator_forward", self._h, blob, x, mask, mu, t, spk, out, ws, ws.numel(), B, T)
         return out
 
     # ---- Diffusion.reverse_diffusion (whole loop)
@@ -578,9 +644,8 @@ class Plan(_Native):
             out = torch.empty_like(z)
 
         def run():          # on the stream that is current where it is called
-            _check(lib().gtts_reverse_diffusion(self._h, _ptr(blob), _ptr(z), _ptr(mask), _ptr(mu), _ptr(spk),
-                                                _ptr(noise), _ptr(out), _ptr(ws), ws.numel(), B, T, int(n_timesteps),
-                                                0, int(n_timesteps), _stream()), "gtts_reverse_diffusion")
+            _launch(z.device, "gtts_reverse_diffusion", self._h, blob, z, mask, mu, spk, noise, out, ws, ws.numel(), B, T, int(n_timesteps),
+                    0, int(n_timesteps))
         with torch.cuda.device(z.device):
             if not self._graph:
                 run()
@@ -611,10 +676,7 @@ class Plan(_Native):
         Tr = int(ref_mask.shape[-1]) if ref_mask is not None else T
         out = torch.empty_like(x)
         ws = self.vc_workspace(B, T, Tr, x.device)
-        with torch.cuda.device(x.device):
-            _check(lib().gtts_vc_estimator_forward(self._h, _ptr(blob), _ptr(x), _ptr(x_mask), _ptr(mean), _ptr(xt_ref),
-                                                   _ptr(ref_mask), _ptr(c), _ptr(t), _ptr(out), _ptr(ws), ws.numel(), B, T, Tr,
-                                                   _stream()), "gtts_vc_estimator_forward")
+        _launch(x.device, "gtts_vc_estimator_forward", self._h, blob, x, x_mask, mean, xt_ref, ref_mask, c, t, out, ws, ws.numel(), B, T, Tr)
         return out
 
     def vc_reverse_diffusion(self, blob, z, mask, mean, ref, ref_mask, mean_ref, c, n_timesteps, mode, noise=None,
@@ -649,10 +711,8 @@ class Plan(_Native):
                     nz = _f32c(draw(i1 - i0), "noise") if draw is not None else noise[i0:i1]
                     if tuple(nz.shape) != (i1 - i0, B, F, T):
                         raise RuntimeError("noise chunk must be [%d, B, F, T]" % (i1 - i0))
-                _check(lib().gtts_vc_reverse_diffusion(self._h, _ptr(blob), _ptr(z), _ptr(mask), _ptr(mean), _ptr(ref),
-                                                       _ptr(ref_mask), _ptr(mean_ref), _ptr(c), _ptr(nz), _ptr(out), _ptr(ws),
-                                                       ws.numel(), B, T, Tr, N, modes[mode], i0, i1, _stream()),
-                       "gtts_vc_reverse_diffusion")
+                _launch(z.device, "gtts_vc_reverse_diffusion", self._h, blob, z, mask, mean, ref, ref_mask, mean_ref, c, nz, out, ws,
+                        ws.numel(), B, T, Tr, N, modes[mode], i0, i1)
                 i0 = i1
         return out
 
@@ -766,9 +826,7 @@ class Vocoder(_Native):
             raise RuntimeError("expected %d mel bins, got %d" % (self.cfg.n_mels, F))
         ws = self.workspace(B, T, mel.device)
         wav = torch.empty((B, 1, T * self.hop), dtype=torch.float32, device=mel.device)
-        with torch.cuda.device(mel.device):
-            _check(lib().gtts_voc_forward(self._h, _ptr(blob), _ptr(mel), _ptr(wav), _ptr(ws), ws.numel(), B, T, _stream()),
-                   "gtts_voc_forward")
+        self._launch(mel.device, "forward", blob, mel, wav, ws, ws.numel(), B, T)
         return wav
 
 
@@ -799,9 +857,8 @@ class Conv1dOp(_Native):
         if not w.is_cuda:
             raise RuntimeError("the weights are packed for a HIP device (got %s)" % w.device)
         blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=w.device)
-        with torch.cuda.device(w.device):
-            self._call("pack", self._h, _ptr(w), _ptr(blob), _stream())
-            torch.cuda.current_stream().synchronize()
+        self._launch(w.device, "pack", w, blob)
+        torch.cuda.current_stream(w.device).synchronize()
         return blob
 
     def _pack_source(self, weight, blob, shape):
@@ -822,8 +879,7 @@ class Conv1dOp(_Native):
         if self.mode != 0:
             raise RuntimeError("pack_into serves Conv1d (mode 0) handles")
         blob = self._pack_source(weight, blob, (self.cout, self.cin, self.K))
-        with _on(weight.device):
-            self._call("pack", self._h, _ptr(weight), _ptr(blob), _stream())
+        self._launch(weight.device, "pack", weight, blob)
         return blob
 
     def pack_dgrad(self, weight, blob=None):
@@ -831,8 +887,7 @@ class Conv1dOp(_Native):
         self.cout, K] as W'[ci][co][t] = W[co][ci][K-1-t], one launch, no synchronise.  forward() of this handle on dy is then the data
         gradient (in_mask = the forward's output mask, out_mask = its input mask, a zero bias)."""
         blob = self._pack_source(weight, blob, (self.cin, self.cout, self.K))
-        with _on(weight.device):
-            self._call("pack_dgrad", self._h, _ptr(weight), _ptr(blob), _stream())
+        self._launch(weight.device, "pack_dgrad", weight, blob)
         return blob
 
     def wgrad_info(self, B, L):
@@ -859,16 +914,13 @@ class Conv1dOp(_Native):
             dw = torch.empty((self.cout, self.cin, self.K), dtype=torch.float32, device=x.device)
         if db is None and want_bias:
             db = torch.empty((self.cout,), dtype=torch.float32, device=x.device)
-        _enc_op_tensors({"x": x, "dy": dy, "in_mask": in_mask, "out_mask": out_mask, "dw": dw, "db": db},
-                        {"x": (B, cin, L), "dy": (B, self.cout, L), "in_mask": (B, L), "out_mask": (B, L), "dw": (self.cout, self.cin, self.K),
-                         "db": (self.cout,)}, x.device)
+        _enc_in("Conv1dOp.wgrad", x.device, ("x", x, (B, cin, L), False), ("dy", dy, (B, self.cout, L), False), ("in_mask", in_mask, (B, L), True),
+                ("out_mask", out_mask, (B, L), True), ("dw", dw, (self.cout, self.cin, self.K), False), ("db", db, (self.cout,), True))
         if workspace is None:
             workspace = torch.empty(self.wgrad_workspace_bytes(B, L), dtype=torch.uint8, device=x.device)
         elif workspace.device != x.device or not workspace.is_contiguous():
             raise RuntimeError("workspace must be a contiguous tensor on %s" % x.device)
-        with _on(x.device):
-            self._call("wgrad", self._h, _ptr(x), _ptr(in_mask), _ptr(dy), _ptr(out_mask), _ptr(dw), _ptr(db), _ptr(workspace),
-                       workspace.numel() * workspace.element_size(), B, L, _stream())
+        self._launch(x.device, "wgrad", x, in_mask, dy, out_mask, dw, db, workspace, workspace.numel() * workspace.element_size(), B, L)
         return dw, db
 
     def forward(self, blob, bias, x, out=None, res=None, accsrc=None, accmode=0, div=1.0, slope=1.0, in_mask=None, out_mask=None):
@@ -891,9 +943,7 @@ class Conv1dOp(_Native):
                 raise RuntimeError("%s must be a contiguous fp32 tensor on %s" % (name, x.device))
             if name in shapes and tuple(t.shape) != shapes[name]:
                 raise RuntimeError("%s has shape %s, expected %s" % (name, tuple(t.shape), shapes[name]))
-        with _on(x.device):
-            self._call("forward", self._h, _ptr(blob), _ptr(bias), _ptr(x), _ptr(out), _ptr(res), _ptr(accsrc), int(accmode), float(div),
-                       float(slope), _ptr(in_mask), _ptr(out_mask), B, Lin, _stream())
+        self._launch(x.device, "forward", blob, bias, x, out, res, accsrc, int(accmode), float(div), float(slope), in_mask, out_mask, B, Lin)
         return out
 
 
@@ -935,21 +985,8 @@ class Encoder(_Native):
         mu = torch.empty((B, self.cfg.n_feats, L), dtype=torch.float32, device=dev)
         logw = torch.empty((B, 1, L), dtype=torch.float32, device=dev) if self.mode == "text" else None
         ws = self.workspace(B, L, dev)
-        with torch.cuda.device(dev):
-            _check(lib().gtts_enc_forward(self._h, _ptr(blob), _ptr(ids), _ptr(mel), _ptr(m), _ptr(mu), _ptr(logw), _ptr(ws),
-                                          ws.numel(), B, L, _stream()), "gtts_enc_forward")
+        self._launch(dev, "forward", blob, ids, mel, m, mu, logw, ws, ws.numel(), B, L)
         return (mu, logw) if self.mode == "text" else mu
-
-
-def _enc_op_tensors(given, shapes, dev):
-    """The stand-alone encoder ops take views into larger allocations as they are: nothing is converted or copied."""
-    for name, t in given.items():
-        if t is None:
-            continue
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("%s must be a contiguous fp32 tensor on %s" % (name, dev))
-        if tuple(t.shape) != shapes[name]:
-            raise RuntimeError("%s has shape %s, expected %s" % (name, tuple(t.shape), shapes[name]))
 
 
 def enc_attention_path(channels, n_heads, window, L):
@@ -958,19 +995,24 @@ def enc_attention_path(channels, n_heads, window, L):
     return int(lib().gtts_enc_attention_path_for(int(channels), int(n_heads), int(window or 0), int(L)))
 
 
+def _enc_in(op, dev, *args):
+    """_in in its strict mode for (name, tensor, shape, optional) of a stand-alone encoder op: views into larger allocations are
+    passed as they are, nothing is converted or copied."""
+    for name, t, shape, optional in args:
+        _in(op, name, t, shape, dev, True, optional)
+
+
 def enc_layernorm(a, gamma, beta, bres=None, a_mask=None, out_mask=None, eps=1e-4, relu_in=False, relu_out=False, out=None):
     """The encoders' LayerNorm kernel on its own: relu_out?(LN_c(relu_in?(a) * a_mask + bres)) * out_mask.  a, bres [B,C,L]; gamma,
     beta [C]; masks [B,L]; written into `out` when given.  The launch gtts_enc_forward makes, for the per-op tests."""
-    if not a.is_cuda:
-        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % a.device)
-    B, C, L = a.shape
-    if out is None:
-        out = torch.empty((B, C, L), dtype=torch.float32, device=a.device)
-    _enc_op_tensors(dict(a=a, bres=bres, gamma=gamma, beta=beta, a_mask=a_mask, out_mask=out_mask, out=out),
-                    dict(a=(B, C, L), bres=(B, C, L), gamma=(C,), beta=(C,), a_mask=(B, L), out_mask=(B, L), out=(B, C, L)), a.device)
-    with _on(a.device):
-        _check(lib().gtts_enc_layernorm(_ptr(a), _ptr(bres), _ptr(gamma), _ptr(beta), _ptr(a_mask), _ptr(out_mask), _ptr(out), B, C, L,
-                                        float(eps), int(bool(relu_in)), int(bool(relu_out)), _stream()), "gtts_enc_layernorm")
+    op = "enc_layernorm"
+    _in(op, "a", a, strict=True)
+    dev, (B, C, L) = a.device, a.shape
+    _enc_in(op, dev, ("bres", bres, (B, C, L), True), ("gamma", gamma, (C,), False), ("beta", beta, (C,), False),
+            ("a_mask", a_mask, (B, L), True), ("out_mask", out_mask, (B, L), True))
+    out = _out(op, out, "out", (B, C, L), dev)
+    _launch(dev, "gtts_enc_layernorm", a, bres, gamma, beta, a_mask, out_mask, out, B, C, L, float(eps), int(bool(relu_in)),
+            int(bool(relu_out)))
     return out
 
 
@@ -978,18 +1020,15 @@ def enc_attention(q, k, v, mask, emb_rel_k=None, emb_rel_v=None, n_heads=2, wind
     """The encoders' windowed relative-position attention kernel on its own: q, k, v [B,C,L], mask [B,L], emb_rel_k / emb_rel_v
     [2 window + 1, C / n_heads] (window 0: none) -> [B,C,L].  path 0: the kernel Encoder.forward would run; 16 / 8: that kernel
     (refused where it cannot serve the shape).  The launch gtts_enc_forward makes, for the per-op tests."""
-    if not q.is_cuda:
-        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % q.device)
-    B, C, L = q.shape
+    op = "enc_attention"
+    _in(op, "q", q, strict=True)
+    dev, (B, C, L) = q.device, q.shape
     window = int(window or 0)
-    if out is None:
-        out = torch.empty((B, C, L), dtype=torch.float32, device=q.device)
     rel = (2 * window + 1, C // max(int(n_heads), 1))
-    _enc_op_tensors(dict(q=q, k=k, v=v, mask=mask, emb_rel_k=emb_rel_k, emb_rel_v=emb_rel_v, out=out),
-                    dict(q=(B, C, L), k=(B, C, L), v=(B, C, L), mask=(B, L), emb_rel_k=rel, emb_rel_v=rel, out=(B, C, L)), q.device)
-    with _on(q.device):
-        _check(lib().gtts_enc_attention(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(emb_rel_k), _ptr(emb_rel_v), _ptr(out), B, C, L,
-                                        int(n_heads), window, int(path), _stream()), "gtts_enc_attention")
+    _enc_in(op, dev, ("k", k, (B, C, L), False), ("v", v, (B, C, L), False), ("mask", mask, (B, L), False),
+            ("emb_rel_k", emb_rel_k, rel, not window), ("emb_rel_v", emb_rel_v, rel, not window))
+    out = _out(op, out, "out", (B, C, L), dev)
+    _launch(dev, "gtts_enc_attention", q, k, v, mask, emb_rel_k, emb_rel_v, out, B, C, L, int(n_heads), window, int(path))
     return out
 
 
@@ -999,81 +1038,58 @@ def enc_attention_train_ok(channels, n_heads, window, L):
     return int(lib().gtts_enc_attention_train_ok(int(channels), int(n_heads), int(window or 0), int(L)))
 
 
-def _att_train_shapes(q, n_heads, window):
-    B, C, L = q.shape
-    H = max(int(n_heads), 1)
+def _att_train_in(op, q, k, v, mask, emb_rel_k, emb_rel_v, drop, n_heads, window):
+    """The inputs the two training attention calls share, checked: (device, B, C, L, H, shape of the relative embeddings)."""
+    _in(op, "q", q, strict=True)
+    dev, (B, C, L), H = q.device, q.shape, max(int(n_heads), 1)
     rel = (2 * window + 1, C // H)
-    return B, C, L, H, dict(q=(B, C, L), k=(B, C, L), v=(B, C, L), mask=(B, L), emb_rel_k=rel, emb_rel_v=rel, drop=(B, H, L, L),
-                            out=(B, C, L), stat=(B, H, L, 2), dout=(B, C, L), dq=(B, C, L), dk=(B, C, L), dv=(B, C, L), dek=rel, dev=rel)
+    _enc_in(op, dev, ("k", k, (B, C, L), False), ("v", v, (B, C, L), False), ("mask", mask, (B, L), False),
+            ("emb_rel_k", emb_rel_k, rel, not window), ("emb_rel_v", emb_rel_v, rel, not window), ("drop", drop, (B, H, L, L), True))
+    return dev, B, C, L, H, rel
 
 
 def enc_attention_train_forward(q, k, v, mask, emb_rel_k=None, emb_rel_v=None, drop=None, n_heads=2, window=0, out=None, stat=None):
     """enc_attention for training: `drop` [B,H,L,L] (0 or 1 / (1 - p)) multiplies the probabilities after the softmax; returns
     (out [B,C,L], stat [B,H,L,2]: each query row's score maximum and reciprocal exponential sum, what the backward recomputes from)."""
-    if not q.is_cuda:
-        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % q.device)
-    window = int(window or 0)
-    B, C, L, H, shapes = _att_train_shapes(q, n_heads, window)
-    if out is None:
-        out = torch.empty((B, C, L), dtype=torch.float32, device=q.device)
-    if stat is None:
-        stat = torch.empty((B, H, L, 2), dtype=torch.float32, device=q.device)
-    _enc_op_tensors(dict(q=q, k=k, v=v, mask=mask, emb_rel_k=emb_rel_k, emb_rel_v=emb_rel_v, drop=drop, out=out, stat=stat), shapes, q.device)
-    with _on(q.device):
-        _check(lib().gtts_enc_attention_train_forward(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(emb_rel_k), _ptr(emb_rel_v), _ptr(drop),
-                                                      _ptr(out), _ptr(stat), B, C, L, int(n_heads), window, _stream()),
-               "gtts_enc_attention_train_forward")
+    op, window = "enc_attention_train_forward", int(window or 0)
+    dev, B, C, L, H, _ = _att_train_in(op, q, k, v, mask, emb_rel_k, emb_rel_v, drop, n_heads, window)
+    out, stat = _out(op, out, "out", (B, C, L), dev), _out(op, stat, "stat", (B, H, L, 2), dev)
+    _launch(dev, "gtts_enc_attention_train_forward", q, k, v, mask, emb_rel_k, emb_rel_v, drop, out, stat, B, C, L, int(n_heads), window)
     return out, stat
 
 
 def enc_attention_train_backward(q, k, v, mask, emb_rel_k, emb_rel_v, drop, stat, dout, n_heads=2, window=0, grads=None):
     """(dq, dk, dv, dek, dev) of enc_attention_train_forward from its inputs, `drop` and `stat` (dek = dev = None without a window).
     grads: optional dict of preallocated outputs by those names."""
-    if not q.is_cuda:
-        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % q.device)
-    window = int(window or 0)
-    B, C, L, H, shapes = _att_train_shapes(q, n_heads, window)
-    g = dict(grads or {})
-    for n in ("dq", "dk", "dv") + (("dek", "dev") if window else ()):
-        if g.get(n) is None:
-            g[n] = torch.empty(shapes[n], dtype=torch.float32, device=q.device)
-    if not window:
-        g["dek"] = g["dev"] = None
-    _enc_op_tensors(dict(q=q, k=k, v=v, mask=mask, emb_rel_k=emb_rel_k, emb_rel_v=emb_rel_v, drop=drop, stat=stat, dout=dout, **g),
-                    shapes, q.device)
+    op, window = "enc_attention_train_backward", int(window or 0)
+    dev, B, C, L, H, rel = _att_train_in(op, q, k, v, mask, emb_rel_k, emb_rel_v, drop, n_heads, window)
+    _enc_in(op, dev, ("stat", stat, (B, H, L, 2), False), ("dout", dout, (B, C, L), False))
+    g = grads or {}
+    dq, dk, dv = (_out(op, g, n, (B, C, L), dev) for n in ("dq", "dk", "dv"))
+    dek, dev_ = (_out(op, g, n, rel, dev) for n in ("dek", "dev")) if window else (None, None)
     need = int(lib().gtts_enc_attention_train_scratch_bytes(B, C, L, int(n_heads), window))
-    scratch = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=q.device)
-    with _on(q.device):
-        _check(lib().gtts_enc_attention_train_backward(_ptr(q), _ptr(k), _ptr(v), _ptr(mask), _ptr(emb_rel_k), _ptr(emb_rel_v), _ptr(drop),
-                                                       _ptr(stat), _ptr(dout), _ptr(g["dq"]), _ptr(g["dk"]), _ptr(g["dv"]), _ptr(g["dek"]),
-                                                       _ptr(g["dev"]), _ptr(scratch), B, C, L, int(n_heads), window, _stream()),
-               "gtts_enc_attention_train_backward")
-    return g["dq"], g["dk"], g["dv"], g["dek"], g["dev"]
+    scratch = torch.empty(max(need, 4) // 4, dtype=torch.float32, device=dev)
+    _launch(dev, "gtts_enc_attention_train_backward", q, k, v, mask, emb_rel_k, emb_rel_v, drop, stat, dout, dq, dk, dv, dek, dev_, scratch,
+            B, C, L, int(n_heads), window)
+    return dq, dk, dv, dek, dev_
 
 
 def enc_layernorm_backward(dout, a, gamma, beta, bres=None, a_mask=None, out_mask=None, eps=1e-4, relu_in=False, relu_out=False,
                            grads=None):
     """(da, dbres, dgamma, dbeta) of enc_layernorm (dbres None without bres).  grads: optional dict of preallocated outputs."""
-    if not a.is_cuda:
-        raise RuntimeError("the encoder kernels need HIP tensors (got %s); there is no CPU fallback here" % a.device)
-    B, C, L = a.shape
-    shapes = dict(dout=(B, C, L), a=(B, C, L), bres=(B, C, L), gamma=(C,), beta=(C,), a_mask=(B, L), out_mask=(B, L), da=(B, C, L),
-                  dbres=(B, C, L), dgamma=(C,), dbeta=(C,))
-    g = dict(grads or {})
-    for n in ("da", "dgamma", "dbeta") + (("dbres",) if bres is not None else ()):
-        if g.get(n) is None:
-            g[n] = torch.empty(shapes[n], dtype=torch.float32, device=a.device)
-    if bres is None:
-        g["dbres"] = None
-    _enc_op_tensors(dict(dout=dout, a=a, bres=bres, gamma=gamma, beta=beta, a_mask=a_mask, out_mask=out_mask, **g), shapes, a.device)
+    op = "enc_layernorm_backward"
+    _in(op, "a", a, strict=True)
+    dev, (B, C, L) = a.device, a.shape
+    _enc_in(op, dev, ("dout", dout, (B, C, L), False), ("bres", bres, (B, C, L), True), ("gamma", gamma, (C,), False),
+            ("beta", beta, (C,), False), ("a_mask", a_mask, (B, L), True), ("out_mask", out_mask, (B, L), True))
+    g = grads or {}
+    da, dgamma, dbeta = _out(op, g, "da", (B, C, L), dev), _out(op, g, "dgamma", (C,), dev), _out(op, g, "dbeta", (C,), dev)
+    dbres = _out(op, g, "dbres", (B, C, L), dev) if bres is not None else None
     need = int(lib().gtts_enc_layernorm_backward_scratch_floats(B, C, L))
-    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=a.device)
-    with _on(a.device):
-        _check(lib().gtts_enc_layernorm_backward(_ptr(dout), _ptr(a), _ptr(bres), _ptr(gamma), _ptr(beta), _ptr(a_mask), _ptr(out_mask),
-                                                 _ptr(g["da"]), _ptr(g["dbres"]), _ptr(g["dgamma"]), _ptr(g["dbeta"]), _ptr(scratch), B, C, L,
-                                                 float(eps), int(bool(relu_in)), int(bool(relu_out)), _stream()),
-               "gtts_enc_layernorm_backward")
-    return g["da"], g["dbres"], g["dgamma"], g["dbeta"]
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    _launch(dev, "gtts_enc_layernorm_backward", dout, a, bres, gamma, beta, a_mask, out_mask, da, dbres, dgamma, dbeta, scratch, B, C, L,
+            float(eps), int(bool(relu_in)), int(bool(relu_out)))
+    return da, dbres, dgamma, dbeta
 
 
 class PostNetPlan(_Native):
@@ -1092,9 +1108,7 @@ class PostNetPlan(_Native):
             raise RuntimeError("shape mismatch: x %s mask %s" % (tuple(x.shape), tuple(mask.shape)))
         ws = self.workspace(B, T, x.device)
         out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _check(lib().gtts_postnet_forward(self._h, _ptr(blob), _ptr(x), _ptr(mask), _ptr(out), _ptr(ws), ws.numel(), B, T,
-                                              _stream()), "gtts_postnet_forward")
+        self._launch(x.device, "forward", blob, x, mask, out, ws, ws.numel(), B, T)
         return out
 
 
@@ -1127,9 +1141,8 @@ class MelPlan(_Native):
         blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
         if not blob.is_cuda:
             raise RuntimeError("the mel tables are packed for a HIP device (got %s)" % blob.device)
-        with torch.cuda.device(blob.device):
-            self._call("pack", self._h, _ptr(blob), _stream())
-            torch.cuda.current_stream().synchronize()
+        self._launch(blob.device, "pack", blob)
+        torch.cuda.current_stream(blob.device).synchronize()
         return blob
 
     def forward(self, blob, y, lengths=None):
@@ -1144,8 +1157,7 @@ class MelPlan(_Native):
                 raise RuntimeError("lengths must be a [B] integer tensor on y's HIP device")
             lengths = lengths.to(torch.int32).contiguous()
         out = torch.empty((B, self.num_mels, self.frames(L)), dtype=torch.float32, device=y.device)
-        with _on(y.device):
-            self._call("forward", self._h, _ptr(blob), _ptr(y), _ptr(lengths), _ptr(out), B, L, _stream())
+        self._launch(y.device, "forward", blob, y, lengths, out, B, L)
         return out
 
     def backward_workspace_bytes(self, B, L):
@@ -1169,9 +1181,7 @@ class MelPlan(_Native):
             lengths = lengths.to(torch.int32).contiguous()
         ws = torch.empty(self.backward_workspace_bytes(B, L), dtype=torch.uint8, device=y.device)
         dwav = torch.empty((B, L), dtype=torch.float32, device=y.device)
-        with _on(y.device):
-            self._call("backward", self._h, _ptr(blob), _ptr(y), _ptr(lengths), _ptr(dmel), _ptr(dwav), _ptr(ws), ws.numel(), B, L,
-                       _stream())
+        self._launch(y.device, "backward", blob, y, lengths, dmel, dwav, ws, ws.numel(), B, L)
         return dwav
 
 
@@ -1202,8 +1212,7 @@ class FglPlan(_Native):
         blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
         if not blob.is_cuda:
             raise RuntimeError("the Griffin-Lim tables are packed for a HIP device (got %s)" % blob.device)
-        with torch.cuda.device(blob.device):
-            self._call("pack", self._h, _ptr(P), _ptr(blob), _stream())
+        self._launch(blob.device, "pack", P, blob)
         return blob
 
     def _mel(self, s):
@@ -1218,8 +1227,7 @@ class FglPlan(_Native):
         ws = self.workspace(B, T, s.device)
         c = torch.empty((B, self.bins, T), dtype=torch.float32, device=s.device)
         x0 = torch.empty((B, L), dtype=torch.float32, device=s.device)
-        with _on(s.device):
-            self._call("init", self._h, _ptr(blob), _ptr(s), _ptr(c), _ptr(x0), _ptr(ws), ws.numel(), B, T, _stream())
+        self._launch(s.device, "init", blob, s, c, x0, ws, ws.numel(), B, T)
         return c, x0
 
     def step(self, blob, c, x, a_prev):
@@ -1237,9 +1245,7 @@ class FglPlan(_Native):
         a_prev = a_prev.contiguous()
         ws = self.workspace(B, T, c.device)
         x_out, a = torch.empty_like(x), torch.empty_like(a_prev)
-        with _on(c.device):
-            self._call("step", self._h, _ptr(blob), _ptr(c), _ptr(x), _ptr(a_prev), _ptr(x_out), _ptr(a), _ptr(ws), ws.numel(), B, T,
-                       _stream())
+        self._launch(c.device, "step", blob, c, x, a_prev, x_out, a, ws, ws.numel(), B, T)
         return x_out, a
 
     def forward(self, blob, s, n_iters=32):
@@ -1247,8 +1253,7 @@ class FglPlan(_Native):
         s, B, T, L = self._mel(s)
         ws = self.workspace(B, T, s.device)
         wav = torch.empty((B, L), dtype=torch.float32, device=s.device)
-        with _on(s.device):
-            self._call("forward", self._h, _ptr(blob), _ptr(s), _ptr(wav), _ptr(ws), ws.numel(), B, T, int(n_iters), _stream())
+        self._launch(s.device, "forward", blob, s, wav, ws, ws.numel(), B, T, int(n_iters))
         return wav
 
 
@@ -1304,9 +1309,8 @@ class WavPlan(_Native):
         blob = torch.empty(self.packed_bytes(), dtype=torch.uint8, device=device)
         if not blob.is_cuda:
             raise RuntimeError("the waveform front end's tables are packed for a HIP device (got %s)" % blob.device)
-        with torch.cuda.device(blob.device):
-            self._call("pack", self._h, _ptr(blob), _stream())
-            torch.cuda.current_stream().synchronize()
+        self._launch(blob.device, "pack", blob)
+        torch.cuda.current_stream(blob.device).synchronize()
         return blob
 
     @staticmethod
@@ -1322,8 +1326,7 @@ class WavPlan(_Native):
         Lo = self.resampled_length(L)
         out = torch.empty((B, Lo), dtype=torch.float32, device=wavs.device)
         partials = torch.empty((B, self.tiles(Lo)), dtype=torch.float32, device=wavs.device)
-        with _on(wavs.device):
-            self._call("resample", self._h, _ptr(blob), _ptr(wavs), _ptr(out), _ptr(partials), B, L, _stream())
+        self._launch(wavs.device, "resample", blob, wavs, out, partials, B, L)
         return out, partials
 
     def normalize(self, blob, wavs, target_dBFS, increase_only=False, decrease_only=False, partials=None):
@@ -1339,17 +1342,15 @@ class WavPlan(_Native):
               or tuple(partials.shape) != (B, self.tiles(L))):
             raise RuntimeError("partials must be the fp32 [%d, %d] tensor resample returned beside these wavs" % (B, self.tiles(L)))
         out = torch.empty_like(wavs)
-        with _on(wavs.device):
-            self._call("normalize", self._h, _ptr(wavs), _ptr(partials), float(target_dBFS), 1 if increase_only else 2 if decrease_only else 0,
-                       _ptr(out), _ptr(ws), 0 if ws is None else ws.numel(), B, L, _stream())
+        self._launch(wavs.device, "normalize", wavs, partials, float(target_dBFS), 1 if increase_only else 2 if decrease_only else 0,
+                     out, ws, 0 if ws is None else ws.numel(), B, L)
         return out
 
     def powmel(self, blob, wavs):
         """wavs [B, L] at sampling_rate -> power mel [B, frames(L), n_mels] in one launch."""
         wavs, B, L = self._rows(wavs)
         out = torch.empty((B, self.frames(L), self.n_mels), dtype=torch.float32, device=wavs.device)
-        with _on(wavs.device):
-            self._call("powmel", self._h, _ptr(blob), _ptr(wavs), _ptr(out), B, L, _stream())
+        self._launch(wavs.device, "powmel", blob, wavs, out, B, L)
         return out
 
 
@@ -1381,9 +1382,7 @@ class SpkPlan(_Native):
         embeds = torch.empty((max(N, 0), self.embed), dtype=torch.float32, device=dev)
         hidden = torch.empty((max(N, 0), self.hidden), dtype=torch.float32, device=dev) if want_hidden else None
         utt = torch.empty((U, self.embed), dtype=torch.float32, device=dev) if want_utt else None
-        with _on(dev):
-            self._call("forward", self._h, _ptr(blob), _ptr(frames), U, T_total, P, S, T, _ptr(embeds), _ptr(hidden), _ptr(utt),
-                       _ptr(ws), ws.numel(), _stream())
+        self._launch(dev, "forward", blob, frames, U, T_total, P, S, T, embeds, hidden, utt, ws, ws.numel())
         out = [embeds] + ([hidden] if want_hidden else []) + ([utt] if want_utt else [])
         return out[0] if len(out) == 1 else tuple(out)
 
@@ -1393,9 +1392,8 @@ class SpkPlan(_Native):
         pack()'s, from the same state."""
         keep, arr = self._params(state, device)
         blob = torch.empty(int(lib().gtts_spktrain_packed_bytes(self._h)), dtype=torch.uint8, device=device)
-        with torch.cuda.device(blob.device):
-            _check(lib().gtts_spktrain_pack(self._h, arr, len(keep), _ptr(blob), _stream()), "gtts_spktrain_pack")
-            torch.cuda.current_stream().synchronize()     # sources in `keep` may be temporaries
+        _launch(blob.device, "gtts_spktrain_pack", self._h, arr, len(keep), blob)
+        torch.cuda.current_stream(blob.device).synchronize()     # sources in `keep` may be temporaries
         return blob
 
     def saved_bytes(self, N, T):
@@ -1415,9 +1413,7 @@ class SpkPlan(_Native):
         dev = frames.device
         embeds = torch.empty((N, self.embed), dtype=torch.float32, device=dev)
         saved = torch.empty(max(self.saved_bytes(N, T) if N > 0 and T > 0 else 0, 256), dtype=torch.uint8, device=dev)
-        with _on(dev):
-            _check(lib().gtts_spktrain_forward(self._h, _ptr(blob), _ptr(frames), N, T, _ptr(embeds), _ptr(saved), saved.numel(),
-                                                _stream()), "gtts_spktrain_forward")
+        _launch(dev, "gtts_spktrain_forward", self._h, blob, frames, N, T, embeds, saved, saved.numel())
         return embeds, saved
 
     def backward(self, blob_train, frames, d_embeds, saved):
@@ -1436,9 +1432,7 @@ class SpkPlan(_Native):
         if ws is None:
             cache.clear()
             ws = cache[(N, T, str(dev))] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-        with _on(dev):
-            _check(lib().gtts_spktrain_backward(self._h, _ptr(blob_train), _ptr(frames), _ptr(d_embeds), _ptr(saved), saved.numel(), arr,
-                                           len(grads), _ptr(ws), ws.numel(), N, T, _stream()), "gtts_spktrain_backward")
+        _launch(dev, "gtts_spktrain_backward", self._h, blob_train, frames, d_embeds, saved, saved.numel(), arr, len(grads), ws, ws.numel(), N, T)
         return grads
 
 
@@ -1449,13 +1443,12 @@ def ge2e_loss(embeds, w, b, want_grad=True):
     """GE2E similarity matrix, loss and gradient in one launch (csrc/spk_train.hip).  embeds [S, U, E], w and b one-element tensors on
     the same HIP device -> (sim [S * U, S], loss [1], d_embeds [S, U, E], dw [1], db [1]) for a loss gradient of 1; with
     want_grad=False the three gradients are None and their phases are skipped."""
-    embeds, w, b = _f32c(embeds, "embeds"), _f32c(w, "w"), _f32c(b, "b")
+    op = "ge2e_loss"
+    embeds = _in(op, "embeds", embeds)
     if embeds.dim() != 3:
-        raise RuntimeError("embeds must be [speakers, utterances, embed] (got %s)" % (tuple(embeds.shape),))
-    if w.numel() != 1 or b.numel() != 1 or w.device != embeds.device or b.device != embeds.device:
-        raise RuntimeError("w and b must be one-element tensors on %s" % embeds.device)
-    S, U, E = embeds.shape
-    dev = embeds.device
+        raise ArgumentError("embeds must be [speakers, utterances, embed] (got %s)" % (tuple(embeds.shape),))
+    dev, (S, U, E) = embeds.device, embeds.shape
+    w, b = _in(op, "w", w, 1, dev), _in(op, "b", b, 1, dev)
     key = (S, U, E, str(dev))
     ws = _GE2E_WS.get(key)
     if ws is None:
@@ -1467,21 +1460,20 @@ def ge2e_loss(embeds, w, b, want_grad=True):
     d_embeds = torch.empty_like(embeds) if want_grad else None
     dw = torch.empty(1, dtype=torch.float32, device=dev) if want_grad else None
     db = torch.empty(1, dtype=torch.float32, device=dev) if want_grad else None
-    with _on(dev):
-        _check(lib().gtts_ge2e_loss(_ptr(embeds), _ptr(w), _ptr(b), S, U, E, _ptr(sim), _ptr(loss), _ptr(d_embeds), _ptr(dw), _ptr(db),
-                                    _ptr(ws), ws.numel(), _stream()), "gtts_ge2e_loss")
+    _launch(dev, "gtts_ge2e_loss", embeds, w, b, S, U, E, sim, loss, d_embeds, dw, db, ws, ws.numel())
     return sim, loss, d_embeds, dw, db
 
 
 def euler_step(xt, mu, est, mask, beta_t, h, noise=None):
-    """In-place update of xt (one step of Diffusion.reverse_diffusion, diffusion.py:264-274)."""
+    """In-place update of xt [B,F,T] (one step of Diffusion.reverse_diffusion, diffusion.py:264-274): mu, est and noise (or None) of
+    xt's shape, mask [B,T] in any view of B * T elements ([B,1,T])."""
+    op = "euler_step"
     if not xt.is_cuda or xt.dtype != torch.float32 or not xt.is_contiguous():
-        raise RuntimeError("xt must be a contiguous fp32 HIP tensor (updated in place)")
-    mu, est, mask, noise = _f32c(mu, "mu"), _f32c(est, "est"), _f32c(mask, "mask"), _f32c(noise, "noise")
-    B, F, T = xt.shape
-    with torch.cuda.device(xt.device):
-        _check(lib().gtts_euler_step(_ptr(xt), _ptr(mu), _ptr(est), _ptr(mask), _ptr(noise), float(beta_t), float(h),
-                                     B, F, T, _stream()), "gtts_euler_step")
+        raise ArgumentError("xt must be a contiguous fp32 HIP tensor (updated in place)")
+    dev, (B, F, T) = xt.device, xt.shape
+    mu, est, mask = _in(op, "mu", mu, (B, F, T), dev), _in(op, "est", est, (B, F, T), dev), _in(op, "mask", mask, B * T, dev)
+    noise = _in(op, "noise", noise, (B, F, T), dev, optional=True)
+    _launch(dev, "gtts_euler_step", xt, mu, est, mask, noise, float(beta_t), float(h), B, F, T)
     return xt
 
 
@@ -1494,6 +1486,8 @@ def mas_maximum_path(value, mask):
     v = value.detach().float().contiguous()
     m = mask.detach().to(device=v.device, dtype=torch.float32).contiguous()
     b, tx, ty = v.shape
+    if m.shape != (b, tx, ty):
+        raise ArgumentError("mas_maximum_path: mask has shape %s, expected %s" % (tuple(m.shape), (b, tx, ty)))
     t_x = m.sum(1)[:, 0].to(torch.int32).contiguous()       # __init__.py:20-21
     t_y = m.sum(2)[:, 0].to(torch.int32).contiguous()
     path = torch.empty((b, tx, ty), dtype=torch.int32, device=v.device)
@@ -1502,9 +1496,7 @@ def mas_maximum_path(value, mask):
                "gtts_mas_maximum_path_cpu")
         return path.to(dtype=value.dtype)
     scratch = torch.empty(int(lib().gtts_mas_scratch_bytes(b, tx, ty)), dtype=torch.uint8, device=v.device)
-    with torch.cuda.device(v.device):
-        _check(lib().gtts_mas_maximum_path(_ptr(v), _ptr(m), _ptr(t_x), _ptr(t_y), _ptr(path), _ptr(scratch), b, tx,
-                                           ty, _stream()), "gtts_mas_maximum_path")
+    _launch(v.device, "gtts_mas_maximum_path", v, m, t_x, t_y, path, scratch, b, tx, ty)
     return path.to(dtype=value.dtype)
 
 
@@ -1572,6 +1564,7 @@ def clear_packed_cache():
 # "dn_T" Downsample's data gradient.
 _PACK_KINDS = {"3x3": ("conv3x3", None, 0), "1x1": ("conv1x1", None, 1), "7x7": ("conv7x7", None, None),
                "dn": ("conv_resample", 0, 2), "up": ("conv_resample", 1, 3), "dn_T": ("conv_resample", 1, 4)}
+_PACK_TAPS = {"3x3": 9, "1x1": 1, "7x7": 49, "dn": 9, "up": 16, "dn_T": 9}      # elements of a kind's weight per (cin, cout) pair
 
 
 def _packed_nbytes(kind, cin, cout):
@@ -1593,8 +1586,7 @@ def _packed_weight(weight, cin, cout, transposed, kind):
     # [in = cout][out = cin])
     src = torch.nn.functional.pad(weight, (0, 1, 0, 1)).contiguous() if kind == "dn_T" else weight
     packed = torch.empty(_packed_nbytes(kind, cin, cout), dtype=torch.uint8, device=weight.device)
-    _check(getattr(lib(), "gtts_%s_pack" % family)(_ptr(src), _ptr(packed), cin, cout, (1 if transposed else 0) if up is None else up,
-                                                   _stream()), "gtts_%s_pack" % family)
+    _launch(weight.device, "gtts_%s_pack" % family, src, packed, cin, cout, (1 if transposed else 0) if up is None else up)
     if len(_PACKED) >= 512:          # (two entries per convolution: ~100 for the Grad-TTS U-Net); dead entries go with the sweep
         for k in [k for k, v in _PACKED.items() if v[0]() is None]:
             del _PACKED[k]
@@ -1618,6 +1610,8 @@ def _build_pack_plan(specs, dev, sig):
     blobs = []
     with _on(dev):
         for k, (w, ci, co, t, kind) in enumerate(specs):
+            # (the packing kernel reads the weight where it lies, at every later step too: nothing may be converted or copied)
+            _in("prepack", "weight %d" % k, w, int(ci) * int(co) * _PACK_TAPS[kind], dev, strict=True)
             blob = torch.empty(_packed_nbytes(kind, ci, co), dtype=torch.uint8, device=dev)
             blobs.append(blob)
             items[k].w, items[k].packed = w.data_ptr(), blob.data_ptr()
@@ -1640,7 +1634,6 @@ def prepack(specs):
     the stream the step runs on."""
     if not specs:
         return
-    L = lib()
     dev = specs[0][0].device
     sig = tuple([w.data_ptr() for w, *_ in specs])          # (cheap per-step check: the addresses the descriptor table holds)
     plan = getattr(specs, "plan", None)
@@ -1648,8 +1641,7 @@ def prepack(specs):
         plan = _build_pack_plan(specs, dev, sig)
         if isinstance(specs, PackSpecs):
             specs.plan = plan
-    with _on(dev):
-        _check(L.gtts_pack_batch(_ptr(plan["desc"]), plan["n"], plan["grid"], _stream()), "gtts_pack_batch")
+    _launch(dev, "gtts_pack_batch", plan["desc"], plan["n"], plan["grid"])
     gen = _PACK_GEN
     for (key, ref, blob), spec in zip(plan["entries"], specs):
         w = spec[0]
@@ -1665,38 +1657,29 @@ def _const(device, kind, *shape):
     return v
 
 
-def _out(out, name, shape, dtype, device, exc=RuntimeError):
-    """A preallocated output of the caller's (`out` dict, tests place them between guard margins) or a fresh one."""
-    t = None if out is None else out.get(name)
+def _out(op, given, name, shape, dev, dtype=torch.float32):
+    """THE rule for a result of the wrapper `op`: the caller's preallocated tensor -- `given`, or `given[name]` of a dict; tests place
+    them between guard margins -- has to be a contiguous `dtype` tensor of exactly `shape` on `dev`; without one a fresh tensor is made."""
+    t = given.get(name) if isinstance(given, dict) else given
     if t is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
-        raise exc("output %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if t.shape != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+        raise ArgumentError("%s: output %s must be a contiguous %s tensor of shape %s on %s" % (op, name, dtype, tuple(shape), dev))
     return t
 
 
-def _given(t, name, shape, device, dtype=torch.float32):
-    """The caller's preallocated tensor `t` for the result `name` (tests place it between guard margins), or a fresh one: ValueError
-    unless it is contiguous, of that shape and dtype, and on that device."""
-    return _out(None if t is None else {name: t}, name, shape, dtype, device, exc=ValueError)
-
-
-def _scratch(out, nbytes, device):
+def _scratch(op, out, nbytes, dev):
     """The workspace of a weight-gradient call: `out["workspace"]` (fp32, exactly the bytes the call asks for) or a fresh one."""
     if out is None or out.get("workspace") is None:
-        return torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return _out(out, "workspace", (nbytes // 4,), torch.float32, device, exc=ValueError)
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return _out(op, out, "workspace", (nbytes // 4,), dev)
 
 
-def _i32c(t, name, device):
+def _i32(op, name, t, shape, dev):
+    """_in for an int32 tensor the caller may give as a list of ints."""
     if not torch.is_tensor(t):
         t = torch.tensor(t, dtype=torch.int32)
-    return t.to(device=device, dtype=torch.int32).contiguous()
-
-
-def _hip_only(t, what):
-    if not t.is_cuda:
-        raise RuntimeError("%s needs HIP tensors (got %s); there is no CPU fallback" % (what, t.device))
+    return _in(op, name, t.to(device=dev, dtype=torch.int32), shape, dev, dtype=torch.int32)
 
 
 # kind -> (kernel size, the entry points take a second source x1 / c0, the forward entry point takes an output mask, the names of
@@ -1720,151 +1703,147 @@ def conv_train_kernel_name(kind, B, cin, cout, H, W, c0=0):
     return buf.value.decode()
 
 
-def _conv_run(kind, x, mask_cols, weight, bias, transposed, x1=None, out_mask=None, out=None):
-    _, two, om, name, _, _ = _CONV_KINDS[kind]
-    B, c0, H, W = x.shape
-    cin = c0 + (int(x1.shape[1]) if x1 is not None else 0)
-    cout = weight.shape[1] if transposed else weight.shape[0]
-    y = _given(out, "out", (B, cout, H, W), x.device)
-    src = (_ptr(x), _ptr(x1), c0, _ptr(mask_cols)) if two else (_ptr(x), _ptr(mask_cols))
-    with _on(x.device):
-        packed = _packed_weight(weight, cin, cout, transposed, kind)
-        _check(getattr(lib(), name)(*src, *((_ptr(out_mask),) if om else ()), _ptr(packed), _ptr(bias), _ptr(y), B, cin, cout, H, W,
-                                    _stream()), name)
+def _conv_run(op, kind, x, mask_cols, weight, bias, transposed, x1=None, out_mask=None, out=None, xname="x"):
+    """The forward (transposed False) or data-gradient (True: x is dy, weight the forward's) call of a packed convolution kind for the
+    wrapper `op`, every tensor checked: x [B,c0,H,W], x1 [B,c1,H,W] or None, masks [B,W], weight [cout,c0+c1,k,k] (transposed:
+    [c0,cout,k,k]), bias [cout]."""
+    ksize, two, om, name, _, _ = _CONV_KINDS[kind]
+    x = _in(op, xname, x)
+    dev, (B, c0, H, W) = x.device, x.shape
+    c1 = 0 if x1 is None else x1.shape[1]
+    x1 = _in(op, "x1", x1, (B, c1, H, W), dev, optional=True)
+    cin, cout = c0 + c1, weight.shape[1 if transposed else 0]
+    weight = _in(op, "weight", weight, (cin, cout, ksize, ksize) if transposed else (cout, cin, ksize, ksize), dev)
+    mask_cols, bias = _in(op, "mask_cols", mask_cols, (B, W), dev), _in(op, "bias", bias, (cout,), dev)
+    out_mask = _in(op, "mask_cols", out_mask, (B, W), dev, optional=True)
+    y = _out(op, out, "out", (B, cout, H, W), dev)
+    packed = _packed_weight(weight, cin, cout, transposed, kind)
+    _launch(dev, name, *((x, x1, c0) if two else (x,)), mask_cols, *((out_mask,) if om else ()), packed, bias, y, B, cin, cout, H, W)
     return y
 
 
-def _conv_dgrad(kind, dy, weight, mask_cols, out=None):
-    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
-    B, cout, H, W = dy.shape
-    return _conv_run(kind, dy, _const(dy.device, "ones", B, W), weight, _const(dy.device, "zeros", int(weight.shape[1])), True,
-                     out_mask=_f32c(mask_cols, "mask"), out=out)
+def _conv_dgrad(op, kind, dy, weight, mask_cols, out=None):
+    B, W = dy.shape[0], dy.shape[-1]
+    return _conv_run(op, kind, dy, _const(dy.device, "ones", B, W), weight, _const(dy.device, "zeros", int(weight.shape[1])), True,
+                     out_mask=mask_cols, out=out, xname="dy")
 
 
-def _tiled_wgrad(kind, x, mask_cols, dy, x1=None, want_bias=True, out=None):
+def _wgrad_in(op, x, mask_cols, dy, x1=None, mask_optional=False):
+    """The tensors a weight-gradient wrapper takes, checked: x [B,c0,H,W], x1 [B,c1,H,W] or None, mask_cols [B,W], dy [B,cout,H,W];
+    returns them with the device and B, cin = c0 + c1, cout, H, W."""
+    x = _in(op, "x", x)
+    dev, (B, c0, H, W) = x.device, x.shape
+    c1 = 0 if x1 is None else x1.shape[1]
+    x1 = _in(op, "x1", x1, (B, c1, H, W), dev, optional=True)
+    mask_cols = _in(op, "mask_cols", mask_cols, (B, W), dev, optional=mask_optional)
+    cout = dy.shape[1]
+    return x, mask_cols, _in(op, "dy", dy, (B, cout, H, W), dev), x1, dev, B, c0 + c1, cout, H, W
+
+
+def _tiled_wgrad(op, kind, x, mask_cols, dy, x1=None, want_bias=True, out=None):
     """(dW [cout,cin,k,k], db [cout] or None) by the kind's LDS-tiled deterministic reduction (train_wgrad.hip, train_wgrad7.hip).
     `out`: optional dict of preallocated dw / db / workspace (fp32, gtts_conv<kind>_wgrad_workspace_bytes / 4 floats)."""
     ksize, two, _, _, name, ws_name = _CONV_KINDS[kind]
-    B, c0, H, W = x.shape
-    cin = c0 + (int(x1.shape[1]) if x1 is not None else 0)
-    cout = int(dy.shape[1])
-    dw = _out(out, "dw", (cout, cin, ksize, ksize), torch.float32, x.device, exc=ValueError)
-    db = _out(out, "db", (cout,), torch.float32, x.device, exc=ValueError) if want_bias else None
-    src = (_ptr(x), _ptr(x1), c0) if two else (_ptr(x),)
-    with _on(x.device):
-        L = lib()
-        nws = int(getattr(L, ws_name)(B, cin, cout, H, W))
-        ws = _scratch(out, nws, x.device)
-        _check(getattr(L, name)(*src, _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), nws, B, cin, cout, H, W, _stream()), name)
+    x, mask_cols, dy, x1, dev, B, cin, cout, H, W = _wgrad_in(op, x, mask_cols, dy, x1, kind == "1x1")
+    dw = _out(op, out, "dw", (cout, cin, ksize, ksize), dev)
+    db = _out(op, out, "db", (cout,), dev) if want_bias else None
+    nws = int(getattr(lib(), ws_name)(B, cin, cout, H, W))
+    ws = _scratch(op, out, nws, dev)
+    _launch(dev, name, *((x, x1, x.shape[1]) if two else (x,)), mask_cols, dy, dw, db, ws, nws, B, cin, cout, H, W)
     return dw, db
 
 
-def _wgrad_small(x, mask_cols, dy, ksize, want_bias=True, out=None):
+def _wgrad_small(op, x, mask_cols, dy, ksize, want_bias=True, out=None):
     """The first layer's weight gradient (cin 2 or 3: its own kernel).  `out`: optional dict of preallocated dw / db / workspace
     (gtts_conv_wgrad_small_scratch_floats floats)."""
-    B, cin, H, W = x.shape
-    cout = int(dy.shape[1])
-    dw = _out(out, "dw", (cout, cin, ksize, ksize), torch.float32, x.device, exc=ValueError)
-    db = _out(out, "db", (cout,), torch.float32, x.device, exc=ValueError) if want_bias else None
-    with _on(x.device):
-        scratch = _out(out, "workspace", (int(lib().gtts_conv_wgrad_small_scratch_floats(B, cin, cout, ksize)),), torch.float32, x.device,
-                       exc=ValueError)
-        _check(lib().gtts_conv_wgrad_small(_ptr(x), _ptr(mask_cols), _ptr(dy), _ptr(dw), _ptr(db), _ptr(scratch), B, cin, cout, H, W, ksize,
-                                           _stream()), "gtts_conv_wgrad_small")
+    x, mask_cols, dy, _, dev, B, cin, cout, H, W = _wgrad_in(op, x, mask_cols, dy)
+    dw = _out(op, out, "dw", (cout, cin, ksize, ksize), dev)
+    db = _out(op, out, "db", (cout,), dev) if want_bias else None
+    scratch = _out(op, out, "workspace", (int(lib().gtts_conv_wgrad_small_scratch_floats(B, cin, cout, ksize)),), dev)
+    _launch(dev, "gtts_conv_wgrad_small", x, mask_cols, dy, dw, db, scratch, B, cin, cout, H, W, ksize)
     return dw, db
 
 
 def conv3x3_masked(x, mask_cols, weight, bias, x1=None, out=None):
     """Conv2d_3x3(cat(x, x1) * mask) + bias (Block.forward, diffusion.py:56-57; the concatenation of the up path, :166, is read in
-    place): x [B,c0,H,W], x1 [B,c1,H,W] or None, mask_cols [B,W], weight [cout,c0+c1,3,3].  `out`: optional preallocated result."""
-    x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
+    place): x [B,c0,H,W], x1 [B,c1,H,W] or None, mask_cols [B,W], weight [cout,c0+c1,3,3], bias [cout].  `out`: optional preallocated
+    result."""
     if x1 is None and conv3x3_narrow(weight.shape[1], weight.shape[0]):
         return conv3x3_narrow_forward(x, mask_cols, weight, bias, out=None if out is None else {"out": out})
-    return _conv_run("3x3", x, mask_cols, weight, bias, False, _f32c(x1, "x1"), out=out)
+    return _conv_run("conv3x3_masked", "3x3", x, mask_cols, weight, bias, False, x1, out=out)
 
 
 def conv3x3_dgrad(dy, weight, mask_cols=None, out=None):
-    """Gradient of conv3x3_masked w.r.t. (x * mask): a 3x3 convolution of dy with the transposed, flipped weights; with
-    mask_cols [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue).  `out`: optional preallocated result."""
+    """Gradient of conv3x3_masked w.r.t. (x * mask): a 3x3 convolution of dy [B,cout,H,W] with the transposed, flipped weights
+    [cout,cin,3,3]; with mask_cols [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue).  `out`: optional
+    preallocated result."""
     if conv3x3_narrow(weight.shape[1], weight.shape[0]):
         return conv3x3_narrow_dgrad(dy, weight, mask_cols, out=None if out is None else {"dx": out})
-    return _conv_dgrad("3x3", dy, weight, mask_cols, out=out)
+    return _conv_dgrad("conv3x3_dgrad", "3x3", dy, weight, mask_cols, out=out)
 
 
 def conv3x3_wgrad(x, mask_cols, dy, x1=None, out=None):
-    """(dW [cout,cin,3,3], db [cout]) of conv3x3_masked (x1: second source of a concatenated input, c0 a multiple of 64).  `out`:
-    optional dict of preallocated dw / db / workspace."""
-    x, mask_cols, dy, x1 = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy"), _f32c(x1, "x1")
+    """(dW [cout,cin,3,3], db [cout]) of conv3x3_masked: x [B,c0,H,W], mask_cols [B,W], dy [B,cout,H,W] (x1 [B,c1,H,W]: second source
+    of a concatenated input, c0 a multiple of 64).  `out`: optional dict of preallocated dw / db / workspace."""
     cin, cout = int(x.shape[1]) + (int(x1.shape[1]) if x1 is not None else 0), int(dy.shape[1])
     if cin in (2, 3) and x1 is None:
-        return _wgrad_small(x, mask_cols, dy, 3, out=out)
+        return _wgrad_small("conv3x3_wgrad", x, mask_cols, dy, 3, out=out)
     if x1 is None and conv3x3_narrow(cin, cout):
         return conv3x3_narrow_wgrad(x, mask_cols, dy, out=out)
     if cin % 64 or cout % 64:
-        raise ValueError("conv3x3_wgrad: cin and cout must be multiples of 64, or cin 2 or 3 from one source (got cin %d, cout %d)"
+        raise ArgumentError("conv3x3_wgrad: cin and cout must be multiples of 64, or cin 2 or 3 from one source (got cin %d, cout %d)"
                          % (cin, cout))
-    return _tiled_wgrad("3x3", x, mask_cols, dy, x1, out=out)
+    return _tiled_wgrad("conv3x3_wgrad", "3x3", x, mask_cols, dy, x1, out=out)
 
 
-def _narrow_ws(out, B, cin, cout, H, W, op, device):
-    nws = int(lib().gtts_conv3x3_narrow_workspace_bytes(B, cin, cout, H, W, op))
+def _narrow_ws(op, out, B, cin, cout, H, W, which, dev):
+    nws = int(lib().gtts_conv3x3_narrow_workspace_bytes(B, cin, cout, H, W, which))
     if nws == 0:
-        raise ValueError("the narrow 3x3 kernels take cin 1 or 32 (the data gradient: 32) and cout 64 or 128 (got cin %d, cout %d, B %d, "
+        raise ArgumentError("the narrow 3x3 kernels take cin 1 or 32 (the data gradient: 32) and cout 64 or 128 (got cin %d, cout %d, B %d, "
                          "%d x %d)" % (cin, cout, B, H, W))
-    return _scratch(out, nws, device), nws
+    return _scratch(op, out, nws, dev), nws
 
 
 def conv3x3_narrow_forward(x, mask_cols, weight, bias, out_mask=None, out=None):
     """Conv2d_3x3(x * mask) + bias [times out_mask] for RefBlock's narrow layers (cin 1 or 32, cout 64 or 128) on csrc/train_narrow.hip:
-    x [B,cin,H,W], mask_cols / out_mask [B,W], weight [cout,cin,3,3] as the module holds it.  `out`: optional dict of a preallocated
-    out / workspace (fp32, gtts_conv3x3_narrow_workspace_bytes / 4 floats)."""
-    _hip_only(x, "conv3x3_narrow_forward")
-    x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
-    B, cin, H, W = x.shape
-    cout = int(weight.shape[0])
-    if tuple(weight.shape) != (cout, cin, 3, 3) or tuple(mask_cols.shape) != (B, W) or tuple(bias.shape) != (cout,):
-        raise ValueError("conv3x3_narrow_forward: x %s, weight %s, bias %s and mask %s do not match" %
-                         (tuple(x.shape), tuple(weight.shape), tuple(bias.shape), tuple(mask_cols.shape)))
-    y = _out(out, "out", (B, cout, H, W), torch.float32, x.device, exc=ValueError)
-    with _on(x.device):
-        ws, nws = _narrow_ws(out, B, cin, cout, H, W, 0, x.device)
-        _check(lib().gtts_conv3x3_narrow_forward(_ptr(x), _ptr(mask_cols), _ptr(_f32c(out_mask, "out_mask")), _ptr(weight), _ptr(bias), _ptr(y),
-                                                 _ptr(ws), nws, B, cin, cout, H, W, _stream()), "gtts_conv3x3_narrow_forward")
+    x [B,cin,H,W], mask_cols / out_mask [B,W], weight [cout,cin,3,3] as the module holds it, bias [cout].  `out`: optional dict of a
+    preallocated out / workspace (fp32, gtts_conv3x3_narrow_workspace_bytes / 4 floats)."""
+    op = "conv3x3_narrow_forward"
+    x = _in(op, "x", x)
+    dev, (B, cin, H, W), cout = x.device, x.shape, int(weight.shape[0])
+    weight, bias = _in(op, "weight", weight, (cout, cin, 3, 3), dev), _in(op, "bias", bias, (cout,), dev)
+    mask_cols, out_mask = _in(op, "mask_cols", mask_cols, (B, W), dev), _in(op, "out_mask", out_mask, (B, W), dev, optional=True)
+    y = _out(op, out, "out", (B, cout, H, W), dev)
+    ws, nws = _narrow_ws(op, out, B, cin, cout, H, W, 0, dev)
+    _launch(dev, "gtts_conv3x3_narrow_forward", x, mask_cols, out_mask, weight, bias, y, ws, nws, B, cin, cout, H, W)
     return y
 
 
 def conv3x3_narrow_dgrad(dy, weight, mask_cols=None, out_mask=None, out=None):
-    """dx [B,cin,H,W] of conv3x3_narrow_forward (cin 32): mask_cols (None: ones) is the forward's input mask, out_mask its output mask.
-    `out`: optional dict of a preallocated dx / workspace."""
-    _hip_only(dy, "conv3x3_narrow_dgrad")
-    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
-    B, cout, H, W = dy.shape
-    cin = int(weight.shape[1])
-    if tuple(weight.shape) != (cout, cin, 3, 3):
-        raise ValueError("conv3x3_narrow_dgrad: weight %s does not match dy %s" % (tuple(weight.shape), tuple(dy.shape)))
-    mask_cols = _const(dy.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
-    dx = _out(out, "dx", (B, cin, H, W), torch.float32, dy.device, exc=ValueError)
-    with _on(dy.device):
-        ws, nws = _narrow_ws(out, B, cin, cout, H, W, 1, dy.device)
-        _check(lib().gtts_conv3x3_narrow_dgrad(_ptr(dy), _ptr(_f32c(out_mask, "out_mask")), _ptr(mask_cols), _ptr(weight), _ptr(dx), _ptr(ws),
-                                               nws, B, cin, cout, H, W, _stream()), "gtts_conv3x3_narrow_dgrad")
+    """dx [B,cin,H,W] of conv3x3_narrow_forward (cin 32) from dy [B,cout,H,W] and weight [cout,cin,3,3]: mask_cols [B,W] (None: ones) is
+    the forward's input mask, out_mask [B,W] its output mask.  `out`: optional dict of a preallocated dx / workspace."""
+    op = "conv3x3_narrow_dgrad"
+    dy = _in(op, "dy", dy)
+    dev, (B, cout, H, W), cin = dy.device, dy.shape, int(weight.shape[1])
+    weight = _in(op, "weight", weight, (cout, cin, 3, 3), dev)
+    mask_cols = _const(dev, "ones", B, W) if mask_cols is None else _in(op, "mask_cols", mask_cols, (B, W), dev)
+    out_mask = _in(op, "out_mask", out_mask, (B, W), dev, optional=True)
+    dx = _out(op, out, "dx", (B, cin, H, W), dev)
+    ws, nws = _narrow_ws(op, out, B, cin, cout, H, W, 1, dev)
+    _launch(dev, "gtts_conv3x3_narrow_dgrad", dy, out_mask, mask_cols, weight, dx, ws, nws, B, cin, cout, H, W)
     return dx
 
 
 def conv3x3_narrow_wgrad(x, mask_cols, dy, out_mask=None, want_bias=True, out=None):
-    """(dW [cout,cin,3,3], db [cout] or None) of conv3x3_narrow_forward.  `out`: optional dict of preallocated dw / db / workspace."""
-    _hip_only(x, "conv3x3_narrow_wgrad")
-    x, mask_cols, dy = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy")
-    B, cin, H, W = x.shape
-    cout = int(dy.shape[1])
-    if tuple(dy.shape) != (B, cout, H, W) or tuple(mask_cols.shape) != (B, W):
-        raise ValueError("conv3x3_narrow_wgrad: x %s, dy %s and mask %s do not match" % (tuple(x.shape), tuple(dy.shape), tuple(mask_cols.shape)))
-    dw = _out(out, "dw", (cout, cin, 3, 3), torch.float32, x.device, exc=ValueError)
-    db = _out(out, "db", (cout,), torch.float32, x.device, exc=ValueError) if want_bias else None
-    with _on(x.device):
-        ws, nws = _narrow_ws(out, B, cin, cout, H, W, 2, x.device)
-        _check(lib().gtts_conv3x3_narrow_wgrad(_ptr(x), _ptr(mask_cols), _ptr(_f32c(out_mask, "out_mask")), _ptr(dy), _ptr(dw), _ptr(db),
-                                               _ptr(ws), nws, B, cin, cout, H, W, _stream()), "gtts_conv3x3_narrow_wgrad")
+    """(dW [cout,cin,3,3], db [cout] or None) of conv3x3_narrow_forward: x [B,cin,H,W], mask_cols / out_mask [B,W], dy [B,cout,H,W].
+    `out`: optional dict of preallocated dw / db / workspace."""
+    op = "conv3x3_narrow_wgrad"
+    x, mask_cols, dy, _, dev, B, cin, cout, H, W = _wgrad_in(op, x, mask_cols, dy)
+    out_mask = _in(op, "out_mask", out_mask, (B, W), dev, optional=True)
+    dw = _out(op, out, "dw", (cout, cin, 3, 3), dev)
+    db = _out(op, out, "db", (cout,), dev) if want_bias else None
+    ws, nws = _narrow_ws(op, out, B, cin, cout, H, W, 2, dev)
+    _launch(dev, "gtts_conv3x3_narrow_wgrad", x, mask_cols, out_mask, dy, dw, db, ws, nws, B, cin, cout, H, W)
     return dw, db
 
 
@@ -1878,61 +1857,63 @@ def conv7x7_supported(cin, cout, need_dgrad=True, shape=None):
 
 def conv7x7_masked(x, mask_cols, weight, bias, out=None):
     """Conv2d_7x7(x * mask, padding 3) + bias (PostNet Block, DiffVC/model/postnet.py:21-23): x [B,cin,H,W], mask_cols [B,W],
-    weight [cout,cin,7,7].  `out`: optional preallocated result."""
-    x, mask_cols, weight, bias = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight"), _f32c(bias, "bias")
-    return _conv_run("7x7", x, mask_cols, weight, bias, False, out=out)
+    weight [cout,cin,7,7], bias [cout].  `out`: optional preallocated result."""
+    return _conv_run("conv7x7_masked", "7x7", x, mask_cols, weight, bias, False, out=out)
 
 
 def conv7x7_dgrad(dy, weight, mask_cols=None, out=None):
-    """Gradient of conv7x7_masked w.r.t. (x * mask): a 7x7 convolution of dy with the transposed, flipped weights; with mask_cols
-    [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue).  `out`: optional preallocated result."""
-    return _conv_dgrad("7x7", dy, weight, mask_cols, out=out)
+    """Gradient of conv7x7_masked w.r.t. (x * mask): a 7x7 convolution of dy [B,cout,H,W] with the transposed, flipped weights
+    [cout,cin,7,7]; with mask_cols [B,W] the gradient w.r.t. x itself (the mask is applied in the kernel's epilogue).  `out`: optional
+    preallocated result."""
+    return _conv_dgrad("conv7x7_dgrad", "7x7", dy, weight, mask_cols, out=out)
 
 
 def conv7x7_wgrad(x, mask_cols, dy, out=None):
-    """(dW [cout,cin,7,7], db [cout]) of conv7x7_masked (train_wgrad7.hip: deterministic split-bf16 MFMA reduction).  `out`: optional
-    dict of preallocated dw / db / workspace."""
-    return _tiled_wgrad("7x7", _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy"), out=out)
+    """(dW [cout,cin,7,7], db [cout]) of conv7x7_masked (train_wgrad7.hip: deterministic split-bf16 MFMA reduction): x [B,cin,H,W],
+    mask_cols [B,W], dy [B,cout,H,W].  `out`: optional dict of preallocated dw / db / workspace."""
+    return _tiled_wgrad("conv7x7_wgrad", "7x7", x, mask_cols, dy, out=out)
 
 
 def postnet_expand(x, mask, w, bias=None, out=None):
-    """out [B,C,F,T] = w[c] * x[b,f,t] * mask[b,t] + bias[c] (PostNet init_conv; final_conv's data gradient with bias None).  `out`:
-    optional preallocated result."""
-    x, mask, w = _f32c(x, "x"), _f32c(mask, "mask"), _f32c(w, "weight")
-    B, F, T = x.shape
-    C = int(w.numel())
-    bias = _const(x.device, "zeros", C) if bias is None else _f32c(bias, "bias")
-    out = _given(out, "out", (B, C, F, T), x.device)
-    with _on(x.device):
-        _check(lib().gtts_postnet_expand(_ptr(x), _ptr(mask), _ptr(w), _ptr(bias), _ptr(out), B, C, F, T, _stream()), "gtts_postnet_expand")
+    """out [B,C,F,T] = w[c] * x[b,f,t] * mask[b,t] + bias[c] (PostNet init_conv; final_conv's data gradient with bias None): x [B,F,T],
+    mask [B,T], w and bias C elements each (the weight flat or as the module's [C,1,1,1]: the element count decides).  `out`: optional
+    preallocated result."""
+    op = "postnet_expand"
+    x = _in(op, "x", x)
+    dev, (B, F, T), C = x.device, x.shape, int(w.numel())
+    mask, w = _in(op, "mask", mask, (B, T), dev), _in(op, "w", w, C, dev)
+    bias = _const(dev, "zeros", C) if bias is None else _in(op, "bias", bias, C, dev)
+    out = _out(op, out, "out", (B, C, F, T), dev)
+    _launch(dev, "gtts_postnet_expand", x, mask, w, bias, out, B, C, F, T)
     return out
 
 
 def postnet_collapse(x, mask, w, bias=None, out=None):
-    """out [B,F,T] = sum_c w[c] * x[b,c,f,t] * mask[b,t] + bias (PostNet final_conv; init_conv's data gradient with bias None).  `out`:
-    optional preallocated result."""
-    x, mask, w = _f32c(x, "x"), _f32c(mask, "mask"), _f32c(w, "weight")
-    B, C, F, T = x.shape
-    bias = _const(x.device, "zeros", 1) if bias is None else _f32c(bias, "bias")
-    out = _given(out, "out", (B, F, T), x.device)
-    with _on(x.device):
-        _check(lib().gtts_postnet_collapse(_ptr(x), _ptr(mask), _ptr(w), _ptr(bias), _ptr(out), B, C, F, T, _stream()), "gtts_postnet_collapse")
+    """out [B,F,T] = sum_c w[c] * x[b,c,f,t] * mask[b,t] + bias (PostNet final_conv; init_conv's data gradient with bias None):
+    x [B,C,F,T], mask [B,T], w C elements (flat or [1,C,1,1]: the element count decides), bias one element.  `out`: optional
+    preallocated result."""
+    op = "postnet_collapse"
+    x = _in(op, "x", x)
+    dev, (B, C, F, T) = x.device, x.shape
+    mask, w = _in(op, "mask", mask, (B, T), dev), _in(op, "w", w, C, dev)
+    bias = _const(dev, "zeros", 1) if bias is None else _in(op, "bias", bias, 1, dev)
+    out = _out(op, out, "out", (B, F, T), dev)
+    _launch(dev, "gtts_postnet_collapse", x, mask, w, bias, out, B, C, F, T)
     return out
 
 
 def postnet_chan_dot(a, v, mask, want_dot=True, want_sum=True, out=None):
-    """(dot [C], sum [C]) over a [B,C,F,T]: dot[c] = sum a[b,c] * v[b] * mask[b,t] (v [B,F,T], v / mask None: 1), sum[c] = sum a[b,c]
-    (fixed-order reduction; an output not wanted is None).  `out`: optional dict of preallocated dot / sum / workspace
+    """(dot [C], sum [C]) over a [B,C,F,T]: dot[c] = sum a[b,c] * v[b] * mask[b,t] (v [B,F,T], mask [B,T]; v / mask None: 1), sum[c] =
+    sum a[b,c] (fixed-order reduction; an output not wanted is None).  `out`: optional dict of preallocated dot / sum / workspace
     (gtts_postnet_chan_dot_scratch_floats floats)."""
-    a, v, mask = _f32c(a, "a"), _f32c(v, "v"), _f32c(mask, "mask")
-    B, C, F, T = a.shape
-    dot = _out(out, "dot", (C,), torch.float32, a.device, exc=ValueError) if want_dot else None
-    sm = _out(out, "sum", (C,), torch.float32, a.device, exc=ValueError) if want_sum else None
-    with _on(a.device):
-        scratch = _out(out, "workspace", (int(lib().gtts_postnet_chan_dot_scratch_floats(B, C, F, T)),), torch.float32, a.device,
-                       exc=ValueError)
-        _check(lib().gtts_postnet_chan_dot(_ptr(a), _ptr(v), _ptr(mask), _ptr(dot), _ptr(sm), _ptr(scratch), B, C, F, T, _stream()),
-               "gtts_postnet_chan_dot")
+    op = "postnet_chan_dot"
+    a = _in(op, "a", a)
+    dev, (B, C, F, T) = a.device, a.shape
+    v, mask = _in(op, "v", v, (B, F, T), dev, optional=True), _in(op, "mask", mask, (B, T), dev, optional=True)
+    dot = _out(op, out, "dot", (C,), dev) if want_dot else None
+    sm = _out(op, out, "sum", (C,), dev) if want_sum else None
+    scratch = _out(op, out, "workspace", (int(lib().gtts_postnet_chan_dot_scratch_floats(B, C, F, T)),), dev)
+    _launch(dev, "gtts_postnet_chan_dot", a, v, mask, dot, sm, scratch, B, C, F, T)
     return dot, sm
 
 
@@ -1949,91 +1930,92 @@ def conv1x1_supported(cin, cout, need_dgrad=True, shape=None):
 def conv1x1_masked(x, mask_cols, weight, bias, out=None):
     """Conv2d_1x1(x * mask) + bias (res_conv / to_qkv / to_out, diffusion.py:70,87-88): x [B,cin,H,W], mask_cols [B,W] or None,
     weight [cout,cin,1,1], bias [cout] or None.  `out`: optional preallocated result."""
-    x, weight = _f32c(x, "x"), _f32c(weight, "weight")
-    B, W = int(x.shape[0]), int(x.shape[3])
-    mask_cols = _const(x.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
-    bias = _const(x.device, "zeros", int(weight.shape[0])) if bias is None else _f32c(bias, "bias")
-    return _conv_run("1x1", x, mask_cols, weight, bias, False, out=out)
+    if mask_cols is None:
+        mask_cols = _const(x.device, "ones", int(x.shape[0]), int(x.shape[3]))
+    if bias is None:
+        bias = _const(x.device, "zeros", int(weight.shape[0]))
+    return _conv_run("conv1x1_masked", "1x1", x, mask_cols, weight, bias, False, out=out)
 
 
 def conv1x1_dgrad(dy, weight, mask_cols=None, out=None):
-    """Gradient of conv1x1_masked w.r.t. x: the 1x1 convolution of dy * mask (columns do not mix) with the transposed weight.  `out`:
-    optional preallocated result."""
-    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
-    B, W = int(dy.shape[0]), int(dy.shape[3])
-    mask_cols = _const(dy.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
-    return _conv_run("1x1", dy, mask_cols, weight, _const(dy.device, "zeros", int(weight.shape[1])), True, out=out)
+    """Gradient of conv1x1_masked w.r.t. x: the 1x1 convolution of dy * mask (columns do not mix) with the transposed weight: dy
+    [B,cout,H,W], weight [cout,cin,1,1], mask_cols [B,W] or None.  `out`: optional preallocated result."""
+    if mask_cols is None:
+        mask_cols = _const(dy.device, "ones", int(dy.shape[0]), int(dy.shape[3]))
+    return _conv_run("conv1x1_dgrad", "1x1", dy, mask_cols, weight, _const(dy.device, "zeros", int(weight.shape[1])), True, out=out, xname="dy")
 
 
 def conv1x1_wgrad(x, mask_cols, dy, want_bias=True, out=None):
-    """(dW [cout,cin,1,1], db [cout] or None) of conv1x1_masked.  `out`: optional dict of preallocated dw / db / workspace."""
-    x, mask_cols, dy = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(dy, "dy")
+    """(dW [cout,cin,1,1], db [cout] or None) of conv1x1_masked: x [B,cin,H,W], mask_cols [B,W] or None, dy [B,cout,H,W].  `out`:
+    optional dict of preallocated dw / db / workspace."""
     if x.shape[1] in (2, 3):
-        return _wgrad_small(x, _const(x.device, "ones", int(x.shape[0]), int(x.shape[3])) if mask_cols is None else mask_cols, dy, 1, want_bias,
-                            out=out)
-    return _tiled_wgrad("1x1", x, mask_cols, dy, want_bias=want_bias, out=out)
+        return _wgrad_small("conv1x1_wgrad", x, _const(x.device, "ones", int(x.shape[0]), int(x.shape[3])) if mask_cols is None else mask_cols,
+                            dy, 1, want_bias, out=out)
+    return _tiled_wgrad("conv1x1_wgrad", "1x1", x, mask_cols, dy, want_bias=want_bias, out=out)
 
 
 def add_masked(a, b, mask_cols, channels=None, out=None):
     """a + b * mask (a None: b * mask; mask_cols None: a + b) over [B,C,H,W] with mask_cols [B,W].  channels = (c_begin, c_end):
-    b is that channel range of a wider contiguous tensor (read in place; the result is contiguous).  `out`: optional preallocated result."""
-    a, b, mask_cols = _f32c(a, "a"), _f32c(b, "b"), _f32c(mask_cols, "mask")
-    B, Cb, H, W = b.shape
+    b is that channel range of a wider contiguous tensor [B,Cb,H,W] (read in place; the result and a have c_end - c_begin channels).
+    `out`: optional preallocated result."""
+    op = "add_masked"
+    b = _in(op, "b", b)
+    dev, (B, Cb, H, W) = b.device, b.shape
     c0, c1 = (0, Cb) if channels is None else channels
-    out = _given(out, "out", (B, c1 - c0, H, W), b.device)
-    with _on(b.device):
-        _check(lib().gtts_add_masked(_ptr(a), ctypes.c_void_p(b.data_ptr() + 4 * c0 * H * W), _ptr(mask_cols), _ptr(out), B, c1 - c0, H, W,
-                                     0 if channels is None else Cb, _stream()), "gtts_add_masked")
+    if not 0 <= c0 < c1 <= Cb:
+        raise ArgumentError("add_masked: channels %s lie outside b's %d" % ((c0, c1), Cb))
+    a = _in(op, "a", a, (B, c1 - c0, H, W), dev, optional=True)
+    mask_cols = _in(op, "mask_cols", mask_cols, (B, W), dev, optional=True)
+    out = _out(op, out, "out", (B, c1 - c0, H, W), dev)
+    _launch(dev, "gtts_add_masked", a, ctypes.c_void_p(b.data_ptr() + 4 * c0 * H * W), mask_cols, out, B, c1 - c0, H, W,
+            0 if channels is None else Cb)
     return out
 
 
 def zero_insert2(x, out=None):
     """[B,C,h,w] -> [B,C,2h,2w] with x at the even positions and zeros elsewhere.  `out`: optional preallocated result."""
-    x = _f32c(x, "x")
+    x = _in("zero_insert2", "x", x)
     B, C, h, w = x.shape
-    out = _given(out, "out", (B, C, 2 * h, 2 * w), x.device)
-    with _on(x.device):
-        _check(lib().gtts_zero_insert2(_ptr(x), _ptr(out), B, C, h, w, _stream()), "gtts_zero_insert2")
+    out = _out("zero_insert2", out, "out", (B, C, 2 * h, 2 * w), x.device)
+    _launch(x.device, "gtts_zero_insert2", x, out, B, C, h, w)
     return out
 
 
 def space_to_depth2(x, out=None):
     """[B,C,2h,2w] -> [B,4C,h,w]: channel block (pr * 2 + pc) holds rows 2y + 1 - pr and columns 2x + 1 - pc.  `out`: optional
     preallocated result."""
-    x = _f32c(x, "x")
+    x = _in("space_to_depth2", "x", x)
     B, C, H2, W2 = x.shape
     if H2 % 2 or W2 % 2:
-        raise ValueError("space_to_depth2: even height and width expected, got %d x %d" % (H2, W2))
-    out = _given(out, "out", (B, 4 * C, H2 // 2, W2 // 2), x.device)
-    with _on(x.device):
-        _check(lib().gtts_space_to_depth2(_ptr(x), _ptr(out), B, C, H2 // 2, W2 // 2, _stream()), "gtts_space_to_depth2")
+        raise ArgumentError("space_to_depth2: even height and width expected, got %d x %d" % (H2, W2))
+    out = _out("space_to_depth2", out, "out", (B, 4 * C, H2 // 2, W2 // 2), x.device)
+    _launch(x.device, "gtts_space_to_depth2", x, out, B, C, H2 // 2, W2 // 2)
     return out
 
 
 def final_conv_forward(x, weight, bias, mask_cols, out=None):
-    """(Conv2d_1x1(x * mask) + bias) * mask for the 64 -> 1 final convolution (diffusion.py:175-176): [B,1,H,W].  `out`: optional
+    """(Conv2d_1x1(x * mask) + bias) * mask for the 64 -> 1 final convolution (diffusion.py:175-176): x [B,C,H,W], weight C elements
+    (the module's [1,C,1,1] or flat: the element count decides), bias one element, mask_cols [B,W] -> [B,1,H,W].  `out`: optional
     preallocated result."""
-    x, weight, bias, mask_cols = _f32c(x, "x"), _f32c(weight, "weight"), _f32c(bias, "bias"), _f32c(mask_cols, "mask")
-    B, C, H, W = x.shape
-    out = _given(out, "out", (B, 1, H, W), x.device)
-    with _on(x.device):
-        _check(lib().gtts_final_conv_forward(_ptr(x), _ptr(weight), _ptr(bias), _ptr(mask_cols), _ptr(out), B, C, H, W, _stream()),
-               "gtts_final_conv_forward")
+    op = "final_conv_forward"
+    x = _in(op, "x", x)
+    dev, (B, C, H, W) = x.device, x.shape
+    weight, bias, mask_cols = _in(op, "weight", weight, C, dev), _in(op, "bias", bias, 1, dev), _in(op, "mask_cols", mask_cols, (B, W), dev)
+    out = _out(op, out, "out", (B, 1, H, W), dev)
+    _launch(dev, "gtts_final_conv_forward", x, weight, bias, mask_cols, out, B, C, H, W)
     return out
 
 
 def final_conv_backward(x, weight, mask_cols, dout, out=None):
-    """(dx, dweight [1,C,1,1], dbias [1]) of final_conv_forward.  `out`: optional dict of preallocated dx / dw / db / workspace
-    (gtts_final_conv_scratch_floats floats)."""
-    x, weight, mask_cols, dout = _f32c(x, "x"), _f32c(weight, "weight"), _f32c(mask_cols, "mask"), _f32c(dout, "dout")
-    B, C, H, W = x.shape
-    dx = _out(out, "dx", (B, C, H, W), torch.float32, x.device, exc=ValueError)
-    dw = _out(out, "dw", (1, C, 1, 1), torch.float32, x.device, exc=ValueError)
-    db = _out(out, "db", (1,), torch.float32, x.device, exc=ValueError)
-    with _on(x.device):
-        scratch = _out(out, "workspace", (int(lib().gtts_final_conv_scratch_floats(B, C, H, W)),), torch.float32, x.device, exc=ValueError)
-        _check(lib().gtts_final_conv_backward(_ptr(x), _ptr(weight), _ptr(mask_cols), _ptr(dout), _ptr(dx), _ptr(dw), _ptr(db),
-                                              _ptr(scratch), B, C, H, W, _stream()), "gtts_final_conv_backward")
+    """(dx, dweight [1,C,1,1], dbias [1]) of final_conv_forward: x [B,C,H,W], weight C elements, mask_cols [B,W], dout [B,1,H,W].
+    `out`: optional dict of preallocated dx / dw / db / workspace (gtts_final_conv_scratch_floats floats)."""
+    op = "final_conv_backward"
+    x = _in(op, "x", x)
+    dev, (B, C, H, W) = x.device, x.shape
+    weight, mask_cols, dout = _in(op, "weight", weight, C, dev), _in(op, "mask_cols", mask_cols, (B, W), dev), _in(op, "dout", dout, (B, 1, H, W), dev)
+    dx, dw, db = _out(op, out, "dx", (B, C, H, W), dev), _out(op, out, "dw", (1, C, 1, 1), dev), _out(op, out, "db", (1,), dev)
+    scratch = _out(op, out, "workspace", (int(lib().gtts_final_conv_scratch_floats(B, C, H, W)),), dev)
+    _launch(dev, "gtts_final_conv_backward", x, weight, mask_cols, dout, dx, dw, db, scratch, B, C, H, W)
     return dx, dw, db
 
 
@@ -2046,146 +2028,148 @@ def resample_supported(cin, cout, H, W, up, B=1):
 
 def conv_resample(x, mask_cols, weight, bias, up, dgrad_of_down=False, out=None):
     """Downsample (up False: Conv2d 3x3 stride 2 pad 1, weight [cout,cin,3,3]) or Upsample (up True: ConvTranspose2d 4x4 stride 2
-    pad 1, weight [cin,cout,4,4]) of x * mask (diffusion.py:19-34).  dgrad_of_down: x is the gradient of a Downsample output and
-    weight that Downsample's forward weight; the result is its data gradient (an Upsample with the zero-padded kernel).  `out`: optional
-    preallocated result."""
-    x, mask_cols, weight = _f32c(x, "x"), _f32c(mask_cols, "mask"), _f32c(weight, "weight")
-    B, cin, H, W = x.shape
+    pad 1, weight [cin,cout,4,4]) of x * mask (diffusion.py:19-34): x [B,cin,H,W], mask_cols [B,W], bias [cout] or None.
+    dgrad_of_down: x is the gradient of a Downsample output and weight that Downsample's forward weight [cin,cout,3,3]; the result is
+    its data gradient (an Upsample with the zero-padded kernel).  `out`: optional preallocated result."""
+    op = "conv_resample"
+    x = _in(op, "x", x)
+    dev, (B, cin, H, W) = x.device, x.shape
     if dgrad_of_down:
-        cout, kind, up = int(weight.shape[1]), "dn_T", True
+        cout, kind, up, wshape = int(weight.shape[1]), "dn_T", True, (cin, int(weight.shape[1]), 3, 3)
+    elif up:
+        cout, kind, wshape = int(weight.shape[1]), "up", (cin, int(weight.shape[1]), 4, 4)
     else:
-        cout, kind = (int(weight.shape[1]), "up") if up else (int(weight.shape[0]), "dn")
-    bias = _const(x.device, "zeros", cout) if bias is None else _f32c(bias, "bias")
-    y = _given(out, "out", (B, cout, 2 * H, 2 * W) if up else (B, cout, H // 2, W // 2), x.device)
-    with _on(x.device):
-        packed = _packed_weight(weight, cin, cout, False, kind)
-        _check(lib().gtts_conv_resample(_ptr(x), _ptr(mask_cols), _ptr(packed), _ptr(bias), _ptr(y), B, cin, cout, H, W, 1 if up else 0,
-                                        _stream()), "gtts_conv_resample")
+        cout, kind, wshape = int(weight.shape[0]), "dn", (int(weight.shape[0]), cin, 3, 3)
+    mask_cols, weight = _in(op, "mask_cols", mask_cols, (B, W), dev), _in(op, "weight", weight, wshape, dev)
+    bias = _const(dev, "zeros", cout) if bias is None else _in(op, "bias", bias, (cout,), dev)
+    y = _out(op, out, "out", (B, cout, 2 * H, 2 * W) if up else (B, cout, H // 2, W // 2), dev)
+    packed = _packed_weight(weight, cin, cout, False, kind)
+    _launch(dev, "gtts_conv_resample", x, mask_cols, packed, bias, y, B, cin, cout, H, W, 1 if up else 0)
     return y
 
 
 def attn_train_forward(qkv, out=None):
     """LinearAttention core (diffusion.py:90-100) on to_qkv's output qkv [B,384,H,W]: (out [B,128,H,W], ctx [B,4,32,32],
     stat [B,4,32,2] = softmax row maxima and reciprocal sums).  `out`: optional dict of preallocated out / ctx / stat."""
-    qkv = _f32c(qkv, "qkv")
-    B, C3, H, W = qkv.shape
+    op = "attn_train_forward"
+    qkv = _in(op, "qkv", qkv)
+    dev, (B, C3, H, W) = qkv.device, qkv.shape
     if C3 != 384:
-        raise ValueError("attn_train_forward: to_qkv output must have 3 x 4 heads x 32 = 384 channels, got %d" % C3)
-    N = H * W
-    res = _out(out, "out", (B, 128, H, W), torch.float32, qkv.device)
-    ctx = _out(out, "ctx", (B, 4, 32, 32), torch.float32, qkv.device)
-    stat = _out(out, "stat", (B, 4, 32, 2), torch.float32, qkv.device)
-    with _on(qkv.device):
-        scratch = torch.empty(int(lib().gtts_attn_train_scratch_floats(B, N)), dtype=torch.float32, device=qkv.device)
-        _check(lib().gtts_attn_train_forward(_ptr(qkv), _ptr(res), _ptr(ctx), _ptr(stat), _ptr(scratch), B, N, _stream()),
-               "gtts_attn_train_forward")
+        raise ArgumentError("attn_train_forward: to_qkv output must have 3 x 4 heads x 32 = 384 channels, got %d" % C3)
+    res, ctx, stat = _out(op, out, "out", (B, 128, H, W), dev), _out(op, out, "ctx", (B, 4, 32, 32), dev), _out(op, out, "stat", (B, 4, 32, 2), dev)
+    scratch = torch.empty(int(lib().gtts_attn_train_scratch_floats(B, H * W)), dtype=torch.float32, device=dev)
+    _launch(dev, "gtts_attn_train_forward", qkv, res, ctx, stat, scratch, B, H * W)
     return res, ctx, stat
 
 
 def attn_train_backward(qkv, dout, ctx, stat, out=None):
-    """d qkv of attn_train_forward given d out.  `out`: optional dict with a preallocated dqkv."""
-    qkv, dout = _f32c(qkv, "qkv"), _f32c(dout, "dout")
-    B, C3, H, W = qkv.shape
-    N = H * W
-    dqkv = _out(out, "dqkv", tuple(qkv.shape), torch.float32, qkv.device)
-    dctx = torch.empty((B, 4, 32, 32), dtype=torch.float32, device=qkv.device)
-    rdot = torch.empty((B, 4, 32), dtype=torch.float32, device=qkv.device)
-    with _on(qkv.device):
-        scratch = torch.empty(int(lib().gtts_attn_train_scratch_floats(B, N)), dtype=torch.float32, device=qkv.device)
-        _check(lib().gtts_attn_train_backward(_ptr(qkv), _ptr(dout), _ptr(ctx), _ptr(stat), _ptr(dqkv), _ptr(dctx), _ptr(rdot),
-                                              _ptr(scratch), B, N, _stream()), "gtts_attn_train_backward")
+    """d qkv of attn_train_forward given d out: qkv [B,384,H,W], dout [B,128,H,W], ctx [B,4,32,32] and stat [B,4,32,2] as the forward
+    left them.  `out`: optional dict with a preallocated dqkv."""
+    op = "attn_train_backward"
+    qkv = _in(op, "qkv", qkv)
+    dev, (B, C3, H, W) = qkv.device, qkv.shape
+    if C3 != 384:
+        raise ArgumentError("attn_train_backward: to_qkv output must have 3 x 4 heads x 32 = 384 channels, got %d" % C3)
+    dout = _in(op, "dout", dout, (B, 128, H, W), dev)
+    ctx, stat = _in(op, "ctx", ctx, (B, 4, 32, 32), dev), _in(op, "stat", stat, (B, 4, 32, 2), dev)
+    dqkv = _out(op, out, "dqkv", (B, 384, H, W), dev)
+    dctx = torch.empty((B, 4, 32, 32), dtype=torch.float32, device=dev)
+    rdot = torch.empty((B, 4, 32), dtype=torch.float32, device=dev)
+    scratch = torch.empty(int(lib().gtts_attn_train_scratch_floats(B, H * W)), dtype=torch.float32, device=dev)
+    _launch(dev, "gtts_attn_train_backward", qkv, dout, ctx, stat, dqkv, dctx, rdot, scratch, B, H * W)
     return dqkv
 
 
 def rezero_forward(f, g, x, out=None):
-    """f * g + x (Rezero + Residual, diffusion.py:40-46,103-108); g a 1-element device tensor.  `out`: optional dict with a
-    preallocated y."""
-    f, x, g = _f32c(f, "f"), _f32c(x, "x"), _f32c(g, "g")
-    y = _out(out, "y", tuple(f.shape), torch.float32, f.device)
-    with _on(f.device):
-        _check(lib().gtts_rezero_forward(_ptr(f), _ptr(x), _ptr(g), _ptr(y), f.numel(), _stream()), "gtts_rezero_forward")
+    """f * g + x (Rezero + Residual, diffusion.py:40-46,103-108); x of f's shape, g a 1-element device tensor.  `out`: optional dict
+    with a preallocated y."""
+    op = "rezero_forward"
+    f = _in(op, "f", f)
+    dev, shape = f.device, f.shape
+    x, g = _in(op, "x", x, shape, dev), _in(op, "g", g, 1, dev)
+    y = _out(op, out, "y", shape, dev)
+    _launch(dev, "gtts_rezero_forward", f, x, g, y, f.numel())
     return y
 
 
 def rezero_backward(dy, f, g, out=None):
-    """(d f = dy * g, d g = sum(dy * f)) of rezero_forward.  `out`: optional dict of preallocated df / dg."""
-    dy, f, g = _f32c(dy, "dy"), _f32c(f, "f"), _f32c(g, "g")
-    df = _out(out, "df", tuple(f.shape), torch.float32, f.device)
-    dg = _out(out, "dg", tuple(g.shape), torch.float32, f.device)
-    with _on(f.device):
-        scratch = torch.empty(int(lib().gtts_rezero_scratch_bytes(f.numel())), dtype=torch.uint8, device=f.device)
-        _check(lib().gtts_rezero_backward(_ptr(dy), _ptr(f), _ptr(g), _ptr(df), _ptr(dg), _ptr(scratch), f.numel(), _stream()),
-               "gtts_rezero_backward")
+    """(d f = dy * g, d g = sum(dy * f)) of rezero_forward: dy of f's shape.  `out`: optional dict of preallocated df / dg."""
+    op = "rezero_backward"
+    f = _in(op, "f", f)
+    dev, shape = f.device, f.shape
+    dy, g = _in(op, "dy", dy, shape, dev), _in(op, "g", g, 1, dev)
+    df, dg = _out(op, out, "df", shape, dev), _out(op, out, "dg", g.shape, dev)
+    scratch = torch.empty(int(lib().gtts_rezero_scratch_bytes(f.numel())), dtype=torch.uint8, device=dev)
+    _launch(dev, "gtts_rezero_backward", dy, f, g, df, dg, scratch, f.numel())
     return df, dg
 
 
 def gn_mish_forward(y, gamma, beta, mask_cols, groups, eps, tb=None, out=None):
     """(Mish(GroupNorm(y)) * mask [+ tb[:, :, None, None]], stats: (mean, rstd) pairs followed by reduction scratch) -- Block.forward
-    after the convolution (diffusion.py:53-58) and, with tb [B,C], ResnetBlock's time term (diffusion.py:75-76).  `out`: optional dict of
-    preallocated out / stats."""
-    y, gamma, beta, mask_cols, tb = _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta"), _f32c(mask_cols, "mask"), _f32c(tb, "tb")
-    B, C, H, W = y.shape
-    res = _out(out, "out", (B, C, H, W), torch.float32, y.device)
-    stats = _out(out, "stats", (int(lib().gtts_gn_mish_stats_floats(B, int(groups))),), torch.float32, y.device)
-    with _on(y.device):
-        _check(lib().gtts_gn_mish_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(mask_cols), _ptr(tb), _ptr(res), _ptr(stats), B, C,
-                                          H, W, int(groups), float(eps), _stream()), "gtts_gn_mish_forward")
+    after the convolution (diffusion.py:53-58) and, with tb [B,C], ResnetBlock's time term (diffusion.py:75-76): y [B,C,H,W], gamma and
+    beta [C], mask_cols [B,W].  `out`: optional dict of preallocated out / stats."""
+    op = "gn_mish_forward"
+    y = _in(op, "y", y)
+    dev, (B, C, H, W) = y.device, y.shape
+    gamma, beta = _in(op, "gamma", gamma, (C,), dev), _in(op, "beta", beta, (C,), dev)
+    mask_cols, tb = _in(op, "mask_cols", mask_cols, (B, W), dev), _in(op, "tb", tb, (B, C), dev, optional=True)
+    res = _out(op, out, "out", (B, C, H, W), dev)
+    stats = _out(op, out, "stats", (int(lib().gtts_gn_mish_stats_floats(B, int(groups))),), dev)
+    _launch(dev, "gtts_gn_mish_forward", y, gamma, beta, mask_cols, tb, res, stats, B, C, H, W, int(groups), float(eps))
     return res, stats
 
 
 def gn_mish_backward(dout, y, gamma, beta, mask_cols, stats, groups, want_dtb=False, out=None):
-    """(dy, dgamma, dbeta[, dtb [B,C]]) of gn_mish_forward.  `out`: optional dict of preallocated dy / dgamma / dbeta / dtb."""
-    dout, y = _f32c(dout, "dout"), _f32c(y, "y")
-    B, C, H, W = y.shape
-    dy = _out(out, "dy", (B, C, H, W), torch.float32, y.device)
-    dg = _out(out, "dgamma", (C,), torch.float32, y.device)
-    db = _out(out, "dbeta", (C,), torch.float32, y.device)
-    dtb = _out(out, "dtb", (B, C), torch.float32, y.device) if want_dtb else None
-    scratch = torch.empty(int(lib().gtts_gn_mish_scratch_bytes(B, C)), dtype=torch.uint8, device=y.device)
-    with _on(y.device):
-        _check(lib().gtts_gn_mish_backward(_ptr(dout), _ptr(y), _ptr(_f32c(gamma, "gamma")), _ptr(_f32c(beta, "beta")),
-                                           _ptr(_f32c(mask_cols, "mask")), _ptr(stats), _ptr(dy), _ptr(dg), _ptr(db), _ptr(dtb),
-                                           _ptr(scratch), B, C, H, W, int(groups), _stream()), "gtts_gn_mish_backward")
+    """(dy, dgamma, dbeta[, dtb [B,C]]) of gn_mish_forward: dout of y's shape, stats as the forward left them
+    (gtts_gn_mish_stats_floats floats).  `out`: optional dict of preallocated dy / dgamma / dbeta / dtb."""
+    op = "gn_mish_backward"
+    y = _in(op, "y", y)
+    dev, (B, C, H, W) = y.device, y.shape
+    dout, gamma, beta = _in(op, "dout", dout, (B, C, H, W), dev), _in(op, "gamma", gamma, (C,), dev), _in(op, "beta", beta, (C,), dev)
+    mask_cols = _in(op, "mask_cols", mask_cols, (B, W), dev)
+    stats = _in(op, "stats", stats, int(lib().gtts_gn_mish_stats_floats(B, int(groups))), dev)
+    dy, dg, db = _out(op, out, "dy", (B, C, H, W), dev), _out(op, out, "dgamma", (C,), dev), _out(op, out, "dbeta", (C,), dev)
+    dtb = _out(op, out, "dtb", (B, C), dev) if want_dtb else None
+    scratch = torch.empty(int(lib().gtts_gn_mish_scratch_bytes(B, C)), dtype=torch.uint8, device=dev)
+    _launch(dev, "gtts_gn_mish_backward", dout, y, gamma, beta, mask_cols, stats, dy, dg, db, dtb, scratch, B, C, H, W, int(groups))
     return (dy, dg, db, dtb) if want_dtb else (dy, dg, db)
 
 
 def in_glu_forward(y, gamma, beta, eps=1e-5, tb=None, out=None):
     """(IN(y[:, :C]) * sigmoid(IN(y[:, C:])) [+ tb[:, :, None, None]], stats) -- InstanceNorm2d(affine) + GLU(dim=1) of DiffVC's RefBlock
-    (modules.py:128-157) and, with tb [B,C], its time-bias add (modules.py:159,162).  `out`: optional dict of preallocated out / stats."""
-    y, gamma, beta, tb = _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta"), _f32c(tb, "tb")
-    B, C2, H, W = y.shape
+    (modules.py:128-157) and, with tb [B,C], its time-bias add (modules.py:159,162): y [B,2C,H,W], gamma and beta [2C].  `out`: optional
+    dict of preallocated out / stats."""
+    op = "in_glu_forward"
+    y = _in(op, "y", y)
+    dev, (B, C2, H, W) = y.device, y.shape
     C = C2 // 2
-    if tb is not None and tuple(tb.shape) != (B, C):
-        raise ValueError("tb %s does not match y %s" % (tuple(tb.shape), tuple(y.shape)))
-    res = _out(out, "out", (B, C, H, W), torch.float32, y.device)
-    stats = _out(out, "stats", (int(lib().gtts_in_glu_stats_floats(B, C)),), torch.float32, y.device)
-    with _on(y.device):
-        if tb is None:
-            _check(lib().gtts_in_glu_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(res), _ptr(stats), B, C, H, W, float(eps), _stream()),
-                   "gtts_in_glu_forward")
-        else:
-            _check(lib().gtts_in_glu_tb_forward(_ptr(y), _ptr(gamma), _ptr(beta), _ptr(tb), _ptr(res), _ptr(stats), B, C, H, W, float(eps),
-                                                _stream()), "gtts_in_glu_tb_forward")
+    gamma, beta = _in(op, "gamma", gamma, (C2,), dev), _in(op, "beta", beta, (C2,), dev)
+    tb = _in(op, "tb", tb, (B, C), dev, optional=True)
+    res = _out(op, out, "out", (B, C, H, W), dev)
+    stats = _out(op, out, "stats", (int(lib().gtts_in_glu_stats_floats(B, C)),), dev)
+    if tb is None:
+        _launch(dev, "gtts_in_glu_forward", y, gamma, beta, res, stats, B, C, H, W, float(eps))
+    else:
+        _launch(dev, "gtts_in_glu_tb_forward", y, gamma, beta, tb, res, stats, B, C, H, W, float(eps))
     return res, stats
 
 
 def in_glu_backward(dout, y, gamma, beta, stats, want_dtb=False, out=None):
-    """(dy, dgamma, dbeta[, dtb [B,C]]) of in_glu_forward.  `out`: optional dict of preallocated dy / dgamma / dbeta / dtb."""
-    dout, y, gamma, beta = _f32c(dout, "dout"), _f32c(y, "y"), _f32c(gamma, "gamma"), _f32c(beta, "beta")
-    B, C2, H, W = y.shape
+    """(dy, dgamma, dbeta[, dtb [B,C]]) of in_glu_forward: dout [B,C,H,W], y [B,2C,H,W], stats as the forward left them
+    (gtts_in_glu_stats_floats floats).  `out`: optional dict of preallocated dy / dgamma / dbeta / dtb."""
+    op = "in_glu_backward"
+    y = _in(op, "y", y)
+    dev, (B, C2, H, W) = y.device, y.shape
     C = C2 // 2
-    dy = _out(out, "dy", (B, C2, H, W), torch.float32, y.device)
-    dg = _out(out, "dgamma", (C2,), torch.float32, y.device)
-    db = _out(out, "dbeta", (C2,), torch.float32, y.device)
-    dtb = _out(out, "dtb", (B, C), torch.float32, y.device) if want_dtb else None
-    scratch = torch.empty(int(lib().gtts_in_glu_scratch_floats(B, C)), dtype=torch.float32, device=y.device)
-    with _on(y.device):
-        if want_dtb:
-            _check(lib().gtts_in_glu_tb_backward(_ptr(dout), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(dy), _ptr(dg), _ptr(db),
-                                                 _ptr(dtb), _ptr(scratch), B, C, H, W, _stream()), "gtts_in_glu_tb_backward")
-        else:
-            _check(lib().gtts_in_glu_backward(_ptr(dout), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(stats), _ptr(dy), _ptr(dg), _ptr(db),
-                                              _ptr(scratch), B, C, H, W, _stream()), "gtts_in_glu_backward")
+    dout, gamma, beta = _in(op, "dout", dout, (B, C, H, W), dev), _in(op, "gamma", gamma, (C2,), dev), _in(op, "beta", beta, (C2,), dev)
+    stats = _in(op, "stats", stats, int(lib().gtts_in_glu_stats_floats(B, C)), dev)
+    dy, dg, db = _out(op, out, "dy", (B, C2, H, W), dev), _out(op, out, "dgamma", (C2,), dev), _out(op, out, "dbeta", (C2,), dev)
+    dtb = _out(op, out, "dtb", (B, C), dev) if want_dtb else None
+    scratch = torch.empty(int(lib().gtts_in_glu_scratch_floats(B, C)), dtype=torch.float32, device=dev)
+    if want_dtb:
+        _launch(dev, "gtts_in_glu_tb_backward", dout, y, gamma, beta, stats, dy, dg, db, dtb, scratch, B, C, H, W)
+    else:
+        _launch(dev, "gtts_in_glu_backward", dout, y, gamma, beta, stats, dy, dg, db, scratch, B, C, H, W)
     return (dy, dg, db, dtb) if want_dtb else (dy, dg, db)
 
 
@@ -2193,196 +2177,178 @@ def cond_field(U, mask_cols, H, base=None, out=None):
     """base + the bias field of a condition vector convolved over the [H, W] plane (gtts_cond_field_forward): U [B,taps,C] with taps 9
     ((kh, kw) order, 3x3 with padding 1) or 1 (1x1), mask_cols [B,W], base [B,C,H,W] or None -> [B,C,H,W].  `out`: optional dict of a
     preallocated out."""
-    _hip_only(U, "cond_field")
-    U, mask_cols, base = _f32c(U, "U"), _f32c(mask_cols, "mask"), _f32c(base, "base")
-    B, taps, C = U.shape
-    W = int(mask_cols.shape[-1])
-    if tuple(mask_cols.shape) != (B, W) or (base is not None and tuple(base.shape) != (B, C, int(H), W)):
-        raise ValueError("cond_field: U %s, mask %s and base %s do not match" % (tuple(U.shape), tuple(mask_cols.shape),
-                                                                                 None if base is None else tuple(base.shape)))
-    res = _out(out, "out", (B, C, int(H), W), torch.float32, U.device, exc=ValueError)
-    with _on(U.device):
-        _check(lib().gtts_cond_field_forward(_ptr(U), _ptr(mask_cols), _ptr(base), _ptr(res), B, C, int(H), W, int(taps), _stream()),
-               "gtts_cond_field_forward")
+    op = "cond_field"
+    U = _in(op, "U", U)
+    dev, (B, taps, C), H, W = U.device, U.shape, int(H), int(mask_cols.shape[-1])
+    mask_cols, base = _in(op, "mask_cols", mask_cols, (B, W), dev), _in(op, "base", base, (B, C, H, W), dev, optional=True)
+    res = _out(op, out, "out", (B, C, H, W), dev)
+    _launch(dev, "gtts_cond_field_forward", U, mask_cols, base, res, B, C, H, W, int(taps))
     return res
 
 
 def cond_field_backward(dy, mask_cols, taps, out=None):
-    """S [B,taps,C]: the gradient of cond_field w.r.t. U (the gradient w.r.t. base is dy itself).  `out`: optional dict of a preallocated S."""
-    _hip_only(dy, "cond_field_backward")
-    dy, mask_cols = _f32c(dy, "dy"), _f32c(mask_cols, "mask")
-    B, C, H, W = dy.shape
-    if tuple(mask_cols.shape) != (B, W):
-        raise ValueError("cond_field_backward: dy %s and mask %s do not match" % (tuple(dy.shape), tuple(mask_cols.shape)))
-    S = _out(out, "S", (B, int(taps), C), torch.float32, dy.device, exc=ValueError)
-    with _on(dy.device):
-        _check(lib().gtts_cond_field_backward(_ptr(dy), _ptr(mask_cols), _ptr(S), B, C, H, W, int(taps), _stream()), "gtts_cond_field_backward")
+    """S [B,taps,C]: the gradient of cond_field w.r.t. U (the gradient w.r.t. base is dy itself): dy [B,C,H,W], mask_cols [B,W].
+    `out`: optional dict of a preallocated S."""
+    op = "cond_field_backward"
+    dy = _in(op, "dy", dy)
+    dev, (B, C, H, W) = dy.device, dy.shape
+    mask_cols = _in(op, "mask_cols", mask_cols, (B, W), dev)
+    S = _out(op, out, "S", (B, int(taps), C), dev)
+    _launch(dev, "gtts_cond_field_backward", dy, mask_cols, S, B, C, H, W, int(taps))
     return S
 
 
 def masked_mean(y, mask_cols, out=None):
     """p [B,C] = sum_{h,w} y mask / (sum_w mask H): RefBlock's masked mean over the plane (modules.py:165-166).  y [B,C,H,W], mask_cols
     [B,W].  `out`: optional dict of a preallocated p."""
-    _hip_only(y, "masked_mean")
-    y, mask_cols = _f32c(y, "y"), _f32c(mask_cols, "mask")
-    B, C, H, W = y.shape
-    if tuple(mask_cols.shape) != (B, W):
-        raise ValueError("masked_mean: y %s and mask %s do not match" % (tuple(y.shape), tuple(mask_cols.shape)))
-    p = _out(out, "p", (B, C), torch.float32, y.device, exc=ValueError)
-    with _on(y.device):
-        _check(lib().gtts_masked_mean_forward(_ptr(y), _ptr(mask_cols), _ptr(p), B, C, H, W, _stream()), "gtts_masked_mean_forward")
+    op = "masked_mean"
+    y = _in(op, "y", y)
+    dev, (B, C, H, W) = y.device, y.shape
+    mask_cols = _in(op, "mask_cols", mask_cols, (B, W), dev)
+    p = _out(op, out, "p", (B, C), dev)
+    _launch(dev, "gtts_masked_mean_forward", y, mask_cols, p, B, C, H, W)
     return p
 
 
 def masked_mean_backward(dp, mask_cols, H, out=None):
-    """dy [B,C,H,W] of masked_mean: dp [B,C] broadcast over the live columns.  `out`: optional dict of a preallocated dy."""
-    _hip_only(dp, "masked_mean_backward")
-    dp, mask_cols = _f32c(dp, "dp"), _f32c(mask_cols, "mask")
-    B, C = dp.shape
-    W = int(mask_cols.shape[-1])
-    if tuple(mask_cols.shape) != (B, W):
-        raise ValueError("masked_mean_backward: dp %s and mask %s do not match" % (tuple(dp.shape), tuple(mask_cols.shape)))
-    dy = _out(out, "dy", (B, C, int(H), W), torch.float32, dp.device, exc=ValueError)
-    with _on(dp.device):
-        _check(lib().gtts_masked_mean_backward(_ptr(dp), _ptr(mask_cols), _ptr(dy), B, C, int(H), W, _stream()), "gtts_masked_mean_backward")
+    """dy [B,C,H,W] of masked_mean: dp [B,C] broadcast over the live columns of mask_cols [B,W].  `out`: optional dict of a
+    preallocated dy."""
+    op = "masked_mean_backward"
+    dp = _in(op, "dp", dp)
+    dev, (B, C), H, W = dp.device, dp.shape, int(H), int(mask_cols.shape[-1])
+    mask_cols = _in(op, "mask_cols", mask_cols, (B, W), dev)
+    dy = _out(op, out, "dy", (B, C, H, W), dev)
+    _launch(dev, "gtts_masked_mean_backward", dp, mask_cols, dy, B, C, H, W)
     return dy
 
 
 def diffusion_noising(x0, mu, z, mask, t, beta_min, beta_max, out=None):
-    """Diffusion.forward_diffusion given the N(0,1) draw z: (xt, z * mask)   (diffusion.py:244-252).  `out`: optional dict of
-    preallocated xt / zm."""
-    x0, mu, z, mask, t = (_f32c(v, n) for v, n in ((x0, "x0"), (mu, "mu"), (z, "z"), (mask, "mask"), (t, "t")))
-    B, F, T = x0.shape
-    xt, zm = _out(out, "xt", (B, F, T), torch.float32, x0.device), _out(out, "zm", (B, F, T), torch.float32, x0.device)
-    with _on(x0.device):
-        _check(lib().gtts_diffusion_noising(_ptr(x0), _ptr(mu), _ptr(z), _ptr(mask), _ptr(t), float(beta_min), float(beta_max),
-                                            _ptr(xt), _ptr(zm), B, F, T, _stream()), "gtts_diffusion_noising")
+    """Diffusion.forward_diffusion given the N(0,1) draw z: (xt, z * mask)   (diffusion.py:244-252): x0, mu, z [B,F,T], mask B * T
+    elements ([B,1,T] or [B,T]: the element count decides), t B elements.  `out`: optional dict of preallocated xt / zm."""
+    op = "diffusion_noising"
+    x0 = _in(op, "x0", x0)
+    dev, (B, F, T) = x0.device, x0.shape
+    mu, z = _in(op, "mu", mu, (B, F, T), dev), _in(op, "z", z, (B, F, T), dev)
+    mask, t = _in(op, "mask", mask, B * T, dev), _in(op, "t", t, B, dev)
+    xt, zm = _out(op, out, "xt", (B, F, T), dev), _out(op, out, "zm", (B, F, T), dev)
+    _launch(dev, "gtts_diffusion_noising", x0, mu, z, mask, t, float(beta_min), float(beta_max), xt, zm, B, F, T)
     return xt, zm
 
 
 def score_loss(eps, z_masked, t, beta_min, beta_max, inv_denom, want_grad=True, out=None):
-    """Diffusion.loss_t's reduction: (sum((eps s + z)^2) * inv_denom as a 0-d tensor, d loss / d eps or None).
-    inv_denom: a Python float, or a 0-d device tensor (then nothing here synchronises with the host: the kernel runs with a
-    unit normaliser and loss and gradient are scaled by tensor ops).  `out`: optional dict of preallocated partials / grad."""
+    """Diffusion.loss_t's reduction: (sum((eps s + z)^2) * inv_denom as a 0-d tensor, d loss / d eps or None): eps, z_masked [B,F,T],
+    t B elements.  inv_denom: a Python float, or a 0-d device tensor (then nothing here synchronises with the host: the kernel runs
+    with a unit normaliser and loss and gradient are scaled by tensor ops).  `out`: optional dict of preallocated partials / grad."""
     if torch.is_tensor(inv_denom):
         loss, g = score_loss(eps, z_masked, t, beta_min, beta_max, 1.0, want_grad, out)
         return loss * inv_denom, (g * inv_denom if g is not None else None)
-    eps, z_masked, t = _f32c(eps, "eps"), _f32c(z_masked, "z"), _f32c(t, "t")
-    B, F, T = eps.shape
-    n = int(lib().gtts_score_loss_partials(B, F, T))
-    part = _out(out, "partials", (n,), torch.float32, eps.device)
-    g = _out(out, "grad", (B, F, T), torch.float32, eps.device) if want_grad else None
-    with _on(eps.device):
-        _check(lib().gtts_score_loss(_ptr(eps), _ptr(z_masked), _ptr(t), float(beta_min), float(beta_max), float(inv_denom),
-                                     _ptr(part), _ptr(g), B, F, T, _stream()), "gtts_score_loss")
+    op = "score_loss"
+    eps = _in(op, "eps", eps)
+    dev, (B, F, T) = eps.device, eps.shape
+    z_masked, t = _in(op, "z_masked", z_masked, (B, F, T), dev), _in(op, "t", t, B, dev)
+    part = _out(op, out, "partials", (int(lib().gtts_score_loss_partials(B, F, T)),), dev)
+    g = _out(op, out, "grad", (B, F, T), dev) if want_grad else None
+    _launch(dev, "gtts_score_loss", eps, z_masked, t, float(beta_min), float(beta_max), float(inv_denom), part, g, B, F, T)
     return part.sum() * inv_denom, g
 
 
 def conv_dgrad_small(dy, weight, mask_cols=None, out=None):
     """The first layer's data gradient (cin 2 or 3, its own kernel): dx [B,cin,H,W] of Conv2d_kxk(x * mask) for k = 3 (padding 1) or 1,
     dy [B,cout,H,W], weight [cout,cin,k,k] (not packed), mask_cols [B,W] or None."""
-    _hip_only(dy, "conv_dgrad_small")
-    dy, weight = _f32c(dy, "dy"), _f32c(weight, "weight")
-    B, cout, H, W = dy.shape
+    op = "conv_dgrad_small"
+    dy = _in(op, "dy", dy)
+    dev, (B, cout, H, W) = dy.device, dy.shape
     cin, ksize = int(weight.shape[1]), int(weight.shape[2])
-    if weight.shape[0] != cout or weight.shape[3] != ksize:
-        raise RuntimeError("weight %s does not match dy %s" % (tuple(weight.shape), tuple(dy.shape)))
-    mask_cols = _const(dy.device, "ones", B, W) if mask_cols is None else _f32c(mask_cols, "mask")
-    dx = _out(out, "dx", (B, cin, H, W), torch.float32, dy.device)
-    with _on(dy.device):
-        _check(lib().gtts_conv_dgrad_small(_ptr(dy), _ptr(weight), _ptr(mask_cols), _ptr(dx), B, cin, cout, H, W, ksize, _stream()),
-               "gtts_conv_dgrad_small")
+    weight = _in(op, "weight", weight, (cout, cin, ksize, ksize), dev)
+    mask_cols = _const(dev, "ones", B, W) if mask_cols is None else _in(op, "mask_cols", mask_cols, (B, W), dev)
+    dx = _out(op, out, "dx", (B, cin, H, W), dev)
+    _launch(dev, "gtts_conv_dgrad_small", dy, weight, mask_cols, dx, B, cin, cout, H, W, ksize)
     return dx
 
 
 def diffusion_noising_backward(dxt, mask, t, beta_min, beta_max, want_dx0=True, want_dmu=True, out=None):
-    """(dx0, dmu) of diffusion_noising (an output not wanted is None)."""
-    _hip_only(dxt, "diffusion_noising_backward")
-    dxt, mask, t = _f32c(dxt, "dxt"), _f32c(mask, "mask"), _f32c(t, "t")
-    B, F, T = dxt.shape
-    dx0 = _out(out, "dx0", (B, F, T), torch.float32, dxt.device) if want_dx0 else None
-    dmu = _out(out, "dmu", (B, F, T), torch.float32, dxt.device) if want_dmu else None
-    with _on(dxt.device):
-        _check(lib().gtts_diffusion_noising_backward(_ptr(dxt), _ptr(mask), _ptr(t), float(beta_min), float(beta_max), _ptr(dx0), _ptr(dmu),
-                                                     B, F, T, _stream()), "gtts_diffusion_noising_backward")
+    """(dx0, dmu) of diffusion_noising (an output not wanted is None): dxt [B,F,T], mask B * T elements, t B elements."""
+    op = "diffusion_noising_backward"
+    dxt = _in(op, "dxt", dxt)
+    dev, (B, F, T) = dxt.device, dxt.shape
+    mask, t = _in(op, "mask", mask, B * T, dev), _in(op, "t", t, B, dev)
+    dx0 = _out(op, out, "dx0", (B, F, T), dev) if want_dx0 else None
+    dmu = _out(op, out, "dmu", (B, F, T), dev) if want_dmu else None
+    _launch(dev, "gtts_diffusion_noising_backward", dxt, mask, t, float(beta_min), float(beta_max), dx0, dmu, B, F, T)
     return dx0, dmu
 
 
 def align_index(path, out=None):
     """The alignment path [B,t_x,T] of monotonic_align.maximum_path as indices: (idx [B,T] int32 token of each frame or -1,
     dur [B,t_x] fp32 frames per token, first [B,t_x] int32 first frame of each token's run or -1)."""
-    _hip_only(path, "align_index")
-    path = _f32c(path, "path")
-    B, tx, T = path.shape
-    idx = _out(out, "idx", (B, T), torch.int32, path.device)
-    dur = _out(out, "dur", (B, tx), torch.float32, path.device)
-    first = _out(out, "first", (B, tx), torch.int32, path.device)
-    with _on(path.device):
-        _check(lib().gtts_align_index(_ptr(path), _ptr(idx), _ptr(dur), _ptr(first), B, tx, T, _stream()), "gtts_align_index")
+    op = "align_index"
+    path = _in(op, "path", path)
+    dev, (B, tx, T) = path.device, path.shape
+    idx, dur, first = _out(op, out, "idx", (B, T), dev, torch.int32), _out(op, out, "dur", (B, tx), dev), _out(op, out, "first", (B, tx), dev, torch.int32)
+    _launch(dev, "gtts_align_index", path, idx, dur, first, B, tx, T)
     return idx, dur, first
 
 
 def duration_loss(logw, dur, x_mask, want_grad=True, out=None):
     """(sum((logw - log(1e-8 + dur) * x_mask)^2) as a 0-d tensor, its gradient w.r.t. logw or None): utils.py:42-44 without the
-    normaliser, which the caller keeps as a device scalar.  logw, dur, x_mask: B * t_x elements each."""
-    _hip_only(logw, "duration_loss")
-    lw, d, m = _f32c(logw, "logw"), _f32c(dur, "dur"), _f32c(x_mask, "x_mask")
-    B, tx = int(d.shape[0]), int(d.shape[-1])
-    if lw.numel() != B * tx or m.numel() != B * tx:
-        raise RuntimeError("logw, dur and x_mask must hold [B, t_x] = [%d, %d] elements each" % (B, tx))
-    part = _out(out, "partials", (B,), torch.float32, lw.device)
-    g = _out(out, "grad", tuple(lw.shape), torch.float32, lw.device) if want_grad else None
-    with _on(lw.device):
-        _check(lib().gtts_duration_loss(_ptr(lw), _ptr(d), _ptr(m), _ptr(part), _ptr(g), B, tx, _stream()), "gtts_duration_loss")
+    normaliser, which the caller keeps as a device scalar.  dur [B,t_x]; logw, x_mask: B * t_x elements each ([B,1,t_x] as the
+    modules hold them: the element count decides)."""
+    op = "duration_loss"
+    lw = _in(op, "logw", logw)
+    dev, B, tx = lw.device, int(dur.shape[0]), int(dur.shape[-1])
+    lw, d, m = _in(op, "logw", lw, B * tx, dev), _in(op, "dur", dur, B * tx, dev), _in(op, "x_mask", x_mask, B * tx, dev)
+    part = _out(op, out, "partials", (B,), dev)
+    g = _out(op, out, "grad", lw.shape, dev) if want_grad else None
+    _launch(dev, "gtts_duration_loss", lw, d, m, part, g, B, tx)
     return part.sum(), g
 
 
 def align_gather(mu_x, y, idx, start, kept, S, out=None):
     """Training crop + aligned prior mean (tts.py:146-172) in one gather: (y_c [B,F,S], mu_y [B,F,S], sum over the live elements of
-    0.5 ((y_c - mu_y)^2 + log 2 pi) as a 0-d tensor).  start, kept: [B] integer tensors (or lists); S: output frames."""
-    _hip_only(mu_x, "align_gather")
-    mx, yy = _f32c(mu_x, "mu_x"), _f32c(y, "y")
-    B, F, tx = mx.shape
-    T, S = int(yy.shape[2]), int(S)
-    if tuple(yy.shape[:2]) != (B, F) or tuple(idx.shape) != (B, T) or idx.dtype != torch.int32:
-        raise RuntimeError("mu_x [B,F,t_x], y [B,F,T] and idx [B,T] int32 disagree: %s, %s, %s" % (tuple(mx.shape), tuple(yy.shape), tuple(idx.shape)))
-    st, kp = _i32c(start, "start", mx.device), _i32c(kept, "kept", mx.device)
-    y_c = _out(out, "y_c", (B, F, S), torch.float32, mx.device)
-    mu_y = _out(out, "mu_y", (B, F, S), torch.float32, mx.device)
-    part = _out(out, "partials", (int(lib().gtts_align_gather_partials(B, F, S)),), torch.float32, mx.device)
-    with _on(mx.device):
-        _check(lib().gtts_align_gather_forward(_ptr(mx), _ptr(yy), _ptr(idx.contiguous()), _ptr(st), _ptr(kp), _ptr(y_c), _ptr(mu_y), _ptr(part),
-                                               B, F, tx, T, S, _stream()), "gtts_align_gather_forward")
+    0.5 ((y_c - mu_y)^2 + log 2 pi) as a 0-d tensor) from mu_x [B,F,t_x], y [B,F,T], idx [B,T] int32.  start, kept: [B] integer
+    tensors (or lists); S: output frames."""
+    op = "align_gather"
+    mx = _in(op, "mu_x", mu_x)
+    dev, (B, F, tx), T, S = mx.device, mx.shape, int(y.shape[2]), int(S)
+    yy = _in(op, "y", y, (B, F, T), dev)
+    if idx.dtype != torch.int32:
+        raise ArgumentError("align_gather: idx must be int32 (got %s)" % idx.dtype)
+    idx, st, kp = _in(op, "idx", idx, (B, T), dev, dtype=torch.int32), _i32(op, "start", start, (B,), dev), _i32(op, "kept", kept, (B,), dev)
+    y_c, mu_y = _out(op, out, "y_c", (B, F, S), dev), _out(op, out, "mu_y", (B, F, S), dev)
+    part = _out(op, out, "partials", (int(lib().gtts_align_gather_partials(B, F, S)),), dev)
+    _launch(dev, "gtts_align_gather_forward", mx, yy, idx, st, kp, y_c, mu_y, part, B, F, tx, T, S)
     return y_c, mu_y, part.sum()
 
 
 def align_gather_backward(g_mu_y, mu_y, y_c, scale, dur, first, start, kept, out=None):
     """dmu_x [B,F,t_x] of align_gather: per token the sum, over its live output frames, of g_mu_y + scale * (mu_y - y_c).  g_mu_y
-    [B,F,S] or None; scale: a one-element device tensor, (gradient of the prior loss) / (sum(kept) F), or None (then mu_y, y_c unused)."""
-    _hip_only(dur, "align_gather_backward")
-    g, my, yc, sc = _f32c(g_mu_y, "g_mu_y"), _f32c(mu_y, "mu_y"), _f32c(y_c, "y_c"), _f32c(scale, "scale")
-    ref = g if g is not None else my
-    B, F, S = ref.shape
-    tx = int(dur.shape[1])
-    st, kp = _i32c(start, "start", dur.device), _i32c(kept, "kept", dur.device)
-    dmu_x = _out(out, "dmu_x", (B, F, tx), torch.float32, dur.device)
-    with _on(dur.device):
-        _check(lib().gtts_align_gather_backward(_ptr(g), _ptr(my), _ptr(yc), _ptr(sc), _ptr(_f32c(dur, "dur")), _ptr(first.contiguous()), _ptr(st),
-                                                _ptr(kp), _ptr(dmu_x), B, F, tx, S, _stream()), "gtts_align_gather_backward")
+    [B,F,S] or None; scale: a one-element device tensor, (gradient of the prior loss) / (sum(kept) F), or None (then mu_y, y_c [B,F,S]
+    are unused and may be None); dur [B,t_x] fp32 and first [B,t_x] int32 as align_index left them."""
+    op = "align_gather_backward"
+    dur = _in(op, "dur", dur)
+    dev, (B, tx) = dur.device, dur.shape
+    ref = g_mu_y if g_mu_y is not None else mu_y
+    if ref is None or ref.dim() != 3 or ref.shape[0] != B:
+        raise ArgumentError("align_gather_backward: g_mu_y or mu_y must be [B,F,S] with dur's B = %d" % B)
+    F, S = ref.shape[1], ref.shape[2]
+    g, sc = _in(op, "g_mu_y", g_mu_y, (B, F, S), dev, optional=True), _in(op, "scale", scale, 1, dev, optional=True)
+    my, yc = (_in(op, n, t, (B, F, S), dev, optional=sc is None) for n, t in (("mu_y", mu_y), ("y_c", y_c)))
+    if first.dtype != torch.int32:
+        raise ArgumentError("align_gather_backward: first must be int32 (got %s)" % first.dtype)
+    first, st, kp = _in(op, "first", first, (B, tx), dev, dtype=torch.int32), _i32(op, "start", start, (B,), dev), _i32(op, "kept", kept, (B,), dev)
+    dmu_x = _out(op, out, "dmu_x", (B, F, tx), dev)
+    _launch(dev, "gtts_align_gather_backward", g, my, yc, sc, dur, first, st, kp, dmu_x, B, F, tx, S)
     return dmu_x
 
 
 def log_prior(mu_x, y):
     """MAS score matrix of GradTTS.compute_loss (tts.py:130-139): [B,F,t_x], [B,F,T] -> [B,t_x,T], one launch."""
-    _hip_only(mu_x, "log_prior")
-    mx, yy = _f32c(mu_x.detach(), "mu_x"), _f32c(y.detach(), "y")
-    B, F, tx = mx.shape
-    if yy.shape[0] != B or yy.shape[1] != F:
-        raise RuntimeError("mu_x [B,F,t_x] and y [B,F,T] disagree: %s vs %s" % (tuple(mx.shape), tuple(yy.shape)))
-    T = yy.shape[2]
-    out = torch.empty((B, tx, T), dtype=torch.float32, device=mx.device)
-    with _on(mx.device):
-        _check(lib().gtts_log_prior(_ptr(mx), _ptr(yy), _ptr(out), B, F, tx, T, _stream()), "gtts_log_prior")
+    op = "log_prior"
+    mx = _in(op, "mu_x", mu_x.detach())
+    dev, (B, F, tx), T = mx.device, mx.shape, y.shape[2]
+    yy = _in(op, "y", y.detach(), (B, F, T), dev)
+    out = torch.empty((B, tx, T), dtype=torch.float32, device=dev)
+    _launch(dev, "gtts_log_prior", mx, yy, out, B, F, tx, T)
     return out
 
 
@@ -2391,21 +2357,15 @@ def expand_alignment(duration, x_mask, y_lengths, mu_x, T, noise=None, temperatu
 
     duration, x_mask: [B, t_x]; y_lengths: [B] integer; mu_x: [B, F, t_x]; noise: [B, F, T] or None.
     Returns (attn [B, t_x, T], mu_y [B, F, T], z [B, F, T] or None), bit-identical to the reference's CPU path."""
-    _hip_only(mu_x, "expand_alignment")
-    d, m, mx = _f32c(duration, "duration"), _f32c(x_mask, "x_mask"), _f32c(mu_x, "mu_x")
-    B, F, tx = mx.shape
-    if d.shape != (B, tx) or m.shape != (B, tx):
-        raise RuntimeError("duration / x_mask must be [B, t_x] = [%d, %d]" % (B, tx))
-    yl = y_lengths.to(device=mx.device, dtype=torch.int32).contiguous()
-    nz = _f32c(noise, "noise")
-    if nz is not None and nz.shape != (B, F, T):
-        raise RuntimeError("noise must be [B, F, T]")
-    attn = torch.empty((B, tx, T), dtype=torch.float32, device=mx.device)
-    mu_y = torch.empty((B, F, T), dtype=torch.float32, device=mx.device)
-    z = torch.empty((B, F, T), dtype=torch.float32, device=mx.device) if nz is not None else None
-    with _on(mx.device):
-        _check(lib().gtts_expand_alignment(_ptr(d), _ptr(m), _ptr(yl), _ptr(mx), _ptr(nz), float(temperature), _ptr(attn),
-                                           _ptr(mu_y), _ptr(z), B, F, tx, int(T), _stream()), "gtts_expand_alignment")
+    op = "expand_alignment"
+    mx = _in(op, "mu_x", mu_x)
+    dev, (B, F, tx), T = mx.device, mx.shape, int(T)
+    d, m = _in(op, "duration", duration, (B, tx), dev), _in(op, "x_mask", x_mask, (B, tx), dev)
+    yl, nz = _i32(op, "y_lengths", y_lengths, (B,), dev), _in(op, "noise", noise, (B, F, T), dev, optional=True)
+    attn = torch.empty((B, tx, T), dtype=torch.float32, device=dev)
+    mu_y = torch.empty((B, F, T), dtype=torch.float32, device=dev)
+    z = torch.empty((B, F, T), dtype=torch.float32, device=dev) if nz is not None else None
+    _launch(dev, "gtts_expand_alignment", d, m, yl, mx, nz, float(temperature), attn, mu_y, z, B, F, tx, T)
     return attn, mu_y, z
 
 
@@ -2415,7 +2375,6 @@ def measured_ceilings(device, seconds=2.0):
     L = lib()
     out = {}
     with _on(device):
-        st = _stream()
         props = torch.cuda.get_device_properties(device)
         cus = int(props.multi_processor_count)
         wgs = cus * 2                                   # 2 workgroups x 4 waves per CU = 2 waves per SIMD
@@ -2438,14 +2397,12 @@ def measured_ceilings(device, seconds=2.0):
 
         iters = 4000                                    # 32 k MFMAs per wave: ~0.55 ms per launch at peak
         for name, src in (("random", rnd), ("zero", zero)):
-            fn = lambda: _check(L.gtts_ubench_mfma(_ptr(src), ctypes.c_size_t(src.numel() * 2), _ptr(sink), wgs, iters,
-                                                   ctypes.byref(flops), st), "gtts_ubench_mfma")
+            fn = lambda: _launch(device, "gtts_ubench_mfma", src, ctypes.c_size_t(src.numel() * 2), sink, wgs, iters, ctypes.byref(flops))
             t1 = timed(fn, 3)
             reps = max(3, int(seconds * 0.3 / max(t1, 1e-6)))      # long enough for the clock to settle at its power budget
             t = timed(fn, reps)
             out["mfma_bf16_tflops_%s" % name] = flops.value / t * 1e-12
-        fn = lambda: _check(L.gtts_ubench_mfma(_ptr(rnd), ctypes.c_size_t(rnd.numel() * 2), _ptr(sink), wgs, -iters,
-                                               ctypes.byref(flops), st), "gtts_ubench_mfma")
+        fn = lambda: _launch(device, "gtts_ubench_mfma", rnd, ctypes.c_size_t(rnd.numel() * 2), sink, wgs, -iters, ctypes.byref(flops))
         t1 = timed(fn, 3)
         out["mfma_bf16_16x16x32_tflops_random"] = flops.value / timed(fn, max(3, int(seconds * 0.3 / max(t1, 1e-6)))) * 1e-12
         # what the vendor's GEMM library reaches on the same chip with the same kind of data (hipBLASLt through torch.matmul,
@@ -2465,8 +2422,7 @@ def measured_ceilings(device, seconds=2.0):
             best = 0.0
             for nt in (0, 4):                           # plain and nontemporal accesses, a few grid sizes: keep the best
                 for wpc in (4, 8, 16):
-                    fn = lambda: _check(L.gtts_ubench_hbm(_ptr(a), _ptr(b), _ptr(c), ctypes.c_size_t(n), mode + nt, cus * wpc,
-                                                          ctypes.byref(nbytes), st), "gtts_ubench_hbm")
+                    fn = lambda: _launch(device, "gtts_ubench_hbm", a, b, c, ctypes.c_size_t(n), mode + nt, cus * wpc, ctypes.byref(nbytes))
                     t = timed(fn, 3)
                     gbs = nbytes.value / t * 1e-9
                     out.setdefault("hbm_detail", {})["%s_%s_wg%d" % (name, "nt" if nt else "plain", wpc)] = round(gbs, 1)

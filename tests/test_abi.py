@@ -7,27 +7,61 @@ import subprocess
 
 import pytest
 
+import abi_util
 from conftest import ROOT, pkg
-
-
-def _declared():
-    src = open(os.path.join(ROOT, "include", "gradtts_abi.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(gtts_[a-z_0-9]+)\s*\(", src)))
 
 
 def test_header_symbols_are_exported():
     S = pkg()
     assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    exported = set(re.findall(r"\bT (gtts_[a-z_0-9]+)", out))
-    declared = _declared()
+    exported = abi_util.exported(S._lib.LIB_PATH)
+    declared = abi_util.declared()
     assert len(declared) >= 15
     assert set(declared) <= exported, sorted(set(declared) - exported)
     assert exported - set(declared) == {"gtts_debug_mas_force_sweep"}     # (a test hook of mas.hip; anything else undeclared is a stray export)
     lib = ctypes.CDLL(S._lib.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name)
+
+
+class _StandInFunction:
+    """What ctypes hands out for a symbol, as far as the binding's declarations go."""
+    def __init__(self):
+        self.argtypes, self.restype = None, ctypes.c_int
+
+    def __call__(self, *args):
+        return 7                                  # (gtts_abi_version, the one call lib() makes)
+
+
+class _StandInLibrary:
+    """In place of ctypes.CDLL while lib() declares its entry points: it records every symbol lib() touches, whatever other tests of
+    this process have looked up on the real library object."""
+    def __init__(self, path):
+        self.touched = {}
+
+    def __getattr__(self, name):
+        if not name.startswith("gtts_"):
+            raise AttributeError(name)
+        return self.touched.setdefault(name, _StandInFunction())
+
+
+def test_the_binding_declares_every_prototype_as_the_header_does(monkeypatch):
+    """argtypes and restype of every entry point against the parsed prototypes of include/gradtts_abi.h: the same number of arguments,
+    each of the same kind (int / float / double / size_t / pointer), the same kind of result -- and nothing bound that the header lacks.
+    (A missing or short argtypes makes ctypes pass a size_t or a pointer as a 32-bit int.)"""
+    L = pkg()._lib
+    protos = abi_util.prototypes()
+    assert len(protos) >= 196 and "gtts_abi_version" in protos and protos["gtts_last_error"] == ("ptr", [])
+    assert protos["gtts_rezero_forward"] == ("int", ["ptr", "ptr", "ptr", "ptr", "size_t", "ptr"])
+    assert protos["gtts_wav_normalize"][1][3] == "double" and protos["gtts_plan_destroy"][0] == "void"
+    monkeypatch.setattr(L, "_lib", None)
+    monkeypatch.setattr(ctypes, "CDLL", _StandInLibrary)
+    bound = L.lib().touched
+    assert sorted(bound) == sorted(protos), (sorted(set(protos) - set(bound)), sorted(set(bound) - set(protos)))
+    for name, (ret, args) in sorted(protos.items()):
+        fn = bound[name]
+        assert [abi_util.ctypes_kind(t) for t in (fn.argtypes or [])] == args, (name, fn.argtypes, args)
+        assert abi_util.ctypes_kind(fn.restype) == ret, (name, fn.restype, ret)
 
 
 def test_cfg_struct_layout_matches_the_header(tmp_path):
@@ -145,8 +179,7 @@ def test_abi_contract_surface():
     if rc == 0:                # event creation needs a HIP device; on a CPU-only box the call fails cleanly instead
         assert p.workspace_bytes(16, 1024) >= w0
         assert L.gtts_plan_set_streams(p._h, None, 0) == 0
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    assert "gtts_debug_trace" not in out
+    assert "gtts_debug_trace" not in abi_util.nm(S._lib.LIB_PATH)
     blob = open(S._lib.LIB_PATH, "rb").read()
     assert b"GTTS_SKIP_OPS" not in blob and b"GTTS_STREAMS" not in blob and b"GTTS_MAS_KERNEL" not in blob
     # gtts_bcast_weights validates its arguments before touching RCCL

@@ -5,37 +5,22 @@ the ABI version at 7, and refuse bad arguments on the host.
 Every call below is made with fake non-null addresses and a null stream and MUST return before anything is dereferenced or launched: each
 is written against the guard it exercises (pointers first, then the shape, then the configuration)."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT, pkg
+import abi_util
+from abi_util import S, _fake, E_NULL, E_SHAPE, E_CONFIG, E_WORKSPACE
 
-OK, E_NULL, E_SHAPE, E_CONFIG, E_WORKSPACE = 0, -1, -2, -3, -6
 NEW = ("gtts_cond_field_forward", "gtts_cond_field_backward", "gtts_masked_mean_forward", "gtts_masked_mean_backward",
        "gtts_in_glu_tb_forward", "gtts_in_glu_tb_backward", "gtts_conv3x3_narrow_workspace_bytes", "gtts_conv3x3_narrow_forward",
        "gtts_conv3x3_narrow_dgrad", "gtts_conv3x3_narrow_wgrad")
 BAD_SHAPES = (dict(B=0), dict(B=-1), dict(C=0), dict(C=-64), dict(H=0), dict(W=0), dict(W=-4), dict(B=65536), dict(H=1 << 16, W=1 << 15))
 
 
-@pytest.fixture(scope="module")
-def S():
-    S = pkg()
-    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
-    return S
-
-
-def _fake(n):
-    return [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(n)]
-
-
 def test_new_symbols_are_exported_declared_and_bound(S):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    exported = set(re.findall(r"\bT (gtts_[a-z_0-9]+)", out))
-    hdr = open(os.path.join(ROOT, "include", "gradtts_abi.h")).read()
-    declared = set(re.findall(r"\b(gtts_[a-z_0-9]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))
+    exported = abi_util.exported(S._lib.LIB_PATH)
+    hdr = open(abi_util.HEADER).read()
+    declared = set(abi_util.declared())
     L = S._lib.lib()
     for name in NEW:
         assert name in exported and name in declared, name

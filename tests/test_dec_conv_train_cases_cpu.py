@@ -1,23 +1,20 @@
 """CPU: the catalogue of tests/dec_conv_train_cases.py proves what it claims without a GPU -- its formulas equal float64 autograd, the
 `integers` cases are exact in fp32, every restated mistake is told from the contract by the bounds the GPU test applies, the documented
 arithmetic itself stays inside them, the weight-gradient regimes and the kernel instances it claims are the ones the library chooses."""
-import os
 
 import pytest
 import torch
 
 import dec_conv_train_cases as C
 import wgrad_regimes as R
-from conftest import pkg
+from abi_util import S
 
 CONV_CASES = [c for c in C.CASES if c.op in C.CONV_OPS]
 GLUE_CASES = [c for c in C.CASES if c.op in C.GLUE_OPS]
 
 
 @pytest.fixture(scope="module")
-def lib():
-    S = pkg()
-    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
+def lib(S):
     return S._lib
 
 

@@ -9,26 +9,12 @@ Every gtts_enc_forward / gtts_enc_layernorm / gtts_enc_attention call below is m
 before anything is dereferenced or launched: each is written against the guard it exercises (a call that passed every guard would
 launch kernels on those addresses)."""
 import ctypes
-import os
 
 import pytest
 
-from conftest import pkg
+from abi_util import S, _fake, OK, E_NULL, E_SHAPE, E_CONFIG, E_WORKSPACE
 
-OK, E_NULL, E_SHAPE, E_CONFIG, E_WORKSPACE = 0, -1, -2, -3, -6
 LDS = 160 * 1024                                    # bytes of LDS one workgroup can have on gfx950
-
-
-@pytest.fixture(scope="module")
-def S():
-    S = pkg()
-    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
-    return S
-
-
-def _fake(n=1):
-    """Non-null host addresses: validation must fail before any of them is dereferenced or handed to the device."""
-    return [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(n)]
 
 
 def lds16(dk, L):

@@ -6,33 +6,19 @@ Every gtts_conv1d_pack_dgrad / gtts_conv1d_wgrad call below is made with fake no
 dereferenced or launched: each is written against the guard it exercises."""
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT, pkg
+import abi_util
+from abi_util import S, _fake, E_NULL, E_SHAPE, E_CONFIG, E_WORKSPACE
+from conftest import ROOT
 
-OK, E_NULL, E_SHAPE, E_CONFIG, E_WORKSPACE = 0, -1, -2, -3, -6
 NEW = ("gtts_conv1d_pack_dgrad", "gtts_conv1d_wgrad_workspace_bytes", "gtts_conv1d_wgrad", "gtts_conv1d_wgrad_info")
 
 
-@pytest.fixture(scope="module")
-def S():
-    S = pkg()
-    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
-    return S
-
-
-def _fake(n):
-    return [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(n)]
-
-
 def test_new_symbols_are_exported_declared_and_bound(S):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    exported = set(re.findall(r"\bT (gtts_[a-z_0-9]+)", out))
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gradtts_abi.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(gtts_[a-z_0-9]+)\s*\(", src))
+    exported = abi_util.exported(S._lib.LIB_PATH)
+    declared = set(abi_util.declared())
     L = S._lib.lib()
     for name in NEW:
         assert name in exported and name in declared, name

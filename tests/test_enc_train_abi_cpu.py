@@ -6,28 +6,16 @@ Every gtts_enc_attention_train_* / gtts_enc_layernorm_backward call below is mad
 anything is dereferenced or launched: each is written against the guard it exercises."""
 import ctypes
 import os
-import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT, pkg
+import abi_util
+from abi_util import S, _fake, E_NULL, E_SHAPE, E_CONFIG
+from conftest import ROOT
 
-OK, E_NULL, E_SHAPE, E_CONFIG = 0, -1, -2, -3
 LDS = 160 * 1024
 NEW = ("gtts_enc_attention_train_ok", "gtts_enc_attention_train_scratch_bytes", "gtts_enc_attention_train_forward",
        "gtts_enc_attention_train_backward", "gtts_enc_layernorm_backward_scratch_floats", "gtts_enc_layernorm_backward")
-
-
-@pytest.fixture(scope="module")
-def S():
-    S = pkg()
-    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
-    return S
-
-
-def _fake(n):
-    return [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(n)]
 
 
 def lds_floats(dk, window, L):
@@ -44,10 +32,8 @@ def expected_ok(C, heads, window, L):
 
 
 def test_new_symbols_are_exported_declared_and_bound(S):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    exported = set(re.findall(r"\bT (gtts_[a-z_0-9]+)", out))
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gradtts_abi.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(gtts_[a-z_0-9]+)\s*\(", src))
+    exported = abi_util.exported(S._lib.LIB_PATH)
+    declared = set(abi_util.declared())
     L = S._lib.lib()
     for name in NEW:
         assert name in exported and name in declared, name

@@ -14,6 +14,7 @@ import torch
 
 import fgl_oracle as FO
 import mel_oracle as MO
+import abi_util
 from conftest import ROOT, pkg
 
 CFGS = {"cfgA": FO.CFGA, "cfgB": FO.CFGB}
@@ -31,8 +32,7 @@ def make(U, cfg, **kw):
 
 def test_fgl_symbols_are_exported_and_the_abi_version_stays():
     S = pkg()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    exported = set(re.findall(r"\bT (gtts_fgl_[a-z_0-9]+)", out))
+    exported = {n for n in abi_util.exported(S._lib.LIB_PATH) if n.startswith("gtts_fgl_")}
     want = {"gtts_fgl_create", "gtts_fgl_destroy", "gtts_fgl_samples", "gtts_fgl_packed_bytes", "gtts_fgl_pack",
             "gtts_fgl_workspace_bytes", "gtts_fgl_init", "gtts_fgl_step", "gtts_fgl_forward"}
     assert exported == want

@@ -7,35 +7,20 @@ is written against the guard it exercises.  `start` and `kept` of the gather liv
 on the host; the kernels count it as S (tests/test_gpu_glue_train_ops.py runs that), and what the host refuses in its place is a window
 longer than the frame axis, S > T."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT, pkg
+import abi_util
+from abi_util import S, _fake, E_NULL, E_SHAPE, E_CONFIG
 
-OK, E_NULL, E_SHAPE, E_CONFIG = 0, -1, -2, -3
 NEW = ("gtts_conv_dgrad_small", "gtts_diffusion_noising_backward", "gtts_align_index", "gtts_duration_loss", "gtts_align_gather_partials",
        "gtts_align_gather_forward", "gtts_align_gather_backward")
 
 
-@pytest.fixture(scope="module")
-def S():
-    S = pkg()
-    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
-    return S
-
-
-def _fake(n):
-    return [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(n)]
-
-
 def test_new_symbols_are_exported_declared_and_bound(S):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    exported = set(re.findall(r"\bT (gtts_[a-z_0-9]+)", out))
-    hdr = open(os.path.join(ROOT, "include", "gradtts_abi.h")).read()
-    declared = set(re.findall(r"\b(gtts_[a-z_0-9]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))
+    exported = abi_util.exported(S._lib.LIB_PATH)
+    hdr = open(abi_util.HEADER).read()
+    declared = set(abi_util.declared())
     L = S._lib.lib()
     for name in NEW:
         assert name in exported and name in declared, name

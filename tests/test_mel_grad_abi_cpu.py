@@ -4,13 +4,13 @@ the torch path of the drop-in under autograd."""
 import ctypes
 import importlib
 import re
-import subprocess
 
 import pytest
 import torch
 
 import mel_grad_cases as C
 import mel_oracle as MO
+import abi_util
 from conftest import pkg
 
 NEW = {"gtts_mel_backward", "gtts_mel_backward_workspace_bytes"}
@@ -23,8 +23,7 @@ def MD():
 
 def test_new_symbols_are_exported_and_declared_and_the_version_stays():
     S = pkg()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    assert set(re.findall(r"\bT (gtts_mel_[a-z_0-9]+)", out)) >= NEW
+    assert abi_util.exported(S._lib.LIB_PATH) >= NEW
     import os
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gradtts_abi.h")).read()
     for name in NEW:

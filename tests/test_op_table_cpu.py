@@ -11,6 +11,7 @@ import subprocess
 
 import pytest
 
+import abi_util
 from conftest import GOLDEN, ROOT
 
 _spec = importlib.util.spec_from_file_location("make_golden_op_table", os.path.join(GOLDEN, "make_golden_op_table.py"))
@@ -49,7 +50,7 @@ def test_kernel_names_match_the_record(table, recorded):
 def _library_kernels(path):
     """Names of the __global__ functions of the library: its host stubs, demangled, without `__device_stub__`, the return type that
     a template instance's name carries and the parameter list."""
-    syms = [line.split()[-1] for line in subprocess.check_output(["nm", "-D", "--defined-only", path]).decode().splitlines()]
+    syms = [line.split()[-1] for line in abi_util.nm(path).splitlines()]
     stubs = [s for s in syms if "__device_stub__" in s]
     # binutils' demangler predates the Itanium ABI's code for __bf16 (DF16b); the vendor-extended spelling demangles to the same text
     plain = subprocess.run(["c++filt"], input="\n".join(stubs).replace("DF16b", "u6__bf16"), stdout=subprocess.PIPE, check=True,

@@ -1,43 +1,22 @@
 """CPU: the DiffVC PostNet training entry points (7x7 convolution forward / data gradient / weight gradient, the single-channel 1x1
 convolutions) are declared, exported and validate their arguments before touching a device; the Python gate takes the train_enc.py
 shape and refuses channel counts the kernels do not tile."""
-import ctypes
-import os
-import re
-import subprocess
-
-import pytest
-
-from conftest import ROOT, pkg
+import abi_util
+from abi_util import L, S, _fake, E_NULL, E_SHAPE, E_CONFIG      # (S: the fixture L asks for)
+from conftest import pkg
 
 NEW = ["gtts_conv7x7_packed_bytes", "gtts_conv7x7_pack", "gtts_conv7x7_masked", "gtts_conv7x7_wgrad_workspace_bytes",
        "gtts_conv7x7_wgrad", "gtts_postnet_expand", "gtts_postnet_collapse", "gtts_postnet_chan_dot_scratch_floats",
        "gtts_postnet_chan_dot"]
-E_NULL, E_SHAPE, E_CONFIG = -1, -2, -3
 
 
-@pytest.fixture(scope="module")
-def L():
-    S = pkg()
-    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
-    return S._lib.lib()
-
-
-def test_new_symbols_declared_and_exported(L):
-    S = pkg()
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gradtts_abi.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(gtts_[a-z_0-9]+)\s*\(", src))
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    exported = set(re.findall(r"\bT (gtts_[a-z_0-9]+)", out))
+def test_new_symbols_declared_and_exported(L, S):
+    declared = set(abi_util.declared())
+    exported = abi_util.exported(S._lib.LIB_PATH)
     for name in NEW:
         assert name in declared, name
         assert name in exported, name
     assert L.gtts_abi_version() == 7
-
-
-def _fake(n=1):
-    """Non-null host addresses: validation must fail before any of them is dereferenced or handed to the device."""
-    return [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(n)]
 
 
 def test_conv7x7_pack_validates(L):

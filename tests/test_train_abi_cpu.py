@@ -6,26 +6,13 @@ workspace sizes have the documented form the regime checks of tests/test_gpu_tra
 Every call below is made with fake non-null addresses and MUST return before anything is dereferenced or launched: each was written
 against the guard it exercises in csrc/train*.hip (a call that passed every guard would launch a kernel on those addresses)."""
 import ctypes
-import os
 
 import pytest
 
 import wgrad_regimes as R
+from abi_util import L, S, _fake, OK, E_NULL, E_SHAPE, E_CONFIG, E_WORKSPACE      # (S: the fixture L asks for)
 from conftest import pkg
 
-OK, E_NULL, E_SHAPE, E_CONFIG, E_WORKSPACE = 0, -1, -2, -3, -6
-
-
-@pytest.fixture(scope="module")
-def L():
-    S = pkg()
-    assert os.path.exists(S._lib.LIB_PATH), "run __graft_entry__.build() first"
-    return S._lib.lib()
-
-
-def _fake(n=1):
-    """Non-null host addresses: validation must fail before any of them is dereferenced or handed to the device."""
-    return [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(n)]
 
 
 def _each_null(call, args, required):

@@ -6,7 +6,6 @@ import ctypes
 import math
 import os
 import pickle
-import re
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 import torch
 
 import wav_oracle as WO
+import abi_util
 from conftest import ROOT, pkg
 
 
@@ -51,8 +51,7 @@ def test_preprocess_wav_batch_needs_no_torchaudio(A, monkeypatch):
 
 def test_wav_symbols_are_exported_and_the_abi_version_stays():
     S = pkg()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S._lib.LIB_PATH]).decode()
-    exported = set(re.findall(r"\bT (gtts_wav_[a-z_0-9]+)", out))
+    exported = {n for n in abi_util.exported(S._lib.LIB_PATH) if n.startswith("gtts_wav_")}
     assert exported >= {"gtts_wav_" + op for op in ("create", "destroy", "resampled_length", "frames", "tiles", "span", "taps", "filterbank",
                                                     "packed_bytes", "pack", "workspace_bytes", "resample", "normalize", "powmel")}
     assert S._lib.lib().gtts_abi_version() == 7
